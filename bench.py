@@ -3,11 +3,17 @@
 
 One "step" = forward + WTA multi-hypothesis loss + backward + gradient all-reduce + Adam on a synthetic batch of
 B windows per GPU of H36M shape (T=243, J=17, K=5, C=512, depth 8), inputs resident in HBM.
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1: one rank per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE set) this process IS a rank; without it the
 process spawns `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself (before anything touches a GPU) and
 relays its output.
-Prints ONE JSON line on rank 0 with
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 with the headline (`metric`, `value` in poses/s,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, `steps`, `warmup`, `config`, `loss`, `model_tflops`,
+`workspace_gib`).  `--dump-outputs DIR` then writes what the last timed step left its caller, as float32 .npy files (32 MiB in all;
+same arguments, same inputs and weights): `loss_terms` (the step's return value), `params_sample` / `grads_sample` (a fixed sample,
+seed 0, of 2^22 entries of the flat parameter buffer after the step's Adam update and of the flat gradient buffer it applied).
+`--full` adds everything else, behind the timed steps (or, for the CPU child and the parity forward, before the GPU work starts); the
+`--no-*` options switch parts of it off.  With `--full` the line also carries
   `roofline`      dominant kernel = gemm_bf16_persist_kernel, the forward + dgrad Linear GEMMs; HIP events inside the engine on the
                   stream each launch goes to;
   `parity`        MPJPE of the TIMED precision against the fp32 CPU oracle at full size (T=243 K=5, the bench's own weights), measured in
@@ -27,7 +33,7 @@ Default precision: "bf16x3" (split operands, fp32 accumulate; bf16 backward) - t
 `config.split_forms`): since round 6 the default is `--f16f8 3` - all four Linear layers of a block of the rotations net as ONE fp16 + ONE block-scaled
 fp8 matrix-core product per 64 reduction indices (hand-scheduled k-steps; the attention products stay three bf16 products; bf16 backward): same-box
 A/B +3.4 % poses/s (+4.3 % on the final round-6 tree) over the three-product form at 1.6e-5 m instead of 0.94e-5 m.  `--f16f8 0` = every product as three
-bf16 products (rounds 2-5; timed for a few steps in every default run as `other_precisions.bf16x3_three_bf16_products`); 1 / 2 = the older partial
+bf16 products (rounds 2-5; timed for a few steps in every --full run as `other_precisions.bf16x3_three_bf16_products`); 1 / 2 = the older partial
 forms (qkv / fc1 [/ fc2 with --f16-backward]).
 """
 import argparse
@@ -162,6 +168,7 @@ def free_port():
 PARITY_BOUND_M = 1e-4          # BASELINE.json north_star: outputs within 1e-4 on MPJPE
 PARITY_WINDOWS = 3             # parity windows per run (oracle forward on the host: ~1 s each), spread over the timed batch
 EXTRA_BATCH = {"fp32": 16, "bf16": 79, "bf16x3": 79}
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: entries sampled from each flat buffer (34.4 M at full size; 16 MiB of float32 each)
 
 
 def _power_pass(step, seconds=3.0):
@@ -236,6 +243,13 @@ def main():
     ap.add_argument("--grad-buckets", action="store_true",
                     help="N > 1: overlap the gradient exchange with the backward (one all-reduce per layer of the rotations net on a communication "
                          "stream) instead of one all-reduce of the flat buffer behind it; off by default (never measured on a multi-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: in-run parity against the CPU oracle, CPU baseline, roofline and kernel classes (HIP events "
+                         "in the timed steps, a one-queue pass), power samples, other precisions / configurations / batch sizes, at N > 1 the RCCL "
+                         "check and both gradient-exchange modes; the --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, 32 MiB): loss_terms, and a fixed "
+                         "sample of the parameters after its update (params_sample) and of the gradients it applied (grads_sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prof", action="store_true")
     ap.add_argument("--no-isolated", action="store_true", help="skip the one-queue pass behind the timed region (profiling runs: a kernel-stats file should hold the timed configuration's launches only)")
@@ -253,6 +267,11 @@ def main():
             parity_oracle(args.parity_io)
         print(json.dumps(cpu_baseline(args.frames, args.hyp) if args.cpu_baseline_only else {}), flush=True)
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:              # a plain run: the headline only (no HIP events in the timed steps, nothing behind them)
+        args.no_cpu_baseline = args.no_parity = args.no_extra = args.no_other_configs = True
+        args.no_prof = args.no_isolated = args.no_power = True
     import subprocess
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: start one rank per GPU as fresh child processes (this process never touches a GPU) and relay
@@ -371,18 +390,19 @@ def main():
         from manipose_amd.distributed import broadcast_parameters
         model._ensure_engine(args.batch, torch.device("cuda", local))
         broadcast_parameters(model._flat)
-        ones = torch.ones(1, device="cuda")
-        dist.all_reduce(ones)                  # every rank contributes 1: the sum is the number of ranks the backend really joined
-        rccl = {"backend": dist.get_backend(), "ranks": int(round(ones.item())), "world_size": world,
-                "device": torch.cuda.get_device_name(local)}
-        dist.broadcast(have_oracle, src=0)
-        if have_oracle.item():
-            K = args.hyp
-            op = oracle_out["poses"].cuda() if rank == 0 else torch.empty(npar, K, args.frames, 17, 3, device="cuda")
-            osc = oracle_out["scores"].cuda() if rank == 0 else torch.empty(npar, K, args.frames, 1, device="cuda")
-            dist.broadcast(op, src=0)
-            dist.broadcast(osc, src=0)
-            oracle_out = {"poses": op, "scores": osc}
+        if args.full:
+            ones = torch.ones(1, device="cuda")
+            dist.all_reduce(ones)                  # every rank contributes 1: the sum is the number of ranks the backend really joined
+            rccl = {"backend": dist.get_backend(), "ranks": int(round(ones.item())), "world_size": world,
+                    "device": torch.cuda.get_device_name(local)}
+            dist.broadcast(have_oracle, src=0)
+            if have_oracle.item():
+                K = args.hyp
+                op = oracle_out["poses"].cuda() if rank == 0 else torch.empty(npar, K, args.frames, 17, 3, device="cuda")
+                osc = oracle_out["scores"].cuda() if rank == 0 else torch.empty(npar, K, args.frames, 1, device="cuda")
+                dist.broadcast(op, src=0)
+                dist.broadcast(osc, src=0)
+                oracle_out = {"poses": op, "scores": osc}
     elif oracle_out is not None:
         oracle_out = {k: v.cuda() for k, v in oracle_out.items()}
 
@@ -435,6 +455,7 @@ def main():
         torch.cuda.synchronize()
 
     log(f"model built, B={B} T={T} precision={args.precision}" + (f", parity at B={B}: {parity['mpjpe_m']:.2e} m" if parity else ""))
+    model._ensure_engine(B, X.device)          # (what the parity forward or the first step would do; here also with --warmup 0)
     for i in range(args.warmup):
         terms = trainer.train_step(X, y)
         if i == 0:
@@ -458,12 +479,24 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
     loss = float(terms.sum().item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left its caller, before anything behind the timed region trains the model further: the returned loss
+        # terms, and a fixed sample (seed 0, sorted indices) of the flat parameters after its Adam update and of the gradients it applied
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        flat = model.flat_parameters()
+        nflat = flat.numel()
+        idx = np.arange(nflat) if nflat <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(nflat, DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(flat.device)
+        for name, t in (("loss_terms", terms), ("params_sample", flat[idx]), ("grads_sample", trainer.flat_grads[idx])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     # N > 1: the open question of DESIGN section 6, answered by the run itself - a few steps in each exchange mode with device events around
     # the backward and the exchange: does the backward get longer with RCCL kernels resident (bucketed), and how much of the single
     # collective is exposed behind it?
     exchange = None
-    if world > 1:
+    if world > 1 and args.full:
         exchange = {}
         nx = max(2, min(5, args.steps))
         for mode in ("single", "bucketed"):

@@ -41,11 +41,11 @@ def clean_env(**extra):
 def test_bench_two_rank_path_rehearsal_on_one_gpu(lib):
     """`python bench.py --gpus 2` with NO launcher around it: bench.py spawns torch.distributed.run itself (before touching a GPU); the two
     ranks are pinned to this GPU with gloo carrying the collectives (a one-GPU box cannot host two RCCL ranks): init, barrier, gradient
-    all-reduce, max-over-ranks timing, one JSON line from rank 0 with the in-run parity block."""
+    all-reduce, max-over-ranks timing, one JSON line from rank 0 with (--full) the in-run parity block."""
     root = ROOT
     env = clean_env(MANIPOSE_BENCH_DEVICE="0", MANIPOSE_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "2", "--frames", "27"], capture_output=True, text=True, timeout=400, env=env, cwd=root)
+                        "--batch", "2", "--frames", "27", "--full"], capture_output=True, text=True, timeout=400, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -62,6 +62,38 @@ def test_bench_two_rank_path_rehearsal_on_one_gpu(lib):
     ex = d["gradient_exchange"]
     assert set(ex) >= {"single", "bucketed"} and ex["single"]["timed_mode"] and not ex["bucketed"]["timed_mode"]
     assert all(ex[m]["backward_ms"] > 0 and ex[m]["exposed_exchange_ms"] >= 0 for m in ("single", "bucketed"))
+
+
+FULL_ONLY_KEYS = {"parity", "roofline", "kernel_classes", "kernel_classes_basis", "power", "other_precisions", "other_configs", "small_batch",
+                  "cpu_baseline", "rccl", "gradient_exchange"}
+
+
+def test_bench_plain_run_is_lean_and_its_dumped_outputs_match_the_full_run(lib, tmp_path):
+    """A plain `python bench.py` run carries the headline only (nothing of --full), `--steps` sets the timed steps and `ms_per_step` is their
+    mean; `--dump-outputs DIR` writes float .npy arrays within 64 MB.  The same arguments with --full (its parity forward in front of the
+    timed steps, HIP events inside them, a one-queue pass behind them) must leave the last timed step with the same bits."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4", "--frames", "27"]
+    runs = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-extra", "--no-power"])):
+        out_dir = tmp_path / tag
+        r = subprocess.run(base + extra + ["--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=400, env=clean_env(), cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        runs[tag] = (json.loads(lines[0]), {p.stem: np.load(p) for p in out_dir.glob("*.npy")})
+    d, arrays = runs["plain"]
+    assert d["unit"] == "poses/s" and d["higher_is_better"] is True and d["dtype"] == "bf16x3" and d["steps"] == 3 and d["warmup"] == 1
+    assert d["metric"].startswith("train poses/sec") and d["value"] > 0
+    assert abs(d["value"] - 4 * 27 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"], d
+    assert not FULL_ONLY_KEYS & set(d), sorted(FULL_ONLY_KEYS & set(d))
+    df = runs["full"][0]
+    assert df["parity"]["within_bound"] and "roofline" in df and "kernel_classes" in df, sorted(df)
+    assert set(arrays) == {"loss_terms", "params_sample", "grads_sample"}, sorted(arrays)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2**20 and arrays["loss_terms"].shape == (4,)
+    assert np.abs(arrays["grads_sample"]).max() > 0
+    for name, a in arrays.items():
+        np.testing.assert_array_equal(a, runs["full"][1][name], err_msg=name)
 
 
 def test_bucketed_gradient_exchange_equals_the_single_all_reduce(lib, tmp_path):
