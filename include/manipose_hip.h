@@ -153,7 +153,8 @@ int mp_linear_fwd_bf16x3_lnres(const void* x_hi, const void* x_lo, const void* W
  *   activation row:  4 x e4m3(2^11 (v - hi))  |  4 x e4m3(hi)
  *   weight row:      4 x e4m3(2^4 hi)         |  4 x e4m3(2^15 (v - hi))
  * so that the fp8 dot product of an activation row and a weight row is 2^15 (x_lo w_hi + x_hi w_lo).  y = x W^T + b in fp32.
- * N must be a multiple of 256, K of 64 (>= 128).  The engine runs its qkv and fc1 forward GEMMs in this form (precision 2, "f16f8_inputs"). */
+ * N must be a multiple of 256, K of 64 (>= 128).  The engine runs its qkv and fc1 forward GEMMs in this form with mp_model_config::f16f8 = 1,
+ * the fc2 GEMM too with f16f8 = 2, and all four Linear layers of a block with f16f8 = 3 (the default of the training configuration). */
 /* fp32 -> the two planes of that format for a matrix whose rows are multiples of 64 elements long (n = rows * K elements; hi16: n fp16
  * values, corr8: 2 n bytes); weight != 0 selects the weight form of the correction rows. */
 int mp_split_f16f8(const float* src, void* hi16, void* corr8, int64_t n, int weight, void* stream);
@@ -163,6 +164,32 @@ int mp_linear_fwd_f16f8(const void* x16, const void* x8, const void* W16, const 
  * shape (spatial: 16 <= J <= 32 tokens, head dim 64 or 16, <= 8 heads; temporal: T <= 256, head dim 64 or 16); NULL otherwise. */
 int mp_attention_fwd_bf16x3(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, float* scratch, int temporal,
                             int B, int T, int J, int C, int H, void* stream);
+/* The other forms of the f16f8 path (mp_model_config::f16f8 >= 1), each through the dispatcher the engine calls.
+ * mp_linear_fwd_f16f8_ex: the Linear above with every epilogue.  epilogue 0 bias, 1 GELU (z: gelu'(pre-activation) as bf16, may be NULL),
+ * 2 residual (y = LN(r_in) + mask * (x W^T + b) with rstats / rgamma / rbeta as in mp_linear_fwd_bf16x3_lnres, or y = r_in + mask * (..)
+ * when they are NULL; rscale must be 0 or 1).  out_form 0: y fp32 (epilogues 0, 2); 1: planar bf16, y = hi plane, y_lo = lo plane
+ * (epilogues 0, 1); 2: y = fp16 plane, y_lo = correction plane of the activation form (epilogue 1).  Other combinations: MP_ERR_ARG. */
+int mp_linear_fwd_f16f8_ex(const void* x16, const void* x8, const void* W16, const void* W8, const float* b, void* y, void* y_lo, void* z,
+                           const float* r_in, const float* rstats, const float* rgamma, const float* rbeta, const float* mask, int mask_mode,
+                           float rscale, int T, int J, int M, int N, int K, int epilogue, int out_form, void* stream);
+/* The fused LayerNorm forward of the engine: stage 1 (g1 non-NULL) x1 = LN(x; g1, b1, eps1) [+ pos[t]] (fp32, x1 may be NULL: not stored),
+ * stats1 = (mean, rstd) per row; stage 2 (g2 non-NULL) y2 = LN(stage-1 output or x; g2, b2, eps2) in out_mode 0 fp32, 1 bf16, 2 planar bf16
+ * (y2_lo the lo plane), 3 f16f8 (y2 the fp16 plane, y2_lo the correction plane; y2_b16 an optional bf16 copy).  C <= 1024. */
+int mp_layernorm_fwd_ex(const float* x, int M, int C, const float* g1, const float* b1, float eps1, const float* pos, int T, int J, float* x1,
+                        float* stats1, const float* g2, const float* b2, float eps2, void* y2, void* y2_lo, void* y2_b16, float* stats2, int out_mode,
+                        void* stream);
+/* mp_attention_fwd_bf16x3 with out_form 1: the output as f16f8 planes (out_hi = fp16 plane, out_lo = correction plane; head dim 64) */
+int mp_attention_fwd_bf16x3_ex(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, float* scratch, int temporal,
+                               int B, int T, int J, int C, int H, int out_form, void* stream);
+/* mp_attention_bwd_bf16 with out_f16 = 1: O is the fp16 plane of an f16f8 output (temporal MFMA backward only; MP_ERR_ARG elsewhere) */
+int mp_attention_bwd_bf16_ex(const void* qkv, const void* out, const void* d_out, const float* lse, float* delta, void* d_qkv, int temporal, int B,
+                             int T, int J, int C, int H, int out_f16, void* stream);
+/* Backward GEMMs of the f16f8 layers.  dgrad (dx non-NULL): dx = dy W (bf16 out), times z = gelu' (bf16) when z is non-NULL; f16 = 1: dy and W
+ * are fp16; gout non-NULL (device address): dx is written as saturating fp16 of *gout x value, clamped at +-65504, non-finite values as 0,
+ * counted in gsat[0] (clamped) and gsat[1] (non-finite), which are added to.  Weight gradient (dW non-NULL): dW += dy^T x, db += colsum(dy);
+ * f16 = 1: dy and x fp16, the sums multiplied by *oscale (device address); x_f16 = 1: dy bf16, x fp16 rounded to bf16; slab as mp_linear_bwd_bf16. */
+int mp_linear_bwd_f16(const void* dy, const void* x, const void* W, void* dx, const void* z, const float* gout, uint32_t* gsat, float* dW, float* db,
+                      int M, int N, int K, int f16, int x_f16, const float* oscale, float* slab, int64_t slab_floats, void* stream);
 
 /* K output heads, head k = LayerNorm(C, eps 1e-5) -> Linear(C, O)  (MCLHead stack, rmcl_manifold_mix_ste.py:291-298; MixSTE.head,
  * mix_ste.py:123-126), all fp32.  Packed parameters: gamma, beta [K][C]; W [K][O][C]; b [K][O].  out [K][M][O]; stats [M][2] (mean, rstd

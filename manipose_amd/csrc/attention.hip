@@ -474,7 +474,7 @@ static int temporal_bwd_t(const TS* qkv, const TS* out, const TS* dout, const fl
 bool attn_tmfma_supported(int T, int D);
 int attn_tmfma_fwd(const bf16* qkv, bf16* out, float* lse, int B, int T, int J, int C, int H, hipStream_t st);
 int attn_tmfma_bwd(const bf16* qkv, const bf16* out, const bf16* dout, const float* lse, bf16* dqkv, int B, int T, int J, int C, int H,
-                   hipStream_t st);
+                   hipStream_t st, int out_f16);
 
 int attn_temporal_fwd(const void* qkv, void* out, float* lse, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st) {
   MP_CHECK(C % H == 0, MP_ERR_ARG, "attn_temporal_fwd: C %% H");
@@ -483,10 +483,12 @@ int attn_temporal_fwd(const void* qkv, void* out, float* lse, int is_bf16, int B
                  : temporal_fwd_t<float>((const float*)qkv, (float*)out, lse, B, T, J, C, H, st);
 }
 int attn_temporal_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int is_bf16,
-                      int B, int T, int J, int C, int H, hipStream_t st) {
+                      int B, int T, int J, int C, int H, hipStream_t st, int out_f16) {
   MP_CHECK(C % H == 0, MP_ERR_ARG, "attn_temporal_bwd: C %% H");
   if (is_bf16 && attn_tmfma_supported(T, C / H))
-    return attn_tmfma_bwd((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, B, T, J, C, H, st);
+    return attn_tmfma_bwd((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, B, T, J, C, H, st, out_f16);
+  // the row kernels below read O in the storage type of qkv: an fp16 O plane would be taken for bf16 bits
+  MP_CHECK(!out_f16, MP_ERR_ARG, "attn_temporal_bwd: O as an fp16 plane needs the MFMA backward (T=%d, head dim %d, is_bf16 %d)", T, C / H, is_bf16);
   return is_bf16 ? temporal_bwd_t<bf16>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, B, T, J, C, H, st)
                  : temporal_bwd_t<float>((const float*)qkv, (const float*)out, (const float*)dout, lse, delta, (float*)dqkv, B, T, J, C,
                                          H, st);

@@ -196,9 +196,6 @@ __device__ __forceinline__ void store4g(bf16* p, const f32x4& v, float s, float 
 // set by the engine for the backward launches issued next on this thread: device address of the scale (null = bf16 outputs); see store4g
 static thread_local const float* g_grad_f16 = nullptr;
 void attn_grad_f16_override(const float* gout) { g_grad_f16 = gout; }
-// set by the engine likewise: the temporal backward launches issued next read `out` as an fp16 plane (f16f8 = 3) instead of bf16
-static thread_local int g_out_f16 = 0;
-void attn_out_f16_override(int on) { g_out_f16 = on; }
 
 // =============================================================================================
 // forward: O = softmax(scale Q K^T) V ; lse = log sum exp of the scaled scores
@@ -1508,7 +1505,7 @@ int attn_tmfma_fwd(const bf16* qkv, bf16* out, float* lse, int B, int T, int J, 
 
 template <int D, int NTC>
 static int launch_tmfma_bwd(const bf16* qkv, const bf16* out, const bf16* dout, const float* lse, bf16* dqkv, int units, int T, int J, int C,
-                            int H, float scale, int dbg, hipStream_t st) {
+                            int H, float scale, int dbg, hipStream_t st, int out_f16) {
   // waves per workgroup: one per 16-frame strip, except 4 for 5-7 strips (T=81: 971 -> 906 us; 8 strips and more measured best at one each)
   const int ntile = (T + 15) >> 4;
   const int waves = NTC ? 16 : ((ntile >= 5 && ntile <= 7) ? 4 : min(16, ntile));
@@ -1523,14 +1520,14 @@ static int launch_tmfma_bwd(const bf16* qkv, const bf16* out, const bf16* dout, 
     attr_set = true;
   }
   if (g_grad_f16 != nullptr)
-    hipLaunchKernelGGL((attn_tmfma_bwd_kernel<D, NTC, true>), dim3(units), dim3(64 * waves), lds, st, qkv, out, dout, lse, dqkv, T, J, C, H, scale, dbg, g_grad_f16, g_out_f16);
+    hipLaunchKernelGGL((attn_tmfma_bwd_kernel<D, NTC, true>), dim3(units), dim3(64 * waves), lds, st, qkv, out, dout, lse, dqkv, T, J, C, H, scale, dbg, g_grad_f16, out_f16);
   else
-    hipLaunchKernelGGL((attn_tmfma_bwd_kernel<D, NTC, false>), dim3(units), dim3(64 * waves), lds, st, qkv, out, dout, lse, dqkv, T, J, C, H, scale, dbg, g_grad_f16, g_out_f16);
+    hipLaunchKernelGGL((attn_tmfma_bwd_kernel<D, NTC, false>), dim3(units), dim3(64 * waves), lds, st, qkv, out, dout, lse, dqkv, T, J, C, H, scale, dbg, g_grad_f16, out_f16);
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
 int attn_tmfma_bwd(const bf16* qkv, const bf16* out, const bf16* dout, const float* lse, bf16* dqkv, int B, int T, int J, int C, int H,
-                   hipStream_t st) {
+                   hipStream_t st, int out_f16) {
   const int D = C / H;
   MP_CHECK(attn_tmfma_supported(T, D) && C % 8 == 0, MP_ERR_ARG, "attn_tmfma_bwd: T=%d D=%d unsupported", T, D);
   const float scale = attn_qk_scale(D);
@@ -1542,10 +1539,10 @@ int attn_tmfma_bwd(const bf16* qkv, const bf16* out, const bf16* dout, const flo
   constexpr int dbg = 0;
 #endif
   const bool full = T > 240;
-  if (D == 64) return full ? launch_tmfma_bwd<64, 16>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st)
-                           : launch_tmfma_bwd<64, 0>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st);
-  return full ? launch_tmfma_bwd<16, 16>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st)
-              : launch_tmfma_bwd<16, 0>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st);
+  if (D == 64) return full ? launch_tmfma_bwd<64, 16>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st, out_f16)
+                           : launch_tmfma_bwd<64, 0>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st, out_f16);
+  return full ? launch_tmfma_bwd<16, 16>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st, out_f16)
+              : launch_tmfma_bwd<16, 0>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st, out_f16);
 }
 
 }  // namespace mp

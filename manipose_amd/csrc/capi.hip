@@ -203,6 +203,72 @@ int mp_attention_fwd_bf16x3(const void* qkv_hi, const void* qkv_lo, void* out_hi
                                         (hipStream_t)stream);
 }
 
+/* unit-test entry points of the f16f8 forms the engine launches (include/manipose_hip.h): each fills the argument block engine.hip fills
+ * and calls the same dispatcher */
+int mp_linear_fwd_f16f8_ex(const void* x16, const void* x8, const void* W16, const void* W8, const float* b, void* y, void* y_lo, void* z,
+                           const float* r_in, const float* rstats, const float* rgamma, const float* rbeta, const float* mask, int mask_mode,
+                           float rscale, int T, int J, int M, int N, int K, int epilogue, int out_form, void* stream) {
+  MP_CHECK(x16 && x8 && W16 && W8 && y, MP_ERR_ARG, "mp_linear_fwd_f16f8_ex: null argument");
+  MP_CHECK(epilogue >= 0 && epilogue <= 2 && out_form >= 0 && out_form <= 2, MP_ERR_ARG, "mp_linear_fwd_f16f8_ex: epilogue %d, out_form %d", epilogue,
+           out_form);
+  MP_CHECK(mask == nullptr || ((mask_mode == 1 || mask_mode == 2) && T > 0 && J > 0 && M % (T * J) == 0), MP_ERR_ARG,
+           "mp_linear_fwd_f16f8_ex: a DropPath mask needs mask_mode 1 or 2 and M a multiple of T*J");
+  MP_CHECK(epilogue != 2 || (r_in && y != r_in), MP_ERR_ARG, "mp_linear_fwd_f16f8_ex: the residual epilogue needs r_in, not aliased with y");
+  GemmB16Args g = {};
+  g.A = x16; g.A_lo = x8; g.lda = K; g.B = W16; g.B_lo = W8; g.ldb = K; g.C = y; g.C_lo = y_lo; g.ldc = N; g.M = M; g.N = N; g.K = K; g.bias = b;
+  g.Z = z; g.R = r_in; g.rstats = rstats; g.rgamma = rgamma; g.rbeta = rbeta; g.mask = mask; g.mask_mode = mask ? mask_mode : 0; g.T = T; g.J = J;
+  g.rscale = rscale; g.out_f16f8 = out_form == 2 ? 1 : 0;
+  const int epi = epilogue == 0 ? EPI_BIAS : (epilogue == 1 ? EPI_BIAS_GELU : EPI_BIAS_RESID);
+  return gemm_f16f8(g, out_form == 0 ? 1 : 0, epi, (hipStream_t)stream);
+}
+int mp_layernorm_fwd_ex(const float* x, int M, int C, const float* g1, const float* b1, float eps1, const float* pos, int T, int J, float* x1,
+                        float* stats1, const float* g2, const float* b2, float eps2, void* y2, void* y2_lo, void* y2_b16, float* stats2, int out_mode,
+                        void* stream) {
+  MP_CHECK(x && M > 0 && out_mode >= 0 && out_mode <= 3, MP_ERR_ARG, "mp_layernorm_fwd_ex: bad argument");
+  MP_CHECK(!g1 || (b1 && stats1 && (!pos || (T > 0 && J > 0))), MP_ERR_ARG, "mp_layernorm_fwd_ex: stage 1 needs b1, stats1 (and T, J with pos)");
+  MP_CHECK(!g2 || (b2 && y2 && stats2), MP_ERR_ARG, "mp_layernorm_fwd_ex: stage 2 needs b2, y2 and stats2");
+  MP_CHECK(!y2_b16 || out_mode == 3, MP_ERR_ARG, "mp_layernorm_fwd_ex: the bf16 copy belongs to out mode 3");
+  LnFwdArgs a = {};
+  a.x = x; a.M = M; a.C = C;
+  a.g1 = g1; a.b1 = b1; a.eps1 = eps1; a.pos = pos; a.T = T; a.J = J; a.x1 = x1; a.stats1 = stats1;
+  a.g2 = g2; a.b2 = b2; a.eps2 = eps2; a.y2 = y2; a.y2_lo = y2_lo; a.y2_b16 = y2_b16; a.stats2 = stats2;
+  return ln_fwd(a, out_mode, (hipStream_t)stream);
+}
+int mp_attention_fwd_bf16x3_ex(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, float* scratch, int temporal,
+                               int B, int T, int J, int C, int H, int out_form, void* stream) {
+  MP_CHECK(qkv_hi && qkv_lo && out_hi && out_lo && (!temporal || lse) && (out_form == 0 || out_form == 1), MP_ERR_ARG,
+           "mp_attention_fwd_bf16x3_ex: bad argument");
+  return temporal ? attn_temporal_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, lse, scratch, B, T, J, C, H,
+                                         (hipStream_t)stream, out_form)
+                  : attn_spatial_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, scratch, B, T, J, C, H,
+                                        (hipStream_t)stream, out_form);
+}
+int mp_attention_bwd_bf16_ex(const void* qkv, const void* out, const void* d_out, const float* lse, float* delta, void* d_qkv, int temporal, int B,
+                             int T, int J, int C, int H, int out_f16, void* stream) {
+  MP_CHECK(qkv && d_out && d_qkv && (!temporal || (out && lse && delta)), MP_ERR_ARG, "mp_attention_bwd_bf16_ex: null pointer");
+  MP_CHECK(!out_f16 || temporal, MP_ERR_ARG, "mp_attention_bwd_bf16_ex: only the temporal backward reads O");
+  return temporal ? attn_temporal_bwd(qkv, out, d_out, lse, delta, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream, out_f16)
+                  : attn_spatial_bwd(qkv, d_out, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream);
+}
+int mp_linear_bwd_f16(const void* dy, const void* x, const void* W, void* dx, const void* z, const float* gout, uint32_t* gsat, float* dW, float* db,
+                      int M, int N, int K, int f16, int x_f16, const float* oscale, float* slab, int64_t slab_floats, void* stream) {
+  MP_CHECK(dy && (dx || dW), MP_ERR_ARG, "mp_linear_bwd_f16: nothing to compute");
+  MP_CHECK(!f16 || !x_f16, MP_ERR_ARG, "mp_linear_bwd_f16: f16 and x_f16 are exclusive");
+  if (dx) {
+    MP_CHECK(W, MP_ERR_ARG, "mp_linear_bwd_f16: dgrad without W");
+    GemmB16Args g = {};
+    g.A = dy; g.lda = N; g.B = W; g.ldb = K; g.C = dx; g.ldc = K; g.M = M; g.N = K; g.K = N; g.Z = const_cast<void*>(z);
+    g.f16 = f16; g.gout = gout; g.gsat = gout != nullptr ? gsat : nullptr;
+    int rc = gemm_bf16(g, 0, 0, 1, 0, z ? EPI_DGELU : EPI_BIAS, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  if (dW) {
+    MP_CHECK(x && slab && (!f16 || oscale), MP_ERR_ARG, "mp_linear_bwd_f16: weight gradient without x / slab (or oscale with f16)");
+    return wgrad_bf16(dy, 0, N, (const bf16*)x, K, M, N, K, dW, db, slab, (long)slab_floats, (hipStream_t)stream, f16, oscale, x_f16);
+  }
+  return MP_OK;
+}
+
 static int heads_pick(int impl, int K, int O, int C, const char* who, bool* mfma) {
   MP_CHECK(impl >= 0 && impl <= 2, MP_ERR_ARG, "%s: impl %d", who, impl);
   MP_CHECK(K >= 1 && K <= 8 && O >= 1, MP_ERR_ARG, "%s: K=%d O=%d unsupported", who, K, O);

@@ -97,6 +97,10 @@ __device__ __forceinline__ void st4(bf16* p, float4 v, long) { st4(p, v); }
 // (groups of four so that a thread holding four consecutive channels writes ONE 8-byte store and a wave whole 128-byte lines; the matrix
 // instruction only needs both operands to use the same byte order).  `f16f8` tags a pointer to the fp16 plane.  Values are clamped to the
 // e4m3 range (+-448) ahead of the conversion.
+// Non-finite values (torch's policy for float8_e4m3fn: NaN stays NaN, everything else saturates at +-448): a NaN v gives an fp16 NaN and NaN
+// in both correction bytes; v = +-inf gives +-inf in the fp16 plane, a NaN correction (v - hi is NaN) and +-448 as e4m3(hi) (weight form:
+// e4m3(16 hi) = +-448, the other byte NaN).  The sign and payload of a NaN are not part of the format (e4m3 NaN is 0x7f or 0xff).
+// tests/test_gpu_f16f8_kernels.py pins this for the splitter and the epilogue packers against the host construction.
 struct f16f8 { unsigned short v; };
 // GEMM epilogue form: p = the element in the fp16 plane, lo_off = distance to the correction plane in 2-byte elements (both planes have 2 bytes per element)
 __device__ __forceinline__ void st4_f16f8(f16f8* hi16, char* corr8, float4 v, bool weight);
@@ -131,9 +135,10 @@ __device__ __forceinline__ uint2 sat_f16x4(float a, float b, float c, float d, u
 __device__ __forceinline__ void st4_f16(void* p, float4 v, float s, unsigned* __restrict__ cnt) {
   *reinterpret_cast<uint2*>(p) = sat_f16x4(v.x * s, v.y * s, v.z * s, v.w * s, cnt);
 }
+// the +-448 clamp ahead of an e4m3 conversion, keeping a NaN a NaN (|NaN| > 448 is false); v_med3_f32 does not promise that for a NaN operand
+__device__ __forceinline__ float clamp448(float a) { return fabsf(a) > 448.f ? copysignf(448.f, a) : a; }
 __device__ __forceinline__ unsigned pack_e4m3x4(float a, float b, float c, float d) {
-  a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f); b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
-  c = __builtin_amdgcn_fmed3f(c, -448.f, 448.f); d = __builtin_amdgcn_fmed3f(d, -448.f, 448.f);
+  a = clamp448(a); b = clamp448(b); c = clamp448(c); d = clamp448(d);
   int r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);       // bytes 0, 1
   r = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);            // bytes 2, 3
   return (unsigned)r;
@@ -143,7 +148,9 @@ __device__ __forceinline__ unsigned pack_e4m3x4(float a, float b, float c, float
 // the same in registers, activation form: h16 = the four fp16 values, c8 = their 8 correction bytes.  20 VALU instructions on the common path
 // (round 6; 30 before): the pairs go through v_cvt_pk_f16_f32, the 2^11 on the lo parts is the scale operand of v_cvt_scalef32_pk_fp8_f32 (it divides by
 // 2^floor(log2 s): tools/probes/cvt_scale.hip), and the +-448 clamps - both fp8 conversions return NaN (0x7f) beyond that, neither saturates - are only
-// taken by lanes that hold a value above 448 (|2^11 lo| <= |v|, so nothing can overflow below it).  Same bytes as the clamped form for every input.
+// taken by lanes that hold a value above 448 (|2^11 lo| <= |v|, so nothing can overflow below it).  Same bytes as the clamped form for every finite
+// input.  A NaN next to finite values <= 448 takes the fast path (fmaxf drops it): both conversions turn the NaN (fp16 NaN hi, NaN lo) into an
+// e4m3 NaN there, as the clamped form does - the NaN policy above, pinned for both branches by the packer sweep of the f16f8 tests.
 __device__ __forceinline__ void pack4_f16f8(float4 v, uint2& h16, uint2& c8) {
   typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
   typedef float f2_t __attribute__((ext_vector_type(2)));
@@ -155,7 +162,7 @@ __device__ __forceinline__ void pack4_f16f8(float4 v, uint2& h16, uint2& c8) {
   const float4 hf = make_float4((float)ha[0], (float)ha[1], (float)hb[0], (float)hb[1]);
   const float4 lo = make_float4(v.x - hf.x, v.y - hf.y, v.z - hf.z, v.w - hf.w);
   const float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-  if (__builtin_expect(!(m <= 448.f), 0)) {      // (also NaN / inf inputs: the clamped conversions below)
+  if (__builtin_expect(!(m <= 448.f), 0)) {      // (also inf inputs, and a NaN in a group with an inf or a value above 448: the clamped conversions below)
     c8 = make_uint2(pack_e4m3x4(lo.x * 2048.f, lo.y * 2048.f, lo.z * 2048.f, lo.w * 2048.f), pack_e4m3x4(hf.x, hf.y, hf.z, hf.w));
   } else {
     s2_t r = {0, 0};

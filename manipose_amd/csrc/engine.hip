@@ -729,10 +729,8 @@ static int backbone_bwd_impl(mp_model* m, Module& md, const float* fp, float* fg
       AttnGradF16Scope f16_out(md.f8g ? m->gsc : nullptr);      // f8g: dqkv leaves as scaled fp16 (its two consumers below run on fp16 operands)
       if (spatial) RUN(PC_ATTN, 10.0 * B * T * N * N * C, attn_spatial_bwd(w.qkv, m->tmpC, m->tmp3C, half, B, T, N, C, H, st));
       else {
-        attn_out_f16_override(md.f8a ? 1 : 0);      // f8a: O exists as an fp16 plane
         ProfScope ps__(m, st, PC_ATTN, 10.0 * B * N * (double)T * T * C);
-        const int rc__ = attn_temporal_bwd(w.qkv, w.ao, m->tmpC, w.lse, m->delta, m->tmp3C, half, B, T, N, C, H, st);
-        attn_out_f16_override(0);
+        const int rc__ = attn_temporal_bwd(w.qkv, w.ao, m->tmpC, w.lse, m->delta, m->tmp3C, half, B, T, N, C, H, st, md.f8a ? 1 : 0);      // f8a: O exists as an fp16 plane
         if (rc__) return rc__;
       }
     }

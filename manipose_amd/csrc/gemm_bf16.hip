@@ -1650,6 +1650,7 @@ int gemm_f16f8(GemmB16Args g, int c_f32, int epi, hipStream_t st) {
            "gemm_f16f8: N must be a multiple of 256, K of 64 (M=%d N=%d K=%d)", g.M, g.N, g.K);
   MP_CHECK(g.A_lo && g.B_lo, MP_ERR_ARG, "gemm_f16f8: correction plane missing");
   MP_CHECK(256L * g.lda * 2 < (1L << 31) && 256L * g.ldb * 2 < (1L << 31), MP_ERR_ARG, "gemm_f16f8: leading dimension too large");
+  MP_CHECK(!g.out_f16f8 || (!c_f32 && epi == EPI_BIAS_GELU), MP_ERR_ARG, "gemm_f16f8: f16f8 output planes exist for the GELU epilogue only (c_f32=%d epi=%d)", c_f32, epi);
   g.k_per_split = g.K;
   int dev = 0, cus = 0;
   MP_HIP(hipGetDevice(&dev));

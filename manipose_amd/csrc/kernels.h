@@ -132,14 +132,14 @@ int droppath_masks(float* masks, const MaskDesc* descs, int ndesc, unsigned long
 
 // ---------------------------------------------------------------- attention.hip
 void attn_grad_f16_override(const float* gout);   // attention_mfma.hip: the MFMA backward launches issued next on this thread write dQ / dK / dV as fp16(*gout x value) (device address; null = bf16)
-void attn_out_f16_override(int on);                // attention_mfma.hip: the temporal MFMA backward launches issued next on this thread read `out` as an fp16 plane (f16f8 = 3)
 void attn_scale_override(float s);   // softmax scale of the attention launches issued next on this thread (0 = head_dim ** -0.5)
 // qkv: [M][3C] (q | k | v, head-major inside each), out: [M][C]; token layout m = (b*T + t)*J + j
 int attn_spatial_fwd(const void* qkv, void* out, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st);
 int attn_spatial_bwd(const void* qkv, const void* dout, void* dqkv, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st);
 int attn_temporal_fwd(const void* qkv, void* out, float* lse, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st);
+// out_f16: O is the fp16 plane of an f16f8 activation (mp_model_config::f16f8 = 3), read as fp16 by the MFMA backward; refused elsewhere
 int attn_temporal_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int is_bf16,
-                      int B, int T, int J, int C, int H, hipStream_t st);
+                      int B, int T, int J, int C, int H, hipStream_t st, int out_f16 = 0);
 // split-precision forward (planar hi/lo qkv and output, common.h).  scratch (4 M C floats) is only used for shapes the MFMA kernels
 // do not cover (the planes are joined to fp32, the fp32 kernels run, the result is split again); may be null otherwise.
 bool attn_x3_needs_scratch(int temporal, int T, int J, int C, int H);
