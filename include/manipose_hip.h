@@ -190,6 +190,25 @@ int mp_attention_bwd_bf16_ex(const void* qkv, const void* out, const void* d_out
  * f16 = 1: dy and x fp16, the sums multiplied by *oscale (device address); x_f16 = 1: dy bf16, x fp16 rounded to bf16; slab as mp_linear_bwd_bf16. */
 int mp_linear_bwd_f16(const void* dy, const void* x, const void* W, void* dx, const void* z, const float* gout, uint32_t* gsat, float* dW, float* db,
                       int M, int N, int K, int f16, int x_f16, const float* oscale, float* slab, int64_t slab_floats, void* stream);
+/* The LayerNorm backward forms of the engine's backbone backward.  mp_layernorm_bwd_ex: dx = rs * dskip + LN'(dy) (dskip may be NULL; dx may
+ * alias dy or dskip, as in the engine); dy fp32 or (dy_bf16) bf16.  dx_b16 (may be NULL): a 2-byte copy of dx times the DropPath multiplier
+ * of its row (mask, mask_mode 1 / 2 as in mp_linear_fwd_bf16x3_lnres; M a multiple of T*J), bf16, or with copy_f16 the saturating fp16 of
+ * dx * mask * gsc[0] (clamped at +-65504, non-finite as 0, counted in the uint32 words gsc[4] / gsc[5], which are added to).  gsc: the
+ * engine's 8-float gradient-scale block {S, 1/S, ..}; dy_scaled multiplies dy by gsc[1] on load.  dgamma / dbeta are ACCUMULATED into;
+ * scratch >= 1024 * 2 * C floats; C <= 1024.  param_stream (may be NULL): the reduction of the partial sums into dgamma / dbeta runs on that
+ * stream, ordered behind the row kernel by an event (the caller keeps scratch until it has run).
+ * mp_layernorm_bwd2_ex: the fused pair t = rs * dskip + LN1'(dy1) with x1 = LN0(x0; stats0, gamma0, beta0) recomputed in fp32, then
+ * dx = LN0'(t); dgamma1 / dbeta1 / dgamma0 / dbeta0 accumulated; C <= 512, scratch >= 1024 * 4 * C floats, dskip and beta0 required.
+ * mp_scale_rows_ex: out = mask(m) * g (the fp32-precision DropPath of a branch gradient), fp32 or (out_bf16) bf16.  Bad arguments: MP_ERR_ARG
+ * before any launch. */
+int mp_layernorm_bwd_ex(const void* dy, int dy_bf16, const float* x, const float* stats, const float* gamma, const float* dskip, float rs, float* dx,
+                        void* dx_b16, const float* mask, int mask_mode, int T, int J, float* gsc, int dy_scaled, int copy_f16, float* dgamma,
+                        float* dbeta, int M, int C, float* scratch, int64_t scratch_floats, void* param_stream, void* stream);
+int mp_layernorm_bwd2_ex(const void* dy1, int dy_bf16, const float* stats1, const float* gamma1, const float* dskip, float rs, const float* x0,
+                         const float* stats0, const float* gamma0, const float* beta0, float* dx, void* dx_b16, const float* mask, int mask_mode, int T,
+                         int J, float* gsc, int dy_scaled, int copy_f16, float* dgamma1, float* dbeta1, float* dgamma0, float* dbeta0, int M, int C,
+                         float* scratch, int64_t scratch_floats, void* param_stream, void* stream);
+int mp_scale_rows_ex(const float* g, const float* mask, int mask_mode, void* out, int out_bf16, int M, int C, int T, int J, void* stream);
 
 /* K output heads, head k = LayerNorm(C, eps 1e-5) -> Linear(C, O)  (MCLHead stack, rmcl_manifold_mix_ste.py:291-298; MixSTE.head,
  * mix_ste.py:123-126), all fp32.  Packed parameters: gamma, beta [K][C]; W [K][O][C]; b [K][O].  out [K][M][O]; stats [M][2] (mean, rstd

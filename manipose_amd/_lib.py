@@ -74,6 +74,9 @@ _SIGNATURES = {
     "mp_attention_fwd_bf16x3_ex": (i32, [vp] * 6 + [i32] * 7 + [vp]),
     "mp_attention_bwd_bf16_ex": (i32, [vp] * 6 + [i32] * 7 + [vp]),
     "mp_linear_bwd_f16": (i32, [vp] * 9 + [i32] * 5 + [vp, vp, i64, vp]),
+    "mp_layernorm_bwd_ex": (i32, [vp, i32, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, i64, vp, vp]),
+    "mp_layernorm_bwd2_ex": (i32, [vp, i32, vp, vp, vp, f32] + [vp] * 7 + [i32] * 3 + [vp, i32, i32] + [vp] * 4 + [i32, i32, vp, i64, vp, vp]),
+    "mp_scale_rows_ex": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "mp_model_create": (i32, [C.POINTER(ModelConfig), C.POINTER(vp)]),
     "mp_model_destroy": (None, [vp]),
     "mp_model_workspace_bytes": (i64, [vp]),

@@ -269,6 +269,63 @@ int mp_linear_bwd_f16(const void* dy, const void* x, const void* W, void* dx, co
   return MP_OK;
 }
 
+/* unit-test entry points of the LayerNorm backward forms the engine launches (include/manipose_hip.h): the same dispatchers with every argument
+ * engine.hip fills.  gsc is the engine's 8-float gradient-scale block (grad_scale): dy_scaled passes gsc + 1 (1 / S) as dy_scale, copy_f16 passes
+ * gsc (S, counters in gsc[4..5]) as b16_gs.  A non-null param_stream runs the parameter-gradient reduction there, behind an event this file owns
+ * (the engine's ev_heads). */
+static int ln_bwd_common(const char* who, const float* mask, int mask_mode, int M, int T, int J, void* dx_b16, const float* gsc, int dy_scaled,
+                         int copy_f16, hipEvent_t* ev, void* param_stream) {
+  MP_CHECK(mask == nullptr || mask_mode == 1 || mask_mode == 2, MP_ERR_ARG, "%s: a DropPath mask needs mask_mode 1 or 2 (got %d)", who, mask_mode);
+  MP_CHECK(mask == nullptr || (T > 0 && J > 0 && M % (T * J) == 0), MP_ERR_ARG, "%s: a DropPath mask needs M=%d a multiple of T*J (T=%d, J=%d)", who, M,
+           T, J);
+  MP_CHECK(!copy_f16 || dx_b16, MP_ERR_ARG, "%s: copy_f16 without dx_b16", who);
+  MP_CHECK((!dy_scaled && !copy_f16) || gsc, MP_ERR_ARG, "%s: dy_scaled / copy_f16 need the gsc block", who);
+  *ev = nullptr;
+  if (param_stream != nullptr) {
+    static hipEvent_t own = nullptr;
+    if (own == nullptr && hipEventCreateWithFlags(&own, hipEventDisableTiming) != hipSuccess) {
+      own = nullptr;
+      MP_CHECK(false, MP_ERR_HIP, "%s: could not create the parameter-stream event", who);
+    }
+    *ev = own;
+  }
+  return MP_OK;
+}
+int mp_layernorm_bwd_ex(const void* dy, int dy_bf16, const float* x, const float* stats, const float* gamma, const float* dskip, float rs, float* dx,
+                        void* dx_b16, const float* mask, int mask_mode, int T, int J, float* gsc, int dy_scaled, int copy_f16, float* dgamma,
+                        float* dbeta, int M, int C, float* scratch, int64_t scratch_floats, void* param_stream, void* stream) {
+  MP_CHECK(dy && x && stats && gamma && dx && dgamma && dbeta && scratch && M > 0, MP_ERR_ARG, "mp_layernorm_bwd_ex: null pointer");
+  MP_CHECK(C > 0 && C % 4 == 0 && C <= 1024, MP_ERR_ARG, "mp_layernorm_bwd_ex: C=%d unsupported", C);
+  MP_CHECK(scratch_floats >= 1024L * 2 * C, MP_ERR_ARG, "mp_layernorm_bwd_ex: scratch needs 1024 * 2 * C floats");
+  hipEvent_t ev = nullptr;
+  if (int rc = ln_bwd_common("mp_layernorm_bwd_ex", mask, mask_mode, M, T, J, dx_b16, gsc, dy_scaled, copy_f16, &ev, param_stream)) return rc;
+  return ln_bwd(dy, dy_bf16, x, stats, gamma, dskip, dx, dx_b16, mask, mask ? mask_mode : 0, T, J, dgamma, dbeta, M, C, scratch, (long)scratch_floats,
+                (hipStream_t)stream, (hipStream_t)param_stream, ev, rs, dy_scaled ? gsc + 1 : nullptr, copy_f16 ? gsc : nullptr);
+}
+int mp_layernorm_bwd2_ex(const void* dy1, int dy_bf16, const float* stats1, const float* gamma1, const float* dskip, float rs, const float* x0,
+                         const float* stats0, const float* gamma0, const float* beta0, float* dx, void* dx_b16, const float* mask, int mask_mode, int T,
+                         int J, float* gsc, int dy_scaled, int copy_f16, float* dgamma1, float* dbeta1, float* dgamma0, float* dbeta0, int M, int C,
+                         float* scratch, int64_t scratch_floats, void* param_stream, void* stream) {
+  MP_CHECK(dy1 && stats1 && gamma1 && x0 && stats0 && gamma0 && dx && dgamma1 && dbeta1 && dgamma0 && dbeta0 && scratch && M > 0, MP_ERR_ARG,
+           "mp_layernorm_bwd2_ex: null pointer");
+  MP_CHECK(beta0, MP_ERR_ARG, "mp_layernorm_bwd2_ex: x1 is recomputed from x0, beta0 is required");
+  MP_CHECK(dskip, MP_ERR_ARG, "mp_layernorm_bwd2_ex: the fused form always adds the skip gradient (dskip is required)");
+  MP_CHECK(C > 0 && C % 4 == 0 && C <= 512, MP_ERR_ARG, "mp_layernorm_bwd2_ex: C=%d unsupported", C);
+  MP_CHECK(scratch_floats >= 1024L * 4 * C, MP_ERR_ARG, "mp_layernorm_bwd2_ex: scratch needs 1024 * 4 * C floats");
+  hipEvent_t ev = nullptr;
+  if (int rc = ln_bwd_common("mp_layernorm_bwd2_ex", mask, mask_mode, M, T, J, dx_b16, gsc, dy_scaled, copy_f16, &ev, param_stream)) return rc;
+  return ln_bwd2(dy1, dy_bf16, nullptr, stats1, gamma1, dskip, x0, stats0, gamma0, beta0, dx, dx_b16, mask, mask ? mask_mode : 0, T, J, dgamma1, dbeta1,
+                 dgamma0, dbeta0, M, C, scratch, (long)scratch_floats, (hipStream_t)stream, (hipStream_t)param_stream, ev, rs,
+                 dy_scaled ? gsc + 1 : nullptr, copy_f16 ? gsc : nullptr);
+}
+int mp_scale_rows_ex(const float* g, const float* mask, int mask_mode, void* out, int out_bf16, int M, int C, int T, int J, void* stream) {
+  MP_CHECK(g && mask && out && M > 0, MP_ERR_ARG, "mp_scale_rows_ex: null pointer");
+  MP_CHECK(C > 0 && C % 4 == 0, MP_ERR_ARG, "mp_scale_rows_ex: C=%d unsupported", C);
+  MP_CHECK(mask_mode == 1 || mask_mode == 2, MP_ERR_ARG, "mp_scale_rows_ex: mask_mode %d (1 or 2)", mask_mode);
+  MP_CHECK(T > 0 && J > 0 && M % (T * J) == 0, MP_ERR_ARG, "mp_scale_rows_ex: M=%d is not a multiple of T*J (T=%d, J=%d)", M, T, J);
+  return scale_rows(g, mask, mask_mode, out, out_bf16, M, C, T, J, (hipStream_t)stream);
+}
+
 static int heads_pick(int impl, int K, int O, int C, const char* who, bool* mfma) {
   MP_CHECK(impl >= 0 && impl <= 2, MP_ERR_ARG, "%s: impl %d", who, impl);
   MP_CHECK(K >= 1 && K <= 8 && O >= 1, MP_ERR_ARG, "%s: K=%d O=%d unsupported", who, K, O);

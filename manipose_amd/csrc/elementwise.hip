@@ -171,7 +171,9 @@ constexpr int LNB_GRID = LNB_GRID_N;
 // LayerNorm class 27.65 / 27.73 -> 27.57 / 27.58 ms with every kernel on one queue, profiles/r04_probes/ab_step3.log.)   // 4 workgroups (16 waves) per CU
 
 // V float4 per lane (C <= 256 V); R rows in flight per wave: every load of the R rows (x, dy, skip gradient, statistics, DropPath
-// scale) is issued before the first row is reduced.
+// scale) is issued before the first row is reduced.  The engine's post-norm call passes dx == dy (and the others dx == dskip): a row is
+// read by one wave, and every store of it depends on the wave sums of all its loads, so no load can follow a store of the same row
+// (tests/test_gpu_layernorm_backward.py checks every aliased form bit for bit against a non-aliased call).
 template <typename TDY, int V, int R>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy, const float* __restrict__ x,
                                                       const float* __restrict__ stats, const float* __restrict__ gamma,

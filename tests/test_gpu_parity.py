@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import manipose_ref as orc
-from helpers import fixture_masks, fixture_state, load_fixture
+from helpers import droppath_mask_names, fixture_masks, fixture_state, load_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -1878,6 +1878,68 @@ def test_bf16x3_full_size_model_meets_the_parity_bound(lib, f16f8):
     seg = (poses[..., 1:, :] - poses[..., par, :]).norm(dim=-1)
     lens = model._engine.peek(1).view(1, 1, 1, 16).abs()
     close(seg, lens.expand_as(seg), rtol=1e-4, atol=2e-6)
+
+
+_MASKED_FULL_SIZE = {}
+
+
+def _masked_full_size_reference(layout):
+    """The masked full-size case (FULL_CFG, B = 2, DropPath 0.1 with injected masks) and its CPU oracle forward, loss and gradients - computed
+    once, shared by the precisions.  Masks: keep 0.9 (values 0 and 1/0.9), every branch drops a sample in each window, window 1 keeps the
+    sample window 0 drops and drops another one."""
+    if not _MASKED_FULL_SIZE:
+        cfg = orc.FULL_CFG
+        st_ = orc.make_state(cfg, seed=3)
+        X, y = orc.synthetic_batch(2, 243, seed=42)
+        gen = torch.Generator().manual_seed(17)
+        masks = {}
+        for name, _, cnt, keep in layout:
+            if keep >= 1.0:
+                continue
+            m = (torch.rand(cnt, generator=gen) < 0.9).float() / 0.9
+            half = cnt // 2
+            m[1], m[half + 1], m[half + 3] = 0.0, 1.0 / 0.9, 0.0
+            masks[name] = m
+        assert sorted(masks) == sorted(droppath_mask_names(cfg, 0.1)), sorted(masks)
+        req = {k: v.clone().requires_grad_(True) for k, v in st_.items()}
+        o_poses, o_scores = orc.rmcl_manifold_forward(X, req, orc.oracle_cfg(cfg), masks=masks)
+        o_total, _ = orc.rmcl_training_loss(o_poses, o_scores, y)
+        o_total.backward()
+        _MASKED_FULL_SIZE.update(st=st_, X=X, y=y, masks=masks, poses=o_poses.detach(), scores=o_scores.detach(), total=o_total.item(),
+                                 grads={k: v.grad for k, v in req.items()})
+    return _MASKED_FULL_SIZE
+
+
+@pytest.mark.parametrize("precision,f16f8", [("fp32", 0), ("bf16x3", 0), ("bf16x3", 3)])
+def test_full_size_model_with_droppath_masks_vs_oracle(lib, precision, f16f8):
+    """The benchmarked training form: the full-size model (FULL_CFG) at B = 2 in train mode with DropPath 0.1 and injected masks in every
+    branch of both nets, against the CPU oracle with the same masks - in fp32 and in the split precision with f16f8 = 0 and 3 (the timed
+    form, whose wide blocks run the f16f8 kernels).  The bounds of the unmasked full-size tests."""
+    from manipose_amd import RMCLManifoldMixSTE, h36m_skeleton
+    from manipose_amd.metrics import mpjpe_error, rmcl_training_loss
+    model = RMCLManifoldMixSTE(h36m_skeleton(), drop_path_rate=0.1)
+    model.load_state_dict(orc.make_state(orc.FULL_CFG, seed=3), strict=True)
+    model.precision, model.f16f8 = precision, f16f8
+    model.max_batch_hint = 2
+    model = model.cuda().train()
+    model._ensure_engine(2, torch.device("cuda"))
+    ref = _masked_full_size_reference(model._engine.mask_layout(2))
+    model.set_droppath_masks({k: v.cuda() for k, v in ref["masks"].items()})
+    poses, scores = model(ref["X"].cuda())
+    total, _ = rmcl_training_loss(poses, scores, ref["y"].cuda())
+    total.backward()
+    mp = mpjpe_error(poses, ref["poses"].cuda(), "average").item()
+    wc, wck, mean, wm, wmk = _grad_report(model.named_parameters(), ref["grads"])
+    print(f"\n[masked full size] {precision} f16f8={f16f8}: MPJPE vs oracle {mp * 1e3:.5f} mm, loss {total.item():.6f} vs {ref['total']:.6f}, gradient "
+          f"cosine mean {mean:.6f} worst {wc:.6f} ({wck}), worst max-norm error {wm:.2e} ({wmk})")
+    assert mp <= MPJPE_TOL_M
+    close(scores, ref["scores"], rtol=1e-3, atol=1e-5)
+    assert abs(total.item() - ref["total"]) <= 1e-3 * abs(ref["total"])
+    if precision == "fp32":
+        _check_grads(model, {"g::" + k: v.numpy() for k, v in ref["grads"].items()})
+    else:
+        assert wc > 0.9999 and mean > 0.99999, (wc, wck, mean)
+        assert wm < 2e-2, (wm, wmk)
 
 
 def test_bf16x3_training_step_and_droppath(lib):
