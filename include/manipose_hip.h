@@ -153,7 +153,8 @@ int mp_linear_fwd_bf16x3_lnres(const void* x_hi, const void* x_lo, const void* W
  *   activation row:  4 x e4m3(2^11 (v - hi))  |  4 x e4m3(hi)
  *   weight row:      4 x e4m3(2^4 hi)         |  4 x e4m3(2^15 (v - hi))
  * so that the fp8 dot product of an activation row and a weight row is 2^15 (x_lo w_hi + x_hi w_lo).  y = x W^T + b in fp32.
- * N must be a multiple of 256, K of 64 (>= 128).  The engine runs its qkv and fc1 forward GEMMs in this form with mp_model_config::f16f8 = 1,
+ * N must be a multiple of 256, K of 64 (>= 128).  Two kernels serve it with the same bits: the persistent 256 x 256 one and a tiled 128 x 128
+ * one (two workgroups per CU) that mp_gemm_plan picks for the token counts of a few windows.  The engine runs its qkv and fc1 forward GEMMs in this form with mp_model_config::f16f8 = 1,
  * the fc2 GEMM too with f16f8 = 2, and all four Linear layers of a block with f16f8 = 3 (the default of the training configuration). */
 /* fp32 -> the two planes of that format for a matrix whose rows are multiples of 64 elements long (n = rows * K elements; hi16: n fp16
  * values, corr8: 2 n bytes); weight != 0 selects the weight form of the correction rows. */
@@ -443,11 +444,24 @@ int mp_procrustes_errors(const float* pred, const float* gt, const uint8_t* mask
 /* test / tuning hooks (no reference counterpart; process-wide, they select between kernels that the GPU tests hold to the same results):
  * "gemm_small_tile" (1 = 128x128 GEMM tiles everywhere), "gemm_persist_min_tiles" (output-tile count from which the persistent GEMM
  * kernels are used; 0 = default), "gemm_persist_mode" (0 tiled kernels only, 1 = default: persistent kernel where it applies),
- * "gemm_persist_wgs" (workgroups = CUs the persistent GEMMs occupy; 0 = default: all), "attn_two_phase" (0 = the one-strip-at-a-time
+ * "gemm_persist_wgs" (workgroups = CUs the persistent GEMMs occupy; 0 = default: all), "gemm_tile" (0 = default: mp_gemm_plan's planner
+ * chooses the tile; 128 / 256 = that tile wherever the operand form has it - "gemm_small_tile" never applied to f16f8, this does; any other
+ * value: MP_ERR_ARG), "attn_two_phase" (0 = the one-strip-at-a-time
  * split-precision temporal attention forward for every shape; 1 = default: the two-phase kernel for head dim 64 and T > 128),
  * "heads_mfma" (0 = row kernels for the output heads, 1 = default: matrix cores wherever covered, 2 = only from 16 outputs up).
  * Everything that changes a model's arithmetic or stream use is a field of mp_model_config. */
 int mp_set_option(const char* name, int value);
+/* Which GEMM kernel serves a Linear of M tokens, N outputs and K inputs (the planner every launch goes through; host-only, no HIP call when
+ * cus > 0; cus == 0 asks the current device for its CU count).  form: 0 bf16, 1 bf16x3, 8 f16f8, 16 fp16; epilogue: 0 bias, 1 GELU, 2 residual,
+ * 3 gelu'-multiplying dgrad, 4 weight-gradient slabs (the layouts are the engine's for that epilogue).
+ * out = {tile (128 or 256), persistent (0 / 1), workgroups, tiles = ceil(M / tile) * ceil(N / tile)}.  The 256 x 256 tile runs one 8-wave workgroup
+ * per CU, the 128 x 128 tile two 4-wave ones: the planner compares ceil(tiles256 / cus) rounds of cost 4 with ceil(tiles128 / (2 cus)) rounds of
+ * the measured cost c of a small tile and takes the small tile only where the large one leaves CUs idle - the batch sizes
+ * of a few windows.  It honours the "gemm_*" options.  A shape no kernel of that form serves (f16f8: N % 256, K % 64, K >= 128): MP_ERR_ARG. */
+int mp_gemm_plan(int M, int N, int K, int form, int epilogue, int cus, int out[4]);
+/* Process-wide counts of GEMM launches since the last reset, by kernel family: out = {persistent 256 x 256, tiled 256 x 256, tiled 128 x 128}.
+ * Plain host counters (no device work); reset != 0 zeroes them after reading.  Tests use it to prove which kernel ran. */
+int mp_gemm_launch_counts(int64_t out[3], int reset);
 
 #ifdef __cplusplus
 }

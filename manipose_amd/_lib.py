@@ -111,6 +111,8 @@ _SIGNATURES = {
     "mp_bone_length_table": (i32, [vp, C.POINTER(i64), vp, C.POINTER(i64), i32, i32, i32, vp, vp]),
     "mp_pose_metrics": (i32, [vp, C.POINTER(i64), vp, C.POINTER(i64), vp, i32, i32, i32, f32, f32, f32, f32, i32, i32, vp, vp, vp, i64, vp]),
     "mp_set_option": (i32, [C.c_char_p, i32]),
+    "mp_gemm_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
+    "mp_gemm_launch_counts": (i32, [C.POINTER(i64), i32]),
     "mp_prof_enable": (i32, [vp, i32]),
     "mp_prof_kinds": (i32, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mp_prof_collect": (i32, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

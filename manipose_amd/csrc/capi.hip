@@ -407,12 +407,40 @@ int mp_pose_metrics(const float* pred, const int64_t* pred_strides, const float*
 
 /* test / tuning hooks (include/manipose_hip.h): process-wide selectors between kernels that are tested to agree; everything that changes a
  * model's arithmetic or its stream use is a field of mp_model_config */
+int mp_gemm_plan(int M, int N, int K, int form, int epilogue, int cus, int out[4]) {
+  MP_CHECK(out, MP_ERR_ARG, "mp_gemm_plan: null out");
+  MP_CHECK(M > 0 && N > 0 && K > 0 && cus >= 0, MP_ERR_ARG, "mp_gemm_plan: bad shape M=%d N=%d K=%d cus=%d", M, N, K, cus);
+  MP_CHECK(form == GEMM_FORM_BF16 || form == GEMM_FORM_BF16X3 || form == GEMM_FORM_F16F8 || form == GEMM_FORM_F16, MP_ERR_ARG,
+           "mp_gemm_plan: form %d (0 bf16, 1 bf16x3, 8 f16f8, 16 fp16)", form);
+  MP_CHECK(epilogue >= EPI_BIAS && epilogue <= EPI_SLAB, MP_ERR_ARG, "mp_gemm_plan: epilogue %d", epilogue);
+  if (cus == 0) cus = gemm_device_cus();
+  MP_CHECK(cus > 0, MP_ERR_HIP, "mp_gemm_plan: no device to ask for its CU count");
+  // the layouts the engine uses for that epilogue: forward "N","N" (lda = ldb = K); gelu'-multiplying dgrad "N","T" (ldb = N); weight
+  // gradient "T","T" (one split)
+  const bool wgrad = epilogue == EPI_SLAB, dgrad = epilogue == EPI_DGELU;
+  const GemmPlanIn in = {M, N, K, form, epilogue, wgrad ? 1 : 0, (wgrad || dgrad) ? 1 : 0, 1, wgrad ? (long)M : (long)K, (wgrad || dgrad) ? (long)N : (long)K, 1.0f, cus};
+  const GemmPlan pl = gemm_plan(in);
+  MP_CHECK(pl.tile != 0, MP_ERR_ARG, "mp_gemm_plan: no kernel of form %d serves M=%d N=%d K=%d with epilogue %d", form, M, N, K, epilogue);
+  out[0] = pl.tile; out[1] = pl.persistent; out[2] = pl.workgroups; out[3] = pl.tiles;
+  return MP_OK;
+}
+int mp_gemm_launch_counts(int64_t out[3], int reset) {
+  MP_CHECK(out, MP_ERR_ARG, "mp_gemm_launch_counts: null out");
+  long long c[3];
+  gemm_launch_counts(c, reset);
+  for (int i = 0; i < 3; ++i) out[i] = (int64_t)c[i];
+  return MP_OK;
+}
 int mp_set_option(const char* name, int value) {
   MP_CHECK(name, MP_ERR_ARG, "mp_set_option: null name");
   if (!strcmp(name, "gemm_small_tile")) { gemm_bf16_force_small_tile(value != 0); return MP_OK; }
   if (!strcmp(name, "gemm_persist_min_tiles")) { gemm_bf16_persist_min_tiles(value); return MP_OK; }
   if (!strcmp(name, "gemm_persist_mode")) { gemm_bf16_persist_mode(value); return MP_OK; }
   if (!strcmp(name, "gemm_persist_wgs")) { gemm_bf16_persist_wgs(value); return MP_OK; }
+  if (!strcmp(name, "gemm_tile")) {
+    MP_CHECK(gemm_bf16_tile(value) == MP_OK, MP_ERR_ARG, "mp_set_option: gemm_tile is 0 (planner), 128 or 256, not %d", value);
+    return MP_OK;
+  }
   if (!strcmp(name, "attn_two_phase")) { attn_two_phase(value); return MP_OK; }
   if (!strcmp(name, "heads_mfma")) { heads_mfma_mode(value); return MP_OK; }
   MP_CHECK(false, MP_ERR_ARG, "mp_set_option: unknown option '%s' (side_streams / f16f8_inputs became mp_model_config::streams / f16f8 in ABI v7)", name);

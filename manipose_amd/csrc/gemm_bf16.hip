@@ -14,6 +14,7 @@
 //       exist in HBM.
 // fp32 operands (the fp32 residual-gradient stream) are converted to bf16 while staging.
 #include <stdlib.h>
+#include <atomic>
 #include "common.h"
 #include "kernels.h"
 
@@ -408,19 +409,21 @@ __device__ __forceinline__ f32x4 mfma_f8(const i32x8_t& a, const i32x8_t& b, con
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f16x8_t half_lo(const i32x8_t& v) { return __builtin_bit_cast(f16x8_t, __builtin_shufflevector(v, v, 0, 1, 2, 3)); }
 __device__ __forceinline__ f16x8_t half_hi(const i32x8_t& v) { return __builtin_bit_cast(f16x8_t, __builtin_shufflevector(v, v, 4, 5, 6, 7)); }
-__device__ __forceinline__ void mma_stage_mix(const char* __restrict__ As, const char* __restrict__ Bs, f32x4 (&acc)[8][4], int wr, int wc, int lane,
+// NI = 16-row A fragments of the wave tile: 8 (128 x 64, the 256-wide tile) or 4 (64 x 64, the 128-wide tile); the LDS image has 128-byte rows in both.
+template <int NI = 8>
+__device__ __forceinline__ void mma_stage_mix(const char* __restrict__ As, const char* __restrict__ Bs, f32x4 (&acc)[NI][4], int wr, int wc, int lane,
                                               bool f8) {
   i32x8_t b[4], a_cur, a_nxt;
 #pragma unroll
   for (int j = 0; j < 4; ++j) b[j] = read_frag8(Bs, wc * 64 + j * 16, lane);
-  a_cur = read_frag8(As, wr * 128, lane);
+  a_cur = read_frag8(As, wr * (16 * NI), lane);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < NI; ++i) {
     __builtin_amdgcn_sched_barrier(0);
     if (f8) acc[i][0] = mfma_f8(b[0], a_cur, acc[i][0]);
     else acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(half_lo(b[0]), half_lo(a_cur), acc[i][0], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
-    if (i + 1 < 8) a_nxt = read_frag8(As, wr * 128 + (i + 1) * 16, lane);
+    if (i + 1 < NI) a_nxt = read_frag8(As, wr * (16 * NI) + (i + 1) * 16, lane);
     __builtin_amdgcn_sched_barrier(0);
     if (f8) {
 #pragma unroll
@@ -432,7 +435,7 @@ __device__ __forceinline__ void mma_stage_mix(const char* __restrict__ As, const
       for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(half_hi(b[j]), half_hi(a_cur), acc[i][j], 0, 0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (i + 1 < 8) a_cur = a_nxt;
+    if (i + 1 < NI) a_cur = a_nxt;
   }
 }
 
@@ -684,6 +687,10 @@ __device__ __forceinline__ void uneven_dma(char* __restrict__ S, const char* __r
 // SPLIT = 1 (split precision, common.h): A and B are the hi planes of planar operands; every 64-wide k-tile is multiplied three
 // times - (A_lo, B_hi), (A_hi, B_hi), (A_hi, B_lo) - into the same fp32 accumulators: three main-loop steps per k-tile over four
 // fetched operand tiles (see the loop).
+// (defined with the persistent kernel below; the tiled f16f8 kernel runs it too)
+template <typename TC, int EPI, bool FULL, bool F16G = false, int NI = 8>
+__device__ __forceinline__ void persist_epilogue(const GemmB16Args& g, const f32x4 (&acc)[NI][4], float* __restrict__ img, int row0, int col,
+                                                 const float4& bias4, TC* __restrict__ C, typename ZType<TC>::type* __restrict__ Z, int l15, int gq);
 #ifndef WG_P0
 #define WG_P0 1      // measured on the four weight-gradient shapes of a block: 4 (even) 1485 us, 2: 1470, 1: 1444, 0: 1680; 6: 1535
 #endif
@@ -728,11 +735,48 @@ __global__ __launch_bounds__(BT * 2) void gemm_bf16_glds_kernel(GemmB16Args g) {
   // neighbouring tiles issue their two operand loads in opposite order: workgroups that share a panel then ask for it at different
   // moments of the k-tile instead of all at once (measured on the weight-gradient shapes: 3-18 % fewer fabric reads, same isolated time)
   const bool b_first = (tm + tn) & 1;
+  if constexpr (SPLIT != 8) {
   if (b_first) glds_tile<TRB, BT, NW>(smem + OPB, B, g.ldb, n0, kbeg, g.N, kend, lane, wave);
   glds_tile<TRA, BT, NW>(smem, (SPLIT & 1) ? reinterpret_cast<const bf16*>(g.A_lo) : A, g.lda, m0, kbeg, g.M, kend, lane, wave);
   if (!b_first) glds_tile<TRB, BT, NW>(smem + OPB, B, g.ldb, n0, kbeg, g.N, kend, lane, wave);
+  }
   int stage = 0;
-  if constexpr (SPLIT & 1) {
+  if constexpr (SPLIT == 8) {
+    // "f16f8" (the persistent kernel's SPLIT == 8 loop on a 128 x 128 tile, four waves of 64 x 64, two workgroups per CU): 2 nk steps over the two
+    // stages - even steps multiply the fp16 planes of k-tile v / 2 (two fp16 k-steps per block), odd steps its 8-bit correction planes (one 128-deep
+    // fp8 MFMA per block) - so every output element sees the persistent kernel's sequence of accumulations and the two tiles agree bit for bit.
+    // The launcher guarantees N % 256 == 0, K % 64 == 0, K >= 128 and one split; rows past M are clamped on load and never stored.  The operand DMA
+    // is the persistent kernel's: per-lane 32-bit offsets computed once, a wave-uniform base per step and plane.
+    static_assert(BT == 128 && TRA == 0 && TRB == 0, "the tiled f16f8 loop exists for the 128-wide tile only");
+    const char* const Ab = reinterpret_cast<const char*>(A);
+    const char* const Bb = reinterpret_cast<const char*>(B);
+    const long a_lo = reinterpret_cast<const char*>(g.A_lo) - Ab, b_lo = reinterpret_cast<const char*>(g.B_lo) - Bb;
+    unsigned aoff[4], boff[4];
+    persist_offsets<0>(aoff, g.lda, m0, g.M, lane, wave);
+    persist_offsets<0>(boff, g.ldb, n0, g.N, lane, wave);
+    const char* pa = Ab + (long)m0 * g.lda * 2;              // fp16 plane of A, k-tile v / 2
+    const char* pb = Bb + (long)n0 * g.ldb * 2;
+    if (b_first) persist_dma(smem + OPB, pb, boff, wave);
+    persist_dma(smem, pa, aoff, wave);
+    if (!b_first) persist_dma(smem + OPB, pb, boff, wave);
+    const int nsteps = 2 * (g.K / GBK);
+    for (int v = 0; v < nsteps; ++v) {
+      __syncthreads();   // (vmcnt(0) + barrier): this step's planes have landed for every wave; nobody still reads the other stage
+      const int par = v & 1;
+      const char* As = smem + par * STAGE;
+      const char* Bs = As + OPB;
+      if (v + 1 < nsteps) {
+        char* nx = smem + (par ^ 1) * STAGE;
+        if (par) { pa += GBK * 2; pb += GBK * 2; }          // odd step: the fp16 planes of the next k-tile; even step: this k-tile's correction planes
+        const long ao = par ? 0 : a_lo, bo = par ? 0 : b_lo;
+        if (b_first) persist_dma(nx + OPB, pb + bo, boff, wave);
+        persist_dma(nx, pa + ao, aoff, wave);
+        if (!b_first) persist_dma(nx + OPB, pb + bo, boff, wave);
+      }
+      mma_stage_mix<MI>(As, Bs, acc, wr, wc, lane, par != 0);
+    }
+    (void)stage;
+  } else if constexpr (SPLIT & 1) {
     // Three steps per k-tile kt, each one mma_stage over 64 reduction indices, with FOUR operand tiles fetched (not six): the buffers are
     // A0 | B0 | A1 | B1 (the two stages of the plain kernel) and
     //   step 0 multiplies (A0 = A_lo[kt], B0 = B_hi[kt])   while A1 <- A_hi[kt] is fetched
@@ -818,6 +862,20 @@ __global__ __launch_bounds__(BT * 2) void gemm_bf16_glds_kernel(GemmB16Args g) {
   }
 
   if (MP_DBG(g, 4) && acc[0][0][0] != 12345.678f) return;
+  if constexpr (SPLIT == 8) {
+    // ---- epilogue of the f16f8 tile: the persistent kernel's own code (persist_epilogue), 16 rows per pass through a wave-private 4 KiB image in the
+    // (finished) operand stages - the same arithmetic per element, hence the same bits, for every output form ----
+    TC* const C8 = reinterpret_cast<TC*>(g.C);
+    typename ZType<TC>::type* const Z8 = reinterpret_cast<typename ZType<TC>::type*>(g.Z);
+    __syncthreads();                                   // every wave is done with the operand stages: reuse them
+    float* const img8 = reinterpret_cast<float*>(smem + wave * 4096);
+    const int e15 = lane & 15, eq = lane >> 4;
+    const int col8 = n0 + wc * 64 + 4 * e15;           // < N: N % 256 == 0
+    float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g.bias != nullptr) b4 = ld4(g.bias + col8);
+    if (m0 + BT <= g.M) persist_epilogue<TC, EPI, true, false, MI>(g, acc, img8, m0 + wr * 64, col8, b4, C8, Z8, e15, eq);
+    else persist_epilogue<TC, EPI, false, false, MI>(g, acc, img8, m0 + wr * 64, col8, b4, C8, Z8, e15, eq);
+  } else {
   // ---- epilogue through LDS: the accumulators (transposed-tile layout: lane = row, 4 consecutive columns per register
   // group) are written to a wave-private 64 x 64 fp32 image (16-byte chunks XOR-swizzled by the row) and read back row-major,
   // so bias / residual / pre-activation loads and the output stores are full 128/256-byte lines, 16 lanes per row. ----
@@ -901,6 +959,7 @@ __global__ __launch_bounds__(BT * 2) void gemm_bf16_glds_kernel(GemmB16Args g) {
       } else st4(C + o, v, lo_off);
     }
   }
+  }
 }
 
 // =================================================================================================================
@@ -920,8 +979,10 @@ __global__ __launch_bounds__(BT * 2) void gemm_bf16_glds_kernel(GemmB16Args g) {
 // F16G (gelu'-multiplying dgrad): dz leaves as saturating scaled fp16 (GemmB16Args::gout) - a template parameter, not a run-time branch: inlined 64 times,
 // the saturating store with its slow path and counters made this kernel 11 600 instructions (93 KB, more than the 64 KB instruction cache) and left
 // its matrix cores 29 % busy where the plain dgrad reaches 47 % (profiles/r04_bf16x3_B79_pmc_mfma_util.csv), although the default backward never takes it
-template <typename TC, int EPI, bool FULL, bool F16G = false>
-__device__ __forceinline__ void persist_epilogue(const GemmB16Args& g, const f32x4 (&acc)[8][4], float* __restrict__ img, int row0, int col,
+// NI = passes (16 rows each): 8 for the persistent kernel's 128 x 64 wave tile, 4 for the 64 x 64 wave tile of the tiled f16f8 kernel (SPLIT = 8,
+// BT = 128), which runs this same code so that both tiles round every element the same way.
+template <typename TC, int EPI, bool FULL, bool F16G, int NI>
+__device__ __forceinline__ void persist_epilogue(const GemmB16Args& g, const f32x4 (&acc)[NI][4], float* __restrict__ img, int row0, int col,
                                                  const float4& bias4, TC* __restrict__ C, typename ZType<TC>::type* __restrict__ Z, int l15, int gq) {
   constexpr bool LOADS = (EPI == EPI_BIAS_RESID || EPI == EPI_DGELU);
   const long lo_off = c_lo_off<TC>(g);
@@ -936,7 +997,7 @@ __device__ __forceinline__ void persist_epilogue(const GemmB16Args& g, const f32
   // the residual / gelu' rows (and DropPath scales) of pass i+1 are requested BEFORE the stores of pass i are issued: memory
   // operations retire in order, so a pass never waits for the previous pass's stores.
   DropPathRows dp;
-  dp.init(EPI == EPI_BIAS_RESID ? g.mask : nullptr, g.mask_mode, g.T, g.J, row0);
+  dp.init(EPI == EPI_BIAS_RESID ? g.mask : nullptr, g.mask_mode, g.T, g.J, FULL ? row0 : min(row0, g.M - 1));      // (a wave whose rows all lie past M looks up row M - 1: never a row below the origin)
   auto request = [&](int i) {
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
@@ -951,7 +1012,7 @@ __device__ __forceinline__ void persist_epilogue(const GemmB16Args& g, const f32
   };
   if (LOADS) request(0);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < NI; ++i) {
     float4 in[4];
     float ds[4];
 #pragma unroll
@@ -965,7 +1026,7 @@ __device__ __forceinline__ void persist_epilogue(const GemmB16Args& g, const f32
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(img + l15 * 64 + (((4 * j + gq) ^ l15) << 2)) = acc[i][j];
-    if (LOADS && i + 1 < 8) request(i + 1);
+    if (LOADS && i + 1 < NI) request(i + 1);
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int lr = it * 4 + gq;
@@ -1453,6 +1514,89 @@ static int persist_workgroups() {
   return g_persist_mode == 0 ? 0 : n;
 }
 
+static bool g_force_small_tile = false;    // test hook: exercise the 128x128 instantiation on big shapes too (the forms that had one before the planner: not f16f8)
+void gemm_bf16_force_small_tile(bool on) { g_force_small_tile = on; }
+static int g_gemm_tile = 0;                // mp_set_option("gemm_tile"): 0 = the planner, 128 / 256 = that tile wherever the form has it (tests, A/B timing)
+int gemm_bf16_tile(int tile) {
+  if (tile != 0 && tile != 128 && tile != 256) return MP_ERR_ARG;
+  g_gemm_tile = tile;
+  return MP_OK;
+}
+
+// process-wide launch counts by kernel family (mp_gemm_launch_counts): plain host counters, no device work
+static std::atomic<long long> g_launches[3];      // persistent 256, tiled 256, tiled 128
+void gemm_launch_counts(long long out[3], int reset) {
+  for (int i = 0; i < 3; ++i) out[i] = reset ? g_launches[i].exchange(0) : g_launches[i].load();
+}
+
+// ---- the planner: which kernel serves a GEMM, from its shape and the CU count alone (a pure host function; launch_glds and gemm_f16f8 launch
+// what it returns).  Model: a 256 x 256 tile costs 4 units and the chip runs `cus` of them at a time (one 8-wave workgroup per CU); a 128 x 128 tile
+// costs c >= 1 units - a quarter of the MFMA work at ~1.5x the LDS bytes per MFMA - and the chip runs 2 cus of them (two 4-wave workgroups per
+// CU).  Estimated time = rounds x cost; the small tile is taken only where it is cheaper by PLAN_MARGIN, i.e. where the large one leaves CUs
+// idle, and never from two large tiles per CU up (where the older forms' persistent kernel starts).
+// The constants are the crossover table's (profiles/small_batch/crossover.log): c = the median over its rows of
+// 4 rounds256 t128 / (rounds128 t256) - f16f8 forward forms 2.87 (2.2 - 3.3 per row; 2.6 - 3.0 at 79 windows, i.e. the small tile runs at ~0.7 of
+// the large tile's rate when both fill the chip); over the rows of the tiled region, bf16 dgrads 2.2 and bf16x3 forward forms 2.04 (fp16 operands share the
+// bf16 loop and its constant).  The margin covers the spread of a row's implied c around the median where the two estimates are close.
+constexpr double PLAN_C_F16F8 = 2.9;
+constexpr double PLAN_C_B16 = 2.2;
+constexpr double PLAN_C_X3 = 2.1;
+constexpr double PLAN_MARGIN = 1.10;       // the 256 estimate must exceed the 128 estimate by this factor
+GemmPlan gemm_plan(const GemmPlanIn& p) {
+  GemmPlan r = {0, 0, 0, 0};
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.cus <= 0) return r;
+  const int splits = p.splits > 0 ? p.splits : 1;
+  const long t256 = (long)cdiv(p.N, 256) * cdiv(p.M, 256), t128 = (long)cdiv(p.N, 128) * cdiv(p.M, 128);
+  const int cus8 = (p.cus / 8) * 8;
+  auto tiled = [&](int tile) { r.tile = tile; r.persistent = 0; r.tiles = (int)(tile == 256 ? t256 : t128); r.workgroups = r.tiles * splits; return r; };
+  auto persistent = [&](int wgs) { r.tile = 256; r.persistent = 1; r.tiles = (int)t256; r.workgroups = wgs; return r; };
+  // does the estimate favour the small tile?  (cus CUs: one large or two small workgroups each)
+  auto small_wins = [&](double c) {
+    if (t256 >= 2L * p.cus) return false;
+    const double cost256 = 4.0 * (double)cdiv(t256, (long)p.cus), cost128 = c * (double)cdiv(t128, 2L * p.cus);
+    return cost128 * PLAN_MARGIN < cost256;
+  };
+  if (p.form == GEMM_FORM_F16F8) {
+    // one persistent 256 kernel and one tiled 128 kernel; gemm_small_tile, gemm_persist_mode and gemm_persist_wgs never applied to this form
+    if (p.tra || p.trb || splits != 1 || p.epi == EPI_SLAB || p.epi == EPI_DGELU || p.N % 256 != 0 || p.K % GBK != 0 || p.K < 2 * GBK ||
+        256L * p.lda * 2 >= (1L << 31) || 256L * p.ldb * 2 >= (1L << 31) || (p.epi == EPI_BIAS_RESID && !(p.rscale == 0.f || p.rscale == 1.0f)))
+      return r;
+    const int wgs = max(8, cus8);
+    if (g_gemm_tile == 128) return tiled(128);
+    if (g_gemm_tile == 256 || g_persist_min_tiles > 0) return persistent(wgs);
+    return small_wins(PLAN_C_F16F8) ? tiled(128) : persistent(wgs);
+  }
+  // bf16 / bf16x3 / fp16 operands through gemm_bf16_glds_kernel and its persistent form
+  const bool has256 = p.M >= 256 && p.N % 256 == 0;
+  const bool wgrad = p.tra != 0 || p.epi == EPI_SLAB || splits != 1;        // split-K launches: their split count and bias slabs were laid out for use_big_tile()'s tile
+  const bool big = has256 && !g_force_small_tile && (wgrad || g_gemm_tile != 128);
+  if (p.tra == 0 && p.epi != EPI_SLAB) {
+    // the boundary between the persistent and the tiled family is where it always was: the two differ by rounding in their epilogues
+    int wgs = cus8;
+    if (g_persist_wgs >= 8 && g_persist_wgs <= wgs) wgs = (g_persist_wgs / 8) * 8;
+    if (g_persist_mode == 0) wgs = 0;
+    if (wgs > 0 && splits == 1 && (p.rscale == 0.f || p.rscale == 1.0f) && big && p.K >= 2 * GBK && p.K % GBK == 0 &&
+        t256 >= (g_persist_min_tiles > 0 ? (long)g_persist_min_tiles : 2L * wgs) && 256L * p.lda * 2 < (1L << 31) && 64L * p.ldb * 2 < (1L << 31) &&
+        256L * p.ldb * 2 < (1L << 31))
+      return persistent(wgs);
+  }
+  if (!big) return tiled(128);
+  // inside the tiled region: the two instantiations of one template.  The weight-gradient launches (split-K, both operands transposed) keep the
+  // large tile - their split count was chosen for it (wgrad_split_b16)
+  if (g_gemm_tile == 256 || wgrad) return tiled(256);
+  return small_wins(p.form == GEMM_FORM_BF16X3 ? PLAN_C_X3 : PLAN_C_B16) ? tiled(128) : tiled(256);
+}
+static int device_cus() {
+  static int cus = -1;
+  if (cus < 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+    cus = n;
+  }
+  return cus;
+}
+int gemm_device_cus() { return device_cus(); }
+
 // profiling tag: 1 if the last gemm_bf16() of this thread went to the persistent kernel (the engine's per-kernel timing)
 static thread_local int g_last_persist = 0;
 int gemm_bf16_take_last_persist() { const int v = g_last_persist; g_last_persist = 0; return v; }
@@ -1473,6 +1617,7 @@ static int persist_go(const GemmB16Args& g, int wgs, int tiles_n, int ntiles, hi
 template <int TRB, typename TC, int EPI, int SPLIT = 0>
 static int launch_persist(const GemmB16Args& g_in, int wgs, hipStream_t st) {
   g_last_persist = 1;
+  ++g_launches[0];
   GemmB16Args g = g_in;
   g.stamps = nullptr; g.stagger = 0;
 #ifdef MP_GEMM_DIAG
@@ -1490,9 +1635,6 @@ static int launch_persist(const GemmB16Args& g_in, int wgs, hipStream_t st) {
   return persist_go<TRB, TC, EPI, SPLIT, false>(g, wgs, tiles_n, ntiles, st);
 }
 
-static bool g_force_small_tile = false;    // test hook: exercise the 128x128 instantiation on big shapes too
-void gemm_bf16_force_small_tile(bool on) { g_force_small_tile = on; }
-
 template <int TRA, int TRB, typename TC, int EPI, int BT, int SPLIT = 0>
 static int launch_glds_bt(const GemmB16Args& g, int splits, hipStream_t st) {
   constexpr size_t lds = 2 * 2 * BT * 128;
@@ -1501,27 +1643,30 @@ static int launch_glds_bt(const GemmB16Args& g, int splits, hipStream_t st) {
     MP_HIP(hipFuncSetAttribute((const void*)gemm_bf16_glds_kernel<TRA, TRB, TC, EPI, BT, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
+  ++g_launches[BT == 256 ? 1 : 2];
   dim3 grid(cdiv(g.N, BT), cdiv(g.M, BT), splits);
   hipLaunchKernelGGL((gemm_bf16_glds_kernel<TRA, TRB, TC, EPI, BT, SPLIT>), grid, dim3(BT * 2), lds, st, g);
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
 // 256x256 tiles (1 workgroup of 8 waves per CU: 2x the MFMA work per byte moved through the CU's vector-memory path and
-// LDS) whenever the problem is wide enough; 128x128 tiles for the narrow bones-net layers.
+// LDS) whenever the problem is wide enough; 128x128 tiles for the narrow bones-net layers.  (The weight-gradient launcher sizes its
+// split-K by this; every launch goes through gemm_plan.)
 static bool use_big_tile(const GemmB16Args& g) {
   if (g_force_small_tile) return false;
   return g.M >= 256 && g.N >= 256 && g.N % 256 == 0;
 }
+template <int SPLIT> constexpr int plan_form() { return SPLIT == 1 ? GEMM_FORM_BF16X3 : ((SPLIT == 16 || SPLIT == 32) ? GEMM_FORM_F16 : GEMM_FORM_BF16); }
 template <int TRA, int TRB, typename TC, int EPI, int SPLIT = 0>
 static int launch_glds(const GemmB16Args& g, int splits, hipStream_t st) {
+  // (a residual scale other than 1 - muP - is served by the tiled kernels only: the persistent residual epilogue sits at the 256-VGPR limit)
+  const GemmPlanIn in = {g.M, g.N, g.K, plan_form<SPLIT>(), EPI, TRA, TRB, splits, g.lda, g.ldb, g.rscale, device_cus()};
+  const GemmPlan pl = gemm_plan(in);
   if constexpr (TRA == 0 && EPI != EPI_SLAB) {
-    const int wgs = persist_workgroups();
-    // (a residual scale other than 1 - muP - is served by the tiled kernels only: the persistent residual epilogue sits at the 256-VGPR limit)
-    if (wgs > 0 && splits == 1 && (g.rscale == 0.f || g.rscale == 1.0f) && use_big_tile(g) && g.K >= 2 * GBK && g.K % GBK == 0 && (long)cdiv(g.N, 256) * cdiv(g.M, 256) >= (g_persist_min_tiles > 0 ? (long)g_persist_min_tiles : 2L * wgs) &&
-        256L * g.lda * 2 < (1L << 31) && 64L * g.ldb * 2 < (1L << 31) && 256L * g.ldb * 2 < (1L << 31))
-      return launch_persist<TRB, TC, EPI, SPLIT>(g, wgs, st);
+    if (pl.persistent) return launch_persist<TRB, TC, EPI, SPLIT>(g, pl.workgroups, st);
   }
-  return use_big_tile(g) ? launch_glds_bt<TRA, TRB, TC, EPI, 256, SPLIT>(g, splits, st) : launch_glds_bt<TRA, TRB, TC, EPI, 128, SPLIT>(g, splits, st);
+  MP_CHECK(pl.tile != 0 && !pl.persistent, MP_ERR_ARG, "gemm_bf16: no kernel for M=%d N=%d K=%d", g.M, g.N, g.K);
+  return pl.tile == 256 ? launch_glds_bt<TRA, TRB, TC, EPI, 256, SPLIT>(g, splits, st) : launch_glds_bt<TRA, TRB, TC, EPI, 128, SPLIT>(g, splits, st);
 }
 
 // dW += sum of the split-K slabs, db += sum of the bias slabs, ONE launch.  A block owns 64 float4 outputs; its four waves each sum
@@ -1575,6 +1720,7 @@ __global__ __launch_bounds__(256) void reduce_slabs_b16_kernel(const float* __re
 
 template <typename TA, int TRA, typename TB, int TRB, typename TC, int EPI>
 static int launch_b16(const GemmB16Args& g, int splits, hipStream_t st) {
+  ++g_launches[2];
   dim3 grid(cdiv(g.N, GBN), cdiv(g.M, GBM), splits);
   hipLaunchKernelGGL((gemm_bf16_kernel<TA, TRA, TB, TRB, TC, EPI>), grid, dim3(256), 0, st, g);
   MP_LAUNCH_CHECK();
@@ -1640,8 +1786,8 @@ int gemm_bf16x3(GemmB16Args g, int c_f32, int epi, hipStream_t st) {
   MP_CHECK(false, MP_ERR_ARG, "gemm_bf16x3: unsupported variant c_f32=%d epi=%d", c_f32, epi);
 }
 
-// y = x W^T + b with x and W carried as fp16 hi planes + 8-bit correction planes (see mma_stage_f8): persistent kernel only
-// (N % 256 == 0, K % 64 == 0, K >= 128).  A_lo / B_lo are the correction planes.  Outputs: c_f32 with EPI_BIAS: fp32; otherwise the planar
+// y = x W^T + b with x and W carried as fp16 hi planes + 8-bit correction planes (see mma_stage_mix): the persistent 256 x 256 kernel or the
+// tiled 128 x 128 one, chosen by gemm_plan (N % 256 == 0, K % 64 == 0, K >= 128).  A_lo / B_lo are the correction planes.  Outputs: c_f32 with EPI_BIAS: fp32; otherwise the planar
 // bf16 hi / lo pair of the bf16x3 kernels (C, C_lo), EPI_BIAS or EPI_BIAS_GELU (+ Z = gelu' as plain bf16) - what the attention kernels and
 // the fc2 GEMM of the engine read.
 int gemm_f16f8(GemmB16Args g, int c_f32, int epi, hipStream_t st) {
@@ -1652,19 +1798,23 @@ int gemm_f16f8(GemmB16Args g, int c_f32, int epi, hipStream_t st) {
   MP_CHECK(256L * g.lda * 2 < (1L << 31) && 256L * g.ldb * 2 < (1L << 31), MP_ERR_ARG, "gemm_f16f8: leading dimension too large");
   MP_CHECK(!g.out_f16f8 || (!c_f32 && epi == EPI_BIAS_GELU), MP_ERR_ARG, "gemm_f16f8: f16f8 output planes exist for the GELU epilogue only (c_f32=%d epi=%d)", c_f32, epi);
   g.k_per_split = g.K;
-  int dev = 0, cus = 0;
-  MP_HIP(hipGetDevice(&dev));
-  MP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int wgs = max(8, (cus / 8) * 8);
-  if (c_f32 && epi == EPI_BIAS) return launch_persist<0, float, EPI_BIAS, 8>(g, wgs, st);
-  if (c_f32 && epi == EPI_BIAS_RESID) {
-    MP_CHECK(g.R != nullptr && (g.rscale == 0.f || g.rscale == 1.0f), MP_ERR_ARG, "gemm_f16f8: residual epilogue needs R and a residual scale of 1");
-    return launch_persist<0, float, EPI_BIAS_RESID, 8>(g, wgs, st);
-  }
-  MP_CHECK(!c_f32 && g.C_lo != nullptr, MP_ERR_ARG, "gemm_f16f8: planar output without its lo plane");
-  if (epi == EPI_BIAS) return launch_persist<0, bf16p, EPI_BIAS, 8>(g, wgs, st);
-  if (epi == EPI_BIAS_GELU && g.out_f16f8) return launch_persist<0, f16f8, EPI_BIAS_GELU, 8>(g, wgs, st);      // C / C_lo = fp16 + correction planes (the fc2 GEMM's f16f8 input)
-  if (epi == EPI_BIAS_GELU) return launch_persist<0, bf16p, EPI_BIAS_GELU, 8>(g, wgs, st);      // Z may be null (inference: gelu' is not kept)
+  MP_CHECK(c_f32 || g.C_lo != nullptr, MP_ERR_ARG, "gemm_f16f8: planar output without its lo plane");
+  MP_CHECK(!(c_f32 && epi == EPI_BIAS_RESID) || (g.R != nullptr && (g.rscale == 0.f || g.rscale == 1.0f)), MP_ERR_ARG,
+           "gemm_f16f8: residual epilogue needs R and a residual scale of 1");
+  const int cus = device_cus();
+  MP_CHECK(cus > 0, MP_ERR_HIP, "gemm_f16f8: no device");
+  const GemmPlanIn in = {g.M, g.N, g.K, GEMM_FORM_F16F8, epi, 0, 0, 1, g.lda, g.ldb, g.rscale, cus};
+  const GemmPlan pl = gemm_plan(in);
+  MP_CHECK(pl.tile != 0, MP_ERR_ARG, "gemm_f16f8: unsupported variant c_f32=%d epi=%d", c_f32, epi);
+  // persistent 256 x 256 kernel or the tiled 128 x 128 one (two workgroups per CU), the planner's choice: same bits from both
+#define MP_F16F8_GO(TC, EPI_)                                                                    \
+  return pl.persistent ? launch_persist<0, TC, EPI_, 8>(g, pl.workgroups, st) : launch_glds_bt<0, 0, TC, EPI_, 128, 8>(g, 1, st)
+  if (c_f32 && epi == EPI_BIAS) MP_F16F8_GO(float, EPI_BIAS);
+  if (c_f32 && epi == EPI_BIAS_RESID) MP_F16F8_GO(float, EPI_BIAS_RESID);
+  if (!c_f32 && epi == EPI_BIAS) MP_F16F8_GO(bf16p, EPI_BIAS);
+  if (!c_f32 && epi == EPI_BIAS_GELU && g.out_f16f8) MP_F16F8_GO(f16f8, EPI_BIAS_GELU);      // C / C_lo = fp16 + correction planes (the fc2 GEMM's f16f8 input)
+  if (!c_f32 && epi == EPI_BIAS_GELU) MP_F16F8_GO(bf16p, EPI_BIAS_GELU);      // Z may be null (inference: gelu' is not kept)
+#undef MP_F16F8_GO
   MP_CHECK(false, MP_ERR_ARG, "gemm_f16f8: unsupported variant c_f32=%d epi=%d", c_f32, epi);
 }
 

@@ -66,13 +66,36 @@ int gemm_bf16(GemmB16Args g, int a_f32, int a_tr, int b_tr, int c_f32, int epi, 
 // C = A B^T on planar hi/lo operands ("N","N" layouts: the forward Linear), three bf16 MFMA products per k-tile, fp32 accumulate.
 // epi EPI_BIAS / EPI_BIAS_GELU: C planar (C, C_lo), Z = gelu' as plain bf16; EPI_BIAS_RESID: C fp32 (c_f32 must be 1)
 int gemm_bf16x3(GemmB16Args g, int c_f32, int epi, hipStream_t st);
-// y = x W^T + b on fp16 hi planes + 8-bit correction planes (gemm_bf16.hip, mma_stage_f8): A / B the fp16 planes, A_lo / B_lo the corrections, C fp32
+// y = x W^T + b on fp16 hi planes + 8-bit correction planes (gemm_bf16.hip, mma_stage_mix): A / B the fp16 planes, A_lo / B_lo the corrections, C fp32
 int gemm_f16f8(GemmB16Args g, int c_f32, int epi, hipStream_t st);
 int cast_to_f16f8(const float* src, void* hi16, void* cat8, long n, int weight, hipStream_t st);     // n % 64 == 0; see common.h "f16f8"
 int cast_to_bf16x2(const float* src, bf16* hi, bf16* lo, long n, hipStream_t st);
 int wgrad_bf16(const void* dY, int dy_f32, long lddy, const bf16* X, long ldx, int Mtok, int Nout, int Kin, float* dW, float* db,
                float* slab, long slab_floats, hipStream_t st, int f16 = 0, const float* oscale = nullptr, int x_f16 = 0);      // f16: dY and X are fp16, dW += *oscale x dY^T X (device address); x_f16: X alone is fp16 (the fp16 plane of an f16f8 activation), rounded to bf16 per fragment
 int cast_to_bf16(const float* src, bf16* dst, long n, hipStream_t st);
+// The planner (gemm_bf16.hip): a pure host function from (shape, operand form, epilogue, layouts, splits, leading dimensions, CU count) to the kernel
+// that runs - the two launch sites launch_glds and gemm_f16f8 launch what it returns.  tile == 0: no kernel serves the problem.
+enum { GEMM_FORM_BF16 = 0, GEMM_FORM_BF16X3 = 1, GEMM_FORM_F16F8 = 8, GEMM_FORM_F16 = 16 };
+struct GemmPlanIn {
+  int M, N, K;
+  int form;            // GEMM_FORM_*
+  int epi;             // EPI_*
+  int tra, trb;        // operand layouts ("T" = 1)
+  int splits;          // split-K count (1: none)
+  long lda, ldb;
+  float rscale;        // residual scale (0 means 1)
+  int cus;             // compute units of the device
+};
+struct GemmPlan {
+  int tile;            // 128 or 256 (0: none)
+  int persistent;      // 1: the persistent 256 x 256 kernel, 0: a tiled kernel
+  int workgroups;      // grid size: persistent workgroups, or tiles x splits
+  int tiles;           // ceil(M / tile) * ceil(N / tile)
+};
+GemmPlan gemm_plan(const GemmPlanIn& p);
+int gemm_device_cus();                             // CU count of the current device (0: none)
+int gemm_bf16_tile(int tile);                      // mp_set_option("gemm_tile"): 0 planner, 128 / 256 forced; MP_ERR_ARG otherwise
+void gemm_launch_counts(long long out[3], int reset);   // GEMM launches since the last reset: persistent 256, tiled 256, tiled 128
 void gemm_bf16_force_small_tile(bool on);          // test hooks (mp_set_option)
 void gemm_bf16_persist_min_tiles(int n);
 void gemm_bf16_persist_mode(int mode);
