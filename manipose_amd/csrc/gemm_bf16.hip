@@ -301,12 +301,6 @@ __device__ __forceinline__ f32x4 mfma16(const bf16x8_t& a, const bf16x8_t& b, co
   else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-struct NoMid { __device__ __forceinline__ void operator()() const {} };
-// DMA_LATE_STEP: the MFMA group (of 8) behind which the waves of group 1 (waves 4-7: the second wave of every SIMD) issue their share of the
-// next k-tile's operand DMA in the plain persistent loop, instead of at the start of the step like group 0 (-1: everybody at the start).
-#ifndef DMA_LATE_STEP
-#define DMA_LATE_STEP -1
-#endif
 template <bool F16>
 __device__ __forceinline__ float lds16_to_float(unsigned short b) {
   if constexpr (F16) return (float)__builtin_bit_cast(_Float16, b);
@@ -319,6 +313,14 @@ __device__ __forceinline__ bf16x8_t frag_f16_to_bf16(const bf16x8_t& f) {
   const uint2 lo = f16x4_to_bf16x4(make_uint2(u.x, u.y)), hi = f16x4_to_bf16x4(make_uint2(u.z, u.w));
   return __builtin_bit_cast(bf16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
 }
+// Mid / MMA_MID_STEP: a hook behind MFMA group MMA_MID_STEP of the stage, through which waves 4-7 - the second wave of every SIMD - issued their
+// share of the next k-tile's operand DMA of the plain persistent loop mid-step instead of at its start.  Measured in round 3 behind group 1 / 3 / 5:
+// block of four dgrads 1263 -> 1249 / 1331 / 1368 us, issued late the tiles land late (profiles/r03_probes/dgrad_late_dma_variants.log); it was a
+// build switch until the commit "Fix the GEMM k-loop build switches at shipped values" and is now fixed at "never".  The hook itself is dead code
+// that is still here for one reason: taking it out changes what hipcc makes of the SPLIT = 16 persistent kernels (register allocation and
+// +-0.1 .. 7 % instructions in three kernels), which is a change to measure on the fp16 backward, not a clean-up.
+struct NoMid { __device__ __forceinline__ void operator()() const {} };
+constexpr int MMA_MID_STEP = -1;
 template <int TRA, int TRB, int BT, int ABL = 0, int F16 = 0, typename Mid = NoMid, int BCVT = 0>
 __device__ __forceinline__ void mma_stage(const char* __restrict__ As, const char* __restrict__ Bs, f32x4 (&acc)[BT / 32][4], int wr, int wc,
                                           int lane, Mid mid = Mid()) {
@@ -367,7 +369,7 @@ __device__ __forceinline__ void mma_stage(const char* __restrict__ As, const cha
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[2 * ip + 1][j] = mfma16<F16>(b_cur[j], a_cur[1], acc[2 * ip + 1][j]);
     __builtin_amdgcn_sched_barrier(0);
-    if (step == DMA_LATE_STEP) { mid(); __builtin_amdgcn_sched_barrier(0); }
+    if (step == MMA_MID_STEP) { mid(); __builtin_amdgcn_sched_barrier(0); }
     if (step + 1 < NSTEP) {
       a_cur[0] = a_nxt[0];
       a_cur[1] = a_nxt[1];
@@ -409,8 +411,9 @@ __device__ __forceinline__ f32x4 mfma_f8(const i32x8_t& a, const i32x8_t& b, con
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f16x8_t half_lo(const i32x8_t& v) { return __builtin_bit_cast(f16x8_t, __builtin_shufflevector(v, v, 0, 1, 2, 3)); }
 __device__ __forceinline__ f16x8_t half_hi(const i32x8_t& v) { return __builtin_bit_cast(f16x8_t, __builtin_shufflevector(v, v, 4, 5, 6, 7)); }
-// NI = 16-row A fragments of the wave tile: 8 (128 x 64, the 256-wide tile) or 4 (64 x 64, the 128-wide tile); the LDS image has 128-byte rows in both.
-template <int NI = 8>
+// NI = 16-row A fragments of the wave tile: 4 (64 x 64, the 128-wide tile: its only caller, the tiled f16f8 kernel; the 256-wide tile's loop is
+// hand-scheduled - kstep_asm_f / kstep_asm_e below - since round 6); the LDS image has 128-byte rows.
+template <int NI>
 __device__ __forceinline__ void mma_stage_mix(const char* __restrict__ As, const char* __restrict__ Bs, f32x4 (&acc)[NI][4], int wr, int wc, int lane,
                                               bool f8) {
   i32x8_t b[4], a_cur, a_nxt;
@@ -439,25 +442,11 @@ __device__ __forceinline__ void mma_stage_mix(const char* __restrict__ As, const
   }
 }
 
-// Per-lane byte offsets of the 4 DMA instructions a wave issues per operand and k-tile, relative to the (wave-uniform)
+// Per-lane byte offsets of the DMA instructions a wave issues per operand and k-tile - NP consecutive 1 KiB pieces of the tile starting at piece
+// `first` (every wave 4: first = 4 wave; the hand-scheduled loops: waves 4-7 take 8 pieces each) - relative to the (wave-uniform)
 // address of the tile's first element of that k-tile; the same source swizzles as glds_tile.  Rows past the end of the
 // matrix are clamped to its last row (their products are never stored), so no lane needs a different base.
-template <int TR>
-__device__ __forceinline__ void persist_offsets(unsigned (&off)[4], long ld, int out0, int OUT, int lane, int wave) {
-#pragma unroll
-  for (int n4 = 0; n4 < 4; ++n4) {
-    const int c = 64 * (wave * 4 + n4) + lane;
-    if (TR == 0) {
-      const int row = c >> 3, kg = (c & 7) ^ (row & 7);
-      off[n4] = (unsigned)(min(row, OUT - 1 - out0) * (int)ld * 2 + kg * 16);
-    } else {
-      const int rr = c >> 5, oc = (c & 31) ^ t_swz(rr);      // OUT % 256 == 0 (launcher): every chunk is in range
-      off[n4] = (unsigned)(rr * (int)ld * 2 + oc * 16);
-    }
-  }
-}
 __device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-// the same for NP consecutive pieces starting at piece `first` (MP_KSTEP_YOUNG: waves 4-7 take 8 pieces of a tile each)
 template <int TR, int NP>
 __device__ __forceinline__ void persist_offsets_n(unsigned (&off)[NP], long ld, int out0, int OUT, int lane, int first) {
 #pragma unroll
@@ -467,7 +456,7 @@ __device__ __forceinline__ void persist_offsets_n(unsigned (&off)[NP], long ld, 
       const int row = c >> 3, kg = (c & 7) ^ (row & 7);
       off[i] = (unsigned)(min(row, OUT - 1 - out0) * (int)ld * 2 + kg * 16);
     } else {
-      const int rr = c >> 5, oc = (c & 31) ^ t_swz(rr);
+      const int rr = c >> 5, oc = (c & 31) ^ t_swz(rr);      // OUT % 256 == 0 (launcher): every chunk is in range
       off[i] = (unsigned)(rr * (int)ld * 2 + oc * 16);
     }
   }
@@ -479,31 +468,33 @@ __device__ __forceinline__ void persist_dma(char* __restrict__ S, const char* __
   for (int n4 = 0; n4 < 4; ++n4) __builtin_amdgcn_global_load_lds((gptr)(base + off[n4]), (lptr)(S + (wave * 4 + n4) * 1024), 16, 0, 0);
 }
 
-// ---- hand-scheduled k-step (MP_KLOOP_ASM; tools/gen_kloop_asm.py -> kloop_asm.inc) -------------------------------------------------------
-// One 64-wide step of a wave's 128 x 64 sub-tile as a single inline-asm block: the 64 MFMAs, the 24 fragment requests (two groups of 8 MFMAs
-// ahead, counted lgkmcnt waits, fragments in the fixed registers v[200:255]) and the wave's share of the step's operand DMA.  What hipcc makes
-// of mma_stage above: requests one group ahead behind lgkmcnt(0) waits, the DMA instructions (and ~60 scalar instructions of address and
-// predicate arithmetic) in front of the step's first fragment request.
-#ifndef MP_KLOOP_ASM
-#define MP_KLOOP_ASM 1      // round 5: block of four split-precision forward GEMMs 3.81 -> 3.61 ms, block of four dgrads 1.235 -> 1.215 ms
-#endif
+// ---- hand-scheduled k-step (tools/gen_kloop_asm.py -> kloop_asm.inc) ----------------------------------------------------------------------
+// One 64-wide step of a wave's 128 x 64 sub-tile as a single inline-asm block: the 64 MFMAs, the 24 fragment requests (one or two groups of 8
+// MFMAs ahead, counted lgkmcnt waits, fragments in the fixed registers v[200:255]) and the wave's share of the step's operand DMA.  What hipcc
+// makes of mma_stage above: requests one group ahead behind lgkmcnt(0) waits, the DMA instructions (and ~60 scalar instructions of address and
+// predicate arithmetic) in front of the step's first fragment request.  The plain (SPLIT = 0), three-product (1) and f16f8 (8) loops of the
+// persistent kernel run in this form and no other; hipcc's loop serves SPLIT = 16 and the diagnostics build's ablations.  What each choice
+// measured (same box, alternating, block of four GEMMs; every alternative was a build switch that nothing set and was removed - the code is in
+// the history up to the commit "Fix the GEMM k-loop build switches at shipped values"):
+//  * hand-scheduled against hipcc's loop (round 5): four split-precision forward GEMMs 3.81 -> 3.61 ms, four dgrads 1.235 -> 1.215 ms (DESIGN
+//    section 5); f16f8 at B = 79 (round 6): hipcc's loop 3280-3290 us, hand-scheduled 2679-2688 (profiles/r06_probes/f16f8_asm_vs_hipcc_gemm_block.log)
+//  * the schedule of a step - DMA jobs in front of / behind the first fragment requests, requests one / two groups ahead: split-precision loop
+//    front / 1: 3626-3635 us, front / 2: 3629-3656, behind / 2: 3608-3615 (kept), DMA spread over MFMA groups 0-3: 3677-3688 (hipcc 3803-3812);
+//    dgrad front / 1: 1213-1218 (kept), front / 2: 1206-1219, behind / 2: 1222, spread: 1244-1246 (hipcc 1231-1240) -
+//    profiles/r05_probes/kstep_variants.log; f16f8 steps front / 1: 2577-2583 us (kept), behind / 2: 2644-2648 (profiles/r06_probes/f16f8_step_variants.log)
+//  * the operand DMA is issued by waves 4-7 only - the younger wave of every SIMD, 8 pieces (1 KiB each) per tile each - instead of 4 pieces by
+//    every wave: the older wave wins the matrix pipe's arbitration, so DMA instructions in its head delay the SIMD's first MFMA of the step
+//    (four split-precision GEMMs 3743-3760 -> 3708-3715 us, four dgrads 1249-1252 -> 1188-1192 us; profiles/r05_probes/kstep_young_ab_gemm.log)
+//  * k-tiles 0 .. nk-2 of a tile of the split-precision forward loop run as ONE asm block with the loop inside and the fragment pipeline continuing
+//    across the steps - every step's barrier stands two MFMA groups before its end instead of in front of it (tools/gen_kloop_asm.py, pipe_loop_x3;
+//    against the block-per-step loop 3675 -> 3636-3656 us per block, per-wave cycles -8 %: profiles/r05_probes/kpipe_ab.log); the tile's last
+//    k-tile keeps the block-per-step form.
 #include "kloop_asm.inc"
-// schedule variant of the generated step (tools/gen_kloop_asm.py, VARIANTS), for the split-precision loop and the plain loop.  Measured (same box,
-// alternating, block of four GEMMs): split 0: 3626-3635, 1: 3629-3656, 2: 3608-3615, 3: 3677-3688 us (hipcc's own schedule 3803-3812);
-// dgrad 0: 1213-1218, 1: 1206-1219, 2: 1222, 3: 1244-1246 us (hipcc 1231-1240) - profiles/r05_probes/kstep_variants.log
-#ifndef MP_KSTEP_VARIANT
-#define MP_KSTEP_VARIANT 2
-#endif
-#ifndef MP_KSTEP_VARIANT_P
-#define MP_KSTEP_VARIANT_P 0
-#endif
 // (Round 5: a five-buffer form of the split-precision loop - A_lo | A_hi | B_lo | B_hi even | B_hi odd k-tile, the epilogue images inside A_hi, TWO
 // barriers per k-tile with (A_hi, B_hi) and (A_hi, B_lo) as one block of 128 MFMAs - was built, passed the parity tests and measured 1.8 % SLOWER
 // (block of four 3941-3951 us against 3875 us, profiles/r05_probes/x3_five_buffer_ab.log): A_hi and B_lo can only be requested behind the k-tile's
-// first barrier and are then both needed 64 MFMAs later.  With the operand DMA moved to the younger waves (MP_KSTEP_YOUNG) the two forms are equal
+// first barrier and are then both needed 64 MFMAs later.  With the operand DMA moved to the younger waves (below) the two forms are equal
 // (3793-3805 against 3781-3787 us, x3_five_buffer_young_ab.log).  Removed; the code is in the history, commit "five-buffer / two-barrier form".)
-#define MP_KSTEP_CLOB2(v) MP_KSTEP_CLOBBERS_V##v
-#define MP_KSTEP_CLOB(v) MP_KSTEP_CLOB2(v)
 __device__ __forceinline__ unsigned lds_u32(const void* p) {
   return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)p;
 }
@@ -533,15 +524,9 @@ __device__ __forceinline__ void kfrag_b(KFragB& f, unsigned base, int wc, int la
     }
   }
 }
-// MP_KSTEP_YOUNG (with MP_KLOOP_ASM): the operand DMA of the hand-scheduled loops is issued by waves 4-7 only - the younger wave of every SIMD, 8
-// pieces per tile each - instead of 4 pieces by every wave (configurations Z0 / Z1 / Z2 / ZP of the generator)
-#ifndef MP_KSTEP_YOUNG
-#define MP_KSTEP_YOUNG 1
-#endif
-// Job configuration of a step = which DMA jobs its asm block can carry (tools/gen_kloop_asm.py, CONFIGS): X0 / X1 / X2 = the three steps of a
-// k-tile of the split-precision loop, P = a step of the plain loop.  ONE block per step type, the jobs that are not always there behind a
-// wave-uniform flag in a scalar register: two blocks on the two sides of a C++ branch make hipcc reconcile the 128 accumulator registers
-// through 500-800 bytes of scratch memory per lane.
+// Step type = which DMA jobs a step's asm block can carry (tools/gen_kloop_asm.py, STEPS): X0 / X1 / X2 = the three steps of a k-tile of the
+// split-precision loop, P = a step of the plain loop.  ONE block per step type, every job behind a wave-uniform flag in a scalar register:
+// two blocks on the two sides of a C++ branch make hipcc reconcile the 128 accumulator registers through 500-800 bytes of scratch memory per lane.
 // The flags are made by the SCALAR ALU from scalar sources (kflag_*): an asm "s" operand takes nothing else, hipcc keeps wave-uniform bools as
 // lane masks + v_cndmask and folds __builtin_amdgcn_readfirstlane of a value it knows to be uniform, and a hand-written v_readfirstlane of such
 // a value was observed stale (round 5: one tile in a few fetched the tile behind the workgroup's last one; the mechanism was worked around, not
@@ -555,38 +540,16 @@ __device__ __forceinline__ int kflag_nonnull(const void* p) { int r; asm volatil
 __device__ __forceinline__ int kflag_more(int a, int b, int x) { int r; asm volatile("s_cmp_lg_u32 %1, %2\n\ts_cselect_b32 %0, 1, %3" : "=s"(r) : "s"(a), "s"(b), "s"(x) : "scc"); return r; }
 // (a == b) ? x : 0
 __device__ __forceinline__ int kflag_last(int a, int b, int x) { int r; asm volatile("s_cmp_eq_u32 %1, %2\n\ts_cselect_b32 %0, %3, 0" : "=s"(r) : "s"(a), "s"(b), "s"(x) : "scc"); return r; }
-// MP_KLOOP_PIPE (with MP_KLOOP_ASM and MP_KSTEP_YOUNG): k-tiles 0 .. nk-2 of a tile of the split-precision forward loop run as ONE asm block with the
-// loop inside and the fragment pipeline continuing across the steps - every step's barrier stands two MFMA groups before its end instead of in front
-// of it (tools/gen_kloop_asm.py, pipe_loop_x3); the tile's last k-tile keeps the block-per-step form.
-#ifndef MP_KLOOP_PIPE
-#define MP_KLOOP_PIPE 1
-#endif
-// MP_KLOOP_ASM8 (with MP_KLOOP_ASM and MP_KSTEP_YOUNG): the "f16f8" loop (SPLIT = 8) in the hand-scheduled form, one block per step (0: hipcc's mma_stage_mix)
-#ifndef MP_KLOOP_ASM8
-#define MP_KLOOP_ASM8 1
-#endif
-// schedule variant of the f16f8 steps (tools/gen_kloop_asm.py, F8_VARIANTS: 0 = DMA in front of the first fragment requests, requests one group ahead;
-// 1 = the same with requests two groups ahead; 2 = DMA behind the first requests, two groups ahead - the three-product loop's best)
-#ifndef MP_KSTEP_VARIANT_F8
-#define MP_KSTEP_VARIANT_F8 0
-#endif
 enum { KC_X0 = 0, KC_X1 = 1, KC_X2 = 2, KC_P = 3 };
-#define MP_KSTEP_SEL2(c, t, v) MP_KSTEP_ASM_##c##_TRB##t##_V##v
-#define MP_KSTEP_SEL(c, t, v) MP_KSTEP_SEL2(c, t, v)
-#if MP_KSTEP_YOUNG
 constexpr int KNP = 8;      // DMA pieces (1 KiB each) per operand tile and issuing wave
 #define MP_KSTEP_OFFS(o, arr) [o##0] "v"(arr[0]), [o##1] "v"(arr[1]), [o##2] "v"(arr[2]), [o##3] "v"(arr[3]), [o##4] "v"(arr[4]), [o##5] "v"(arr[5]), [o##6] "v"(arr[6]), [o##7] "v"(arr[7])
-#else
-constexpr int KNP = 4;
-#define MP_KSTEP_OFFS(o, arr) [o##0] "v"(arr[0]), [o##1] "v"(arr[1]), [o##2] "v"(arr[2]), [o##3] "v"(arr[3])
-#endif
 #define MP_KSTEP_JOBS                                                                                    \
   [ena] "s"(ja.en), [ldsa] "s"(ja.lds), [gba] "s"(ja.base), MP_KSTEP_OFFS(ao, aoff),                       \
   [enb] "s"(jb.en), [ldsb] "s"(jb.lds), [gbb] "s"(jb.base), MP_KSTEP_OFFS(bo, boff),                       \
   [enc] "s"(jc.en), [ldsc] "s"(jc.lds), [gbc] "s"(jc.base), [co] "v"(coff)
 #define MP_KSTEP_OPS_0 [aa0] "v"(fa.a[0]), [aa1] "v"(fa.a[1]), [ba0] "v"(fb.b[0]), [ba1] "v"(fb.b[1]), MP_KSTEP_JOBS
 #define MP_KSTEP_OPS_1 [aa0] "v"(fa.a[0]), [aa1] "v"(fa.a[1]), [bt0] "v"(fb.b[0]), [bt1] "v"(fb.b[1]), [bt2] "v"(fb.b[2]), [bt3] "v"(fb.b[3]), MP_KSTEP_JOBS
-#define MP_KSTEP_EMIT(c, t, v) asm volatile(MP_KSTEP_SEL(c, t, v) : MP_KSTEP_ACC_OPERANDS : MP_KSTEP_OPS_##t : MP_KSTEP_CLOB(v))
+#define MP_KSTEP_EMIT(c, t) asm volatile(MP_KSTEP_ASM_##c##_TRB##t : MP_KSTEP_ACC_OPERANDS : MP_KSTEP_OPS_##t : MP_KSTEP_CLOBBERS)
 // ("m0" is on the blocks' clobber lists - their DMA set-up writes it, and a compiler-made global_load_lds / readlane behind a block must
 // re-initialise it; clang accepts the reserved register and warns about it)
 #pragma clang diagnostic push
@@ -594,33 +557,13 @@ constexpr int KNP = 4;
 template <int TRB, int CFG>
 __device__ __forceinline__ void kstep_asm(f32x4 (&acc)[8][4], const KFragA& fa, const KFragB& fb, const KJob& ja, const unsigned (&aoff)[KNP],
                                           const KJob& jb, const unsigned (&boff)[KNP], const KJob& jc, unsigned coff) {
-  if constexpr (TRB == 0) {
-#if MP_KSTEP_YOUNG
-    if constexpr (CFG == KC_X0) MP_KSTEP_EMIT(Z0, 0, MP_KSTEP_VARIANT);
-    else if constexpr (CFG == KC_X1) MP_KSTEP_EMIT(Z1, 0, MP_KSTEP_VARIANT);
-    else if constexpr (CFG == KC_X2) MP_KSTEP_EMIT(Z2, 0, MP_KSTEP_VARIANT);
-    else MP_KSTEP_EMIT(ZP, 0, MP_KSTEP_VARIANT_P);
-#else
-    if constexpr (CFG == KC_X0) MP_KSTEP_EMIT(X0, 0, MP_KSTEP_VARIANT);
-    else if constexpr (CFG == KC_X1) MP_KSTEP_EMIT(X1, 0, MP_KSTEP_VARIANT);
-    else if constexpr (CFG == KC_X2) MP_KSTEP_EMIT(X2, 0, MP_KSTEP_VARIANT);
-    else MP_KSTEP_EMIT(P, 0, MP_KSTEP_VARIANT_P);
-#endif
-  } else {
-#if MP_KSTEP_YOUNG
-    if constexpr (CFG == KC_X0) MP_KSTEP_EMIT(Z0, 1, MP_KSTEP_VARIANT);
-    else if constexpr (CFG == KC_X1) MP_KSTEP_EMIT(Z1, 1, MP_KSTEP_VARIANT);
-    else if constexpr (CFG == KC_X2) MP_KSTEP_EMIT(Z2, 1, MP_KSTEP_VARIANT);
-    else MP_KSTEP_EMIT(ZP, 1, MP_KSTEP_VARIANT_P);
-#else
-    if constexpr (CFG == KC_X0) MP_KSTEP_EMIT(X0, 1, MP_KSTEP_VARIANT);
-    else if constexpr (CFG == KC_X1) MP_KSTEP_EMIT(X1, 1, MP_KSTEP_VARIANT);
-    else if constexpr (CFG == KC_X2) MP_KSTEP_EMIT(X2, 1, MP_KSTEP_VARIANT);
-    else MP_KSTEP_EMIT(P, 1, MP_KSTEP_VARIANT_P);
-#endif
-  }
+  static_assert(TRB == 0 || CFG == KC_P, "only the plain loop has a \"T\" B operand (dgrad); the split-precision steps are forward only");
+  if constexpr (CFG == KC_X0) MP_KSTEP_EMIT(X0, 0);
+  else if constexpr (CFG == KC_X1) MP_KSTEP_EMIT(X1, 0);
+  else if constexpr (CFG == KC_X2) MP_KSTEP_EMIT(X2, 0);
+  else if constexpr (TRB == 0) MP_KSTEP_EMIT(P, 0);
+  else MP_KSTEP_EMIT(P, 1);
 }
-#if MP_KSTEP_YOUNG
 // The two steps of a k-tile of the "f16f8" loop (SPLIT = 8) in the hand-scheduled form (round 6; generator: step(.., mfma = fp16) and step_f8):
 // F multiplies the fp16 tiles (64 v_mfma_f32_16x16x32_f16), E the 8-bit correction tiles (32 v_mfma_scale_f32_16x16x128_f8f6f4, block scales
 // 2^-15 x 1 in two vector registers); both carry the A / B jobs of the NEXT step's tiles behind scalar flags, E the bias behind a tile's last step.
@@ -628,12 +571,12 @@ __device__ __forceinline__ void kstep_asm_f(f32x4 (&acc)[8][4], const KFragA& fa
                                             const KJob& jb, const unsigned (&boff)[KNP]) {
   const KJob jc = {0, 0u, nullptr};
   const unsigned coff = 0;
-  asm volatile(MP_KSTEP_SEL(ZF, 0, MP_KSTEP_VARIANT_F8) : MP_KSTEP_ACC_OPERANDS : MP_KSTEP_OPS_0 : MP_KSTEP_CLOB(2));
+  MP_KSTEP_EMIT(F, 0);
 }
 #define MP_KSTEP_OPS_E [aa0] "v"(fa.a[0]), [aa1] "v"(fa.a[1]), [ba0] "v"(fb.b[0]), [ba1] "v"(fb.b[1]), [sca] "v"(sca), [scb] "v"(scb), MP_KSTEP_JOBS
 __device__ __forceinline__ void kstep_asm_e(f32x4 (&acc)[8][4], const KFragA& fa, const KFragB& fb, const KJob& ja, const unsigned (&aoff)[KNP],
                                             const KJob& jb, const unsigned (&boff)[KNP], const KJob& jc, unsigned coff, int sca, int scb) {
-  asm volatile(MP_KSTEP_SEL(ZE, 0, MP_KSTEP_VARIANT_F8) : MP_KSTEP_ACC_OPERANDS : MP_KSTEP_OPS_E : MP_KSTEP_CLOB(2));
+  asm volatile(MP_KSTEP_ASM_E_TRB0 : MP_KSTEP_ACC_OPERANDS : MP_KSTEP_OPS_E : MP_KSTEP_CLOBBERS);
 }
 // k-tiles 0 .. n-1 (n = nk - 1 >= 1) of a split-precision forward tile, behind the tile's first barrier (A_lo[0], B_hi[0] landed in A0, B0; A1, B1 free).
 // pa / pb: the hi planes' addresses of the tile's k-tile 0.  aoff / boff come back advanced by n k-tiles (128 bytes each) in the waves that issue DMA.
@@ -652,9 +595,8 @@ __device__ __forceinline__ void kpipe_x3(f32x4 (&acc)[8][4], const KFragA (&kfa)
                : [a0k0] "v"(kfa[0].a[0]), [a0k1] "v"(kfa[0].a[1]), [a1k0] "v"(kfa[1].a[0]), [a1k1] "v"(kfa[1].a[1]),
                  [b0k0] "v"(kfb[0].b[0]), [b0k1] "v"(kfb[0].b[1]), [b1k0] "v"(kfb[1].b[0]), [b1k1] "v"(kfb[1].b[1]),
                  [dmaw] "s"(dma_wave), [lds] "s"(dma_l), [pahi0] "s"(pahi0), [pblo0] "s"(pblo0), [pahi1] "s"(pahi1), [palo1] "s"(palo1), [pbhi1] "s"(pbhi1), [pblo1] "s"(pblo1)
-               : MP_KSTEP_CLOB(MP_KSTEP_VARIANT));
+               : MP_KSTEP_CLOBBERS);
 }
-#endif
 #pragma clang diagnostic pop
 
 // The same with an UNEVEN split of a tile's 32 DMA pieces over the waves (weight-gradient kernel): the waves of group 0 (0-3) take P0 pieces
@@ -691,9 +633,7 @@ __device__ __forceinline__ void uneven_dma(char* __restrict__ S, const char* __r
 template <typename TC, int EPI, bool FULL, bool F16G = false, int NI = 8>
 __device__ __forceinline__ void persist_epilogue(const GemmB16Args& g, const f32x4 (&acc)[NI][4], float* __restrict__ img, int row0, int col,
                                                  const float4& bias4, TC* __restrict__ C, typename ZType<TC>::type* __restrict__ Z, int l15, int gq);
-#ifndef WG_P0
-#define WG_P0 1      // measured on the four weight-gradient shapes of a block: 4 (even) 1485 us, 2: 1470, 1: 1444, 0: 1680; 6: 1535
-#endif
+constexpr int WG_P0 = 1;      // measured on the four weight-gradient shapes of a block: 4 (even) 1485 us, 2: 1470, 1: 1444, 0: 1680; 6: 1535
 template <int TRA, int TRB, typename TC, int EPI, int BT, int SPLIT = 0>
 __global__ __launch_bounds__(BT * 2) void gemm_bf16_glds_kernel(GemmB16Args g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -752,8 +692,8 @@ __global__ __launch_bounds__(BT * 2) void gemm_bf16_glds_kernel(GemmB16Args g) {
     const char* const Bb = reinterpret_cast<const char*>(B);
     const long a_lo = reinterpret_cast<const char*>(g.A_lo) - Ab, b_lo = reinterpret_cast<const char*>(g.B_lo) - Bb;
     unsigned aoff[4], boff[4];
-    persist_offsets<0>(aoff, g.lda, m0, g.M, lane, wave);
-    persist_offsets<0>(boff, g.ldb, n0, g.N, lane, wave);
+    persist_offsets_n<0, 4>(aoff, g.lda, m0, g.M, lane, 4 * wave);
+    persist_offsets_n<0, 4>(boff, g.ldb, n0, g.N, lane, 4 * wave);
     const char* pa = Ab + (long)m0 * g.lda * 2;              // fp16 plane of A, k-tile v / 2
     const char* pb = Bb + (long)n0 * g.ldb * 2;
     if (b_first) persist_dma(smem + OPB, pb, boff, wave);
@@ -1115,9 +1055,10 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist_kernel(GemmB16Args g, i
   if (id >= ntiles) return;
   const int nk = g.K / GBK;                                 // K % 64 == 0, nk >= 2 (launcher)
   int m0 = (id / tiles_n) * BT, n0 = (id % tiles_n) * BT;
-  constexpr bool KASM8 = MP_KLOOP_ASM && MP_KLOOP_ASM8 && MP_KSTEP_YOUNG && SPLIT == 8 && TRB == 0;      // f16f8 loop, hand-scheduled (round 6)
-  constexpr bool KASM = MP_KLOOP_ASM && (SPLIT == 0 || SPLIT == 1 || KASM8);      // the hand-scheduled k-step (plain, three-product and f16f8 loops)
-  constexpr bool YOUNG = KASM && MP_KSTEP_YOUNG;                         // its operand DMA comes from waves 4-7 only (8 pieces of a tile each)
+  constexpr bool KASM8 = SPLIT == 8;                                     // f16f8 loop, hand-scheduled (round 6)
+  constexpr bool KASM = SPLIT == 0 || SPLIT == 1 || KASM8;               // the hand-scheduled k-step (plain, three-product and f16f8 loops)
+  constexpr bool YOUNG = KASM;                                           // its operand DMA comes from waves 4-7 only (8 pieces of a tile each)
+  static_assert(TRB == 0 || (SPLIT != 1 && SPLIT != 8), "the hand-scheduled three-product and f16f8 loops are forward only (\"N\" B operand)");
   constexpr int NP = YOUNG ? 8 : 4;
   const int dma_first = YOUNG ? (wave >= 4 ? (wave - 4) * 8 : 0) : wave * 4;      // this wave's first piece of an operand tile
   unsigned aoff[NP], boff[NP];
@@ -1216,33 +1157,50 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist_kernel(GemmB16Args g, i
         MP_KDIAG_C();
       }
       (void)stage;
-    } else if constexpr (SPLIT == 8) {
-      // "f16f8": 2 nk steps over the two stages - even steps multiply the fp16 planes of k-tile v / 2 (fp16 MFMA), odd steps its 8-bit
-      // correction planes (one 128-deep fp8 MFMA per 16 x 16 block); the plain kernel's pipeline with alternating source planes
-      for (int v = 0; v < 2 * nk; ++v) {
-        if (v == 0 && landed) __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0) only
-        else __builtin_amdgcn_s_waitcnt(0x0070);                       // vmcnt(0) lgkmcnt(0)
-        __builtin_amdgcn_s_barrier();
-        const int par = v & 1;
-        const char* As = smem + par * STAGE;
-        const char* Bs = As + OPB;
-        char* nx = smem + (par ^ 1) * STAGE;
-        const bool last = v + 1 == 2 * nk;
-        if (!last || has_next) {
-          if (last) persist_offsets_n<0, NP>(aoff, g.lda, m0n, g.M, opaque(lane), dma_first);      // (opaque: the rows are recomputed here, not kept - spilled - across the tile)
-          const int ktn = last ? 0 : (v + 1) >> 1;
-          persist_dma(nx, a_base(last ? m0n : m0, ktn) + (par ? 0 : a_lo), aoff, wave);
-          persist_dma(nx + OPB, b_base(last ? n0n : n0, ktn) + (par ? 0 : b_lo), boff, wave);
-        }
-        if (last && has_bias) {
-          typedef __attribute__((address_space(3))) void* lptr;
-          typedef const __attribute__((address_space(1))) void* gptr;
-          __builtin_amdgcn_global_load_lds((gptr)(g.bias + n0 + wc * 64 + lane), (lptr)img, 4, 0, 0);
-        }
-        mma_stage_mix(As, Bs, acc, wr, wc, lane, par != 0);
-      }
+    } else if constexpr (SPLIT == 1) {
+      // three steps per k-tile over four fetched operand tiles, hand-scheduled form: the buffers (A0 | B0 | A1 | B1 = the two stages), DMA schedule
+      // and waits of the loop below, the three steps of a k-tile written out (one asm block each, with the DMA jobs that step can carry:
+      // KC_X0 / X1 / X2); running operand addresses, fragment addresses per buffer: a step's scalar set-up is a handful of instructions
+      const char* pa = tile_a;                           // A_hi of k-tile kt
+      const char* pb = tile_b;                           // B_hi of k-tile kt
+      const KJob none = {0, 0u, nullptr};
+      const unsigned coff = 4u * lane;
+      // k-tiles 0 .. nk-2 in one block (pipeline across the steps, barriers inside), then the last k-tile block by block: its step 0 needs no
+      // barrier (A0, B0 landed before the block's last barrier; it requests nothing - A_hi, B_lo of this k-tile are on their way since then)
+      if (landed) __builtin_amdgcn_s_waitcnt(0xC07F);
+      else __builtin_amdgcn_s_waitcnt(0x0070);
+      __builtin_amdgcn_s_barrier();
+#ifdef MP_GEMM_DIAG
+      const unsigned long long tp0 = __builtin_readcyclecounter();
+#endif
+      kpipe_x3(acc, kfa, kfb, aoff, boff, dma_wave, dma_l, pa, pb, a_lo, b_lo, nk - 1);
+#pragma unroll
+      for (int i = 0; i < NP; ++i) boff[i] -= (unsigned)(nk - 1) * (GBK * 2);      // (the B offsets are the same for every tile: back to k-tile 0)
+      pa += (long)(nk - 1) * GBK * 2; pb += (long)(nk - 1) * kstep_b;
+      const int more_i = has_next_i;
+      kstep_asm<TRB, KC_X0>(acc, kfa[0], kfb[0], none, aoff, none, boff, none, coff);
+      if (more_i) persist_offsets_n<0, NP>(aoff, g.lda, m0n, g.M, opaque(lane), dma_first);
+#ifdef MP_GEMM_DIAG
+      unsigned long long tk0 = __builtin_readcyclecounter(), tk1, tk2;
+      dg_mma += tk0 - tp0;
+#endif
+      __builtin_amdgcn_s_waitcnt(0x0078);               // vmcnt(8): A_hi has landed, B_lo behind it may still be in flight
+      MP_KDIAG_A();
+      __builtin_amdgcn_s_barrier();
+      MP_KDIAG_B();
+      kstep_asm<TRB, KC_X1>(acc, kfa[1], kfb[0], KJob{more_i & dma_wave, dma_l, tile_an + a_lo}, aoff, none, boff, none, coff);
+      MP_KDIAG_C();
+      if (more_i) __builtin_amdgcn_s_waitcnt(0x0078);   // B_lo has landed, the next tile's A_lo may still be in flight
+      else __builtin_amdgcn_s_waitcnt(0x0070);
+      MP_KDIAG_A();
+      __builtin_amdgcn_s_barrier();
+      MP_KDIAG_B();
+      kstep_asm<TRB, KC_X2>(acc, kfa[1], kfb[1], none, aoff, KJob{more_i & dma_wave, dma_l + OPB, tile_bn}, boff,
+                            KJob{has_bias_i, img_l, reinterpret_cast<const char*>(g.bias + n0 + wc * 64)}, coff);
+      MP_KDIAG_C();
       (void)stage;
     } else if constexpr (SPLIT & 1) {
+      // hipcc's three-product loop (diagnostics build: the MFMA-stage ablations SPLIT = 3 / 5 / 7).
       // three steps per k-tile over four fetched operand tiles; buffers A0 | B0 | A1 | B1 = the two stages (see gemm_bf16_glds_kernel)
       char* const A0 = smem;
       char* const B0 = smem + OPB;
@@ -1255,85 +1213,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist_kernel(GemmB16Args g, i
       // vmcnt(4): requests retire in order, so B_lo has landed while the four A_lo requests issued behind it may still be in flight -
       // one of the two tiles the next step 0 needs has two steps to arrive instead of one.
       bool early = false;
-      if constexpr (KASM) {
-        // hand-scheduled form: the same buffers, DMA schedule and waits, the three steps of a k-tile written out (one asm block each, with the
-        // DMA jobs that step can carry: KC_X0 / X1 / X2); running operand addresses, fragment addresses per buffer: a step's scalar set-up
-        // is a handful of instructions
-        const char* pa = tile_a;                           // A_hi of k-tile kt
-        const char* pb = tile_b;                           // B_hi of k-tile kt
-        const KJob none = {0, 0u, nullptr};
-        const unsigned coff = 4u * lane;
-        constexpr bool PIPE = MP_KLOOP_PIPE && YOUNG && TRB == 0;
-        if constexpr (PIPE) {
-          // k-tiles 0 .. nk-2 in one block (pipeline across the steps, barriers inside), then the last k-tile block by block: its step 0 needs no
-          // barrier (A0, B0 landed before the block's last barrier; it requests nothing - A_hi, B_lo of this k-tile are on their way since then)
-          if (landed) __builtin_amdgcn_s_waitcnt(0xC07F);
-          else __builtin_amdgcn_s_waitcnt(0x0070);
-          __builtin_amdgcn_s_barrier();
-#ifdef MP_GEMM_DIAG
-          const unsigned long long tp0 = __builtin_readcyclecounter();
-#endif
-          kpipe_x3(acc, kfa, kfb, aoff, boff, dma_wave, dma_l, pa, pb, a_lo, b_lo, nk - 1);
-#pragma unroll
-          for (int i = 0; i < NP; ++i) boff[i] -= (unsigned)(nk - 1) * (GBK * 2);      // (the B offsets are the same for every tile: back to k-tile 0)
-          pa += (long)(nk - 1) * GBK * 2; pb += (long)(nk - 1) * kstep_b;
-          const int more_i = has_next_i;
-          kstep_asm<TRB, KC_X0>(acc, kfa[0], kfb[0], none, aoff, none, boff, none, coff);
-          if (more_i) persist_offsets_n<0, NP>(aoff, g.lda, m0n, g.M, opaque(lane), dma_first);
-#ifdef MP_GEMM_DIAG
-          unsigned long long tk0 = __builtin_readcyclecounter(), tk1, tk2;
-          dg_mma += tk0 - tp0;
-#endif
-          __builtin_amdgcn_s_waitcnt(0x0078);               // vmcnt(8): A_hi has landed, B_lo behind it may still be in flight
-          MP_KDIAG_A();
-          __builtin_amdgcn_s_barrier();
-          MP_KDIAG_B();
-          kstep_asm<TRB, KC_X1>(acc, kfa[1], kfb[0], KJob{more_i & dma_wave, dma_l, tile_an + a_lo}, aoff, none, boff, none, coff);
-          MP_KDIAG_C();
-          if (more_i) __builtin_amdgcn_s_waitcnt(0x0078);   // B_lo has landed, the next tile's A_lo may still be in flight
-          else __builtin_amdgcn_s_waitcnt(0x0070);
-          MP_KDIAG_A();
-          __builtin_amdgcn_s_barrier();
-          MP_KDIAG_B();
-          kstep_asm<TRB, KC_X2>(acc, kfa[1], kfb[1], none, aoff, KJob{more_i & dma_wave, dma_l + OPB, tile_bn}, boff,
-                                KJob{has_bias_i, img_l, reinterpret_cast<const char*>(g.bias + n0 + wc * 64)}, coff);
-          MP_KDIAG_C();
-        } else
-        for (int kt = 0; kt < nk; ++kt, pa += GBK * 2, pb += kstep_b) {
-          const bool last = kt + 1 == nk;
-          const int more_i = kflag_more(kt + 1, nk, has_next_i);
-#ifdef MP_GEMM_DIAG
-          unsigned long long tk0 = __builtin_readcyclecounter(), tk1, tk2;
-#endif
-          // step 0: (A0 = A_lo, B0 = B_hi); requests A_hi[kt] -> A1
-          if (kt == 0 && landed) __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0) only: (A_lo, B_hi) of this tile were waited for before the previous epilogue
-          else __builtin_amdgcn_s_waitcnt(0x0070);
-          MP_KDIAG_A();
-          __builtin_amdgcn_s_barrier();
-          MP_KDIAG_B();
-          kstep_asm<TRB, KC_X0>(acc, kfa[0], kfb[0], KJob{dma_wave, dma_l + STAGE, pa}, aoff, none, boff, none, coff);
-          MP_KDIAG_C();
-          // step 1: (A1 = A_hi, B0 = B_hi); requests B_lo[kt] -> B1, then A_lo of the next k-tile / tile -> A0
-          if (last && more_i) persist_offsets_n<0, NP>(aoff, g.lda, m0n, g.M, opaque(lane), dma_first);      // (opaque: the rows are recomputed here, not kept - spilled - across the tile)
-          __builtin_amdgcn_s_waitcnt(0x0070);
-          MP_KDIAG_A();
-          __builtin_amdgcn_s_barrier();
-          MP_KDIAG_B();
-          kstep_asm<TRB, KC_X1>(acc, kfa[1], kfb[0], KJob{more_i & dma_wave, dma_l, (last ? tile_an : pa + GBK * 2) + a_lo}, aoff, KJob{dma_wave, dma_l + STAGE + OPB, pb + b_lo}, boff,
-                                none, coff);
-          MP_KDIAG_C();
-          // step 2: (A1 = A_hi, B1 = B_lo); requests B_hi of the next k-tile / tile -> B0, and the bias behind the tile's last step.  It waits with
-          // vmcnt(4): B_lo has landed, the four A_lo requests issued behind it may still be in flight
-          if (more_i) __builtin_amdgcn_s_waitcnt(YOUNG ? 0x0078 : 0x0074);      // (younger-wave DMA: the A_lo job behind B_lo is 8 pieces)
-          else __builtin_amdgcn_s_waitcnt(0x0070);
-          MP_KDIAG_A();
-          __builtin_amdgcn_s_barrier();
-          MP_KDIAG_B();
-          kstep_asm<TRB, KC_X2>(acc, kfa[1], kfb[1], none, aoff, KJob{more_i & dma_wave, dma_l + OPB, last ? tile_bn : pb + kstep_b}, boff,
-                                KJob{kflag_last(kt + 1, nk, has_bias_i), img_l, reinterpret_cast<const char*>(g.bias + n0 + wc * 64)}, coff);
-          MP_KDIAG_C();
-        }
-      } else
       for (int kt = 0, term = 0; kt < nk;) {
 #ifdef MP_GEMM_DIAG
         const unsigned long long tk0 = __builtin_readcyclecounter();
@@ -1426,7 +1305,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist_kernel(GemmB16Args g, i
       char* nx = smem + (stage ^ 1) * STAGE;
       const bool last = ks + 1 == nk;
       const bool fetch = !MP_DBG(g, 2) && (!last || has_next);
-      const bool late = DMA_LATE_STEP >= 0 && wave >= 4;      // the SIMD partners of waves 0-3 multiply first and issue their DMA mid-step
+      const bool late = MMA_MID_STEP >= 0 && wave >= 4;      // (never: see mma_stage) the SIMD partners of waves 0-3 multiply first and issue their DMA mid-step
       auto issue = [&]() {
         persist_dma(nx, a_base(last ? m0n : m0, last ? 0 : ks + 1), aoff, wave);
         persist_dma(nx + OPB, b_base(last ? n0n : n0, last ? 0 : ks + 1), boff, wave);

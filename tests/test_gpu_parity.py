@@ -1435,7 +1435,7 @@ def test_bf16x3_linear_forward_epilogues(lib, M, N, K):
 
 @pytest.mark.parametrize("M,N,K,wgs", [(300, 256, 128, 0), (1027, 768, 192, 8), (2049, 768, 320, 8), (777, 512, 1024, 0), (5000, 1536, 512, 16), (4131, 256, 128, 8)])
 def test_bf16x3_persistent_loop_shapes(lib, M, N, K, wgs):
-    """The persistent split-precision kernel's hand-scheduled loop (csrc/gemm_bf16.hip, MP_KLOOP_PIPE: k-tiles 0 .. nk-2 of a tile in one
+    """The persistent split-precision kernel's hand-scheduled loop (csrc/gemm_bf16.hip, kpipe_x3: k-tiles 0 .. nk-2 of a tile in one
     pipelined asm block, the last k-tile block by block) forced on at small sizes: two k-tiles (one pass of the loop), odd k-tile counts, 16
     k-tiles, one tile per workgroup (no next tile to prefetch) and several (few workgroups: the next tile's first k-tile is fetched during
     the last), ragged last row panel; all three epilogues against the fp64 product and against the tiled kernels."""

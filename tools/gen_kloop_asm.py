@@ -2,12 +2,20 @@
 block per step - 64 v_mfma_f32_16x16x32_bf16 of a wave's 128 x 64 sub-tile, the 24 LDS fragment reads (ds_read_b128; the "T" operand of the
 dgrad through ds_read_b64_tr_b16), and the step's share of the operand DMA (global_load_lds_dwordx4), in a written-out order:
 
-  * fragments are requested TWO groups of 8 MFMAs ahead (hipcc's schedule: one group ahead, every wait an lgkmcnt(0)), into a ring of three A
-    slots and two B sets held in FIXED registers v[200:255] (clobbers of the block: sub-registers of an asm operand cannot be named, and the
-    transpose reads fill a fragment in two 64-bit halves); every wait is a counted lgkmcnt(N) that leaves the younger requests in flight;
-  * the first fragments of the step are requested BEFORE the step's DMA instructions are issued (hipcc: after), and the DMA instructions are
-    spread over the first four MFMA groups, one behind the third and one behind the sixth MFMA of a group (job b in groups 0-1, job a in 2-3);
-  * no VALU / SALU instruction except the DMA's m0 set-up stands between the MFMAs.
+  * fragments are requested one or two groups of 8 MFMAs ahead (hipcc's schedule: one group ahead, every wait an lgkmcnt(0)), into a ring of
+    three A slots and two B sets held in FIXED registers v[200:255] (clobbers of the block: sub-registers of an asm operand cannot be named, and
+    the transpose reads fill a fragment in two 64-bit halves); every wait is a counted lgkmcnt(N) that leaves the younger requests in flight;
+  * the step's DMA instructions stand at the head of the block, in front of its first fragment requests or right behind them (STEPS below);
+  * no VALU / SALU instruction stands between the MFMAs.
+
+The operand DMA is issued by the YOUNGER wave of every SIMD only (waves 4-7: eight pieces per tile each, every job behind a flag that is 0 in
+waves 0-3): the older wave wins the matrix pipe's arbitration, so DMA instructions in ITS head delay the SIMD's first MFMA of the step, while
+the younger wave waits for the pipe anyway.
+
+Exactly the blocks the kernel uses are emitted.  What was generated, measured and dropped (profiles/r05_probes,
+profiles/r06_probes; the code is in the history up to the commit "Fix the GEMM k-loop build switches at shipped values"): the same steps with
+the DMA from all eight waves (four pieces each), the DMA instructions spread over the first four MFMA groups, and the other placement / depth
+combinations of every step type.
 
     python tools/gen_kloop_asm.py            # rewrites the .inc
     python tools/gen_kloop_asm.py --check    # exit 1 if the committed .inc differs (CPU test)
@@ -18,8 +26,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "manipose_amd", "csrc", "kloop_asm.inc")
 
-FA0, FB0 = 200, 224          # A ring: 3 slots x 2 fragments x 4 registers; B: 2 sets (k-step parity) x 4 fragments x 4 registers (set per variant: `base`)
+FA0, FB0 = 200, 224          # A ring: 3 slots x 2 fragments x 4 registers; B: 2 sets (k-step parity) x 4 fragments x 4 registers
 NGROUP = 8                   # groups of 8 MFMAs: group g = (k-step g / 4, A fragments 2 (g % 4), 2 (g % 4) + 1) against the four B fragments
+PIECES = 8                   # DMA instructions (1 KiB each) per operand tile and issuing wave
 
 
 def vr(base, n=4):
@@ -40,90 +49,70 @@ def reads_a(g):
     return [f"ds_read_b128 {vr(fa(g % 3, f))}, %[aa{ks}] offset:{(2 * p + f) * 2048}" for f in range(2)], 2
 
 
-def reads_b(kidx, trb, img="ba"):
-    """requests of the four B fragments of the k-step with running index kidx (register set kidx % 2, address operands of image `img`)"""
+def reads_b(kidx, trb):
+    """requests of the four B fragments of the k-step with running index kidx (register set kidx % 2)"""
     out = []
     ks = kidx % 2
     if trb == 0:
         for j in range(4):
-            out.append(f"ds_read_b128 {vr(fb(ks, j))}, %[{img}{ks}] offset:{j * 2048}")
+            out.append(f"ds_read_b128 {vr(fb(ks, j))}, %[ba{ks}] offset:{j * 2048}")
         return out, 4
-    t = {"ba": "bt", "bb": "bu"}[img]
     for j in range(4):       # "T" image (256 output columns per reduction row, 512-byte rows): two transpose reads, 4 rows apart, per fragment
         for h in range(2):
-            out.append(f"ds_read_b64_tr_b16 {vr(fb(ks, j) + 2 * h, 2)}, %[{t}{j}] offset:{ks * 16384 + h * 2048}")
+            out.append(f"ds_read_b64_tr_b16 {vr(fb(ks, j) + 2 * h, 2)}, %[bt{j}] offset:{ks * 16384 + h * 2048}")
     return out, 8
 
 
-def dma(job, n, guarded=True):
-    """DMA instruction n of job 'a' / 'b': 1 KiB = 64 lanes x 16 bytes from (SGPR base + per-lane offset) to the LDS address in m0"""
-    L = f".Lkd{job}{n}_%="
-    body = [f"s_add_u32 m0, %[lds{job}], {n * 1024}",
-            "s_nop 0",
-            f"global_load_lds_dwordx4 %[{job}o{n}], %[gb{job}]"]
-    if not guarded:
-        return body
-    return [f"s_cmp_eq_u32 %[en{job}], 0", f"s_cbranch_scc1 {L}"] + body + [f"{L}:"]
-
-
-def dma_job(job, mode="cond", pieces=4):
-    """all instructions of a job: mode 'always' (unconditional), 'cond' (behind ONE test of its enable flag), 'none' (nothing)"""
-    if mode == "none":
+def dma_job(job, jobs):
+    """the instructions of operand job 'a' / 'b' if the step carries it, behind ONE test of its enable flag; an instruction moves 1 KiB =
+    64 lanes x 16 bytes from (SGPR base + per-lane offset) to the LDS address in m0"""
+    if job not in jobs:
         return []
     out = []
-    for n in range(pieces):
-        out += dma(job, n, guarded=False)
-    if mode == "always":
-        return out
+    for n in range(PIECES):
+        out += [f"s_add_u32 m0, %[lds{job}], {n * 1024}", "s_nop 0", f"global_load_lds_dwordx4 %[{job}o{n}], %[gb{job}]"]
     L = f".Lkj{job}_%="
     return [f"s_cmp_eq_u32 %[en{job}], 0", f"s_cbranch_scc1 {L}"] + out + [f"{L}:"]
 
 
-def bias_dma(mode="always"):
-    if mode == "none":
+def bias_dma(jobs):
+    if "c" not in jobs:
         return []
-    out = ["s_mov_b32 m0, %[ldsc]", "s_nop 0", "global_load_lds_dword %[co], %[gbc]"]
-    if mode == "always":
-        return out
-    return ["s_cmp_eq_u32 %[enc], 0", "s_cbranch_scc1 .Lkdc_%="] + out + [".Lkdc_%=:"]
+    return ["s_cmp_eq_u32 %[enc], 0", "s_cbranch_scc1 .Lkdc_%=", "s_mov_b32 m0, %[ldsc]", "s_nop 0", "global_load_lds_dword %[co], %[gbc]", ".Lkdc_%=:"]
 
 
-# Job configurations of a step: which DMA jobs it can carry (a / b = the four pieces of an A / B operand tile, c = the bias row); a job is
-# 'always' there, 'none', or 'cond' = behind one test of a wave-uniform flag in a scalar register (%[ena] / %[enb] / %[enc]):
+# The step types.  jobs = the DMA jobs a step can carry (a / b = the eight pieces of an A / B operand tile, c = the bias row), each behind one
+# test of a wave-uniform flag in a scalar register (%[ena] / %[enb] / %[enc]).  ONE asm block per step type: two blocks on the two sides of a
+# branch make hipcc reconcile the 128 accumulator registers through scratch memory.
 #   X0 / X1 / X2  the three steps of a k-tile of the split-precision loop: (A_lo, B_hi) requests A_hi; (A_hi, B_hi) requests B_lo and - unless
 #                 this is the launch's last k-tile - the next A_lo; (A_hi, B_lo) requests the next B_hi likewise, and the bias behind the tile's last step
 #   P             a step of the plain loop: both operands of the next k-tile unless it is the launch's last, the bias behind a tile's last step
-# ONE asm block per step type: two blocks on the two sides of a branch make hipcc reconcile the 128 accumulator registers through scratch memory.
-CONFIGS = {"X0": dict(a="always", b="none", c="none"), "X1": dict(a="cond", b="always", c="none"), "X2": dict(a="none", b="cond", c="cond"),
-           "P": dict(a="cond", b="cond", c="cond"),
-           # the same steps with the operand DMA issued by the YOUNGER wave of every SIMD only (waves 4-7: eight pieces per tile each, every job
-           # behind a flag that is 0 in waves 0-3): the older wave wins the matrix pipe's arbitration, so DMA instructions in ITS head delay the
-           # SIMD's first MFMA of the step, while the younger wave waits for the pipe anyway
-           "Z0": dict(a="cond", b="none", c="none", pieces=8), "Z1": dict(a="cond", b="cond", c="none", pieces=8),
-           "Z2": dict(a="none", b="cond", c="cond", pieces=8), "ZP": dict(a="cond", b="cond", c="cond", pieces=8)}
-# schedule variants of the f16f8 steps (MP_KSTEP_VARIANT_F8): measured on the block of four GEMMs at B = 79, same box (profiles/r06_probes/f16f8_step_variants.log)
-F8_VARIANTS = {0: dict(dma="head_before", ahead=1), 1: dict(dma="head_before", ahead=2), 2: dict(dma="head_after", ahead=2)}
-# (emitted separately, "N" operands only) the f16f8 loop's steps
-F8_CONFIGS = {"ZF": dict(a="cond", b="cond", c="none", pieces=8), "ZE": dict(a="cond", b="cond", c="cond", pieces=8)}
-
-# Variants (MP_KSTEP_VARIANT selects one at compile time; the A/B of round 5 is in DESIGN.md section 5):
-#   dma    'spread'       one DMA instruction behind the third and the sixth MFMA of groups 0-3 (job b in groups 0-1, job a in 2-3)
-#          'head_before'  both jobs in front of the step's first fragment request (what hipcc makes of the HIP source)
-#          'head_after'   both jobs behind the step's first fragment requests, in front of the first wait (their issue overlaps the LDS latency)
-#   ahead  1 / 2          fragment requests one / two groups of 8 MFMAs ahead of their use
-VARIANTS = {
-    0: dict(dma="head_before", ahead=1),     # hipcc's own order, written out (measured: best for the plain loop)
-    2: dict(dma="head_after", ahead=2),      # (measured: best for the split-precision loop; 1 = head_before / ahead 2 and 3 = spread / ahead 2 were slower)
+#   F / E         the two steps of a k-tile of the "f16f8" loop (SPLIT = 8; forward): F = the fp16 planes (the plain step with the fp16
+#                 instruction; requests the k-tile's correction tiles), E = the correction planes (step_f8; requests the next k-tile's / tile's fp16 tiles)
+# dma    'head_before'  the jobs in front of the step's first fragment request (what hipcc makes of the HIP source)
+#        'head_after'   the jobs behind the step's first fragment requests, in front of the first wait (their issue overlaps the LDS latency)
+# ahead  1 / 2          fragment requests one / two groups of 8 MFMAs ahead of their use
+# trb    the B operand's LDS images the step exists for: 0 = "N" (forward), 1 = "T" (dgrad; only the plain loop has one)
+# Measured, same box, alternating, block of four GEMMs (DESIGN.md section 5):
+#   split-precision loop (profiles/r05_probes/kstep_variants.log): head_before / 1: 3626-3635 us, head_before / 2: 3629-3656, head_after / 2:
+#     3608-3615 (kept), DMA spread over MFMA groups 0-3 / 2: 3677-3688; hipcc's own schedule 3803-3812
+#   plain loop, dgrad (same log): head_before / 1: 1213-1218 us (kept), head_before / 2: 1206-1219, head_after / 2: 1222, spread / 2: 1244-1246;
+#     hipcc 1231-1240
+#   f16f8 steps at B = 79 (profiles/r06_probes/f16f8_step_variants.log): head_before / 1: 2577-2583 us (kept), head_after / 2: 2644-2648
+STEPS = {
+    "X0": dict(jobs="a", dma="head_after", ahead=2, trb=(0,)),
+    "X1": dict(jobs="ab", dma="head_after", ahead=2, trb=(0,)),
+    "X2": dict(jobs="bc", dma="head_after", ahead=2, trb=(0,)),
+    "P": dict(jobs="abc", dma="head_before", ahead=1, trb=(0, 1)),
+    "F": dict(jobs="ab", dma="head_before", ahead=1, trb=(0,), mfma="v_mfma_f32_16x16x32_f16"),
 }
+E_JOBS = "abc"
 
 
-def step(trb, cfg, dma="spread", ahead=2, base=200, pad=False, mfma="v_mfma_f32_16x16x32_bf16"):
+def step(trb, jobs, dma, ahead, mfma="v_mfma_f32_16x16x32_bf16"):
     """the instruction list of one step; `pend` = request batches in flight, oldest first, as (group that needs them, count)"""
-    global FA0, FB0
-    FA0, FB0 = base, base + 24
     ins = []
     pend = []
-    jm = CONFIGS.get(cfg) or F8_CONFIGS[cfg]
 
     def request(lines, n, needed_by):
         ins.extend(lines)
@@ -132,20 +121,11 @@ def step(trb, cfg, dma="spread", ahead=2, base=200, pad=False, mfma="v_mfma_f32_
     def wait_for(g):          # everything group g needs has landed; younger batches stay in flight
         younger = sum(n for need, n in pend if need > g)
         ins.append(f"s_waitcnt lgkmcnt({younger})")
-        if pad:
-            ins.append("s_nop 0")
         pend[:] = [(need, n) for need, n in pend if need > g]
 
-    images = jm.get("images", ("ba",))
-    npc = jm.get("pieces", 4)
-    ng = NGROUP * len(images)             # groups of 8 MFMAs in this block: 8 per (A image, B image) pair
-
-    def img_of(g):
-        return images[g // NGROUP]
-
     if dma == "head_before":
-        ins.extend(dma_job("b", jm["b"], npc) + dma_job("a", jm["a"], npc))
-    rb, nb = reads_b(0, trb, img_of(0))
+        ins.extend(dma_job("b", jobs) + dma_job("a", jobs))
+    rb, nb = reads_b(0, trb)
     request(rb, nb, 0)
     r, n = reads_a(0)
     request(r, n, 0)
@@ -153,10 +133,10 @@ def step(trb, cfg, dma="spread", ahead=2, base=200, pad=False, mfma="v_mfma_f32_
         r, n = reads_a(1)
         request(r, n, 1)
     if dma == "head_after":
-        ins.extend(dma_job("b", jm["b"], npc) + dma_job("a", jm["a"], npc))
+        ins.extend(dma_job("b", jobs) + dma_job("a", jobs))
     wait_for(0)
-    for g in range(ng):
-        kidx, p = g // 4, g % 4           # running k-step index (two per image pair), A fragment pair inside it
+    for g in range(NGROUP):
+        kidx, p = g // 4, g % 4           # k-step index, A fragment pair inside it
         slot = g % 3
         mf = []
         for f in range(2):
@@ -166,39 +146,33 @@ def step(trb, cfg, dma="spread", ahead=2, base=200, pad=False, mfma="v_mfma_f32_
         ins.append(mf[0])
         # requests issued behind the first MFMA of the group: the fragments of group g + ahead (B of the next k-step with its first A)
         t = g + ahead
-        if t < ng:
+        if t < NGROUP:
             if t % 4 == 0:
-                rb, nb = reads_b(t // 4, trb, img_of(t))
+                rb, nb = reads_b(t // 4, trb)
                 request(rb, nb, t)
             r, n = reads_a(t)
             request(r, n, t)
-        ins.extend(mf[1:3])
-        if dma == "spread" and g < 4 and jm["ba"[g // 2]] != "none":
-            ins.extend(globals()["dma"]("ba"[g // 2], 2 * (g % 2), guarded=jm["ba"[g // 2]] == "cond"))
-        ins.extend(mf[3:6])
-        if dma == "spread" and g < 4 and jm["ba"[g // 2]] != "none":
-            ins.extend(globals()["dma"]("ba"[g // 2], 2 * (g % 2) + 1, guarded=jm["ba"[g // 2]] == "cond"))
+        ins.extend(mf[1:6])
         if g == 4:
-            ins.extend(bias_dma(jm["c"]))
+            ins.extend(bias_dma(jobs))
         ins.extend(mf[6:8])
-        if g + 1 < ng:
+        if g + 1 < NGROUP:
             wait_for(g + 1)
     assert not pend, pend
     return ins
 
 
-def step_f8(cfg, dma="head_after", ahead=2, base=200):
+def step_f8(jobs):
     """The correction step of the "f16f8" operand form (gemm_bf16.hip, SPLIT = 8) as one block: 32 v_mfma_scale_f32_16x16x128_f8f6f4 of a wave's
     128 x 64 sub-tile - one per 16 x 16 block, 128 reduction BYTES deep (the whole 64-index k-tile of the 2-byte correction planes), 8 passes each:
     the same 1024 matrix-pipe cycles as the 64 bf16 / fp16 MFMAs of the other steps.  A fragment = the lane's 16-byte chunks g and g + 4 of its
     row (two ds_read_b128 through the step's two A address operands: exactly the k-step 0 / 1 fragments of the 16-bit steps), 8 registers; ring of
     three A fragments (one group of four MFMAs each), the four B fragments stay for the step: 24 + 32 = the same 56 fixed registers.  The E8M0 block
-    scales (2^-15 on the first source, 1 on the second; all lanes and blocks alike) come in two VGPR operands.  Requests: B0, A0 first - the first
-    MFMA waits for those four reads only - then B1..B3 and A1; A(g + ahead) behind the first MFMA of group g; counted waits throughout."""
+    scales (2^-15 on the first source, 1 on the second; all lanes and blocks alike) come in two VGPR operands.  The DMA jobs stand in front of the
+    first request (head_before).  Requests: B0, A0 first - the first MFMA waits for those four reads only - then B1..B3; A(g + 1) behind the
+    second MFMA of group g; counted waits throughout."""
     ins, pend = [], []          # pend: request batches in flight, oldest first, as (tag, count)
-    jm = F8_CONFIGS[cfg]
-    npc = jm.get("pieces", 4)
-    A0, B0 = base, base + 24
+    A0, B0 = FA0, FB0
 
     def req(tag, lines):
         ins.extend(lines)
@@ -217,38 +191,28 @@ def step_f8(cfg, dma="head_after", ahead=2, base=200):
         r = B0 + j * 8
         return [f"ds_read_b128 {vr(r)}, %[ba0] offset:{j * 2048}", f"ds_read_b128 {vr(r + 4)}, %[ba1] offset:{j * 2048}"]
 
-    jobs = dma_job("b", jm["b"], npc) + dma_job("a", jm["a"], npc)
-    if dma == "head_before":
-        ins.extend(jobs)
+    ins.extend(dma_job("b", jobs) + dma_job("a", jobs))
     req("b0", rb(0)); req("a0", ra(0))
     for j in (1, 2, 3):
         req(f"b{j}", rb(j))
-    if ahead >= 2:
-        req("a1", ra(1))
-    if dma != "head_before":
-        ins.extend(jobs)
-    live = {"b0", "a0", "b1", "b2", "b3"} | ({"a1"} if ahead >= 2 else set())
     for g in range(8):
-        if f"a{g}" in live:
-            wait(f"a{g}") if g else wait("a0")
-            live.discard(f"a{g}")
+        wait(f"a{g}")
         for j in range(4):
-            if f"b{j}" in live and any(t == f"b{j}" for t, _ in pend):
+            if any(t == f"b{j}" for t, _ in pend):
                 wait(f"b{j}")
-            live.discard(f"b{j}")
             c = f"%[c{g}{j}]"
             ins.append(f"v_mfma_scale_f32_16x16x128_f8f6f4 {c}, {vr(B0 + j * 8, 8)}, {vr(A0 + (g % 3) * 8, 8)}, {c}, %[sca], %[scb] op_sel_hi:[0,0,0]")
             # (behind the group's SECOND MFMA: the ring slot's last reader - the previous group's last MFMA - is then two 8-pass MFMAs back)
-            if j == 1 and g + ahead < 8:
-                req(f"a{g + ahead}", ra(g + ahead)); live.add(f"a{g + ahead}")
+            if j == 1 and g + 1 < 8:
+                req(f"a{g + 1}", ra(g + 1))
             if j == 2 and g == 4:
-                ins.extend(bias_dma(jm["c"]))
+                ins.extend(bias_dma(jobs))
     assert not pend, pend
     return ins
 
 
 def pipe_loop_x3(ahead=2):
-    """The split-precision loop's k-tiles 0 .. nk-2 of a tile as ONE asm block with the loop inside (MP_KLOOP_PIPE): the fragment pipeline runs
+    """The split-precision loop's k-tiles 0 .. nk-2 of a tile as ONE asm block with the loop inside: the fragment pipeline runs
     ACROSS the steps.  A step's barrier does not stand in front of it but two groups of 8 MFMAs before its end, in front of the first
     request that reads the NEXT step's buffers: behind `s_waitcnt vmcnt(V) lgkmcnt(0); s_barrier` every wave has finished reading this
     step's buffers (so the DMA into them may be issued at once) and the next step's tiles have landed for every wave; each wave still holds
@@ -260,8 +224,6 @@ def pipe_loop_x3(ahead=2):
     Entry (behind the tile's first barrier): the head requests, then A_hi[0], B_lo[0].  DMA by waves 4-7 only (8 pieces of a tile each);
     source = a constant base per plane (+ 128 bytes: "the next k-tile") + the per-lane offsets, which advance by 128 bytes per k-tile.
     The tile's last k-tile runs in the block-per-step form (its jobs depend on the next tile).  "N" operand layout only (forward)."""
-    global FA0, FB0
-    FA0, FB0 = 200, 224
     OPB, STAGE = 32768, 65536
     ins, pend = [], []
     A = {0: ("a0k0", "a0k1"), 1: ("a1k0", "a1k1")}
@@ -289,7 +251,7 @@ def pipe_loop_x3(ahead=2):
 
     def job(lds_const, base, offs, imm=0):
         out = []
-        for n in range(8):
+        for n in range(PIECES):
             out += [f"s_add_u32 m0, %[lds], {lds_const + n * 1024}", "s_nop 0",
                     f"global_load_lds_dwordx4 %[{offs}{n}], %[{base}]" + (f" offset:{imm}" if imm else "")]
         return out
@@ -353,38 +315,23 @@ HEADER = """// GENERATED by tools/gen_kloop_asm.py - do not edit (tests/test_hos
 
 def emit():
     out = [HEADER]
-    for v, opt in sorted(VARIANTS.items()):
-        for cfg in CONFIGS:
-            for trb in (0, 1):
-                lines = step(trb, cfg, **opt)
-                out.append(f"#define MP_KSTEP_ASM_{cfg}_TRB{trb}_V{v} \\")
-                for i, l in enumerate(lines):
-                    out.append(f'  "{l}\\n"' + (" \\" if i + 1 < len(lines) else ""))
-                out.append("")
-    # the two steps of a k-tile of the "f16f8" loop (SPLIT = 8; forward, "N" operands, DMA by waves 4-7): F = the fp16 planes (the plain step with the
-    # fp16 instruction; it always requests the k-tile's correction tiles), E = the correction planes (requests the next k-tile's / tile's fp16 tiles)
-    for v, opt in sorted(F8_VARIANTS.items()):
-        lines = step(0, "ZF", mfma="v_mfma_f32_16x16x32_f16", **opt)
-        out.append(f"#define MP_KSTEP_ASM_ZF_TRB0_V{v} \\")
+
+    def macro(name, lines):
+        out.append(f"#define {name} \\")
         for i, l in enumerate(lines):
             out.append(f'  "{l}\\n"' + (" \\" if i + 1 < len(lines) else ""))
         out.append("")
-        lines = step_f8("ZE", **opt)
-        out.append(f"#define MP_KSTEP_ASM_ZE_TRB0_V{v} \\")
-        for i, l in enumerate(lines):
-            out.append(f'  "{l}\\n"' + (" \\" if i + 1 < len(lines) else ""))
-        out.append("")
-    lines = pipe_loop_x3()
-    out.append("#define MP_KPIPE_X3_ASM \\")
-    for i, l in enumerate(lines):
-        out.append(f'  "{l}\\n"' + (" \\" if i + 1 < len(lines) else ""))
-    out.append("")
+
+    for cfg, opt in STEPS.items():
+        opt = dict(opt)
+        for trb in opt.pop("trb"):
+            macro(f"MP_KSTEP_ASM_{cfg}_TRB{trb}", step(trb, **opt))
+    macro("MP_KSTEP_ASM_E_TRB0", step_f8(E_JOBS))
+    macro("MP_KPIPE_X3_ASM", pipe_loop_x3())
     acc = ", ".join(f'[c{i}{j}] "+v"(acc[{i}][{j}])' for i in range(8) for j in range(4))
     out.append(f"#define MP_KSTEP_ACC_OPERANDS {acc}")
-    for v, opt in sorted(VARIANTS.items()):
-        b = opt.get("base", 200)
-        clob = ", ".join(f'"v{r}"' for r in range(b, b + 56))
-        out.append(f'#define MP_KSTEP_CLOBBERS_V{v} "memory", "scc", "m0", {clob}')      # m0: every block's DMA set-up writes it (a later compiler-made global_load_lds / readlane must re-initialise it)
+    clob = ", ".join(f'"v{r}"' for r in range(FA0, FA0 + 56))
+    out.append(f'#define MP_KSTEP_CLOBBERS "memory", "scc", "m0", {clob}')      # m0: every block's DMA set-up writes it (a later compiler-made global_load_lds / readlane must re-initialise it)
     out.append("")
     return "\n".join(out)
 
