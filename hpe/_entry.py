@@ -237,6 +237,33 @@ def sk_device(model):
     return next(model.parameters()).device
 
 
+def lift_sequences_to_file(model, cfg, groups, path):
+    """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
+    hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
+    it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4)."""
+    from manipose_amd import lift_sequences
+    out = {}
+    for name, seqs in groups.items():
+        res = lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=cfg.lift.agg, blend=cfg.lift.blend,
+                             return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test)
+        poses, hyps = res if cfg.lift.hyps else (res, None)
+        for i, p in enumerate(poses):
+            key = name if len(poses) == 1 else f"{name}.{i}"
+            out[key] = p.cpu().numpy()
+            if hyps is not None:
+                out[key + "__hyps"] = hyps[i].cpu().numpy()
+    np.savez(path, **out)
+    return out
+
+
+def synthetic_sequences_2d(cfg, seed):
+    """The 2-D side of the synthetic H36M-shaped action sequences (synthetic_generator), one group per sequence."""
+    rng = np.random.default_rng(seed)
+    n_seq = int(cfg.data.get("synthetic_sequences", 16))
+    lens = [int(cfg.data.seq_len) * 4 + 37 * (i % 5) + 11 for i in range(n_seq)]
+    return {f"synthetic_{i:03d}": [np.clip(0.3 * rng.standard_normal((n, 17, 2)), -1, 1).astype(np.float32)] for i, n in enumerate(lens)}
+
+
 def save_state(model, trainer, scheduler_state, epoch, folder, tag=None):
     tag = f"_{tag}" if tag else ""
     torch.save(model.state_dict(), os.path.join(folder, f"model{tag}.pth"))
@@ -396,4 +423,9 @@ def run(argv, extra_defaults=None):
         if len(rows) > 1 and rank == 0:
             keys = sorted({k for r in rows.values() for k in r})
             print("test [average over groups]:", {k: round(float(np.mean([r[k] for r in rows.values() if k in r])), 3) for k in keys}, flush=True)
+    if cfg.run.lift and rank == 0:         # after run.checkpoint_model / the training above: the weights the test ran on
+        groups = {name: sq[1] for name, sq in seqs["test"].items()} if real else synthetic_sequences_2d(cfg, cfg.run.seed)
+        path = cfg.lift.output if os.path.isabs(str(cfg.lift.output)) else os.path.join(out_dir, str(cfg.lift.output))
+        lifted = lift_sequences_to_file(model, cfg, groups, path)
+        print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if not k.endswith('__hyps'))} frames of {len(groups)} groups -> {path}", flush=True)
     return best_val

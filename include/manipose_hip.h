@@ -391,6 +391,31 @@ int mp_gather_windows(const float* poses_2d, const float* poses_3d, const int64_
                       const int32_t* win_start, const uint8_t* win_flip, const int32_t* mirror, const float* mask2d, const float* noise2d,
                       int B, int T, int J, float* X, float* y, void* stream);
 
+/* Sequence lifting: one 3-D pose per frame of whole 2-D keypoint sequences - the reference's lift_action (hpe/eval_utils.py:226-253, used by
+ * hpe/viz.py:84-91): windows with drop_last=False replicate padding (hpe/mh_so3_hpe/data/generators.py:93-104,135-154), the flip-TTA evaluation
+ * loop (eval_utils.py:84-142), predictions flattened to (windows * T, 17, 3) or, with return_hyps, (windows * T, K, 17, 4) with the score in the
+ * fourth channel.  Here the windows may also overlap (stride < T).
+ * mp_lift_windows_2d: mp_gather_windows for sequences that have no 3-D side - X (B,T,J,2) only, same tables, flags and padding.
+ * mp_lift_merge: the output side in one pass.  poses (F*W, K, T, J, 3) and scores (F*W, K, T[, 1]) as mp_model_forward leaves them (scores may be
+ * null when K == 1); F = 2 with tta != 0: windows W .. 2W-1 are the mirrored copies of windows 0 .. W-1.  win_seq / win_start (W) device int32 and
+ * seq_offset (S+1) device int64 as for mp_gather_windows; h_win_seq / h_win_start / h_seq_offset: HOST copies of the three tables, checked before
+ * anything is launched - windows sorted by sequence and then by start, every window starting inside its sequence, every frame of every sequence
+ * covered by a window (otherwise MP_ERR_ARG; a seq_offset that describes the padded lengths keeps the padded frames).  mirror (J) HOST int32.
+ * Per output frame f, over the windows w that cover it (win_start <= f < win_start + T), in increasing w:
+ *   p_w = sum_k score * pose (agg 0, "weighted_ave") or the pose of the first maximal score (agg 1, "best_score"; mp_aggregate's tie rule);
+ *   with tta, p_w = (p_w(window w) + unflip(p_w(window W + w))) / 2, unflip = x negated and joint j read from mirror[j], the mirrored half
+ *   aggregated with its own scores;
+ *   blend 0 "mean": out = mean of p_w; blend 1 "center": p_w of the window whose centre frame win_start + (T-1)/2 is nearest to f (the lower w on a
+ *   tie), no averaging.
+ * out (Ntot, J, 3) = scale * that (scale 1: metres).  hyps (Ntot, K, J, 4) or null: every hypothesis (times scale) and its score (never scaled) of
+ * the un-mirrored windows, blended over the windows by the same rule.  Gather, fixed summation order, no atomics: identical bits on every call. */
+int mp_lift_windows_2d(const float* poses_2d, const int64_t* seq_offset, int S, const int32_t* win_seq, const int32_t* win_start,
+                       const uint8_t* win_flip, const int32_t* mirror, int B, int T, int J, float* X, void* stream);
+int mp_lift_merge(const float* poses, const float* scores, int W, int K, int T, int J, int tta, const int32_t* win_seq,
+                  const int32_t* win_start, const int64_t* seq_offset, int S, const int32_t* h_win_seq, const int32_t* h_win_start,
+                  const int64_t* h_seq_offset, const int32_t* mirror, int agg, int blend, float scale, float* out, float* hyps,
+                  void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

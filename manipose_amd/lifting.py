@@ -1,0 +1,214 @@
+"""Whole-sequence lifting: 2-D keypoints ``(N, 17, 2)`` of any length in, one 3-D pose per frame out.
+
+Counterpart of the reference's ``lift_action`` (hpe/eval_utils.py:226-253, used by hpe/viz.py:84-91): windows with the
+``drop_last=False`` replicate padding of its generator (hpe/mh_so3_hpe/data/generators.py:93-104,135-154), the flip test-time
+augmentation of its evaluation loop (eval_utils.py:84-142) and the flattening of the predictions - here with windows that may
+overlap (``stride < T``) and everything on the device: the raw keypoints are uploaded once, ``mp_lift_windows_2d`` cuts the
+(mirrored) windows, the engine runs its no-backward forward, and ONE kernel (``mp_lift_merge``) aggregates the hypotheses, undoes
+the mirroring and blends the windows that cover a frame, reading every hypothesis once.
+
+Scheduling: a sequence is lifted on its own - its windows are cut into forwards of ``batch`` (``2 * batch`` with TTA), all of them
+stay resident until the sequence is merged, and no forward mixes two sequences.  A frame's covering windows are therefore always
+resident when it is merged (no partial sum is ever carried), and a sequence's result does not depend on what else is lifted with
+it: the engine's GEMM tile plan depends on the batch, so a window's bits do.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+AGG = {"weighted_ave": 0, "best_score": 1}
+BLEND = {"mean": 0, "center": 1}
+
+
+def plan_windows(lengths: Sequence[int], T: int, stride: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(win_seq, win_start) int32 tables of the windows that cover sequences of ``lengths`` frames: per sequence of N frames
+    ``1 + ceil(max(0, N - T) / stride)`` windows at starts 0, stride, 2 stride, ...  ``stride == T`` gives the reference's
+    ``_map_index_to_pose`` / ``_map_index_to_frame`` for ``drop_last=False`` (generators.py:93-104)."""
+    T, stride = int(T), int(stride)
+    if T < 1 or not 1 <= stride <= T:
+        raise ValueError(f"plan_windows: stride {stride} outside 1..T (T={T})")
+    seq, start = [], []
+    for s, n in enumerate(lengths):
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"plan_windows: sequence {s} has {n} frames")
+        nw = 1 + -(-max(0, n - T) // stride)
+        seq.append(np.full(nw, s, dtype=np.int32))
+        start.append(np.arange(nw, dtype=np.int32) * np.int32(stride))
+    if not seq:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32)
+    return np.concatenate(seq), np.concatenate(start)
+
+
+def _model_shape(model):
+    cfg = getattr(model, "_engine_cfg", None)
+    if cfg is None:
+        raise RuntimeError("manipose_amd: lift_sequences needs a MixSTE, ManifoldMixSTE or RMCLManifoldMixSTE model")
+    from .architectures import RMCLManifoldMixSTE
+    return int(cfg["num_frame"]), int(cfg["num_joints"]), int(model.n_hyp) if isinstance(model, RMCLManifoldMixSTE) else 1
+
+
+def _mirror(model, J):
+    from .data import h36m_skeleton
+    sk = model.decoder.skeleton if hasattr(model, "decoder") else h36m_skeleton()
+    m = list(range(J))
+    for l, r in zip(sk.joints_left, sk.joints_right):
+        m[l], m[r] = r, l
+    return (C.c_int32 * J)(*m)
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirror, agg="weighted_ave", blend="mean", scale=1.0,
+                  return_hyps=False, out=None, hyps=None, device_tables=None):
+    """``mp_lift_merge`` on device tensors: poses (F*W, K, T, J, 3), scores (F*W, K, T, 1) or None (K == 1); win_seq / win_start (W)
+    and seq_offset (S + 1) HOST numpy tables (uploaded here unless ``device_tables`` = their device copies is given).
+    Returns (out (Ntot, J, 3), hyps (Ntot, K, J, 4) or None)."""
+    if agg not in AGG:
+        raise ValueError(f"agg must be one of {sorted(AGG)}, got {agg!r} ('oracle' needs ground truth: hpe/_entry.py::evaluate)")
+    if blend not in BLEND:
+        raise ValueError(f"blend must be one of {sorted(BLEND)}, got {blend!r}")
+    lib = _lib.load()
+    F = 2 if tta else 1
+    h_seq = np.ascontiguousarray(win_seq, dtype=np.int32)
+    h_start = np.ascontiguousarray(win_start, dtype=np.int32)
+    h_off = np.ascontiguousarray(seq_offset, dtype=np.int64)
+    W, S = int(h_seq.size), int(h_off.size) - 1
+    K, J = int(poses.shape[1]), int(poses.shape[3])
+    assert poses.shape[0] == F * W and poses.shape[2] == T and poses.shape[4] == 3, "poses must be (F*W, K, T, J, 3)"
+    dev = poses.device
+    if device_tables is None:
+        device_tables = (torch.from_numpy(h_seq).to(dev), torch.from_numpy(h_start).to(dev), torch.from_numpy(h_off).to(dev))
+    d_seq, d_start, d_off = device_tables
+    ntot = int(h_off[-1]) if S >= 0 and h_off.size else 0
+    if out is None:
+        out = torch.empty(ntot, J, 3, dtype=torch.float32, device=dev)
+    if return_hyps and hyps is None:
+        hyps = torch.empty(ntot, K, J, 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mp_lift_merge(_lib.ptr(poses), _lib.ptr(scores), W, K, int(T), J, int(bool(tta)), _lib.ptr(d_seq), _lib.ptr(d_start),
+                                     _lib.ptr(d_off), S, _i32p(h_seq), _i32p(h_start), h_off.ctypes.data_as(C.POINTER(C.c_int64)), mirror,
+                                     AGG[agg], BLEND[blend], float(scale), _lib.ptr(out), _lib.ptr(hyps) if return_hyps else None,
+                                     _lib.stream_ptr()), "mp_lift_merge")
+    return out, (hyps if return_hyps else None)
+
+
+@torch.no_grad()
+def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
+                   keep_padding=False):
+    """One 3-D pose per frame of every sequence.  ``poses_2d``: a list of (N_i, 17, 2) device tensors or numpy arrays (or one such
+    array); returns a list of (N_i, 17, 3) device tensors, and with ``return_hyps`` also a list of (N_i, K, 17, 4) (every hypothesis
+    and its score, from the un-mirrored pass).  ``stride`` (default T: non-overlapping windows) in 1..T; ``blend`` "mean" averages the
+    windows that cover a frame, "center" takes the one whose centre is nearest; ``batch`` windows per forward (``2 * batch`` with
+    TTA; default: the model's ``max_batch_hint`` or 16).  ``keep_padding`` (stride == T only) also returns the replicate-padded
+    frames of the last window, as the reference's lift_action does."""
+    single = torch.is_tensor(poses_2d) or isinstance(poses_2d, np.ndarray)
+    seqs = [poses_2d] if single else list(poses_2d)
+    if not seqs:
+        return ([], []) if return_hyps else []
+    params = list(model.parameters())
+    if not params or not params[0].is_cuda:
+        raise RuntimeError("manipose_amd: lift_sequences needs the model on a ROCm device; there is no CPU fallback")
+    dev = params[0].device
+    for s in seqs:
+        if torch.is_tensor(s) and not s.is_cuda:
+            raise RuntimeError("manipose_amd: lift_sequences takes device tensors or numpy arrays (got a CPU tensor); there is no CPU fallback")
+    T, J, K = _model_shape(model)
+    stride = T if stride is None else int(stride)
+    if agg not in AGG or blend not in BLEND:
+        raise ValueError(f"agg in {sorted(AGG)} and blend in {sorted(BLEND)} expected, got {agg!r}, {blend!r}")
+    if keep_padding and stride != T:
+        raise ValueError("keep_padding describes the reference's non-overlapping windows: stride must be T")
+    for s in seqs:
+        if s.ndim != 3 or s.shape[1] != J or s.shape[2] != 2:
+            raise ValueError(f"every sequence must be (N, {J}, 2), got {tuple(s.shape)}")
+    lens = [int(s.shape[0]) for s in seqs]
+    win_seq, win_start = plan_windows(lens, T, stride)
+    first = np.concatenate([[0], np.cumsum(np.bincount(win_seq, minlength=len(lens)))]).astype(np.int64)     # first window of every sequence
+    if batch is None:
+        batch = (int(getattr(model, "max_batch_hint", 0)) // (2 if tta else 1)) or 16
+    batch = max(1, int(batch))
+    # everything the kernels read is uploaded once, up front
+    if all(torch.is_tensor(s) for s in seqs):
+        p2 = torch.cat([s.to(dev, torch.float32) for s in seqs], dim=0).contiguous()
+    else:
+        host = [s.detach().cpu().numpy() if torch.is_tensor(s) else np.asarray(s) for s in seqs]
+        p2 = torch.from_numpy(np.concatenate([h.astype(np.float32, copy=False) for h in host], axis=0)).to(dev).contiguous()
+    off = np.zeros(len(lens) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lens)
+    out_lens = [int(first[s + 1] - first[s]) * T if keep_padding else lens[s] for s in range(len(lens))]
+    merge_off = np.zeros((len(lens), 2), dtype=np.int64)                     # per sequence: the (S + 1 = 2) offsets of a one-sequence merge
+    merge_off[:, 1] = out_lens
+    d_off, d_merge_off = torch.from_numpy(off).to(dev), torch.from_numpy(merge_off).to(dev)
+    d_seq, d_start = torch.from_numpy(win_seq).to(dev), torch.from_numpy(win_start).to(dev)
+    max_nw = int(np.max(first[1:] - first[:-1]))
+    d_zero = torch.zeros(max_nw, dtype=torch.int32, device=dev)
+    h_zero = np.zeros(max_nw, dtype=np.int32)
+    d_flip = torch.ones(batch, dtype=torch.uint8, device=dev)
+    mirror = _mirror(model, J)
+    out_all = torch.empty(sum(out_lens), J, 3, dtype=torch.float32, device=dev)
+    hyp_all = torch.empty(sum(out_lens), K, J, 4, dtype=torch.float32, device=dev) if return_hyps else None
+    lib = _lib.load()
+    F = 2 if tta else 1
+    was_training = model.training
+    model.eval()
+    try:
+        o0 = 0
+        for s in range(len(lens)):
+            a0, nw = int(first[s]), int(first[s + 1] - first[s])
+            buf_p = buf_s = None
+            for a in range(0, nw, batch):
+                n = min(batch, nw - a)
+                X = torch.empty(F * n, T, J, 2, dtype=torch.float32, device=dev)
+                with torch.cuda.device(dev):
+                    for h in range(F):           # the mirrored copies of the n windows follow them, as evaluate() batches them
+                        _lib.check(lib.mp_lift_windows_2d(_lib.ptr(p2), _lib.ptr(d_off), len(lens), _lib.ptr(d_seq[a0 + a:]), _lib.ptr(d_start[a0 + a:]),
+                                                          _lib.ptr(d_flip) if h else None, mirror, n, T, J, _lib.ptr(X[h * n:]), _lib.stream_ptr()),
+                                   "mp_lift_windows_2d")
+                res = model(X)
+                poses, scores = res if isinstance(res, tuple) else (res, None)
+                poses = poses.reshape(F * n, K, T, J, 3)
+                if n == nw:                      # the whole sequence in one forward: merged where the engine left it
+                    buf_p, buf_s = poses, scores
+                    break
+                if buf_p is None:
+                    buf_p = torch.empty(F * nw, K, T, J, 3, dtype=torch.float32, device=dev)
+                    buf_s = torch.empty(F * nw, K, T, 1, dtype=torch.float32, device=dev) if scores is not None else None
+                for h in range(F):
+                    buf_p[h * nw + a:h * nw + a + n] = poses[h * n:(h + 1) * n]
+                    if scores is not None:
+                        buf_s[h * nw + a:h * nw + a + n] = scores[h * n:(h + 1) * n]
+            merge_windows(buf_p, buf_s, h_zero[:nw], win_start[a0:a0 + nw], merge_off[s], T=T, tta=tta, mirror=mirror, agg=agg, blend=blend,
+                          scale=scale, return_hyps=return_hyps, out=out_all[o0:o0 + out_lens[s]],
+                          hyps=hyp_all[o0:o0 + out_lens[s]] if return_hyps else None,
+                          device_tables=(d_zero[:nw], d_start[a0:a0 + nw], d_merge_off[s]))
+            o0 += out_lens[s]
+    finally:
+        model.train(was_training)
+    outs = list(torch.split(out_all, out_lens, dim=0))
+    if return_hyps:
+        return outs, list(torch.split(hyp_all, out_lens, dim=0))
+    return outs
+
+
+def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
+    """The reference-shaped wrapper (lift_action, hpe/eval_utils.py:226-253): non-overlapping windows, ``config.train.tta``, the padded
+    frames of every sequence's last window kept; numpy (windows * T, 17, 3) in metres, or with ``return_hyps`` (multi-hypothesis
+    models only, as in the reference) (windows * T, K, 17, 4) with the score in the fourth channel."""
+    from .architectures import RMCLManifoldMixSTE
+    tta = bool(config.train.tta) if hasattr(config, "train") else bool(config["train"]["tta"])
+    hyps = bool(return_hyps) and isinstance(model, RMCLManifoldMixSTE)
+    res = lift_sequences(model, poses_2d, stride=None, tta=tta, return_hyps=hyps, keep_padding=True)
+    res = res[1] if hyps else res
+    return torch.cat(res, dim=0).cpu().numpy()
+
+
+__all__ = ["plan_windows", "merge_windows", "lift_sequences", "lift_action"]

@@ -1,0 +1,91 @@
+"""Output stage of sequence lifting, two forms on the same hypotheses and scores in one process (frames per second, HIP events):
+  (a) the composition of existing ops the evaluation path uses (hpe/_entry.py::evaluate): mp_aggregate on the original half, clone +
+      pose_flip of the mirrored hypotheses, mp_aggregate, average - "weighted_ave" only, and with "best_score" as evaluate computes both;
+  (b) mp_lift_merge (one kernel).
+Then lift_sequences end to end (gather + forward + merge) at the same batch.
+    python tools/lift_bench.py [W=158] [T=243] [K=5] [precision=bf16x3] [reps=50]"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+from manipose_amd import RMCLManifoldMixSTE, h36m_skeleton, lift_sequences, plan_windows
+from manipose_amd.augmentations import pose_flip
+from manipose_amd.lifting import _mirror, merge_windows
+
+W = int(sys.argv[1]) if len(sys.argv) > 1 else 158
+T = int(sys.argv[2]) if len(sys.argv) > 2 else 243
+K = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+prec = sys.argv[4] if len(sys.argv) > 4 else "bf16x3"
+reps = int(sys.argv[5]) if len(sys.argv) > 5 else 50
+assert torch.cuda.is_available(), "needs an MI355X"
+sk = h36m_skeleton()
+torch.manual_seed(0)
+model = RMCLManifoldMixSTE(sk, num_frame=T, n_hyp=K, drop_path_rate=0.1)
+model.precision = prec
+model.max_batch_hint = 2 * W
+model = model.cuda().eval()
+g = torch.Generator(device="cuda").manual_seed(1)
+poses = 0.3 * torch.randn(2 * W, K, T, 17, 3, device="cuda", generator=g)
+scores = torch.softmax(torch.randn(2 * W, K, T, 1, device="cuda", generator=g), dim=1).contiguous()
+N = W * T
+win_seq, win_start = plan_windows([N], T, T)
+off = np.array([0, N], dtype=np.int64)
+tables = tuple(torch.from_numpy(a).cuda() for a in (win_seq, win_start, off))
+mirror = _mirror(model, 17)
+out = torch.empty(N, 17, 3, device="cuda")
+
+
+def composition(best):
+    pred = model.aggregate(poses[:W], scores[:W], "weighted_ave")
+    hyp_f = pose_flip((poses[W:].clone(),), sk)[0]
+    pred = (pred + model.aggregate(hyp_f, scores[W:], "weighted_ave")) / 2
+    if best:
+        b = (model.aggregate(poses[:W], scores[:W], "best_score") + model.aggregate(hyp_f, scores[W:], "best_score")) / 2
+        return pred, b
+    return pred
+
+
+def merge(agg="weighted_ave"):
+    return merge_windows(poses, scores, win_seq, win_start, off, T=T, tta=True, mirror=mirror, agg=agg, out=out, device_tables=tables)[0]
+
+
+def timed(fn):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(reps):
+        fn()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) / reps
+
+
+a = composition(False).reshape(N, 17, 3)
+b = merge().clone()
+print(f"W={W} T={T} K={K} TTA on, stride=T, {N} frames; max |composition - merge| = {(a - b).abs().max().item():.2e}", flush=True)
+must = 2 * W * K * T * (51 + 1) * 4 + N * 51 * 4           # every hypothesis and score read once, every output float written once
+rows = (("(a) composition, weighted_ave", lambda: composition(False)), ("(a) composition, weighted_ave + best_score (evaluate)", lambda: composition(True)),
+        ("(b) mp_lift_merge, weighted_ave", merge), ("(b) mp_lift_merge x2, weighted_ave + best_score", lambda: (merge(), merge("best_score"))))
+for name, fn in rows:
+    ms = timed(fn)
+    extra = f", {must / ms / 1e6:,.0f} GB/s of the {must / 1e6:.1f} MB it must move" if name.startswith("(b) mp_lift_merge,") else ""
+    print(f"{name}: {ms * 1e3:,.1f} us  {N / ms / 1e3:,.2f} M frames/s{extra}", flush=True)
+# end to end: one sequence of W windows, lifted at the bench's batch
+p2 = (0.3 * torch.randn(N, 17, 2, device="cuda", generator=g)).clamp(-1, 1)
+lift_sequences(model, [p2], batch=W)
+torch.cuda.synchronize()
+ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+n_e2e = 3
+ev[0].record()
+for _ in range(n_e2e):
+    lift_sequences(model, [p2], batch=W)
+ev[1].record()
+torch.cuda.synchronize()
+ms = ev[0].elapsed_time(ev[1]) / n_e2e
+print(f"lift_sequences end to end ({prec}, batch {W}, TTA on): {ms:,.1f} ms per {N} frames = {N / ms * 1e3:,.0f} frames/s", flush=True)
