@@ -6,6 +6,9 @@ evaluation of evaluate() (hpe/eval_utils.py:16-223: weighted-average, best-score
 With `data.data_dir` the reference's files (data_3d_h36m.npz + data_2d_h36m_<keypoints>.npz, or data_{train,test}_3dhp.npz) are
 ingested on the device (manipose_amd/data/ingest.py) and stay resident in HBM; without it the script trains / evaluates on synthetic
 H36M-shaped sequences so that the whole MI355X path (window kernel, engine, fused loss, RCCL data parallelism, fused Adam) runs.
+With `run.test` the files of the reference's test pass (main_h36m_lifting.py:840-1186: protocol_1_err.csv, seg_symmetry.csv, seg_consistency.csv,
+seg_max_strech.csv, seg_max_delta_strech.csv, cw_err.csv, jw_err.csv, all_seg_errs.npy, all_jw_err_var.npy; main_3dhp.py:769-988: its four single-row
+tables) are written into the experiment folder by rank 0 (manipose_amd/report.py); all_pred_hyps.pkl and the mlflow calls are not reproduced.
 Launch on N GPUs with `python -m torch.distributed.run --nproc-per-node N hpe/main_h36m_lifting.py ...`.
 """
 from __future__ import annotations
@@ -167,18 +170,23 @@ def tensor_batches(X, y, batch):
 
 
 @torch.no_grad()
-def evaluate(model, X, y=None, batch=None, tta=True, analytics=False, distributed=False):
+def evaluate(model, X, y=None, batch=None, tta=True, analytics=False, distributed=False, seg_err_samples=0):
     """MPJPE (mm) of the aggregated / best-score / oracle hypotheses, with the reference's flip test-time augmentation
     (hpe/eval_utils.py:16-223).  The flipped copy is batched with the original into ONE forward of 2B windows
     instead of a second pass.  ``analytics=True`` adds the reference's evaluation table (main_h36m_lifting.py:933-990,
     main_3dhp.py:860-910: MPSSE, MPSCE, segment-length error, MSE / error variance, 3DPCK, AUC, per-joint errors) of the
-    aggregated prediction in millimetres, from the one-pass HIP analytics kernel.  ``distributed=True``: every rank
+    aggregated prediction in millimetres, from the one-pass HIP analytics kernel, and the quantities that are not sums -
+    per-bone length extremes, the largest frame-to-frame jump of a bone length, MPJVE, per-coordinate errors, per-joint error variance
+    (main_h36m_lifting.py:1044-1089) - with all windows of all batches chained into ONE sequence (mp_bone_extremes).
+    ``seg_err_samples`` > 0 also returns ``seg_errs``: that many rows of the per-frame table gt - predicted bone length (mm), drawn like
+    the reference's all_seg_errs.npy (:992-1004) from the frames this rank evaluated.  ``distributed=True``: every rank
     evaluates its own share of the batches and the error sums / frame counts are sum-reduced at the end."""
     from manipose_amd import RMCLManifoldMixSTE
     from manipose_amd.augmentations import pose_flip
     from manipose_amd.metrics import mpjpe_error
     from manipose_amd.metrics.analytics import AnalyticsAccumulator, pose_analytics, procrustes_sums
     acc = AnalyticsAccumulator() if analytics else None
+    seg_tables = []
     model.eval()
     sk = model.decoder.skeleton if hasattr(model, "decoder") else _h36m()
     rmcl = isinstance(model, RMCLManifoldMixSTE)
@@ -213,6 +221,10 @@ def evaluate(model, X, y=None, batch=None, tta=True, analytics=False, distribute
         if acc is not None:
             acc.add(pose_analytics(pred.detach().contiguous(), yb.contiguous(), pred_scale=1000.0, gt_scale=1000.0))
             acc.add_procrustes(procrustes_sums(pred.detach(), yb, pred_scale=1000.0, gt_scale=1000.0))
+            acc.add_extremes(pred.detach().contiguous(), yb.contiguous(), pred_scale=1000.0, gt_scale=1000.0)
+            if seg_err_samples > 0:
+                from manipose_amd.metrics import segments_len_err
+                seg_tables.append(segments_len_err(pred.detach().permute(0, 3, 2, 1), yb.permute(0, 3, 2, 1), sk, mode="no_agg"))
     if distributed:
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -225,6 +237,11 @@ def evaluate(model, X, y=None, batch=None, tta=True, analytics=False, distribute
     out = {k: 1000.0 * v / n for k, v in sums.items() if v > 0}
     if acc is not None:
         out["analytics"] = acc.report()
+    if seg_tables:
+        from manipose_amd.report import draw_seg_err_rows
+        table = torch.cat(seg_tables, dim=0)
+        idx = draw_seg_err_rows(table.shape[0], seg_err_samples)             # the draw on the host, the gather on the device
+        out["seg_errs"] = (1000.0 * table[torch.as_tensor(idx, device=table.device)]).cpu().numpy()
     return out
 
 
@@ -410,12 +427,15 @@ def run(argv, extra_defaults=None):
         groups = {"synthetic": (valid_batches, valid_shared)}
         if real:        # per action (H36M: subject S11, main_h36m_lifting.py:884-990) or the whole 3DHP test set (main_3dhp.py:800-910)
             groups = {name: sharded(window_generator(cfg, sq, False, dev)) for name, sq in seqs["test"].items()}
-        rows = {}
+        from manipose_amd import report
+        rows, reports = {}, {}
         for name, (make, shared) in groups.items():
             if rank != 0 and not shared:
                 continue
-            res = evaluate(model, make(), tta=cfg.train.tta, analytics=True, distributed=shared)
+            res = evaluate(model, make(), tta=cfg.train.tta, analytics=True, distributed=shared, seg_err_samples=report.SEG_ERR_SAMPLES)
             table = res.pop("analytics")
+            reports[name] = dict(res, analytics=table)
+            res.pop("seg_errs", None)
             rows[name] = res
             if rank == 0:
                 print(f"test [{name}]:", {k: round(v, 3) for k, v in res.items()}, flush=True)
@@ -423,6 +443,13 @@ def run(argv, extra_defaults=None):
         if len(rows) > 1 and rank == 0:
             keys = sorted({k for r in rows.values() for k in r})
             print("test [average over groups]:", {k: round(float(np.mean([r[k] for r in rows.values() if k in r])), 3) for k in keys}, flush=True)
+        if rank == 0 and reports:              # the files behind the paper's tables (main_h36m_lifting.py:1158-1186, main_3dhp.py:978-988)
+            if real and cfg.data.dataset == "3dhp":
+                written = report.write_3dhp_report(out_dir, next(iter(reports.values()))["analytics"])
+            else:
+                from manipose_amd import RMCLManifoldMixSTE
+                written = report.write_h36m_report(out_dir, reports, rmcl=isinstance(model, RMCLManifoldMixSTE))
+            print(f"report: {len(written)} files -> {out_dir}", flush=True)
     if cfg.run.lift and rank == 0:         # after run.checkpoint_model / the training above: the weights the test ran on
         groups = {name: sq[1] for name, sq in seqs["test"].items()} if real else synthetic_sequences_2d(cfg, cfg.run.seed)
         path = cfg.lift.output if os.path.isabs(str(cfg.lift.output)) else os.path.join(out_dir, str(cfg.lift.output))

@@ -457,6 +457,27 @@ int mp_pose_metrics(const float* pred, const int64_t* pred_strides, const float*
                     int L, int J, float pred_scale, float gt_scale, float pck_threshold, float auc_max, int auc_steps, int scale_align,
                     float* out, float* len0, float* scratch, int64_t scratch_floats, void* stream);
 
+/* The evaluation quantities that are not sums (17-joint tree compiled in; bone k = (joint k+1, its parent)): per bone the smallest and the
+ * largest length over all B*L frames (segments_max_strech_per_bone, metrics/regularizations.py:63-74), the largest |len(f) - len(f-1)| with
+ * the index of the FIRST difference that attains it (segments_max_diff_strech_per_bone, :77-94; torch.max(dim) returns the first maximum),
+ * and the sums over all frames and joints of |gt - pred| per coordinate (coordwise_error, metrics/mean_joint_errors.py:133-141).  pred / gt
+ * are addressed through element strides of (b, t, j, c) as in mp_pose_metrics; a length is sqrtf(dx^2 + dy^2 + dz^2) of the scaled
+ * coordinates.  gt, gt_strides and coord_sums (3 floats) may be null together.
+ * chain = 0: differences inside every batch item only, index b (L-1) + t of the difference between frames t and t+1 of item b - the
+ *   reference function on a (B,3,J,L) tensor.
+ * chain = 1: the B*L frames are ONE sequence (the last frame of item b is followed by frame 0 of item b+1: the reference's (1,3,J,B*L)
+ *   reshape, main_h36m_lifting.py:1061-1085); the difference between frames f-1 and f has index frame_base + f - 1; with prev_len (16 floats
+ *   on the device, or null) frame 0 is differenced against it.  last_len (16 floats) receives the bone lengths of the last frame: pass it
+ *   as prev_len of the next call, with frame_base advanced by B*L, and a sequence can be fed in pieces with the result of one call.
+ * Outputs, on the device: min_len, max_len, max_delta (16 floats each), max_delta_idx (16 int64); without any difference (one frame and no
+ * prev_len, or chain = 0 with L = 1) max_delta is -1 and the index -1.  Deterministic (no atomics): the same bits in every run.
+ * scratch: >= mp_bone_extremes_scratch_floats(B*L) floats, 8-byte aligned. */
+int64_t mp_bone_extremes_scratch_floats(int64_t frames);
+int mp_bone_extremes(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int B, int L, int J,
+                     float pred_scale, float gt_scale, int chain, const float* prev_len, int64_t frame_base, float* min_len, float* max_len,
+                     float* max_delta, int64_t* max_delta_idx, float* coord_sums, float* last_len, float* scratch, int64_t scratch_floats,
+                     void* stream);
+
 /* Procrustes-aligned errors: per frame the similarity transform (scale, proper rotation, translation) taking the predicted joints onto
  * the target ones in the least-squares sense - p_mpjpe (hpe/mh_so3_hpe/metrics/mean_joint_errors.py:148-189, batched numpy SVD on the
  * host in the reference) and the 'procrustes' alignment of keypoint_3d_pck / keypoint_3d_auc (metrics/pck.py:5-60,127-131) - solved on

@@ -405,6 +405,19 @@ int mp_pose_metrics(const float* pred, const int64_t* pred_strides, const float*
                       scale_align, out, len0, scratch, (long)scratch_floats, (hipStream_t)stream);
 }
 
+int64_t mp_bone_extremes_scratch_floats(int64_t frames) { return (int64_t)bone_extremes_scratch_floats((long)frames); }
+int mp_bone_extremes(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int B, int L, int J,
+                     float pred_scale, float gt_scale, int chain, const float* prev_len, int64_t frame_base, float* min_len, float* max_len,
+                     float* max_delta, int64_t* max_delta_idx, float* coord_sums, float* last_len, float* scratch, int64_t scratch_floats,
+                     void* stream) {
+  MP_CHECK(pred && pred_strides, MP_ERR_ARG, "mp_bone_extremes: null pointer");
+  long ps[4], gs[4] = {0, 0, 0, 0};
+  for (int i = 0; i < 4; ++i) { ps[i] = (long)pred_strides[i]; if (gt_strides) gs[i] = (long)gt_strides[i]; }
+  return bone_extremes(pred, ps, gt, gt_strides ? gs : nullptr, B, L, J, pred_scale, gt_scale, chain, prev_len, (long)frame_base, min_len,
+                       max_len, max_delta, reinterpret_cast<long*>(max_delta_idx), coord_sums, last_len, scratch, (long)scratch_floats,
+                       (hipStream_t)stream);
+}
+
 /* test / tuning hooks (include/manipose_hip.h): process-wide selectors between kernels that are tested to agree; everything that changes a
  * model's arithmetic or its stream use is a field of mp_model_config */
 int mp_gemm_plan(int M, int N, int K, int form, int epilogue, int cus, int out[4]) {

@@ -232,6 +232,14 @@ int pose_metrics(const float* pred, const long* ps, const float* gt, const long*
                  float pred_scale, float gt_scale, float pck_thr, float auc_max, int auc_n, int scale_align, float* out, float* len0,
                  float* scratch, long scratch_floats, hipStream_t st);
 
+// ---------------------------------------------------------------- bone_extremes.hip
+// per-bone min / max length, largest frame-to-frame jump of a bone length with the index of its first occurrence, per-coordinate sums of
+// |gt - pred| and the last frame's bone lengths (include/manipose_hip.h, mp_bone_extremes)
+long bone_extremes_scratch_floats(long frames);
+int bone_extremes(const float* pred, const long* ps, const float* gt, const long* gs, int B, int L, int J, float pred_scale, float gt_scale,
+                  int chain, const float* prev_len, long frame_base, float* min_len, float* max_len, float* max_delta, long* max_delta_idx,
+                  float* coord_sums, float* last_len, float* scratch, long scratch_floats, hipStream_t st);
+
 // ---------------------------------------------------------------- windows.hip
 int gather_windows(const float* p2, const float* p3, const long* seq_offset, int S, const int* win_seq, const int* win_start,
                    const unsigned char* win_flip, const int* mirror, const float* mask2d, const float* noise2d, int B, int T, int J,

@@ -97,10 +97,73 @@ def pose_analytics(pred: torch.Tensor, gt: Optional[torch.Tensor] = None, layout
     return PoseAnalytics(rows, len0, B, L)
 
 
+@dataclass
+class BoneExtremes:
+    """Result of ``mp_bone_extremes`` (include/manipose_hip.h), all on the device."""
+    min_len: torch.Tensor       # (16,)
+    max_len: torch.Tensor       # (16,)
+    max_delta: torch.Tensor     # (16,) largest |len(f) - len(f-1)|; -1 without any difference
+    max_delta_idx: torch.Tensor  # (16,) int64 index of its first occurrence; -1 without any difference
+    coord_sums: Optional[torch.Tensor]   # (3,) sum of |gt - pred| per coordinate, or None without a target
+    last_len: torch.Tensor      # (16,) bone lengths of the last frame: ``prev_len`` of the next call
+    B: int
+    L: int
+
+
+def bone_extremes(pred: torch.Tensor, gt: Optional[torch.Tensor] = None, layout: str = "BLJC", pred_scale: float = 1.0,
+                  gt_scale: float = 1.0, chain: bool = False, prev_len: Optional[torch.Tensor] = None, frame_base: int = 0,
+                  skeleton=None) -> BoneExtremes:
+    """Per-bone length extremes, the largest frame-to-frame jump of every bone length and the per-coordinate error sums of one
+    tensor of frames (C ABI ``mp_bone_extremes``).  ``layout`` as in ``pose_analytics``.  ``chain=False``: jumps inside every batch
+    item, index ``b (L-1) + t``; ``chain=True``: the B*L frames are one sequence, continued from ``prev_len`` (the ``last_len`` of
+    the call before) when given, index ``frame_base + f - 1``."""
+    if skeleton is not None:
+        assert_h36m(skeleton)
+    if pred.device.type != "cuda":
+        raise RuntimeError("manipose_amd: bone extremes run on the ROCm device only (HIP kernel, no CPU fallback)")
+    order = {"BLJC": (0, 1, 2, 3), "BCJL": (0, 3, 2, 1)}[layout]
+    if pred.dim() != 4 or pred.dtype != torch.float32:
+        raise AssertionError(f"expected a 4-D float32 tensor in layout {layout}, got {tuple(pred.shape)} {pred.dtype}")
+    B, L, J, Cc = (pred.shape[i] for i in order)
+    if Cc != 3 or J != NJ:
+        raise AssertionError(f"expected 3 coordinates of {NJ} joints, got J={J}, C={Cc}")
+    if gt is not None and (gt.shape != pred.shape or gt.dtype != torch.float32 or gt.device != pred.device):
+        raise AssertionError("prediction and target must have the same shape, dtype and device")
+    if prev_len is not None and (prev_len.device != pred.device or prev_len.dtype != torch.float32 or prev_len.numel() != NB):
+        raise AssertionError("prev_len must hold 16 float32 bone lengths on the prediction's device")
+    lib = _lib.load()
+    dev = pred.device
+    vals = torch.empty(4, NB, device=dev)                    # min, max, largest jump, last_len
+    idx = torch.empty(NB, dtype=torch.int64, device=dev)
+    cs = torch.empty(3, device=dev) if gt is not None else None
+    scratch = torch.empty(int(lib.mp_bone_extremes_scratch_floats(B * L)), device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mp_bone_extremes(_dptr(pred), _strides(pred, order), _dptr(gt), _strides(gt, order) if gt is not None else None,
+                                        B, L, J, float(pred_scale), float(gt_scale), int(bool(chain)),
+                                        _lib.ptr(prev_len.contiguous()) if prev_len is not None else None, int(frame_base),
+                                        _lib.ptr(vals[0]), _lib.ptr(vals[1]), _lib.ptr(vals[2]), _lib.ptr(idx), _lib.ptr(cs), _lib.ptr(vals[3]),
+                                        _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr()), "mp_bone_extremes")
+    return BoneExtremes(vals[0], vals[1], vals[2], idx, cs, vals[3], B, L)
+
+
+def merge_extremes(min_len, max_len, max_delta, max_delta_idx):
+    """The rank merge rule of ``AnalyticsAccumulator.all_reduce`` on plain tensors, every argument (ranks, 16): MIN / MAX of the bone
+    lengths; for the largest jump the largest value wins and a tie goes to the LOWEST rank (torch.max(dim) returns the first maximum),
+    whose index is kept.  Returns (min (16,), max (16,), max_delta (16,), max_delta_idx (16,))."""
+    v, r = max_delta.max(dim=0)
+    return min_len.min(dim=0)[0], max_len.max(dim=0)[0], v, max_delta_idx.gather(0, r[None])[0]
+
+
 class AnalyticsAccumulator:
     """Adds up ``pose_analytics`` results over evaluation batches and reports the reference's analytics table
     (main_h36m_lifting.py:933-990, main_3dhp.py:860-910): all frames of all windows form ONE sequence, as in the reference's
-    ``(1, 3, J, B*L)`` reshape for the time consistency.  Only (B, 16)-sized float64 bookkeeping happens here."""
+    ``(1, 3, J, B*L)`` reshape for the time consistency.  Only (B, 16)-sized float64 bookkeeping happens here.
+
+    ``add_extremes`` keeps the quantities that are not sums (per-bone min / max length, the largest frame-to-frame jump of a bone length
+    and where it is) over that same ONE sequence: every call continues the chain of the call before (``last_len`` -> ``prev_len``), so a
+    jump across two evaluation batches is seen, and the index counts frames from the first call.  With more than one rank every rank
+    chains the windows IT evaluates, in its own order: jumps across window boundaries are those of that order and the reported index is
+    local to the rank that holds the largest jump (``all_reduce``).  With one rank the result is the reference's."""
 
     def __init__(self):
         self.scal = None            # (12,) float64
@@ -112,6 +175,16 @@ class AnalyticsAccumulator:
         self.s1 = None              # (16,) sum (len - ref)
         self.s2 = None              # (16,) sum (len - ref)^2
         self.proc = None            # (5,) Procrustes sums (procrustes_sums)
+        self.nvel = 0.0             # sum B (L - 1): frame pairs behind the velocity sums (scalars 9, 10)
+        self.win_std = None         # (16,) sum over windows of the per-window std of every bone length (main_3dhp.py:870-878)
+        self.nwin = 0.0
+        self.seg_min = None         # (16,) float32, add_extremes
+        self.seg_max = None
+        self.jump = None            # (16,) largest |len(f) - len(f-1)| so far, -1 before the first difference
+        self.jump_idx = None        # (16,) int64
+        self.coord = None           # (3,) float64 sum |gt - pred| per coordinate
+        self.last_len = None        # (16,) carried into the next add_extremes call
+        self.frames_seen = 0        # frames given to add_extremes so far (frame_base of the next call)
 
     def add(self, a: PoseAnalytics) -> None:
         rows = a.rows.double()
@@ -131,6 +204,29 @@ class AnalyticsAccumulator:
         self.s1 += (pb[..., 0] + n * d).sum(0)
         self.s2 += (pb[..., 1] + 2.0 * d * pb[..., 0] + n * d * d).sum(0)
         self.n += n * a.B
+        self.nvel += float(a.B * (a.L - 1))
+        if a.L > 1:
+            ws = a.bone_variance(unbiased=True).double().sqrt().sum(0)
+            self.win_std = ws if self.win_std is None else self.win_std + ws
+        self.nwin += float(a.B)
+
+    def add_extremes(self, pred: torch.Tensor, gt: Optional[torch.Tensor] = None, layout: str = "BLJC", pred_scale: float = 1.0,
+                     gt_scale: float = 1.0) -> None:
+        """One evaluation batch of windows, continuing the sequence of the earlier calls (``bone_extremes(chain=True)``)."""
+        e = bone_extremes(pred, gt, layout=layout, pred_scale=pred_scale, gt_scale=gt_scale, chain=True, prev_len=self.last_len,
+                          frame_base=self.frames_seen)
+        if self.seg_min is None:
+            self.seg_min, self.seg_max, self.jump, self.jump_idx = e.min_len.clone(), e.max_len.clone(), e.max_delta.clone(), e.max_delta_idx.clone()
+        else:
+            self.seg_min = torch.minimum(self.seg_min, e.min_len)
+            self.seg_max = torch.maximum(self.seg_max, e.max_len)
+            newer = e.max_delta > self.jump                      # strictly larger: the earlier (smaller) index keeps a tie
+            self.jump = torch.where(newer, e.max_delta, self.jump)
+            self.jump_idx = torch.where(newer, e.max_delta_idx, self.jump_idx)
+        if e.coord_sums is not None:
+            self.coord = e.coord_sums.double() if self.coord is None else self.coord + e.coord_sums.double()
+        self.last_len = e.last_len
+        self.frames_seen += e.B * e.L
 
     def add_procrustes(self, sums: torch.Tensor) -> None:
         self.proc = sums.clone() if self.proc is None else self.proc + sums
@@ -138,7 +234,10 @@ class AnalyticsAccumulator:
     def all_reduce(self, group=None) -> None:
         """Merge the accumulators of all ranks (evaluation sharded over windows, SURVEY 8e: "a final sum-reduce of (sum of per-joint
         error, count)"): one SUM all-reduce of the packed sums, one all-gather of the shifted variance sums, which are re-centred on
-        rank 0's reference before they are added.  Every rank ends with the merged accumulator."""
+        rank 0's reference before they are added.  Every rank ends with the merged accumulator.
+        The extremes of ``add_extremes`` are all-gathered and merged by ``merge_extremes``: MIN / MAX of the bone lengths; the largest
+        jump is the largest value, ties to the lowest rank - its index stays the winning rank's own frame count (every rank chains the
+        windows it evaluates itself, so jumps across window boundaries are taken in that rank's order)."""
         import torch.distributed as dist
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
             return
@@ -146,8 +245,12 @@ class AnalyticsAccumulator:
             raise RuntimeError("AnalyticsAccumulator.all_reduce: every rank must have added at least one batch")
         world = dist.get_world_size(group)
         has_proc = self.proc is not None
-        n_t = torch.tensor([self.n], dtype=torch.float64, device=self.scal.device)
-        parts = [self.scal, self.pairs.reshape(-1), self.joints.reshape(-1), self.bone_err.reshape(-1), n_t] + ([self.proc] if has_proc else [])
+        dev = self.scal.device
+        n_t = torch.tensor([self.n], dtype=torch.float64, device=dev)
+        z = lambda k: torch.zeros(k, dtype=torch.float64, device=dev)
+        extra = torch.cat([torch.tensor([self.nvel, self.nwin], dtype=torch.float64, device=dev),
+                           self.win_std if self.win_std is not None else z(NB), self.coord if self.coord is not None else z(3)])
+        parts = [self.scal, self.pairs.reshape(-1), self.joints.reshape(-1), self.bone_err.reshape(-1), n_t] + ([self.proc] if has_proc else []) + [extra]
         flat = torch.cat([p.reshape(-1).double() for p in parts])
         var = torch.cat([self.ref, self.s1, self.s2, n_t])                       # (3 * 16 + 1,)
         gathered = [torch.empty_like(var) for _ in range(world)]
@@ -162,7 +265,20 @@ class AnalyticsAccumulator:
             o += k
         self.n = float(flat[o].item()); o += 1
         if has_proc:
-            self.proc = flat[o:o + 5].clone()
+            self.proc = flat[o:o + 5].clone(); o += 5
+        self.nvel, self.nwin = float(flat[o].item()), float(flat[o + 1].item())
+        if self.win_std is not None:
+            self.win_std = flat[o + 2:o + 2 + NB].clone()
+        if self.coord is not None:
+            self.coord = flat[o + 2 + NB:o + 5 + NB].clone()
+        if self.seg_min is not None:
+            mine = torch.stack([self.seg_min, self.seg_max, self.jump])
+            ev = [torch.empty_like(mine) for _ in range(world)]
+            ei = [torch.empty_like(self.jump_idx) for _ in range(world)]
+            dist.all_gather(ev, mine, group=group)
+            dist.all_gather(ei, self.jump_idx, group=group)
+            ev = torch.stack(ev)
+            self.seg_min, self.seg_max, self.jump, self.jump_idx = merge_extremes(ev[:, 0], ev[:, 1], ev[:, 2], torch.stack(ei))
         ref0 = gathered[0][:NB]
         s1, s2 = torch.zeros_like(self.s1), torch.zeros_like(self.s2)
         for g in gathered:        # sum (x - c0) = S1 + n (c - c0);  sum (x - c0)^2 = S2 + 2 (c - c0) S1 + n (c - c0)^2
@@ -186,6 +302,20 @@ class AnalyticsAccumulator:
                "auc": (100.0 * s[7] / (31.0 * s[8])).item() if s[8] > 0 else float("nan"),
                "jointwise_err": (self.joints[:, 0] / n).tolist(),
                "mpsce_per_bone": var.sqrt().tolist(), "mpsse_per_pair": (self.pairs[:, 0] / n).tolist()}
+        # mean_velocity_error(axis=1, squared=False): mean over (window, frame pair, joint)
+        out["mvjpe"] = (s[9] / (self.nvel * NJ)).item() if self.nvel > 0 else float("nan")
+        jw, jw2 = self.joints[:, 0] / n, self.joints[:, 1] / n
+        out["jw_err_var"] = (jw2 - jw * jw).tolist()                     # jointwise_mse - jointwise_error^2 (main_h36m_lifting.py:1053-1059)
+        if self.win_std is not None:                                     # segments_time_consistency_per_bone(mode="std") on the windows
+            out["mpsce_per_bone_windows"] = (self.win_std / self.nwin).tolist()
+        if self.coord is not None:
+            out["cw_err"] = (self.coord / nj).tolist()                   # coordwise_error(mode="average")
+        if self.seg_min is not None:
+            out["seg_min_len"] = self.seg_min.tolist()
+            out["seg_max_len"] = self.seg_max.tolist()
+            out["seg_max_strech"] = (self.seg_max - self.seg_min).tolist()
+            out["seg_max_delta_strech"] = self.jump.tolist()
+            out["seg_max_delta_idx"] = self.jump_idx.tolist()
         if self.proc is not None:                # Protocol #2 and the Procrustes-aligned 3DPCK / AUC
             out["p_mpjpe"] = (self.proc[0] / (self.proc[4] * NJ)).item()
             out["pck_procrustes"] = (100.0 * self.proc[1] / self.proc[3]).item()

@@ -88,6 +88,21 @@ def segments_len_err(batch_imp: torch.Tensor, batch_gt: torch.Tensor, skeleton, 
     return (tot / (r.B * r.L * 16) if mode == "average" else tot).float()
 
 
+def coordwise_error(batch_imp: torch.Tensor, batch_gt: torch.Tensor, mode: str) -> torch.Tensor:
+    """mean_joint_errors.py:133-141: |gt - prediction| per coordinate, mean or sum over all joints of all frames -> (3,);
+    "no_agg": the (N, 3) table itself."""
+    if batch_imp.device.type != "cuda" or batch_gt.device.type != "cuda":     # before any shape check: a CPU tensor is never looked at
+        raise RuntimeError("manipose_amd: coordwise_error runs on the ROCm device only (no CPU fallback)")
+    if mode == "no_agg":
+        assert batch_imp.shape[-1] == batch_gt.shape[-1] == 3
+        return torch.abs(batch_gt.reshape(-1, 3) - batch_imp.reshape(-1, 3))
+    from .analytics import bone_extremes
+    _mode(mode)
+    a, b = _frames(batch_imp, batch_gt)
+    tot = bone_extremes(a, b).coord_sums.double()
+    return (tot / (a.shape[1] * a.shape[2]) if mode == "average" else tot).float()
+
+
 def p_mpjpe(predicted: torch.Tensor, target: torch.Tensor) -> float:
     """mean_joint_errors.py:148-189: MPJPE after per-frame rigid alignment with scale ("Protocol #2"); solved on the device
     (Horn's closed form) instead of a batched numpy SVD on the host.  predicted / target: (B, L, J, 3)."""

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import torch
 
-from .analytics import pose_analytics
+from .analytics import bone_extremes, pose_analytics
 
 
 def _time_stat(joints_coords, skeleton, mode):
@@ -56,6 +56,21 @@ def segments_time_consistency_per_bone(joints_coords: torch.Tensor, skeleton, mo
     stat, agg = _time_stat(joints_coords, skeleton, mode)
     out = agg(stat, dim=0)
     return out if mode in ("average", "sum", "std") else out      # min / max return (values, indices) like torch
+
+
+def segments_max_strech_per_bone(joints_coords: torch.Tensor, skeleton):
+    """regularizations.py:63-74: (min, max) length of every bone over all frames of all batch items -> two (num_bones,) tensors."""
+    e = bone_extremes(joints_coords.detach().float(), layout="BCJL", skeleton=skeleton)
+    return e.min_len, e.max_len
+
+
+def segments_max_diff_strech_per_bone(joints_coords: torch.Tensor, skeleton):
+    """regularizations.py:77-94: the largest |len(t+1) - len(t)| of every bone inside the batch items and the index b (L-1) + t of its
+    first occurrence -> (values (num_bones,), indices (num_bones,) int64), like torch.max(dim=0) on the reference's (B (L-1), 16) table."""
+    if joints_coords.shape[-1] < 2:          # the reference takes torch.max over an empty dimension here
+        raise IndexError("segments_max_diff_strech_per_bone: no frame-to-frame difference in a series of length 1")
+    e = bone_extremes(joints_coords.detach().float(), layout="BCJL", skeleton=skeleton)
+    return torch.return_types.max((e.max_delta, e.max_delta_idx))
 
 
 def _sym(joints_coords, skeleton, mode):
