@@ -170,7 +170,7 @@ def tensor_batches(X, y, batch):
 
 
 @torch.no_grad()
-def evaluate(model, X, y=None, batch=None, tta=True, analytics=False, distributed=False, seg_err_samples=0):
+def evaluate(model, X, y=None, batch=None, tta=True, analytics=False, distributed=False, seg_err_samples=0, hypotheses=False):
     """MPJPE (mm) of the aggregated / best-score / oracle hypotheses, with the reference's flip test-time augmentation
     (hpe/eval_utils.py:16-223).  The flipped copy is batched with the original into ONE forward of 2B windows
     instead of a second pass.  ``analytics=True`` adds the reference's evaluation table (main_h36m_lifting.py:933-990,
@@ -180,16 +180,24 @@ def evaluate(model, X, y=None, batch=None, tta=True, analytics=False, distribute
     (main_h36m_lifting.py:1044-1089) - with all windows of all batches chained into ONE sequence (mp_bone_extremes).
     ``seg_err_samples`` > 0 also returns ``seg_errs``: that many rows of the per-frame table gt - predicted bone length (mm), drawn like
     the reference's all_seg_errs.npy (:992-1004) from the frames this rank evaluated.  ``distributed=True``: every rank
-    evaluates its own share of the batches and the error sums / frame counts are sum-reduced at the end."""
+    evaluates its own share of the batches and the error sums / frame counts are sum-reduced at the end.
+    ``hypotheses=True`` adds, for an RMCLManifoldMixSTE only (the key is absent for the other architectures), ``out["hypotheses"]``: the
+    multi-hypothesis study of manipose_amd/metrics/hypotheses.py (J-Best, top-m oracle, spread, head usage, score calibration and the
+    consistency of the J-Best pose) in millimetres.  It is computed on the hypotheses of the UN-flipped forward - the ones the reference stores
+    in all_pred_hyps.pkl (hpe/eval_utils.py:155-160) - also when ``tta`` averages the aggregated predictions with the flipped pass."""
     from manipose_amd import RMCLManifoldMixSTE
     from manipose_amd.augmentations import pose_flip
     from manipose_amd.metrics import mpjpe_error
     from manipose_amd.metrics.analytics import AnalyticsAccumulator, pose_analytics, procrustes_sums
     acc = AnalyticsAccumulator() if analytics else None
+    hyp = None
     seg_tables = []
     model.eval()
     sk = model.decoder.skeleton if hasattr(model, "decoder") else _h36m()
     rmcl = isinstance(model, RMCLManifoldMixSTE)
+    if hypotheses and rmcl:
+        from manipose_amd.metrics.hypotheses import HypothesisAccumulator
+        hyp = HypothesisAccumulator()
     sums = {"mpjpe": 0.0, "ps_oracle_mpjpe": 0.0, "oracle_mpjpe": 0.0}
     n = 0
     for xb, yb in (tensor_batches(X, y, batch) if torch.is_tensor(X) else X):      # tensors, or any iterable of (X, y) batches
@@ -212,6 +220,8 @@ def evaluate(model, X, y=None, batch=None, tta=True, analytics=False, distribute
             sums["mpjpe"] += mpjpe_error(pred, yb, "sum").item()
             sums["ps_oracle_mpjpe"] += mpjpe_error(best, yb, "sum").item()
             sums["oracle_mpjpe"] += mpjpe_error(orac, yb, "sum").item()
+            if hyp is not None:
+                hyp.add(poses[:nb], scores[:nb], yb, pose_scale=1000.0, target_scale=1000.0, consistency=True)
         else:
             pred = out[:nb]
             if tta:
@@ -234,9 +244,13 @@ def evaluate(model, X, y=None, batch=None, tta=True, analytics=False, distribute
             n = t[3].item()
             if acc is not None:
                 acc.all_reduce()
+            if hyp is not None:
+                hyp.all_reduce()
     out = {k: 1000.0 * v / n for k, v in sums.items() if v > 0}
     if acc is not None:
         out["analytics"] = acc.report()
+    if hyp is not None:
+        out["hypotheses"] = hyp.report()
     if seg_tables:
         from manipose_amd.report import draw_seg_err_rows
         table = torch.cat(seg_tables, dim=0)
@@ -428,12 +442,16 @@ def run(argv, extra_defaults=None):
         if real:        # per action (H36M: subject S11, main_h36m_lifting.py:884-990) or the whole 3DHP test set (main_3dhp.py:800-910)
             groups = {name: sharded(window_generator(cfg, sq, False, dev)) for name, sq in seqs["test"].items()}
         from manipose_amd import report
-        rows, reports = {}, {}
+        rows, reports, hyps = {}, {}, {}
+        want_hyps = bool(cfg.run.get("hyp_report", False))
         for name, (make, shared) in groups.items():
             if rank != 0 and not shared:
                 continue
-            res = evaluate(model, make(), tta=cfg.train.tta, analytics=True, distributed=shared, seg_err_samples=report.SEG_ERR_SAMPLES)
+            res = evaluate(model, make(), tta=cfg.train.tta, analytics=True, distributed=shared, seg_err_samples=report.SEG_ERR_SAMPLES,
+                           hypotheses=want_hyps)
             table = res.pop("analytics")
+            if "hypotheses" in res:
+                hyps[name] = res.pop("hypotheses")
             reports[name] = dict(res, analytics=table)
             res.pop("seg_errs", None)
             rows[name] = res
@@ -449,6 +467,8 @@ def run(argv, extra_defaults=None):
             else:
                 from manipose_amd import RMCLManifoldMixSTE
                 written = report.write_h36m_report(out_dir, reports, rmcl=isinstance(model, RMCLManifoldMixSTE))
+            if hyps:                           # run.hyp_report: the hypothesis study, one row per group (3DHP: single-row tables)
+                written += report.write_hypothesis_report(out_dir, hyps, single=real and cfg.data.dataset == "3dhp")
             print(f"report: {len(written)} files -> {out_dir}", flush=True)
     if cfg.run.lift and rank == 0:         # after run.checkpoint_model / the training above: the weights the test ran on
         groups = {name: sq[1] for name, sq in seqs["test"].items()} if real else synthetic_sequences_2d(cfg, cfg.run.seed)

@@ -478,6 +478,34 @@ int mp_bone_extremes(const float* pred, const int64_t* pred_strides, const float
                      float* max_delta, int64_t* max_delta_idx, float* coord_sums, float* last_len, float* scratch, int64_t scratch_floats,
                      void* stream);
 
+/* The multi-hypothesis study of K hypotheses, their scores and the target in one pass (17 joints): what the reference's follow-up scripts
+ * compute on the host from all_pred_hyps.pkl - calc_jbest_mpjpe / calc_jbest_pose (hpe/useful_aux_scripts/eval_baselines.py:451-481), the
+ * error against the number of hypotheses (plot_nhyps_lineplot.py), the per-joint spread (inspect_multimodality.py) - and the oracle /
+ * best_score / weighted_ave aggregations of RMCLManifoldMixSTE.aggregate (rmcl_manifold_mix_ste.py:141-185) with mpjpe_error, without
+ * test-time augmentation.  poses (B,K,T,17,3), scores (B,K,T), target (B,T,17,3), contiguous; 1 <= K <= 8, T >= 1, B*T < 2^31.
+ * Per frame, with q_k = pose_scale * p_k and g = target_scale * target:  e[k][j] = ||q_k[j] - g[j]|| (sqrtf of the scaled coordinates),
+ * E[k] = sum_j e[k][j];  k* = the FIRST arg-min of E (torch.min), k_s = the FIRST arg-max of the score; the score order is descending,
+ * equal scores in the order of their indices; per joint the FIRST arg-min over k of e[k][j] wins.
+ * sums: mp_hypothesis_stats_row_floats() floats, every entry a sum over the B*T frames:
+ *   [0] frames  [1] E[k_s] (pseudo-oracle)  [2] E[k*] (oracle, "P-Best")  [3] sum_j min_k e[k][j] (J-Best)
+ *   [4] sum_j ||sum_k s_k q_k[j] - g[j]|| (weighted average)  [5] s[k*]  [6] s[k_s]
+ *   [7] 2 / (K (K-1)) sum_{k<k'} sum_j ||q_k[j] - q_k'[j]|| (mean pairwise distance; 0 for K = 1)
+ *   [8,16) top-m: min of E over the m best-scored hypotheses, m = 1..K, slots K.. are 0 ([8] = [1], [8+K-1] = [2], the same bits)
+ *   [16,33) per joint: min_k e[k][j]    [33,50) per joint: sqrt(sum_k s_k ||q_k[j] - w[j]||^2), w = sum_k s_k q_k
+ *   [50,58) per head k: s_k (slots K.. are 0).
+ * counts: mp_hypothesis_stats_row_counts() int64, exact:
+ *   [0] frames with k_s == k*   [1,9) place of k* in the score order (0 = best-scored)   [9,17) k*   [17,25) k_s
+ *   [25,33) (frame, joint) pairs whose per-joint winner is head k.
+ * jbest_pose (B,T,17,3) or null: per joint the three input floats of the winning hypothesis, UNSCALED (the bits of `poses`);
+ * jbest_idx (B,T,17) bytes or null: that hypothesis.  Deterministic (no atomics): the same bits in every run.
+ * scratch: >= mp_hypothesis_stats_scratch_floats(B*T) floats; counts 8-byte aligned. */
+int64_t mp_hypothesis_stats_scratch_floats(int64_t frames);
+int mp_hypothesis_stats_row_floats(void);
+int mp_hypothesis_stats_row_counts(void);
+int mp_hypothesis_stats(const float* poses, const float* scores, const float* target, int B, int K, int T, float pose_scale, float target_scale,
+                        float* sums, int64_t* counts, float* jbest_pose, uint8_t* jbest_idx, float* scratch, int64_t scratch_floats,
+                        void* stream);
+
 /* Procrustes-aligned errors: per frame the similarity transform (scale, proper rotation, translation) taking the predicted joints onto
  * the target ones in the least-squares sense - p_mpjpe (hpe/mh_so3_hpe/metrics/mean_joint_errors.py:148-189, batched numpy SVD on the
  * host in the reference) and the 'procrustes' alignment of keypoint_3d_pck / keypoint_3d_auc (metrics/pck.py:5-60,127-131) - solved on

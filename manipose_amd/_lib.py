@@ -115,6 +115,10 @@ _SIGNATURES = {
     "mp_pose_metrics": (i32, [vp, C.POINTER(i64), vp, C.POINTER(i64), vp, i32, i32, i32, f32, f32, f32, f32, i32, i32, vp, vp, vp, i64, vp]),
     "mp_bone_extremes_scratch_floats": (i64, [i64]),
     "mp_bone_extremes": (i32, [vp, C.POINTER(i64), vp, C.POINTER(i64), i32, i32, i32, f32, f32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "mp_hypothesis_stats_scratch_floats": (i64, [i64]),
+    "mp_hypothesis_stats_row_floats": (i32, []),
+    "mp_hypothesis_stats_row_counts": (i32, []),
+    "mp_hypothesis_stats": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, i64, vp]),
     "mp_set_option": (i32, [C.c_char_p, i32]),
     "mp_gemm_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     "mp_gemm_launch_counts": (i32, [C.POINTER(i64), i32]),

@@ -418,6 +418,16 @@ int mp_bone_extremes(const float* pred, const int64_t* pred_strides, const float
                        (hipStream_t)stream);
 }
 
+int64_t mp_hypothesis_stats_scratch_floats(int64_t frames) { return (int64_t)hypothesis_stats_scratch_floats((long)frames); }
+int mp_hypothesis_stats_row_floats(void) { return hypothesis_stats_row_floats(); }
+int mp_hypothesis_stats_row_counts(void) { return hypothesis_stats_row_counts(); }
+int mp_hypothesis_stats(const float* poses, const float* scores, const float* target, int B, int K, int T, float pose_scale, float target_scale,
+                        float* sums, int64_t* counts, float* jbest_pose, uint8_t* jbest_idx, float* scratch, int64_t scratch_floats,
+                        void* stream) {
+  return hypothesis_stats(poses, scores, target, B, K, T, pose_scale, target_scale, sums, reinterpret_cast<long*>(counts), jbest_pose, jbest_idx,
+                          scratch, (long)scratch_floats, (hipStream_t)stream);
+}
+
 /* test / tuning hooks (include/manipose_hip.h): process-wide selectors between kernels that are tested to agree; everything that changes a
  * model's arithmetic or its stream use is a field of mp_model_config */
 int mp_gemm_plan(int M, int N, int K, int form, int epilogue, int cus, int out[4]) {

@@ -240,6 +240,16 @@ int bone_extremes(const float* pred, const long* ps, const float* gt, const long
                   int chain, const float* prev_len, long frame_base, float* min_len, float* max_len, float* max_delta, long* max_delta_idx,
                   float* coord_sums, float* last_len, float* scratch, long scratch_floats, hipStream_t st);
 
+// ---------------------------------------------------------------- hypothesis_stats.hip
+// the multi-hypothesis study of one batch of (B,K,T,17,3) hypotheses: J-Best, oracle, best-score, weighted average, top-m, spread, pairwise
+// distance and the head-usage counts as sums over the B*T frames (include/manipose_hip.h, mp_hypothesis_stats)
+long hypothesis_stats_scratch_floats(long frames);
+int hypothesis_stats_row_floats();
+int hypothesis_stats_row_counts();
+int hypothesis_stats(const float* poses, const float* scores, const float* target, int B, int K, int T, float pose_scale, float target_scale,
+                     float* sums, long* counts, float* jbest_pose, unsigned char* jbest_idx, float* scratch, long scratch_floats,
+                     hipStream_t st);
+
 // ---------------------------------------------------------------- windows.hip
 int gather_windows(const float* p2, const float* p3, const long* seq_offset, int S, const int* win_seq, const int* win_start,
                    const unsigned char* win_flip, const int* mirror, const float* mask2d, const float* noise2d, int B, int T, int J,

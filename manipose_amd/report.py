@@ -8,7 +8,9 @@ ends, minimal quoting - so ``pd.read_csv(path, index_col=0)`` reads the files th
 H36M (one row per action and a last row "average" of column means): protocol_1_err.csv, seg_symmetry.csv, seg_consistency.csv,
 seg_max_strech.csv, seg_max_delta_strech.csv, cw_err.csv, jw_err.csv, all_seg_errs.npy, all_jw_err_var.npy.
 3DHP (one row, no row label): seg_symmetry.csv, seg_consistency.csv, cw_err.csv, jw_err.csv.
-all_pred_hyps.pkl and the mlflow calls of the reference are not reproduced."""
+all_pred_hyps.pkl and the mlflow calls of the reference are not reproduced.
+run.hyp_report (no file of the reference: it does this study in follow-up scripts on the pickle): hyp_report.csv, hyp_heads.csv, hyp_joints.csv
+from ``HypothesisAccumulator.report()`` (write_hypothesis_report)."""
 from __future__ import annotations
 
 import csv
@@ -132,4 +134,42 @@ def write_3dhp_report(out_dir: str, analytics: Mapping, skeleton=None) -> List[s
     for name, (h, row) in tables.items():
         paths.append(os.path.join(out_dir, name + ".csv"))
         write_csv(paths[-1], h, [list(row)])
+    return paths
+
+
+# column of hyp_report.csv = key of HypothesisAccumulator.report(); the two consistency columns only when every group carries them
+HYP_SCALAR_KEYS = ("mpjpe_weighted_ave", "mpjpe_best_score", "mpjpe_oracle", "mpjpe_jbest", "pairwise_distance", "score_of_oracle", "score_max",
+                   "top1_agreement")
+HYP_CONSISTENCY_KEYS = ("jbest_mpsse", "jbest_mpsce")
+HYP_HEAD_TABLES = ("pbest_head_share", "score_head_share", "jbest_head_share", "score_mass_per_head")
+
+
+def write_hypothesis_report(out_dir: str, groups: Mapping[str, Mapping], skeleton=None, single: bool = False) -> List[str]:
+    """``groups``: {action: HypothesisAccumulator.report()} in the order of the rows.  Three tables in the layout of the other report files
+    (a label column "act", one row per group and a last row "average" of column means):
+      hyp_report.csv   the scalar keys, then top_1 .. top_K (``mpjpe_top_m``);
+      hyp_heads.csv    K columns ``<table>_<k>`` for each of pbest_head_share, score_head_share, jbest_head_share, score_mass_per_head;
+      hyp_joints.csv   the J-Best error per joint under the joints' names, then the spread per joint under "spread <joint>".
+    ``single=True`` (3DHP): the first group only, as single-row tables without the label column.  Returns the paths written."""
+    acts = list(groups)
+    if not acts:
+        raise ValueError("write_hypothesis_report: no group to report")
+    reps = [groups[a] for a in acts]
+    K = len(reps[0]["mpjpe_top_m"])
+    if any(len(r["mpjpe_top_m"]) != K for r in reps):
+        raise ValueError("write_hypothesis_report: the groups differ in their number of hypotheses")
+    jn = joints_names(skeleton)
+    scalars = list(HYP_SCALAR_KEYS) + [k for k in HYP_CONSISTENCY_KEYS if all(k in r for r in reps)]
+    tables = {
+        "hyp_report": (scalars + [f"top_{m + 1}" for m in range(K)], [[r[k] for k in scalars] + list(r["mpjpe_top_m"]) for r in reps]),
+        "hyp_heads": ([f"{t}_{k}" for t in HYP_HEAD_TABLES for k in range(K)], [[v for t in HYP_HEAD_TABLES for v in r[t]] for r in reps]),
+        "hyp_joints": (jn + [f"spread {n}" for n in jn], [list(r["jbest_per_joint"]) + list(r["spread_per_joint"]) for r in reps]),
+    }
+    paths = []
+    for name, (h, values) in tables.items():
+        paths.append(os.path.join(out_dir, name + ".csv"))
+        if single:
+            write_csv(paths[-1], h, [list(values[0])])
+        else:
+            write_csv(paths[-1], ["act", *h], _table(acts, values))
     return paths
