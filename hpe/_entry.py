@@ -271,18 +271,24 @@ def sk_device(model):
 def lift_sequences_to_file(model, cfg, groups, path):
     """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
     hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
-    it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4)."""
+    it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
+    lengths per sequence; lift.lengths, lift.symmetric) also ``<key>__bones`` -> (16,), the sequence's bone lengths in metres."""
     from manipose_amd import lift_sequences
     out = {}
+    rigid = bool(cfg.lift.get("rigid", False))
     for name, seqs in groups.items():
         res = lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=cfg.lift.agg, blend=cfg.lift.blend,
-                             return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test)
-        poses, hyps = res if cfg.lift.hyps else (res, None)
+                             return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
+                             symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid)
+        res = list(res) if cfg.lift.hyps or rigid else [res]
+        poses, hyps, bones = res[0], (res[1] if cfg.lift.hyps else None), (res[-1] if rigid else None)
         for i, p in enumerate(poses):
             key = name if len(poses) == 1 else f"{name}.{i}"
             out[key] = p.cpu().numpy()
             if hyps is not None:
                 out[key + "__hyps"] = hyps[i].cpu().numpy()
+            if bones is not None:
+                out[key + "__bones"] = bones[i].cpu().numpy()
     np.savez(path, **out)
     return out
 
@@ -474,5 +480,5 @@ def run(argv, extra_defaults=None):
         groups = {name: sq[1] for name, sq in seqs["test"].items()} if real else synthetic_sequences_2d(cfg, cfg.run.seed)
         path = cfg.lift.output if os.path.isabs(str(cfg.lift.output)) else os.path.join(out_dir, str(cfg.lift.output))
         lifted = lift_sequences_to_file(model, cfg, groups, path)
-        print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if not k.endswith('__hyps'))} frames of {len(groups)} groups -> {path}", flush=True)
+        print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if not k.endswith(('__hyps', '__bones')))} frames of {len(groups)} groups -> {path}", flush=True)
     return best_val

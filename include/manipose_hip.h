@@ -416,6 +416,28 @@ int mp_lift_merge(const float* poses, const float* scores, int W, int K, int T, 
                   const int64_t* h_seq_offset, const int32_t* mirror, int agg, int blend, float scale, float* out, float* hyps,
                   void* stream);
 
+/* Rigid lifting: one skeleton per lifted sequence.  The model's hypotheses of a window share their bone lengths; what mp_lift_merge emits does not
+ * (weighted_ave averages poses that differ in rotation, blend "mean" averages windows whose lengths differ, and every window predicts its own
+ * lengths), so a lifted sequence has a non-zero MPSCE (segments_time_consistency, hpe/mh_so3_hpe/metrics/regularizations.py:8-60).  The reference
+ * has no counterpart (hpe/viz.py renders the hypotheses as they come).  parents (J) HOST int32: parents[0] = -1, 0 <= parents[j] < j (parents
+ * precede their children), 2 <= J <= 32, otherwise MP_ERR_ARG before anything is launched; bone b = j - 1 joins joint j to parents[j]
+ * (Skeleton.bones order, the layout of the model's (B, 16) lengths).
+ * mp_lift_rigid: poses (Ntot, inner, J, C) device floats, C = 3 (poses) or 4 (hypotheses; channel 3, the score, is neither read nor written),
+ * updated IN PLACE; seq_offset (S + 1) device int64 as for mp_lift_merge: frame g belongs to the last sequence s with seq_offset[s] <= g and is
+ * re-assembled with row s of lengths (S, J - 1) device floats.  Per pose p, in fp32:  q[0] = p[0];  for j = 1 .. J-1:  d = p[j] - p[parents[j]]
+ * (the INPUT positions), n = sqrtf(d . d), u = d / n if n > 0 and finite, otherwise the u of the bone of parents[j] ((0, 0, 1) when parents[j] is
+ * the root);  q[j] = q[parents[j]] + lengths[s][j-1] u.  sqrtf and the division are correctly rounded.  One lane owns one pose and holds it in
+ * registers, so nothing it stores is read again.
+ * mp_bone_length_means: lengths (S, J - 1) = per sequence the mean over its frames of the bone lengths of poses (Ntot, J, 3); seq_real (S) device
+ * int64 or null: only the first min(seq_real[s], frames of s) frames of sequence s count (a sequence kept with its replicate-padded frames);
+ * a sequence without frames gets lengths 0, and no frame at or beyond Ntot is read whatever the device tables say.
+ * Differences, square roots and sums in fp64, rounded to fp32 once; one workgroup per sequence, fixed summation order, no atomics: identical bits
+ * on every call.  Neither call synchronises. */
+int mp_lift_rigid(float* poses, int64_t Ntot, int inner, int J, int C, const int64_t* seq_offset, int S, const float* lengths,
+                  const int32_t* parents, void* stream);
+int mp_bone_length_means(const float* poses, int64_t Ntot, int J, const int64_t* seq_offset, const int64_t* seq_real, int S, const int32_t* parents,
+                         float* lengths, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -7,6 +7,11 @@ overlap (``stride < T``) and everything on the device: the raw keypoints are upl
 (mirrored) windows, the engine runs its no-backward forward, and ONE kernel (``mp_lift_merge``) aggregates the hypotheses, undoes
 the mirroring and blends the windows that cover a frame, reading every hypothesis once.
 
+Rigid lifting (``rigid=True``, off by default): the merged poses of a sequence do not share their bone lengths (averaged hypotheses, blended
+windows, one length prediction per window), so after the merge every sequence gets ONE table of J - 1 bone lengths - the model's own
+(``"model"``), the mean lengths of the merged poses (``"measured"``, ``mp_bone_length_means``) or the caller's - and ``mp_lift_rigid``
+re-assembles every emitted pose and hypothesis along its own bone directions with them (include/manipose_hip.h has the definition).
+
 Scheduling: a sequence is lifted on its own - its windows are cut into forwards of ``batch`` (``2 * batch`` with TTA), all of them
 stay resident until the sequence is merged, and no forward mixes two sequences.  A frame's covering windows are therefore always
 resident when it is merged (no partial sum is ever carried), and a sequence's result does not depend on what else is lifted with
@@ -67,6 +72,92 @@ def _i32p(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _skeleton_of(model=None, skeleton=None):
+    from .data import h36m_skeleton
+    if skeleton is not None:
+        return skeleton
+    return model.decoder.skeleton if model is not None and hasattr(model, "decoder") else h36m_skeleton()
+
+
+def _parents_c(sk):
+    par = [int(p) for p in sk.parents]
+    if par[0] != -1 or any(not 0 <= p < j for j, p in enumerate(par) if j):
+        raise ValueError("rigid lifting: joint 0 must be the root and parents must precede their children")
+    return (C.c_int32 * len(par))(*par)
+
+
+def _check_lengths_table(lengths, S, J):
+    """A caller's bone-length table as float32 numpy (S, J - 1); ValueError for a wrong shape or a negative / non-finite entry."""
+    a = lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
+    if a.dtype.kind not in "fiu":
+        raise ValueError(f"lengths must be None, 'model', 'measured' or a numeric table, got dtype {a.dtype}")
+    if a.shape == (J - 1,):
+        a = np.broadcast_to(a, (S, J - 1))
+    if a.shape != (S, J - 1):
+        raise ValueError(f"lengths must be ({S}, {J - 1}) or ({J - 1},) bone lengths in metres, got {tuple(np.shape(lengths))}")
+    a = np.array(a, dtype=np.float32, order="C")             # a copy: the caller's table is never aliased
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError("lengths must be finite and non-negative")
+    return a
+
+
+def _rigid(lib, poses4, d_off, S, d_lengths, parents):
+    ntot, inner, J, ch = (int(v) for v in poses4.shape)
+    with torch.cuda.device(poses4.device):
+        _lib.check(lib.mp_lift_rigid(_lib.ptr(poses4), ntot, inner, J, ch, _lib.ptr(d_off), S, _lib.ptr(d_lengths), parents, _lib.stream_ptr()),
+                   "mp_lift_rigid")
+
+
+def bone_length_means(poses, seq_offset=None, real_frames=None, skeleton=None):
+    """``mp_bone_length_means``: (S, J - 1) mean bone lengths per sequence of the device tensor poses (Ntot, J, 3); ``seq_offset`` (S + 1) HOST
+    table or device int64 tensor (default: one sequence); ``real_frames`` (S) or None: only the first that many frames of a sequence count."""
+    if poses.dim() != 3 or poses.shape[2] != 3 or poses.dtype != torch.float32:
+        raise ValueError(f"poses must be float32 (Ntot, J, 3), got {tuple(poses.shape)} {poses.dtype}")
+    dev, J = poses.device, int(poses.shape[1])
+    parents = _parents_c(_skeleton_of(skeleton=skeleton))
+    if len(parents) != J:
+        raise ValueError(f"poses have {J} joints, the skeleton {len(parents)}")
+    d_off = _device_i64(seq_offset if seq_offset is not None else [0, int(poses.shape[0])], dev)
+    S = int(d_off.numel()) - 1
+    d_real = _device_i64(real_frames, dev) if real_frames is not None else None
+    if d_real is not None and int(d_real.numel()) != S:
+        raise ValueError(f"real_frames must have {S} entries")
+    out = torch.empty(S, J - 1, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mp_bone_length_means(_lib.ptr(poses), int(poses.shape[0]), J, _lib.ptr(d_off), _lib.ptr(d_real), S, parents, _lib.ptr(out), _lib.stream_ptr()),
+                   "mp_bone_length_means")
+    return out
+
+
+def _device_i64(a, dev):
+    if torch.is_tensor(a):
+        return a.to(dev, torch.int64).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+
+
+def project_rigid(poses, lengths, seq_offset=None, skeleton=None):
+    """``mp_lift_rigid`` on a device tensor, IN PLACE (and returned): poses (Ntot, J, 3), or (Ntot, inner, J, C) with C = 3 or 4 (channel 3, a
+    hypothesis' score, is left alone).  Every pose keeps its root and its bone directions and gets the bone lengths of its sequence:
+    ``lengths`` (S, J - 1) or (J - 1,), tensor or array, in the unit of the poses; ``seq_offset`` (S + 1): first frame of every sequence, HOST
+    table or device int64 tensor (default: all frames are one sequence).  A bone of length zero takes its parent bone's direction, (0, 0, 1)
+    under the root.  ``skeleton``: default the 17-joint H36M tree."""
+    if not poses.is_cuda:
+        raise RuntimeError("manipose_amd: project_rigid takes device tensors; there is no CPU fallback")
+    p4 = poses.unsqueeze(1) if poses.dim() == 3 else poses
+    if p4.dim() != 4 or p4.shape[3] not in (3, 4) or poses.dtype != torch.float32 or not poses.is_contiguous():
+        raise ValueError(f"poses must be contiguous float32 (Ntot, J, 3) or (Ntot, inner, J, 3 | 4), got {tuple(poses.shape)} {poses.dtype}")
+    J = int(p4.shape[2])
+    parents = _parents_c(_skeleton_of(skeleton=skeleton))
+    if len(parents) != J:
+        raise ValueError(f"poses have {J} joints, the skeleton {len(parents)}")
+    d_off = _device_i64(seq_offset if seq_offset is not None else [0, int(p4.shape[0])], poses.device)
+    S = int(d_off.numel()) - 1
+    table = torch.from_numpy(_check_lengths_table(lengths, S, J)).to(poses.device)
+    if p4.shape[0] > 0:
+        _rigid(_lib.load(), p4, d_off, S, table, parents)
+    return poses
+
+
 def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirror, agg="weighted_ave", blend="mean", scale=1.0,
                   return_hyps=False, out=None, hyps=None, device_tables=None):
     """``mp_lift_merge`` on device tensors: poses (F*W, K, T, J, 3), scores (F*W, K, T, 1) or None (K == 1); win_seq / win_start (W)
@@ -103,17 +194,40 @@ def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirr
 
 @torch.no_grad()
 def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
-                   keep_padding=False):
+                   keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False):
     """One 3-D pose per frame of every sequence.  ``poses_2d``: a list of (N_i, 17, 2) device tensors or numpy arrays (or one such
     array); returns a list of (N_i, 17, 3) device tensors, and with ``return_hyps`` also a list of (N_i, K, 17, 4) (every hypothesis
     and its score, from the un-mirrored pass).  ``stride`` (default T: non-overlapping windows) in 1..T; ``blend`` "mean" averages the
     windows that cover a frame, "center" takes the one whose centre is nearest; ``batch`` windows per forward (``2 * batch`` with
     TTA; default: the model's ``max_batch_hint`` or 16).  ``keep_padding`` (stride == T only) also returns the replicate-padded
-    frames of the last window, as the reference's lift_action does."""
+    frames of the last window, as the reference's lift_action does.
+
+    ``rigid`` (default off: nothing changes by a bit): every sequence is re-assembled with ONE table of J - 1 bone lengths - each emitted pose and,
+    with ``return_hyps``, each hypothesis keeps its root and its bone directions (``project_rigid``).  ``lengths``: "model" = the mean over the
+    sequence's windows of the lengths the model predicted (with TTA the mirrored copy's, left and right swapped back, averaged in), the
+    default of the two manifold models; "measured" = the mean bone lengths of the sequence's merged poses over its real frames, the default of
+    MixSTE, which predicts none; or an (S, J - 1) / (J - 1,) table in metres.  ``symmetric`` replaces every left / right pair of the table
+    by its mean.  ``return_bones`` appends the list of (J - 1,) tables used, in metres (``scale`` multiplies poses and lengths alike)."""
+    if not rigid and (lengths is not None or symmetric or return_bones):
+        raise ValueError("lengths, symmetric and return_bones describe rigid lifting: pass rigid=True")
     single = torch.is_tensor(poses_2d) or isinstance(poses_2d, np.ndarray)
     seqs = [poses_2d] if single else list(poses_2d)
     if not seqs:
-        return ([], []) if return_hyps else []
+        return tuple([] for _ in range(1 + bool(return_hyps) + bool(return_bones))) if return_hyps or return_bones else []
+    table = None
+    if rigid:                                                # argument errors first: nothing has touched the device yet
+        T, J, K = _model_shape(model)
+        mixste = getattr(model, "_arch", None) == "mixste"
+        if lengths is None:
+            lengths = "measured" if mixste else "model"
+        if isinstance(lengths, str):
+            if lengths not in ("model", "measured"):
+                raise ValueError(f"lengths must be None, 'model', 'measured' or a table, got {lengths!r}")
+            if lengths == "model" and mixste:
+                raise ValueError("lengths='model': MixSTE predicts no bone lengths; use 'measured' or pass a table")
+        else:
+            table = _check_lengths_table(lengths, len(seqs), J)
+            lengths = "table"
     params = list(model.parameters())
     if not params or not params[0].is_cuda:
         raise RuntimeError("manipose_amd: lift_sequences needs the model on a ROCm device; there is no CPU fallback")
@@ -158,6 +272,13 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
     hyp_all = torch.empty(sum(out_lens), K, J, 4, dtype=torch.float32, device=dev) if return_hyps else None
     lib = _lib.load()
     F = 2 if tta else 1
+    if rigid:
+        sk = _skeleton_of(model)
+        parents = _parents_c(sk)
+        if len(parents) != J:
+            raise ValueError(f"the model has {J} joints, its skeleton {len(parents)}")
+        bone_mirror = torch.tensor([int(mirror[j]) - 1 for j in range(1, J)], device=dev)      # bone of joint j <- bone of joint mirror[j]
+        model_rows = []
     was_training = model.training
     model.eval()
     try:
@@ -176,6 +297,9 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
                 res = model(X)
                 poses, scores = res if isinstance(res, tuple) else (res, None)
                 poses = poses.reshape(F * n, K, T, J, 3)
+                if rigid and lengths == "model":             # the (F n, J - 1) lengths this forward left in the engine
+                    lw = model._engine.peek(1).view(F * n, J - 1).abs()
+                    model_rows.append((lw[:n] + lw[n:][:, bone_mirror]) / 2 if tta else lw)
                 if n == nw:                      # the whole sequence in one forward: merged where the engine left it
                     buf_p, buf_s = poses, scores
                     break
@@ -193,10 +317,36 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
             o0 += out_lens[s]
     finally:
         model.train(was_training)
-    outs = list(torch.split(out_all, out_lens, dim=0))
+    bones = None
+    if rigid:
+        rigid_off = np.zeros(len(lens) + 1, dtype=np.int64)
+        rigid_off[1:] = np.cumsum(out_lens)
+        d_rigid_off = torch.from_numpy(rigid_off).to(dev)
+        if lengths == "model":                               # plain mean over each sequence's windows, in window order
+            rows = torch.cat(model_rows, dim=0)
+            bones = torch.stack([rows[int(first[s]):int(first[s + 1])].mean(dim=0) for s in range(len(lens))])
+        elif lengths == "measured":                          # of the merged poses, which mp_lift_merge has already multiplied by scale
+            bones = bone_length_means(out_all, d_rigid_off, real_frames=np.asarray(lens, dtype=np.int64) if keep_padding else None, skeleton=sk)
+            if float(scale) != 1.0:
+                bones = bones / float(scale)
+        else:
+            bones = torch.from_numpy(table).to(dev)
+        if symmetric:
+            bl, br = list(sk.bones_left), list(sk.bones_right)
+            mean = (bones[:, bl] + bones[:, br]) / 2
+            bones = bones.clone()
+            bones[:, bl] = mean
+            bones[:, br] = mean
+        used = (bones * float(scale)).contiguous()
+        _rigid(lib, out_all.unsqueeze(1), d_rigid_off, len(lens), used, parents)
+        if return_hyps:
+            _rigid(lib, hyp_all, d_rigid_off, len(lens), used, parents)
+    res = [list(torch.split(out_all, out_lens, dim=0))]
     if return_hyps:
-        return outs, list(torch.split(hyp_all, out_lens, dim=0))
-    return outs
+        res.append(list(torch.split(hyp_all, out_lens, dim=0)))
+    if return_bones:
+        res.append(list(bones.unbind(0)))
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
@@ -211,4 +361,4 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
     return torch.cat(res, dim=0).cpu().numpy()
 
 
-__all__ = ["plan_windows", "merge_windows", "lift_sequences", "lift_action"]
+__all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "lift_sequences", "lift_action"]
