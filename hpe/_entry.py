@@ -104,7 +104,9 @@ def synthetic_generator(cfg, device, seed, rank, world):
 
 def load_sequences(cfg, device):
     """fetch_and_prepare_data + get_subjects_and_actions + the fetch() calls of create_dataloader (main_h36m_lifting.py:511-583,
-    main_3dhp.py:503-532): {"train" | "valid": (poses_3d, poses_2d, cameras), "test": {group: (...)}} as lists of device tensors.
+    main_3dhp.py:503-532): {"train" | "valid": (poses_3d, poses_2d, cameras), "test": {group: (...)}} as lists of device tensors; H36M also
+    "test_cams": {group: [the 17 camera numbers fetch() returns per sequence]} (the tuples' third slot stays None: window_generator hands it
+    to the generator as its ``actions``).
     The reference's pickle cache of the prepared dataset is not needed: the ingest is a few hundred kernel launches."""
     from manipose_amd.data import Dataset3DHP, Human36mDataset, create_2d_data, fetch, read_3d_data
     from manipose_amd.data.ingest import TEST_SUBJECTS, TRAIN_SUBJECTS
@@ -129,11 +131,12 @@ def load_sequences(cfg, device):
             s_train = [s_train[0]]
         actions = None if cfg.data.actions == "*" else [ds.define_actions(a)[0] for a in str(cfg.data.actions).split(",")]
         have = lambda subjects: [s for s in subjects if s in kp]
-        out = {"train": fetch(have(s_train), ds, kp, actions)[:2] + (None,), "valid": fetch(have(s_val), ds, kp, actions)[:2] + (None,), "test": {}}
+        out = {"train": fetch(have(s_train), ds, kp, actions)[:2] + (None,), "valid": fetch(have(s_val), ds, kp, actions)[:2] + (None,), "test": {}, "test_cams": {}}
         for a in (actions or ds.define_actions()):                 # per-action test on S11, main_h36m_lifting.py:884-893
-            p3, p2, _, _ = fetch(have(["S11"]), ds, kp, [a])
+            p3, p2, _, cams = fetch(have(["S11"]), ds, kp, [a])
             if p3:
                 out["test"][a] = (p3, p2, None)
+                out["test_cams"][a] = cams
         return out
 
 
@@ -268,20 +271,57 @@ def sk_device(model):
     return next(model.parameters()).device
 
 
-def lift_sequences_to_file(model, cfg, groups, path):
+LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj", "__hyps_reproj", "__hyps_ok", "__floor", "__cam")
+
+
+def lift_place_options(cfg):
+    """(place, world, floor) of lift.place / lift.frame / lift.floor; ValueError for a combination that cannot run - before any model is built."""
+    place, frame, floor = bool(cfg.lift.get("place", False)), str(cfg.lift.get("frame", "camera")), bool(cfg.lift.get("floor", False))
+    if frame not in ("camera", "world"):
+        raise ValueError(f"lift.frame must be camera or world, got {frame!r}")
+    if floor and frame != "world":
+        raise ValueError("lift.floor=true puts the world frame's z on the floor: set lift.frame=world")
+    if (place or frame == "world") and str(cfg.data.dataset) == "3dhp":
+        raise ValueError("lift.place / lift.frame=world need the cameras' calibration, and the MPI-INF-3DHP files (data.dataset=3dhp) carry none")
+    return place, frame == "world", floor
+
+
+def synthetic_cameras(groups):
+    """Synthetic-data mode has no calibration of its own: sequence i (in the order of ``groups``) gets camera i % 4 of subject S11 (h36m_cameras())."""
+    from manipose_amd.data.ingest import h36m_cameras
+    s11 = h36m_cameras()["S11"]
+    cams, i = {}, 0
+    for name, seqs in groups.items():
+        cams[name] = [s11[(i + k) % 4] for k in range(len(seqs))]
+        i += len(seqs)
+    return cams
+
+
+def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
     """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
     hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
     it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
-    lengths per sequence; lift.lengths, lift.symmetric) also ``<key>__bones`` -> (16,), the sequence's bone lengths in metres."""
-    from manipose_amd import lift_sequences
+    lengths per sequence; lift.lengths, lift.symmetric) also ``<key>__bones`` -> (16,), the sequence's bone lengths in metres.
+    ``cameras`` = {name: [one camera per sequence]} (camera_table's forms) is needed by lift.place (also ``<key>__traj`` (N, 3), ``<key>__reproj``
+    (N,), ``<key>__ok`` (N,) uint8 and with lift.hyps ``<key>__hyps_traj`` (N, K, 3), ``<key>__hyps_reproj``, ``<key>__hyps_ok`` (N, K)) and by
+    lift.frame=world (poses and hypotheses in the world frame; with lift.floor on z = 0 and ``<key>__floor``, the offset subtracted); whenever
+    cameras were used ``<key>__cam`` holds the 16 numbers (intrinsic 9, orientation 4, translation 3)."""
+    from manipose_amd import camera_table, lift_sequences
     out = {}
     rigid = bool(cfg.lift.get("rigid", False))
+    place, world, floor = lift_place_options(cfg)
+    use_cams = place or world
+    if use_cams and cameras is None:
+        raise ValueError("lift.place / lift.frame=world need the sequences' cameras")
     for name, seqs in groups.items():
         res = lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=cfg.lift.agg, blend=cfg.lift.blend,
                              return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
-                             symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid)
-        res = list(res) if cfg.lift.hyps or rigid else [res]
+                             symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid, cameras=cameras[name] if use_cams else None,
+                             place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor)
+        res = list(res) if cfg.lift.hyps or rigid or place or floor else [res]
+        placed = res.pop() if place or floor else None
         poses, hyps, bones = res[0], (res[1] if cfg.lift.hyps else None), (res[-1] if rigid else None)
+        cam_rows = np.concatenate(camera_table(cameras[name]), axis=1) if use_cams else None
         for i, p in enumerate(poses):
             key = name if len(poses) == 1 else f"{name}.{i}"
             out[key] = p.cpu().numpy()
@@ -289,6 +329,11 @@ def lift_sequences_to_file(model, cfg, groups, path):
                 out[key + "__hyps"] = hyps[i].cpu().numpy()
             if bones is not None:
                 out[key + "__bones"] = bones[i].cpu().numpy()
+            if placed is not None:
+                for k, v in placed[i].items():
+                    out[f"{key}__{k}"] = v.cpu().numpy()
+            if cam_rows is not None:
+                out[key + "__cam"] = cam_rows[i]
     np.savez(path, **out)
     return out
 
@@ -312,6 +357,7 @@ def run(argv, extra_defaults=None):
     from manipose_amd.distributed import broadcast_parameters, init_from_env
     from manipose_amd.training import LiftingTrainer
     cfg = load_config(argv, extra_defaults)
+    lift_place_options(cfg)                    # a lift.place / lift.frame / lift.floor that cannot run fails here, before the model is built
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")
@@ -479,6 +525,9 @@ def run(argv, extra_defaults=None):
     if cfg.run.lift and rank == 0:         # after run.checkpoint_model / the training above: the weights the test ran on
         groups = {name: sq[1] for name, sq in seqs["test"].items()} if real else synthetic_sequences_2d(cfg, cfg.run.seed)
         path = cfg.lift.output if os.path.isabs(str(cfg.lift.output)) else os.path.join(out_dir, str(cfg.lift.output))
-        lifted = lift_sequences_to_file(model, cfg, groups, path)
-        print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if not k.endswith(('__hyps', '__bones')))} frames of {len(groups)} groups -> {path}", flush=True)
+        cams = None
+        if any(lift_place_options(cfg)[:2]):
+            cams = seqs["test_cams"] if real else synthetic_cameras(groups)
+        lifted = lift_sequences_to_file(model, cfg, groups, path, cams)
+        print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if not k.endswith(LIFT_SUFFIXES))} frames of {len(groups)} groups -> {path}", flush=True)
     return best_val

@@ -438,6 +438,38 @@ int mp_lift_rigid(float* poses, int64_t Ntot, int inner, int J, int C, const int
 int mp_bone_length_means(const float* poses, int64_t Ntot, int J, const int64_t* seq_offset, const int64_t* seq_real, int S, const int32_t* parents,
                          float* lengths, void* stream);
 
+/* Placing lifted sequences in the scene.  What mp_lift_merge / mp_lift_rigid leave is root-relative and in the camera's frame; the reference's
+ * consumer of lift_action rotates it into the world and puts it on the floor first (hpe/viz.py:93-98: camera_to_world(prediction, R, t = 0), then
+ * z -= min z), and its data/camera.py ships the H36M camera model (project_to_2d).  Conventions of mp_lift_rigid: poses (Ntot, inner, J, C) device
+ * floats, C = 3 or 4 (channel 3, a hypothesis' score, is neither read nor written), 2 <= J <= 32, seq_offset (S + 1) device int64: frame g belongs
+ * to the last sequence s with seq_offset[s] <= g; one lane owns one pose.  All arithmetic between the float32 loads and the float32 stores is fp64.
+ * A null pointer, C outside {3, 4}, J outside 2..32, Ntot / inner / S <= 0 or S > Ntot, or more poses than one grid holds: MP_ERR_ARG before
+ * anything is launched.  Neither call synchronises.
+ * mp_lift_place (poses read only): per pose the root translation t that fits the 2-D keypoints kp (Ntot, J, 2) of its frame (normalised screen
+ * coordinates, shared by the frame's `inner` poses) under the pinhole part of the camera intr (S, 9) = (fx, fy, cx, cy, k1, k2, k3, p1, p2) of its
+ * sequence, and the reprojection error of the placed pose.  weights (J) device floats or null (all ones); a joint of weight 0 is skipped.  With
+ * a_j = (u_j - cx) / fx, b_j = (v_j - cy) / fy, ex_j = X_j - a_j Z_j, ey_j = Y_j - b_j Z_j, t minimises
+ * sum_j w_j [(ex_j + tx - a_j tz)^2 + (ey_j + ty - b_j tz)^2]: with W = sum w, A = sum w a, B = sum w b, Q = sum w (a^2 + b^2) (sums in joint order)
+ *   [[W, 0, -A], [0, W, -B], [-A, -B, Q]] t = [-sum w ex, -sum w ey, sum w (a ex + b ey)],
+ * solved as  D = W Q - A^2 - B^2,  tz = (W sum w (a ex + b ey) - A sum w ex - B sum w ey) / D,  tx = (A tz - sum w ex) / W,  ty = (B tz - sum w ey) / W.
+ * reproj = sum_j w_j d_j / W, d_j the distance between (u_j, v_j) and pi(P_j), P_j = (X_j, Y_j, Z_j) + t; distort = 1: pi is project_to_2d
+ * (XX = clamp(P.xy / P.z, -1, 1), r2 = |XX|^2, XXX = XX (1 + k1 r2 + k2 r2^2 + k3 r2^3 + p . XX) + p r2, pi = f XXX + c); distort = 0: pi is
+ * project_to_2d_linear (f XX + c, the clamp included).  Normalised screen units: times res_w / 2 gives pixels.
+ * traj (Ntot, inner, 3) and reproj (Ntot, inner) floats, ok (Ntot, inner) bytes.  ok = 0 with t = (0, 0, 0) and reproj = 0: W <= 0, a non-finite sum,
+ * or D <= 1e-9 W Q (D / (W Q) lies in [0, 1]; 0: all weighted keypoints coincide).  ok = 0 with t and reproj stored as computed: a weighted joint
+ * with Z_j + tz <= 0.  Otherwise ok = 1.  A pose's result depends on no other pose.
+ * mp_lift_world (poses updated IN PLACE): every joint p <- qrot(q_s, p + traj) + trans_s,  qrot(q, v) = v + 2 (w (q_xyz x v) + q_xyz x (q_xyz x v))
+ * (the reference's qrot, data/quaternion.py:6-20: q is not normalised); quat (S, 4) = (w, x, y, z); traj (Ntot, inner, 3) or null, trans (S, 3) or
+ * null: with both null this is camera_to_world(., R, t = 0).  floor_mode 0: nothing more.  1: after the float32 results are stored, floor[s] (S floats,
+ * written) = the minimum stored z over every frame, inner index and joint of sequence s (fminf: a NaN is passed over), and every z of the sequence
+ * becomes the ONE float32 difference z - floor[s]; scratch holds at least S * MP_LIFT_WORLD_SHARES floats (one partial minimum per workgroup, merged
+ * in a fixed order; no atomics: identical bits on every call).  2: z - floor[s] with the caller's floor (read; scratch may be null). */
+#define MP_LIFT_WORLD_SHARES 16
+int mp_lift_place(const float* poses, int64_t Ntot, int inner, int J, int C, const float* kp, const int64_t* seq_offset, int S, const float* intr,
+                  const float* weights, int distort, float* traj, float* reproj, uint8_t* ok, void* stream);
+int mp_lift_world(float* poses, int64_t Ntot, int inner, int J, int C, const float* traj, const int64_t* seq_offset, int S, const float* quat,
+                  const float* trans, int floor_mode, float* floor, float* scratch, int64_t scratch_floats, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

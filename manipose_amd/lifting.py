@@ -12,6 +12,11 @@ windows, one length prediction per window), so after the merge every sequence ge
 (``"model"``), the mean lengths of the merged poses (``"measured"``, ``mp_bone_length_means``) or the caller's - and ``mp_lift_rigid``
 re-assembles every emitted pose and hypothesis along its own bone directions with them (include/manipose_hip.h has the definition).
 
+Placing (``place`` / ``frame="world"`` / ``floor``, all off by default): the merged poses are root-relative and in the camera's frame.  With
+the sequences' cameras (``camera_table``) ``mp_lift_place`` fits, per pose and per hypothesis, the root translation whose pinhole projection meets
+the 2-D keypoints the pose was lifted from, and reports the reprojection error under the full H36M camera model; ``mp_lift_world`` rotates
+everything into the world frame (the reference's ``camera_to_world``, hpe/viz.py:93-98) and, with ``floor``, puts the sequence on z = 0.
+
 Scheduling: a sequence is lifted on its own - its windows are cut into forwards of ``batch`` (``2 * batch`` with TTA), all of them
 stay resident until the sequence is merged, and no forward mixes two sequences.  A frame's covering windows are therefore always
 resident when it is merged (no partial sum is ever carried), and a sequence's result does not depend on what else is lifted with
@@ -158,6 +163,157 @@ def project_rigid(poses, lengths, seq_offset=None, skeleton=None):
     return poses
 
 
+FLOOR_SHARES = 16            # MP_LIFT_WORLD_SHARES of include/manipose_hip.h: partial minima per sequence in mp_lift_world's scratch
+
+
+def camera_table(cameras):
+    """Per-sequence cameras as the float32 numpy tables the kernels read: ``intr`` (S, 9) = (fx, fy, cx, cy, k1, k2, k3, p1, p2) in normalised
+    screen units, ``quat`` (S, 4) = (w, x, y, z), ``trans`` (S, 3) in metres.  ``cameras``: one entry per sequence, either a dict as
+    ``h36m_cameras()`` gives (``intrinsic``, ``orientation``, optionally ``translation``: zeros when absent) or a 1-D array of at least 16
+    numbers in ``fetch()``'s order (intrinsic 9, orientation 4, translation 3[, camera index]).  ValueError for a wrong shape or a non-finite entry."""
+    if isinstance(cameras, dict) or (hasattr(cameras, "ndim") and getattr(cameras, "ndim", 0) == 1):
+        raise ValueError("cameras must be a list with one camera per sequence (a dict or a 1-D array of >= 16 numbers each)")
+    cams = list(cameras)
+    if not cams:
+        raise ValueError("cameras is empty: one camera per sequence expected")
+    rows = np.zeros((len(cams), 16), dtype=np.float32)
+    for s, cam in enumerate(cams):
+        if isinstance(cam, dict):
+            if "intrinsic" not in cam or "orientation" not in cam:
+                raise ValueError(f"camera {s}: a camera dict needs 'intrinsic' (9) and 'orientation' (4)")
+            parts = [np.asarray(cam["intrinsic"]), np.asarray(cam["orientation"]), np.asarray(cam.get("translation", np.zeros(3)))]
+            for name, a, n in zip(("intrinsic", "orientation", "translation"), parts, (9, 4, 3)):
+                if a.shape != (n,) or a.dtype.kind not in "fiu":
+                    raise ValueError(f"camera {s}: '{name}' must be {n} numbers, got shape {a.shape} {a.dtype}")
+            row = np.concatenate([a.astype(np.float64) for a in parts])
+        else:
+            a = cam.detach().cpu().numpy() if torch.is_tensor(cam) else np.asarray(cam)
+            if a.ndim != 1 or a.shape[0] < 16 or a.dtype.kind not in "fiu":
+                raise ValueError(f"camera {s}: expected a dict or a 1-D array of at least 16 numbers (intrinsic 9, orientation 4, translation 3), "
+                                 f"got shape {a.shape} {a.dtype}")
+            row = a[:16].astype(np.float64)
+        if not np.isfinite(row).all():
+            raise ValueError(f"camera {s}: non-finite entry")
+        rows[s] = row
+    return rows[:, :9].copy(), rows[:, 9:13].copy(), rows[:, 13:16].copy()
+
+
+def _poses4(poses, who):
+    if not torch.is_tensor(poses) or not poses.is_cuda:
+        raise RuntimeError(f"manipose_amd: {who} takes device tensors; there is no CPU fallback")
+    p4 = poses.unsqueeze(1) if poses.dim() == 3 else poses
+    if p4.dim() != 4 or p4.shape[3] not in (3, 4) or (poses.dim() == 3 and poses.shape[2] != 3) or poses.dtype != torch.float32 \
+            or not poses.is_contiguous():
+        raise ValueError(f"poses must be contiguous float32 (Ntot, J, 3) or (Ntot, inner, J, 3 | 4), got {tuple(poses.shape)} {poses.dtype}")
+    if not 2 <= int(p4.shape[2]) <= 32:
+        raise ValueError(f"poses have {int(p4.shape[2])} joints: 2..32 expected")
+    return p4
+
+
+def _device_f32(a, dev, shape, what):
+    """a float32 device copy of a per-sequence table (tensor or array) after its shape and finiteness were checked on the host"""
+    h = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    if h.dtype.kind not in "fiu" or h.shape != shape:
+        raise ValueError(f"{what} must be {shape} numbers, got shape {tuple(h.shape)} {h.dtype}")
+    h = np.array(h, dtype=np.float32, order="C")
+    if not np.isfinite(h).all():
+        raise ValueError(f"{what} must be finite")
+    return torch.from_numpy(h).to(dev)
+
+
+def _seq_table(seq_offset, ntot, dev):
+    d_off = _device_i64(seq_offset if seq_offset is not None else [0, ntot], dev)
+    if d_off.dim() != 1 or d_off.numel() < 2:
+        raise ValueError("seq_offset must hold S + 1 >= 2 frame numbers")
+    return d_off, int(d_off.numel()) - 1
+
+
+def _place(lib, p4, kp, d_off, S, d_intr, d_w, distort):
+    ntot, inner, J, ch = (int(v) for v in p4.shape)
+    dev = p4.device
+    traj = torch.empty(ntot, inner, 3, dtype=torch.float32, device=dev)
+    reproj = torch.empty(ntot, inner, dtype=torch.float32, device=dev)
+    ok = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
+    if ntot > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_place(_lib.ptr(p4), ntot, inner, J, ch, _lib.ptr(kp), _lib.ptr(d_off), S, _lib.ptr(d_intr), _lib.ptr(d_w),
+                                         int(bool(distort)), _lib.ptr(traj), _lib.ptr(reproj), _lib.ptr(ok), _lib.stream_ptr()), "mp_lift_place")
+    return traj, reproj, ok
+
+
+def _world(lib, p4, traj, d_off, S, d_quat, d_trans, floor_mode=0, d_floor=None):
+    ntot, inner, J, ch = (int(v) for v in p4.shape)
+    if ntot == 0:
+        return
+    scratch = torch.empty(S * FLOOR_SHARES, dtype=torch.float32, device=p4.device) if floor_mode == 1 else None
+    with torch.cuda.device(p4.device):
+        _lib.check(lib.mp_lift_world(_lib.ptr(p4), ntot, inner, J, ch, _lib.ptr(traj), _lib.ptr(d_off), S, _lib.ptr(d_quat), _lib.ptr(d_trans),
+                                     int(floor_mode), _lib.ptr(d_floor), _lib.ptr(scratch), S * FLOOR_SHARES if floor_mode == 1 else 0,
+                                     _lib.stream_ptr()), "mp_lift_world")
+
+
+def place_poses(poses, keypoints_2d, intrinsics, seq_offset=None, weights=None, distort=True):
+    """``mp_lift_place`` on device tensors: per pose the root translation that fits the frame's 2-D keypoints, and the reprojection error.
+    ``poses`` (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32 (channel 3, a hypothesis' score, is not read); ``keypoints_2d`` (Ntot, J, 2) in
+    normalised screen coordinates, shared by the ``inner`` poses of a frame; ``intrinsics`` (S, 9) or (9,), tensor or array, as
+    ``camera_table`` / ``h36m_cameras()[s][i]["intrinsic"]``; ``seq_offset`` (S + 1): first frame of every sequence, HOST table or device int64
+    tensor (default: one sequence); ``weights`` (J) non-negative or None (all ones; a joint of weight 0 is skipped).  The fit uses the pinhole
+    part of the camera; the error the full model (``distort=True``, the reference's project_to_2d) or project_to_2d_linear, in normalised screen
+    units (times res_w / 2: pixels).  Returns ``traj`` (Ntot[, inner], 3) in the poses' unit, ``reproj`` (Ntot[, inner]), ``ok`` uint8: 0 where the
+    fit is degenerate (no weight, a non-finite input, all keypoints on one spot: traj and reproj are 0) or puts a joint behind the camera."""
+    p4 = _poses4(poses, "place_poses")
+    dev, ntot, J = poses.device, int(p4.shape[0]), int(p4.shape[2])
+    if not torch.is_tensor(keypoints_2d) or not keypoints_2d.is_cuda:
+        raise RuntimeError("manipose_amd: place_poses takes device tensors; there is no CPU fallback")
+    if tuple(keypoints_2d.shape) != (ntot, J, 2) or keypoints_2d.dtype != torch.float32:
+        raise ValueError(f"keypoints_2d must be float32 ({ntot}, {J}, 2), got {tuple(keypoints_2d.shape)} {keypoints_2d.dtype}")
+    d_off, S = _seq_table(seq_offset, ntot, dev)
+    h = intrinsics.detach().cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics)
+    d_intr = _device_f32(h[None] if h.shape == (9,) and S == 1 else h, dev, (S, 9), "intrinsics")
+    d_w = None
+    if weights is not None:
+        d_w = _device_f32(weights, dev, (J,), "weights")
+        if bool((d_w < 0).any()):
+            raise ValueError("weights must be non-negative")
+    traj, reproj, ok = _place(_lib.load(), p4, keypoints_2d.contiguous(), d_off, S, d_intr, d_w, distort)
+    return (traj[:, 0], reproj[:, 0], ok[:, 0]) if poses.dim() == 3 else (traj, reproj, ok)
+
+
+def to_world(poses, orientation, translation=None, traj=None, seq_offset=None, floor=False):
+    """``mp_lift_world`` on a device tensor, IN PLACE (and returned): every joint p <- qrot(q_s, p + traj) + t_s.  ``poses`` (Ntot, J, 3) or
+    (Ntot, inner, J, 3 | 4) (channel 3 is left alone); ``orientation`` (S, 4) or (4,) quaternions (w, x, y, z) as the dataset stores them (not
+    normalised here, like the reference's qrot); ``translation`` (S, 3) / (3,) or None; ``traj`` (Ntot[, inner], 3) device tensor as
+    ``place_poses`` returns it, or None - with both None this is the reference's camera_to_world(., R, t = 0); ``seq_offset`` as for
+    ``place_poses``.  ``floor=True``: every sequence's lowest joint is put on z = 0 and ``(poses, offsets)`` is returned, offsets (S,) = the
+    minimum z subtracted; ``floor`` = a tensor or array (S,): those offsets are subtracted instead (one scene for several arrays)."""
+    p4 = _poses4(poses, "to_world")
+    dev, ntot = poses.device, int(p4.shape[0])
+    d_off, S = _seq_table(seq_offset, ntot, dev)
+
+    def table(a, n, what):
+        h = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return _device_f32(h[None] if h.shape == (n,) and S == 1 else h, dev, (S, n), what)
+    d_quat = table(orientation, 4, "orientation")
+    d_trans = table(translation, 3, "translation") if translation is not None else None
+    if traj is not None:
+        if not torch.is_tensor(traj) or not traj.is_cuda:
+            raise RuntimeError("manipose_amd: to_world takes device tensors; there is no CPU fallback")
+        if tuple(traj.shape) != tuple(poses.shape[:-2]) + (3,) or traj.dtype != torch.float32:
+            raise ValueError(f"traj must be float32 {tuple(poses.shape[:-2]) + (3,)}, got {tuple(traj.shape)} {traj.dtype}")
+        traj = traj.contiguous()
+    if floor is True:
+        d_floor = torch.empty(S, dtype=torch.float32, device=dev)
+        _world(_lib.load(), p4, traj, d_off, S, d_quat, d_trans, 1, d_floor)
+        return poses, d_floor
+    if floor is False or floor is None:
+        _world(_lib.load(), p4, traj, d_off, S, d_quat, d_trans)
+        return poses
+    h = floor.detach().cpu().numpy() if torch.is_tensor(floor) else np.asarray(floor)
+    d_floor = _device_f32(h.reshape(1) if h.ndim == 0 and S == 1 else h, dev, (S,), "floor")
+    _world(_lib.load(), p4, traj, d_off, S, d_quat, d_trans, 2, d_floor)
+    return poses
+
+
 def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirror, agg="weighted_ave", blend="mean", scale=1.0,
                   return_hyps=False, out=None, hyps=None, device_tables=None):
     """``mp_lift_merge`` on device tensors: poses (F*W, K, T, J, 3), scores (F*W, K, T, 1) or None (K == 1); win_seq / win_start (W)
@@ -194,7 +350,8 @@ def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirr
 
 @torch.no_grad()
 def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
-                   keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False):
+                   keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
+                   floor=False, return_place=False):
     """One 3-D pose per frame of every sequence.  ``poses_2d``: a list of (N_i, 17, 2) device tensors or numpy arrays (or one such
     array); returns a list of (N_i, 17, 3) device tensors, and with ``return_hyps`` also a list of (N_i, K, 17, 4) (every hypothesis
     and its score, from the un-mirrored pass).  ``stride`` (default T: non-overlapping windows) in 1..T; ``blend`` "mean" averages the
@@ -207,13 +364,47 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
     sequence's windows of the lengths the model predicted (with TTA the mirrored copy's, left and right swapped back, averaged in), the
     default of the two manifold models; "measured" = the mean bone lengths of the sequence's merged poses over its real frames, the default of
     MixSTE, which predicts none; or an (S, J - 1) / (J - 1,) table in metres.  ``symmetric`` replaces every left / right pair of the table
-    by its mean.  ``return_bones`` appends the list of (J - 1,) tables used, in metres (``scale`` multiplies poses and lengths alike)."""
+    by its mean.  ``return_bones`` appends the list of (J - 1,) tables used, in metres (``scale`` multiplies poses and lengths alike).
+
+    Placing (all off by default: nothing changes by a bit), after the merge and the rigid stage.  ``cameras``: one camera per sequence
+    (``camera_table``).  ``place``: ``mp_lift_place`` fits the root translation of every merged pose and, with ``return_hyps``, of every
+    hypothesis (each its own) to the sequence's 2-D keypoints; ``return_place`` appends a list of per-sequence dicts ``traj`` (N, 3), ``reproj``
+    (N,), ``ok`` (N,) uint8 and with hypotheses ``hyps_traj`` (N, K, 3), ``hyps_reproj`` (N, K), ``hyps_ok`` (N, K) - and ``floor`` (a scalar)
+    when ``floor`` is on, the only key without ``place``; the results come in the order poses, hyps, bones, place.  ``frame="world"``:
+    ``mp_lift_world`` rotates the merged poses and the hypotheses by the camera's orientation; with ``place`` their trajectories are added
+    first and the camera's translation (times ``scale``, so ``traj`` and the world poses are in the poses' unit) afterwards, without it the
+    rotation alone (the reference's prepare_prediction_for_viz before its floor line).  ``floor`` (needs ``frame="world"``): every sequence's
+    lowest merged joint is put on z = 0, and the SAME offset is subtracted from the hypotheses - merged pose and hypotheses stand in one scene
+    (the reference floors each array on its own).  Not with ``keep_padding``: padded frames have no keypoints of their own."""
     if not rigid and (lengths is not None or symmetric or return_bones):
         raise ValueError("lengths, symmetric and return_bones describe rigid lifting: pass rigid=True")
+    if frame not in ("camera", "world"):
+        raise ValueError(f"frame must be 'camera' or 'world', got {frame!r}")
+    if not isinstance(place, (bool, np.bool_)) or not isinstance(floor, (bool, np.bool_)):
+        raise ValueError("place and floor are switches (True / False); to_world takes given floor offsets")
+    world = frame == "world"
+    if place and cameras is None:
+        raise ValueError("place=True needs cameras: one camera per sequence (camera_table)")
+    if world and cameras is None:
+        raise ValueError("frame='world' needs cameras: one camera per sequence (camera_table)")
+    if floor and not world:
+        raise ValueError("floor=True puts the world frame's z on the floor: pass frame='world'")
+    if cameras is not None and not (place or world):
+        raise ValueError("cameras describe place=True and frame='world': pass one of them")
+    if return_place and not (place or floor):
+        raise ValueError("return_place returns what place=True (and floor=True) computed: pass place=True")
+    if (place or world) and keep_padding:
+        raise ValueError("place / frame='world' with keep_padding=True: padded frames have no keypoints of their own")
     single = torch.is_tensor(poses_2d) or isinstance(poses_2d, np.ndarray)
     seqs = [poses_2d] if single else list(poses_2d)
+    n_res = 1 + bool(return_hyps) + bool(return_bones) + bool(return_place)
     if not seqs:
-        return tuple([] for _ in range(1 + bool(return_hyps) + bool(return_bones))) if return_hyps or return_bones else []
+        return tuple([] for _ in range(n_res)) if n_res > 1 else []
+    cam_tables = None
+    if place or world:
+        cam_tables = camera_table(cameras)
+        if cam_tables[0].shape[0] != len(seqs):
+            raise ValueError(f"cameras: {cam_tables[0].shape[0]} cameras for {len(seqs)} sequences")
     table = None
     if rigid:                                                # argument errors first: nothing has touched the device yet
         T, J, K = _model_shape(model)
@@ -341,11 +532,30 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
         _rigid(lib, out_all.unsqueeze(1), d_rigid_off, len(lens), used, parents)
         if return_hyps:
             _rigid(lib, hyp_all, d_rigid_off, len(lens), used, parents)
+    placed = None
+    if place or world:                                       # (no padded frames here: a frame of out_all is the frame of p2 with the same number)
+        S = len(lens)
+        d_intr, d_quat = torch.from_numpy(cam_tables[0]).to(dev), torch.from_numpy(cam_tables[1]).to(dev)
+        d_trans = torch.from_numpy(cam_tables[2] * np.float32(scale)).to(dev) if place else None
+        placed = {}
+        if place:
+            placed["traj"], placed["reproj"], placed["ok"] = (t[:, 0] for t in _place(lib, out_all.unsqueeze(1), p2, d_off, S, d_intr, None, True))
+            if return_hyps:
+                placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"] = _place(lib, hyp_all, p2, d_off, S, d_intr, None, True)
+        if world:
+            d_floor = torch.empty(S, dtype=torch.float32, device=dev) if floor else None
+            _world(lib, out_all.unsqueeze(1), placed["traj"].unsqueeze(1).contiguous() if place else None, d_off, S, d_quat, d_trans,
+                   1 if floor else 0, d_floor)
+            if return_hyps:                                  # the hypotheses stand on the merged poses' floor
+                _world(lib, hyp_all, placed.get("hyps_traj"), d_off, S, d_quat, d_trans, 2 if floor else 0, d_floor)
     res = [list(torch.split(out_all, out_lens, dim=0))]
     if return_hyps:
         res.append(list(torch.split(hyp_all, out_lens, dim=0)))
     if return_bones:
         res.append(list(bones.unbind(0)))
+    if return_place:
+        per_seq = {k: torch.split(v, out_lens, dim=0) for k, v in placed.items()}
+        res.append([dict({k: v[i] for k, v in per_seq.items()}, **({"floor": d_floor[i]} if floor else {})) for i in range(len(lens))])
     return res[0] if len(res) == 1 else tuple(res)
 
 
@@ -361,4 +571,5 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
     return torch.cat(res, dim=0).cpu().numpy()
 
 
-__all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "lift_sequences", "lift_action"]
+__all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "to_world", "lift_sequences",
+           "lift_action"]

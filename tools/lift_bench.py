@@ -3,7 +3,10 @@
       pose_flip of the mirrored hypotheses, mp_aggregate, average - "weighted_ave" only, and with "best_score" as evaluate computes both;
   (b) mp_lift_merge (one kernel).
 Then lift_sequences end to end (gather + forward + merge) at the same batch.
-    python tools/lift_bench.py [W=158] [T=243] [K=5] [precision=bf16x3] [reps=50]"""
+    python tools/lift_bench.py [W=158] [T=243] [K=5] [precision=bf16x3] [reps=50]
+    python tools/lift_bench.py --place [frames=3000] [K=5] [reps=50]
+--place times only the two kernels that put a lifted sequence in the scene (mp_lift_place: root translation and reprojection error of every
+hypothesis; mp_lift_world: world frame, with and without the floor) on `frames` frames x K hypotheses of one sequence with S11's first camera."""
 import os
 import sys
 
@@ -16,6 +19,50 @@ from manipose_amd import RMCLManifoldMixSTE, h36m_skeleton, lift_sequences, plan
 from manipose_amd.augmentations import pose_flip
 from manipose_amd.lifting import _mirror, merge_windows
 
+
+
+def timed_us(fn, reps):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(reps):
+        fn()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) / reps * 1e3
+
+
+def place_bench(argv):
+    from manipose_amd import camera_table, place_poses, to_world
+    from manipose_amd.data.ingest import h36m_cameras
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    K = int(argv[1]) if len(argv) > 1 else 5
+    reps = int(argv[2]) if len(argv) > 2 else 50
+    assert torch.cuda.is_available(), "needs an MI355X"
+    intr, quat, trans = camera_table(h36m_cameras()["S11"][:1])
+    g = torch.Generator(device="cuda").manual_seed(1)
+    hyps = 0.3 * torch.randn(frames, K, 17, 4, device="cuda", generator=g)
+    hyps[:, 1:, :, :3] = hyps[:, :1, :, :3] + 0.05 * torch.randn(frames, K - 1, 17, 3, device="cuda", generator=g)      # hypotheses of ONE frame
+    hyps[:, :, 0, :3] = 0
+    centre = torch.tensor([0.0, 0.0, 5.0], device="cuda")
+    P = hyps[:, 0, :, :3] + centre
+    kp = (torch.from_numpy(intr[0, 0:2]).cuda() * P[..., :2] / P[..., 2:3] + torch.from_numpy(intr[0, 2:4]).cuda()).contiguous()
+    traj, _, ok = place_poses(hyps, kp, intr)
+    print(f"--place: {frames} frames x {K} hypotheses, {hyps.numel() * 4 / 1e6:.2f} MB of poses; ok on {ok.float().mean().item():.3f} of them", flush=True)
+    work = hyps.clone()
+    for name, fn in (("mp_lift_place (full camera model)", lambda: place_poses(hyps, kp, intr)),
+                     ("mp_lift_place (linear projection)", lambda: place_poses(hyps, kp, intr, distort=False)),
+                     ("mp_lift_world", lambda: to_world(work, quat, trans, traj)),
+                     ("mp_lift_world + floor (3 kernels)", lambda: to_world(work, quat, trans, traj, floor=True))):
+        us = timed_us(fn, reps)            # (the public functions: their table uploads are inside the time)
+        print(f"{name}: {us:,.1f} us  {frames * K / us:,.2f} M poses/s", flush=True)
+
+
+if "--place" in sys.argv:
+    place_bench([a for a in sys.argv[1:] if a != "--place"])
+    sys.exit(0)
 W = int(sys.argv[1]) if len(sys.argv) > 1 else 158
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 243
 K = int(sys.argv[3]) if len(sys.argv) > 3 else 5
