@@ -306,7 +306,8 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
     (N,), ``<key>__ok`` (N,) uint8 and with lift.hyps ``<key>__hyps_traj`` (N, K, 3), ``<key>__hyps_reproj``, ``<key>__hyps_ok`` (N, K)) and by
     lift.frame=world (poses and hypotheses in the world frame; with lift.floor on z = 0 and ``<key>__floor``, the offset subtracted); whenever
     cameras were used ``<key>__cam`` holds the 16 numbers (intrinsic 9, orientation 4, translation 3)."""
-    from manipose_amd import camera_table, lift_sequences
+    from manipose_amd import camera_table
+    from manipose_amd.lifting import _lift_sequences
     out = {}
     rigid = bool(cfg.lift.get("rigid", False))
     place, world, floor = lift_place_options(cfg)
@@ -314,23 +315,20 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
     if use_cams and cameras is None:
         raise ValueError("lift.place / lift.frame=world need the sequences' cameras")
     for name, seqs in groups.items():
-        res = lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=cfg.lift.agg, blend=cfg.lift.blend,
-                             return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
-                             symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid, cameras=cameras[name] if use_cams else None,
-                             place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor)
-        res = list(res) if cfg.lift.hyps or rigid or place or floor else [res]
-        placed = res.pop() if place or floor else None
-        poses, hyps, bones = res[0], (res[1] if cfg.lift.hyps else None), (res[-1] if rigid else None)
+        res = _lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=cfg.lift.agg, blend=cfg.lift.blend,
+                              return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
+                              symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid, cameras=cameras[name] if use_cams else None,
+                              place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor)
         cam_rows = np.concatenate(camera_table(cameras[name]), axis=1) if use_cams else None
-        for i, p in enumerate(poses):
-            key = name if len(poses) == 1 else f"{name}.{i}"
+        for i, p in enumerate(res.poses):
+            key = name if len(res.poses) == 1 else f"{name}.{i}"
             out[key] = p.cpu().numpy()
-            if hyps is not None:
-                out[key + "__hyps"] = hyps[i].cpu().numpy()
-            if bones is not None:
-                out[key + "__bones"] = bones[i].cpu().numpy()
-            if placed is not None:
-                for k, v in placed[i].items():
+            if res.hyps is not None:
+                out[key + "__hyps"] = res.hyps[i].cpu().numpy()
+            if res.bones is not None:
+                out[key + "__bones"] = res.bones[i].cpu().numpy()
+            if res.place is not None:
+                for k, v in res.place[i].items():
                     out[f"{key}__{k}"] = v.cpu().numpy()
             if cam_rows is not None:
                 out[key + "__cam"] = cam_rows[i]

@@ -11,12 +11,12 @@
 // 256 / (3 J) whole frames; one thread per frame first finds the covering windows in the tables (binary search over the windows in
 // their sorted order, or arithmetic when the host found one uniform stride) and leaves them in LDS for the frame's 3 J lanes.
 // Traffic: every hypothesis float the output needs is read once, 4 F K B per output float at stride = T; HBM-bound.
-#include "common.h"
+#include "lift_common.h"
 #include "../../include/manipose_hip.h"
 
 namespace mp {
 
-constexpr int LIFT_MAXJ = 32, LIFT_MAXK = 8, LIFT_THREADS = 256;
+constexpr int LIFT_MAXK = 8, LIFT_THREADS = 256;
 struct LiftArgs {
   const float* poses; const float* scores;
   const long* seq_offset; const int* win_seq; const int* win_start;

@@ -13,22 +13,12 @@
 // Floor (mode 1): the minimum is taken from the STORED float32 values by a second kernel - MP_LIFT_WORLD_SHARES workgroups per sequence, each
 // over one contiguous share of the sequence's poses, DPP inside a wave, LDS across the 4 waves, one partial per workgroup - and the third
 // kernel merges a sequence's partials in share order, subtracts, and writes floor[s].  No atomics: the same bits on every call.
-#include "common.h"
+#include "lift_common.h"
 #include "../../include/manipose_hip.h"
 
 namespace mp {
 
-constexpr int PLACE_MAXJ = 32, PLACE_THREADS = 256, FLOOR_SHARES = MP_LIFT_WORLD_SHARES;
-
-// the sequence of frame g: last s with seq_offset[s] <= g (always inside 0 .. S-1, whatever the device table holds)
-__device__ __forceinline__ int place_seq_of(const long* seq_offset, int S, long g) {
-  int lo = 0, hi = S - 1;
-  while (lo < hi) {
-    const int m = (lo + hi + 1) >> 1;
-    if (seq_offset[m] <= g) lo = m; else hi = m - 1;
-  }
-  return lo;
-}
+constexpr int FLOOR_SHARES = MP_LIFT_WORLD_SHARES;
 
 // torch.clamp(x, -1, 1): a NaN stays a NaN
 __device__ __forceinline__ double place_clamp1(double x) { return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x); }
@@ -46,11 +36,11 @@ struct PlaceArgs {
   int inner, J, C, S, distort;
 };
 
-__global__ __launch_bounds__(PLACE_THREADS) void lift_place_kernel(PlaceArgs A) {
-  const long i = (long)blockIdx.x * PLACE_THREADS + threadIdx.x;       // pose (frame, inner index)
+__global__ __launch_bounds__(POSE_THREADS) void lift_place_kernel(PlaceArgs A) {
+  const long i = (long)blockIdx.x * POSE_THREADS + threadIdx.x;        // pose (frame, inner index)
   if (i >= A.npose) return;
   const long g = i / A.inner;                                          // frame
-  const int s = place_seq_of(A.seq_offset, A.S, g);
+  const int s = lift_seq_of(A.seq_offset, A.S, g);
   const float* cam = A.intr + (long)s * 9;
   const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
   const float* P = A.poses + i * A.J * A.C;
@@ -113,10 +103,10 @@ struct WorldArgs {
 };
 
 // p <- qrot(q, p + traj) + trans; mode 2 also subtracts the caller's floor from the float32 z it would have stored
-__global__ __launch_bounds__(PLACE_THREADS) void lift_world_kernel(WorldArgs A) {
-  const long i = (long)blockIdx.x * PLACE_THREADS + threadIdx.x;
+__global__ __launch_bounds__(POSE_THREADS) void lift_world_kernel(WorldArgs A) {
+  const long i = (long)blockIdx.x * POSE_THREADS + threadIdx.x;
   if (i >= A.npose) return;
-  const int s = place_seq_of(A.seq_offset, A.S, i / A.inner);
+  const int s = lift_seq_of(A.seq_offset, A.S, i / A.inner);
   const float* q = A.quat + (long)s * 4;
   const double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
   const bool move = A.traj != nullptr, shift = A.trans != nullptr;
@@ -138,15 +128,15 @@ __global__ __launch_bounds__(PLACE_THREADS) void lift_world_kernel(WorldArgs A) 
 }
 
 // workgroup (c, s): the minimum stored z over share c of the poses of sequence s (+inf for an empty share)
-__global__ __launch_bounds__(PLACE_THREADS) void floor_partial_kernel(WorldArgs A) {
-  __shared__ float w_min[PLACE_THREADS / 64];
+__global__ __launch_bounds__(POSE_THREADS) void floor_partial_kernel(WorldArgs A) {
+  __shared__ float w_min[POSE_THREADS / 64];
   const int c = blockIdx.x % FLOOR_SHARES, s = blockIdx.x / FLOOR_SHARES, tid = threadIdx.x;
-  // (the offsets are device data no host check has seen: clamped to the Ntot frames the caller vouches for)
-  const long f0 = min(max(A.seq_offset[s], 0L), A.Ntot), f1 = min(max(A.seq_offset[s + 1], f0), A.Ntot);
+  const FrameRange r = lift_seq_frames(A.seq_offset, s, A.Ntot);
+  const long f0 = r.f0, f1 = r.f1;
   const long n = (f1 - f0) * A.inner, per = (n + FLOOR_SHARES - 1) / FLOOR_SHARES;
   const long p0 = f0 * A.inner + min((long)c * per, n), p1 = f0 * A.inner + min((long)(c + 1) * per, n);
   float m = __builtin_inff();
-  for (long p = p0 + tid; p < p1; p += PLACE_THREADS) {
+  for (long p = p0 + tid; p < p1; p += POSE_THREADS) {
     const float* base = A.poses + p * A.J * A.C;
     for (int j = 0; j < A.J; ++j) m = fminf(m, base[j * A.C + 2]);
   }
@@ -154,7 +144,7 @@ __global__ __launch_bounds__(PLACE_THREADS) void floor_partial_kernel(WorldArgs 
   if ((tid & 63) == 0) w_min[tid >> 6] = m;
   __syncthreads();
   if (tid == 0) {
-    for (int w = 1; w < PLACE_THREADS / 64; ++w) m = fminf(m, w_min[w]);
+    for (int w = 1; w < POSE_THREADS / 64; ++w) m = fminf(m, w_min[w]);
     A.partial[(long)s * FLOOR_SHARES + c] = m;
   }
 }
@@ -166,24 +156,14 @@ __device__ __forceinline__ float floor_merge(const float* partial, int s) {
 }
 
 // z <- z - floor[s], one float32 subtraction; mode 1: floor[s] is the merge of the sequence's partials, written by lane s of the grid
-__global__ __launch_bounds__(PLACE_THREADS) void floor_apply_kernel(WorldArgs A) {
-  const long i = (long)blockIdx.x * PLACE_THREADS + threadIdx.x;
+__global__ __launch_bounds__(POSE_THREADS) void floor_apply_kernel(WorldArgs A) {
+  const long i = (long)blockIdx.x * POSE_THREADS + threadIdx.x;
   if (i >= A.npose) return;
-  const int s = place_seq_of(A.seq_offset, A.S, i / A.inner);
+  const int s = lift_seq_of(A.seq_offset, A.S, i / A.inner);
   const float fl = A.floor_mode == 1 ? floor_merge(A.partial, s) : A.floor[s];
   float* base = A.poses + i * A.J * A.C;
   for (int j = 0; j < A.J; ++j) base[j * A.C + 2] = base[j * A.C + 2] - fl;
   if (A.floor_mode == 1 && i < A.S) A.floor[i] = floor_merge(A.partial, (int)i);                  // (S <= Ntot <= npose: every sequence has its lane)
-}
-
-static int place_shape(const char* who, long Ntot, int inner, int J, int C, int S, long* blocks) {
-  MP_CHECK(C == 3 || C == 4, MP_ERR_ARG, "%s: C=%d (3: poses, 4: hypotheses with their score)", who, C);
-  MP_CHECK(J >= 2 && J <= PLACE_MAXJ, MP_ERR_ARG, "%s: J=%d outside 2..%d", who, J, PLACE_MAXJ);
-  MP_CHECK(Ntot > 0 && inner > 0 && S > 0 && (long)S <= Ntot, MP_ERR_ARG, "%s: Ntot=%ld inner=%d S=%d out of range", who, Ntot, inner, S);
-  MP_CHECK(Ntot <= 0x7fffffffL * (long)PLACE_THREADS / inner, MP_ERR_ARG, "%s: %ld frames of %d poses: too many for one launch", who, Ntot, inner);
-  *blocks = (Ntot * inner + PLACE_THREADS - 1) / PLACE_THREADS;
-  MP_CHECK(*blocks <= 0x7fffffffL, MP_ERR_ARG, "%s: %ld poses: too many for one launch", who, Ntot * inner);
-  return MP_OK;
 }
 
 }  // namespace mp
@@ -197,12 +177,12 @@ int mp_lift_place(const float* poses, int64_t Ntot, int inner, int J, int C, con
   MP_CHECK(poses && kp && seq_offset && intr && traj && reproj && ok, MP_ERR_ARG, "mp_lift_place: null pointer");
   MP_CHECK(distort == 0 || distort == 1, MP_ERR_ARG, "mp_lift_place: distort=%d (0: project_to_2d_linear, 1: project_to_2d)", distort);
   long blocks = 0;
-  if (int rc = place_shape("mp_lift_place", (long)Ntot, inner, J, C, S, &blocks)) return rc;
+  if (int rc = lift_pose_shape("mp_lift_place", (long)Ntot, inner, J, C, S, &blocks)) return rc;
   PlaceArgs a = {};
   a.poses = poses; a.kp = kp; a.seq_offset = (const long*)seq_offset; a.intr = intr; a.weights = weights;
   a.traj = traj; a.reproj = reproj; a.ok = ok; a.npose = (long)Ntot * inner;
   a.inner = inner; a.J = J; a.C = C; a.S = S; a.distort = distort;
-  hipLaunchKernelGGL(lift_place_kernel, dim3((unsigned)blocks), dim3(PLACE_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(lift_place_kernel, dim3((unsigned)blocks), dim3(POSE_THREADS), 0, (hipStream_t)stream, a);
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
@@ -213,7 +193,7 @@ int mp_lift_world(float* poses, int64_t Ntot, int inner, int J, int C, const flo
   MP_CHECK(floor_mode >= 0 && floor_mode <= 2, MP_ERR_ARG, "mp_lift_world: floor_mode=%d (0 none, 1 compute, 2 given)", floor_mode);
   MP_CHECK(floor_mode == 0 || floor != nullptr, MP_ERR_ARG, "mp_lift_world: floor_mode=%d without a floor table: null pointer", floor_mode);
   long blocks = 0;
-  if (int rc = place_shape("mp_lift_world", (long)Ntot, inner, J, C, S, &blocks)) return rc;
+  if (int rc = lift_pose_shape("mp_lift_world", (long)Ntot, inner, J, C, S, &blocks)) return rc;
   MP_CHECK(floor_mode != 1 || (scratch != nullptr && scratch_floats >= (int64_t)S * FLOOR_SHARES), MP_ERR_ARG,
            "mp_lift_world: floor_mode=1 needs %ld scratch floats (S * MP_LIFT_WORLD_SHARES), got %ld", (long)S * FLOOR_SHARES,
            scratch ? (long)scratch_floats : 0L);
@@ -222,12 +202,12 @@ int mp_lift_world(float* poses, int64_t Ntot, int inner, int J, int C, const flo
   a.poses = poses; a.traj = traj; a.seq_offset = (const long*)seq_offset; a.quat = quat; a.trans = trans; a.floor = floor;
   a.partial = scratch; a.npose = (long)Ntot * inner; a.Ntot = Ntot;
   a.inner = inner; a.J = J; a.C = C; a.S = S; a.floor_mode = floor_mode;
-  hipLaunchKernelGGL(lift_world_kernel, dim3((unsigned)blocks), dim3(PLACE_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(lift_world_kernel, dim3((unsigned)blocks), dim3(POSE_THREADS), 0, (hipStream_t)stream, a);
   MP_LAUNCH_CHECK();
   if (floor_mode == 1) {
-    hipLaunchKernelGGL(floor_partial_kernel, dim3((unsigned)S * FLOOR_SHARES), dim3(PLACE_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(floor_partial_kernel, dim3((unsigned)S * FLOOR_SHARES), dim3(POSE_THREADS), 0, (hipStream_t)stream, a);
     MP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(floor_apply_kernel, dim3((unsigned)blocks), dim3(PLACE_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(floor_apply_kernel, dim3((unsigned)blocks), dim3(POSE_THREADS), 0, (hipStream_t)stream, a);
     MP_LAUNCH_CHECK();
   }
   return MP_OK;

@@ -18,12 +18,10 @@
 // bone_length_means_kernel: one workgroup per sequence.  Thread t adds up the bone lengths of frames t, t + 256, ... of its sequence in fp64
 // (differences, dot product and square root in fp64 too), the 64 lanes of a wave are added in a fixed butterfly order, the 4 waves in wave
 // order: a fixed summation order and no atomics, identical bits on every call.
-#include "common.h"
+#include "lift_common.h"
 #include "../../include/manipose_hip.h"
 
 namespace mp {
-
-constexpr int RIGID_MAXJ = 32, RIGID_THREADS = 256;
 
 struct RigidArgs {
   float* poses;                  // (Ntot, inner, J, C), updated in place
@@ -31,7 +29,7 @@ struct RigidArgs {
   const float* lengths;          // (S, J - 1) device
   long npose;                    // Ntot * inner
   int inner, J, C, S;
-  signed char parent[RIGID_MAXJ];
+  signed char parent[LIFT_MAXJ];
 };
 
 // a[par] for par < j: selects over compile-time indices (par is wave-uniform)
@@ -45,16 +43,12 @@ __device__ __forceinline__ void rigid_pick(const float (&a)[JT][3], int j, int p
 }
 
 template <int JT>
-__global__ __launch_bounds__(RIGID_THREADS) void lift_rigid_kernel(RigidArgs A) {
-  const long i = (long)blockIdx.x * RIGID_THREADS + threadIdx.x;       // pose (frame, inner index)
+__global__ __launch_bounds__(POSE_THREADS) void lift_rigid_kernel(RigidArgs A) {
+  const long i = (long)blockIdx.x * POSE_THREADS + threadIdx.x;        // pose (frame, inner index)
   if (i >= A.npose) return;
   const long g = i / A.inner;                                          // frame
-  int lo = 0, hi = A.S - 1;                                            // the sequence of frame g: last s with seq_offset[s] <= g
-  while (lo < hi) {
-    const int m = (lo + hi + 1) >> 1;
-    if (A.seq_offset[m] <= g) lo = m; else hi = m - 1;
-  }
-  const float* L = A.lengths + (long)lo * (A.J - 1);
+  const int s = lift_seq_of(A.seq_offset, A.S, g);
+  const float* L = A.lengths + (long)s * (A.J - 1);
   float* base = A.poses + i * A.J * A.C;
   float a[JT][3];
 #pragma unroll
@@ -105,7 +99,7 @@ struct BoneMeanArgs {
   float* lengths;                // (S, J - 1)
   long Ntot;
   int J;
-  signed char parent[RIGID_MAXJ];
+  signed char parent[LIFT_MAXJ];
 };
 
 __device__ __forceinline__ double wave_sum_f64(double v) {             // fixed butterfly: the same order on every call
@@ -114,18 +108,18 @@ __device__ __forceinline__ double wave_sum_f64(double v) {             // fixed 
   return v;
 }
 
-__global__ __launch_bounds__(RIGID_THREADS) void bone_length_means_kernel(BoneMeanArgs A) {
-  __shared__ double part[RIGID_THREADS / 64][RIGID_MAXJ];
+__global__ __launch_bounds__(POSE_THREADS) void bone_length_means_kernel(BoneMeanArgs A) {
+  __shared__ double part[POSE_THREADS / 64][LIFT_MAXJ];
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  // (the offsets are device data no host check has seen: clamped to the Ntot frames the caller vouches for, so no frame outside `poses` is read)
-  const long f0 = min(max(A.seq_offset[s], 0L), A.Ntot), len = min(max(A.seq_offset[s + 1], f0), A.Ntot) - f0;
+  const FrameRange r = lift_seq_frames(A.seq_offset, s, A.Ntot);
+  const long f0 = r.f0, len = r.f1 - f0;
   long n = A.seq_real != nullptr ? A.seq_real[s] : len;
   n = n < len ? n : len;                                               // never past the sequence's own frames
   const int J3 = A.J * 3;
   for (int b = 0; b < A.J - 1; ++b) {                                  // one bone at a time: no per-thread array, the frame rows stay in L1 / L2
     const int j = b + 1, p = A.parent[j];
     double acc = 0.0;
-    for (long f = tid; f < n; f += RIGID_THREADS) {
+    for (long f = tid; f < n; f += POSE_THREADS) {
       const float* r = A.poses + (f0 + f) * J3;
       const double dx = (double)r[j * 3] - (double)r[p * 3], dy = (double)r[j * 3 + 1] - (double)r[p * 3 + 1],
                    dz = (double)r[j * 3 + 2] - (double)r[p * 3 + 2];
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(RIGID_THREADS) void bone_length_means_kernel(BoneMe
   __syncthreads();
   if (tid < A.J - 1) {
     double t = part[0][tid];
-    for (int w = 1; w < RIGID_THREADS / 64; ++w) t += part[w][tid];
+    for (int w = 1; w < POSE_THREADS / 64; ++w) t += part[w][tid];
     A.lengths[(long)s * (A.J - 1) + tid] = n > 0 ? (float)(t / (double)n) : 0.f;
   }
 }
@@ -145,7 +139,7 @@ __global__ __launch_bounds__(RIGID_THREADS) void bone_length_means_kernel(BoneMe
 // parents precede children, exactly one root (joint 0)
 static int rigid_parents(const char* who, const int* parents, int J, signed char* dst) {
   MP_CHECK(parents != nullptr, MP_ERR_ARG, "%s: null parent table", who);
-  MP_CHECK(J >= 2 && J <= RIGID_MAXJ, MP_ERR_ARG, "%s: J=%d outside 2..%d", who, J, RIGID_MAXJ);
+  MP_CHECK(J >= 2 && J <= LIFT_MAXJ, MP_ERR_ARG, "%s: J=%d outside 2..%d", who, J, LIFT_MAXJ);
   MP_CHECK(parents[0] == -1, MP_ERR_ARG, "%s: parents[0] = %d: joint 0 must be the root (-1)", who, parents[0]);
   for (int j = 1; j < J; ++j) {
     MP_CHECK(parents[j] >= 0 && parents[j] < j, MP_ERR_ARG, "%s: parents[%d] = %d: parents precede their children", who, j, parents[j]);
@@ -164,18 +158,14 @@ int mp_lift_rigid(float* poses, int64_t Ntot, int inner, int J, int C, const int
                   const int32_t* parents, void* stream) {
   static_assert(sizeof(long) == sizeof(int64_t), "LP64");
   MP_CHECK(poses && seq_offset && lengths, MP_ERR_ARG, "mp_lift_rigid: null pointer");
-  MP_CHECK(C == 3 || C == 4, MP_ERR_ARG, "mp_lift_rigid: C=%d (3: poses, 4: hypotheses with their score)", C);
-  MP_CHECK(Ntot > 0 && inner > 0 && S > 0 && (long)S <= Ntot, MP_ERR_ARG, "mp_lift_rigid: Ntot=%ld inner=%d S=%d out of range", (long)Ntot, inner, S);
+  long blocks = 0;
+  if (int rc = lift_pose_shape("mp_lift_rigid", (long)Ntot, inner, J, C, S, &blocks)) return rc;
   RigidArgs a = {};
   if (int rc = rigid_parents("mp_lift_rigid", parents, J, a.parent)) return rc;
-  MP_CHECK(Ntot <= 0x7fffffffL * (long)RIGID_THREADS / inner, MP_ERR_ARG, "mp_lift_rigid: %ld frames of %d poses: too many for one launch", (long)Ntot,
-           inner);
   a.poses = poses; a.seq_offset = (const long*)seq_offset; a.lengths = lengths; a.npose = (long)Ntot * inner;
   a.inner = inner; a.J = J; a.C = C; a.S = S;
-  const long blocks = (a.npose + RIGID_THREADS - 1) / RIGID_THREADS;
-  MP_CHECK(blocks <= 0x7fffffffL, MP_ERR_ARG, "mp_lift_rigid: %ld poses: too many for one launch", a.npose);
-  if (J <= 17) hipLaunchKernelGGL(lift_rigid_kernel<17>, dim3((unsigned)blocks), dim3(RIGID_THREADS), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(lift_rigid_kernel<RIGID_MAXJ>, dim3((unsigned)blocks), dim3(RIGID_THREADS), 0, (hipStream_t)stream, a);
+  if (J <= 17) hipLaunchKernelGGL(lift_rigid_kernel<17>, dim3((unsigned)blocks), dim3(POSE_THREADS), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(lift_rigid_kernel<LIFT_MAXJ>, dim3((unsigned)blocks), dim3(POSE_THREADS), 0, (hipStream_t)stream, a);
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
@@ -188,7 +178,7 @@ int mp_bone_length_means(const float* poses, int64_t Ntot, int J, const int64_t*
   if (int rc = rigid_parents("mp_bone_length_means", parents, J, a.parent)) return rc;
   a.poses = poses; a.seq_offset = (const long*)seq_offset; a.seq_real = (const long*)seq_real; a.lengths = lengths; a.Ntot = Ntot;
   a.J = J;
-  hipLaunchKernelGGL(bone_length_means_kernel, dim3((unsigned)S), dim3(RIGID_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(bone_length_means_kernel, dim3((unsigned)S), dim3(POSE_THREADS), 0, (hipStream_t)stream, a);
   MP_LAUNCH_CHECK();
   return MP_OK;
 }

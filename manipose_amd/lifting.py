@@ -21,11 +21,17 @@ Scheduling: a sequence is lifted on its own - its windows are cut into forwards 
 stay resident until the sequence is merged, and no forward mixes two sequences.  A frame's covering windows are therefore always
 resident when it is merged (no partial sum is ever carried), and a sequence's result does not depend on what else is lifted with
 it: the engine's GEMM tile plan depends on the batch, so a window's bits do.
+
+Structure: ``lift_sequences`` is a chain of private stages - ``_check_options`` (every argument error, then an immutable record of resolved
+options), ``_upload`` (keypoints, window tables, offsets and output buffers, once), ``_lift_one`` per sequence (forwards and ONE merge),
+``_rigid_stage``, ``_place_stage``, ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place.  The
+public function turns the record into its documented list / tuple in one place; ``lift_action`` and hpe/_entry.py read the fields by name.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Sequence, Tuple
+from collections import namedtuple
+from typing import Sequence, Tuple
 
 import numpy as np
 import torch
@@ -64,9 +70,16 @@ def _model_shape(model):
     return int(cfg["num_frame"]), int(cfg["num_joints"]), int(model.n_hyp) if isinstance(model, RMCLManifoldMixSTE) else 1
 
 
-def _mirror(model, J):
+def _skeleton_of(model=None, skeleton=None):
+    """``skeleton`` if given, else the model's own, else the 17-joint H36M tree (MixSTE carries none)"""
     from .data import h36m_skeleton
-    sk = model.decoder.skeleton if hasattr(model, "decoder") else h36m_skeleton()
+    if skeleton is not None:
+        return skeleton
+    return model.decoder.skeleton if model is not None and hasattr(model, "decoder") else h36m_skeleton()
+
+
+def _mirror(model, J):
+    sk = _skeleton_of(model)
     m = list(range(J))
     for l, r in zip(sk.joints_left, sk.joints_right):
         m[l], m[r] = r, l
@@ -77,33 +90,57 @@ def _i32p(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
-def _skeleton_of(model=None, skeleton=None):
-    from .data import h36m_skeleton
-    if skeleton is not None:
-        return skeleton
-    return model.decoder.skeleton if model is not None and hasattr(model, "decoder") else h36m_skeleton()
-
-
-def _parents_c(sk):
+def _parents_c(sk, J):
     par = [int(p) for p in sk.parents]
     if par[0] != -1 or any(not 0 <= p < j for j, p in enumerate(par) if j):
         raise ValueError("rigid lifting: joint 0 must be the root and parents must precede their children")
-    return (C.c_int32 * len(par))(*par)
+    if len(par) != J:
+        raise ValueError(f"{J} joints, but the skeleton has {len(par)}")
+    return (C.c_int32 * J)(*par)
 
 
-def _check_lengths_table(lengths, S, J):
-    """A caller's bone-length table as float32 numpy (S, J - 1); ValueError for a wrong shape or a negative / non-finite entry."""
-    a = lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
-    if a.dtype.kind not in "fiu":
-        raise ValueError(f"lengths must be None, 'model', 'measured' or a numeric table, got dtype {a.dtype}")
-    if a.shape == (J - 1,):
-        a = np.broadcast_to(a, (S, J - 1))
-    if a.shape != (S, J - 1):
-        raise ValueError(f"lengths must be ({S}, {J - 1}) or ({J - 1},) bone lengths in metres, got {tuple(np.shape(lengths))}")
-    a = np.array(a, dtype=np.float32, order="C")             # a copy: the caller's table is never aliased
-    if not np.isfinite(a).all() or (a < 0).any():
-        raise ValueError("lengths must be finite and non-negative")
-    return a
+def _host_f32(a, shape, what, row=None, nonneg=False):
+    """A per-sequence table (tensor or array) as float32 numpy of ``shape``, after its dtype, shape and finiteness were checked on the host; a
+    copy: the caller's table is never aliased.  A table of shape ``row`` is one row for every sequence; ``nonneg`` also refuses negative entries."""
+    h = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    got = h.shape
+    if row is not None and h.shape == row:
+        h = np.broadcast_to(h, shape)
+    if h.dtype.kind not in "fiu" or h.shape != shape:
+        raise ValueError(f"{what} must be {shape}{'' if row is None else f' or {row}'} numbers, got shape {tuple(got)} {h.dtype}")
+    h = np.array(h, dtype=np.float32, order="C")
+    if not np.isfinite(h).all() or (nonneg and (h < 0).any()):
+        raise ValueError(f"{what} must be finite{' and non-negative' if nonneg else ''}")
+    return h
+
+
+def _device_f32(a, dev, shape, what, row=None, nonneg=False):
+    return torch.from_numpy(_host_f32(a, shape, what, row, nonneg)).to(dev)
+
+
+def _device_i64(a, dev):
+    if torch.is_tensor(a):
+        return a.to(dev, torch.int64).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+
+
+def _seq_table(seq_offset, ntot, dev):
+    d_off = _device_i64(seq_offset if seq_offset is not None else [0, ntot], dev)
+    if d_off.dim() != 1 or d_off.numel() < 2:
+        raise ValueError("seq_offset must hold S + 1 >= 2 frame numbers")
+    return d_off, int(d_off.numel()) - 1
+
+
+def _poses4(poses, who):
+    if not torch.is_tensor(poses) or not poses.is_cuda:
+        raise RuntimeError(f"manipose_amd: {who} takes device tensors; there is no CPU fallback")
+    p4 = poses.unsqueeze(1) if poses.dim() == 3 else poses
+    if p4.dim() != 4 or p4.shape[3] not in (3, 4) or (poses.dim() == 3 and poses.shape[2] != 3) or poses.dtype != torch.float32 \
+            or not poses.is_contiguous():
+        raise ValueError(f"poses must be contiguous float32 (Ntot, J, 3) or (Ntot, inner, J, 3 | 4), got {tuple(poses.shape)} {poses.dtype}")
+    if not 2 <= int(p4.shape[2]) <= 32:
+        raise ValueError(f"poses have {int(p4.shape[2])} joints: 2..32 expected")
+    return p4
 
 
 def _rigid(lib, poses4, d_off, S, d_lengths, parents):
@@ -119,11 +156,8 @@ def bone_length_means(poses, seq_offset=None, real_frames=None, skeleton=None):
     if poses.dim() != 3 or poses.shape[2] != 3 or poses.dtype != torch.float32:
         raise ValueError(f"poses must be float32 (Ntot, J, 3), got {tuple(poses.shape)} {poses.dtype}")
     dev, J = poses.device, int(poses.shape[1])
-    parents = _parents_c(_skeleton_of(skeleton=skeleton))
-    if len(parents) != J:
-        raise ValueError(f"poses have {J} joints, the skeleton {len(parents)}")
-    d_off = _device_i64(seq_offset if seq_offset is not None else [0, int(poses.shape[0])], dev)
-    S = int(d_off.numel()) - 1
+    parents = _parents_c(_skeleton_of(skeleton=skeleton), J)
+    d_off, S = _seq_table(seq_offset, int(poses.shape[0]), dev)
     d_real = _device_i64(real_frames, dev) if real_frames is not None else None
     if d_real is not None and int(d_real.numel()) != S:
         raise ValueError(f"real_frames must have {S} entries")
@@ -134,31 +168,18 @@ def bone_length_means(poses, seq_offset=None, real_frames=None, skeleton=None):
     return out
 
 
-def _device_i64(a, dev):
-    if torch.is_tensor(a):
-        return a.to(dev, torch.int64).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
-
-
 def project_rigid(poses, lengths, seq_offset=None, skeleton=None):
     """``mp_lift_rigid`` on a device tensor, IN PLACE (and returned): poses (Ntot, J, 3), or (Ntot, inner, J, C) with C = 3 or 4 (channel 3, a
     hypothesis' score, is left alone).  Every pose keeps its root and its bone directions and gets the bone lengths of its sequence:
     ``lengths`` (S, J - 1) or (J - 1,), tensor or array, in the unit of the poses; ``seq_offset`` (S + 1): first frame of every sequence, HOST
     table or device int64 tensor (default: all frames are one sequence).  A bone of length zero takes its parent bone's direction, (0, 0, 1)
     under the root.  ``skeleton``: default the 17-joint H36M tree."""
-    if not poses.is_cuda:
-        raise RuntimeError("manipose_amd: project_rigid takes device tensors; there is no CPU fallback")
-    p4 = poses.unsqueeze(1) if poses.dim() == 3 else poses
-    if p4.dim() != 4 or p4.shape[3] not in (3, 4) or poses.dtype != torch.float32 or not poses.is_contiguous():
-        raise ValueError(f"poses must be contiguous float32 (Ntot, J, 3) or (Ntot, inner, J, 3 | 4), got {tuple(poses.shape)} {poses.dtype}")
-    J = int(p4.shape[2])
-    parents = _parents_c(_skeleton_of(skeleton=skeleton))
-    if len(parents) != J:
-        raise ValueError(f"poses have {J} joints, the skeleton {len(parents)}")
-    d_off = _device_i64(seq_offset if seq_offset is not None else [0, int(p4.shape[0])], poses.device)
-    S = int(d_off.numel()) - 1
-    table = torch.from_numpy(_check_lengths_table(lengths, S, J)).to(poses.device)
-    if p4.shape[0] > 0:
+    p4 = _poses4(poses, "project_rigid")
+    ntot, J = int(p4.shape[0]), int(p4.shape[2])
+    parents = _parents_c(_skeleton_of(skeleton=skeleton), J)
+    d_off, S = _seq_table(seq_offset, ntot, poses.device)
+    table = _device_f32(lengths, poses.device, (S, J - 1), "lengths", row=(J - 1,), nonneg=True)
+    if ntot > 0:
         _rigid(_lib.load(), p4, d_off, S, table, parents)
     return poses
 
@@ -196,36 +217,6 @@ def camera_table(cameras):
             raise ValueError(f"camera {s}: non-finite entry")
         rows[s] = row
     return rows[:, :9].copy(), rows[:, 9:13].copy(), rows[:, 13:16].copy()
-
-
-def _poses4(poses, who):
-    if not torch.is_tensor(poses) or not poses.is_cuda:
-        raise RuntimeError(f"manipose_amd: {who} takes device tensors; there is no CPU fallback")
-    p4 = poses.unsqueeze(1) if poses.dim() == 3 else poses
-    if p4.dim() != 4 or p4.shape[3] not in (3, 4) or (poses.dim() == 3 and poses.shape[2] != 3) or poses.dtype != torch.float32 \
-            or not poses.is_contiguous():
-        raise ValueError(f"poses must be contiguous float32 (Ntot, J, 3) or (Ntot, inner, J, 3 | 4), got {tuple(poses.shape)} {poses.dtype}")
-    if not 2 <= int(p4.shape[2]) <= 32:
-        raise ValueError(f"poses have {int(p4.shape[2])} joints: 2..32 expected")
-    return p4
-
-
-def _device_f32(a, dev, shape, what):
-    """a float32 device copy of a per-sequence table (tensor or array) after its shape and finiteness were checked on the host"""
-    h = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-    if h.dtype.kind not in "fiu" or h.shape != shape:
-        raise ValueError(f"{what} must be {shape} numbers, got shape {tuple(h.shape)} {h.dtype}")
-    h = np.array(h, dtype=np.float32, order="C")
-    if not np.isfinite(h).all():
-        raise ValueError(f"{what} must be finite")
-    return torch.from_numpy(h).to(dev)
-
-
-def _seq_table(seq_offset, ntot, dev):
-    d_off = _device_i64(seq_offset if seq_offset is not None else [0, ntot], dev)
-    if d_off.dim() != 1 or d_off.numel() < 2:
-        raise ValueError("seq_offset must hold S + 1 >= 2 frame numbers")
-    return d_off, int(d_off.numel()) - 1
 
 
 def _place(lib, p4, kp, d_off, S, d_intr, d_w, distort):
@@ -268,13 +259,8 @@ def place_poses(poses, keypoints_2d, intrinsics, seq_offset=None, weights=None, 
     if tuple(keypoints_2d.shape) != (ntot, J, 2) or keypoints_2d.dtype != torch.float32:
         raise ValueError(f"keypoints_2d must be float32 ({ntot}, {J}, 2), got {tuple(keypoints_2d.shape)} {keypoints_2d.dtype}")
     d_off, S = _seq_table(seq_offset, ntot, dev)
-    h = intrinsics.detach().cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics)
-    d_intr = _device_f32(h[None] if h.shape == (9,) and S == 1 else h, dev, (S, 9), "intrinsics")
-    d_w = None
-    if weights is not None:
-        d_w = _device_f32(weights, dev, (J,), "weights")
-        if bool((d_w < 0).any()):
-            raise ValueError("weights must be non-negative")
+    d_intr = _device_f32(intrinsics, dev, (S, 9), "intrinsics", row=(9,) if S == 1 else None)
+    d_w = _device_f32(weights, dev, (J,), "weights", nonneg=True) if weights is not None else None
     traj, reproj, ok = _place(_lib.load(), p4, keypoints_2d.contiguous(), d_off, S, d_intr, d_w, distort)
     return (traj[:, 0], reproj[:, 0], ok[:, 0]) if poses.dim() == 3 else (traj, reproj, ok)
 
@@ -289,12 +275,8 @@ def to_world(poses, orientation, translation=None, traj=None, seq_offset=None, f
     p4 = _poses4(poses, "to_world")
     dev, ntot = poses.device, int(p4.shape[0])
     d_off, S = _seq_table(seq_offset, ntot, dev)
-
-    def table(a, n, what):
-        h = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-        return _device_f32(h[None] if h.shape == (n,) and S == 1 else h, dev, (S, n), what)
-    d_quat = table(orientation, 4, "orientation")
-    d_trans = table(translation, 3, "translation") if translation is not None else None
+    d_quat = _device_f32(orientation, dev, (S, 4), "orientation", row=(4,) if S == 1 else None)
+    d_trans = _device_f32(translation, dev, (S, 3), "translation", row=(3,) if S == 1 else None) if translation is not None else None
     if traj is not None:
         if not torch.is_tensor(traj) or not traj.is_cuda:
             raise RuntimeError("manipose_amd: to_world takes device tensors; there is no CPU fallback")
@@ -308,8 +290,7 @@ def to_world(poses, orientation, translation=None, traj=None, seq_offset=None, f
     if floor is False or floor is None:
         _world(_lib.load(), p4, traj, d_off, S, d_quat, d_trans)
         return poses
-    h = floor.detach().cpu().numpy() if torch.is_tensor(floor) else np.asarray(floor)
-    d_floor = _device_f32(h.reshape(1) if h.ndim == 0 and S == 1 else h, dev, (S,), "floor")
+    d_floor = _device_f32(floor, dev, (S,), "floor", row=() if S == 1 else None)
     _world(_lib.load(), p4, traj, d_off, S, d_quat, d_trans, 2, d_floor)
     return poses
 
@@ -348,7 +329,243 @@ def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirr
     return out, (hyps if return_hyps else None)
 
 
+# What a lift was asked for, checked and resolved by _check_options; no stage after it validates anything.  seqs: the 2-D sequences;
+# cam_tables: camera_table(cameras) with place / world; lengths: "model", "measured" or "table" with rigid, and table: the caller's checked
+# (S, J - 1) one; skeleton, parents: the model's, with rigid; windows: plan_windows' (win_seq, win_start)
+_Options = namedtuple("_Options", "seqs tta agg blend scale return_hyps keep_padding rigid symmetric return_bones place world floor return_place "
+                                  "cam_tables T J K lengths table skeleton parents windows batch dev", defaults=(None,) * 11)
+# Everything the kernels of a lift read, uploaded once by _upload, and the buffers they write.  p2: (sum N_i, J, 2) keypoints of all sequences,
+# lens: N_i; out_lens: frames emitted per sequence (whole windows with keep_padding), out_off: their (S + 1) offsets in out_all (., J, 3) and
+# hyp_all (., K, J, 4); first: (S + 1) first window of every sequence; merge_off (S, 2), h_zero / d_zero: the offsets (0, out_lens[s]) and the
+# win_seq (zeros) of a one-sequence merge; bone_mirror (lengths="model"): bone of joint j <- bone of joint mirror[j]; d_*: device copies
+_Plan = namedtuple("_Plan", "p2 lens out_lens out_off first win_start merge_off h_zero d_off d_merge_off d_seq d_start d_zero d_flip mirror "
+                            "bone_mirror out_all hyp_all")
+# Per-sequence lists of what a lift returns; a field that was not asked for is None
+_Lifted = namedtuple("_Lifted", "poses hyps bones place", defaults=(None,) * 3)
+
+
+def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
+                   keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
+                   floor=False, return_place=False):
+    """Every argument error of ``lift_sequences``, in a fixed order and before anything touches a device: the ValueErrors first, the "no CPU
+    fallback" RuntimeErrors last.  No sequences: the record ends after ``return_place``."""
+    if not rigid and (lengths is not None or symmetric or return_bones):
+        raise ValueError("lengths, symmetric and return_bones describe rigid lifting: pass rigid=True")
+    if frame not in ("camera", "world"):
+        raise ValueError(f"frame must be 'camera' or 'world', got {frame!r}")
+    if not isinstance(place, (bool, np.bool_)) or not isinstance(floor, (bool, np.bool_)):
+        raise ValueError("place and floor are switches (True / False); to_world takes given floor offsets")
+    world = frame == "world"
+    if place and cameras is None:
+        raise ValueError("place=True needs cameras: one camera per sequence (camera_table)")
+    if world and cameras is None:
+        raise ValueError("frame='world' needs cameras: one camera per sequence (camera_table)")
+    if floor and not world:
+        raise ValueError("floor=True puts the world frame's z on the floor: pass frame='world'")
+    if cameras is not None and not (place or world):
+        raise ValueError("cameras describe place=True and frame='world': pass one of them")
+    if return_place and not (place or floor):
+        raise ValueError("return_place returns what place=True (and floor=True) computed: pass place=True")
+    if (place or world) and keep_padding:
+        raise ValueError("place / frame='world' with keep_padding=True: padded frames have no keypoints of their own")
+    single = torch.is_tensor(poses_2d) or isinstance(poses_2d, np.ndarray)
+    seqs = [poses_2d] if single else list(poses_2d)
+    opt = _Options(seqs, tta, agg, blend, scale, bool(return_hyps), keep_padding, rigid, symmetric, bool(return_bones), place, world, floor,
+                   bool(return_place))
+    if not seqs:
+        return opt
+    cam_tables = None
+    if place or world:
+        cam_tables = camera_table(cameras)
+        if cam_tables[0].shape[0] != len(seqs):
+            raise ValueError(f"cameras: {cam_tables[0].shape[0]} cameras for {len(seqs)} sequences")
+    T, J, K = _model_shape(model)
+    table = sk = parents = None
+    if rigid:
+        mixste = getattr(model, "_arch", None) == "mixste"
+        if lengths is None:
+            lengths = "measured" if mixste else "model"
+        if isinstance(lengths, str):
+            if lengths not in ("model", "measured"):
+                raise ValueError(f"lengths must be None, 'model', 'measured' or a table, got {lengths!r}")
+            if lengths == "model" and mixste:
+                raise ValueError("lengths='model': MixSTE predicts no bone lengths; use 'measured' or pass a table")
+        else:
+            table, lengths = _host_f32(lengths, (len(seqs), J - 1), "lengths", row=(J - 1,), nonneg=True), "table"
+        sk = _skeleton_of(model)
+        parents = _parents_c(sk, J)
+    stride = T if stride is None else int(stride)
+    if agg not in AGG or blend not in BLEND:
+        raise ValueError(f"agg in {sorted(AGG)} and blend in {sorted(BLEND)} expected, got {agg!r}, {blend!r}")
+    if keep_padding and stride != T:
+        raise ValueError("keep_padding describes the reference's non-overlapping windows: stride must be T")
+    for s in seqs:
+        if s.ndim != 3 or s.shape[1] != J or s.shape[2] != 2:
+            raise ValueError(f"every sequence must be (N, {J}, 2), got {tuple(s.shape)}")
+    windows = plan_windows([int(s.shape[0]) for s in seqs], T, stride)       # (its own ValueErrors: the stride, a sequence without frames)
+    params = list(model.parameters())
+    if not params or not params[0].is_cuda:
+        raise RuntimeError("manipose_amd: lift_sequences needs the model on a ROCm device; there is no CPU fallback")
+    for s in seqs:
+        if torch.is_tensor(s) and not s.is_cuda:
+            raise RuntimeError("manipose_amd: lift_sequences takes device tensors or numpy arrays (got a CPU tensor); there is no CPU fallback")
+    if batch is None:
+        batch = (int(getattr(model, "max_batch_hint", 0)) // (2 if tta else 1)) or 16
+    return opt._replace(cam_tables=cam_tables, T=T, J=J, K=K, lengths=lengths, table=table, skeleton=sk, parents=parents,
+                        windows=windows, batch=max(1, int(batch)), dev=params[0].device)
+
+
+def _upload(model, opt):
+    """The 2-D keypoints, the window tables and the offsets of all sequences go to the device once, up front; the output buffers are allocated."""
+    dev, T, J, seqs = opt.dev, opt.T, opt.J, opt.seqs
+    lens = [int(s.shape[0]) for s in seqs]
+    win_seq, win_start = opt.windows
+    first = np.concatenate([[0], np.cumsum(np.bincount(win_seq, minlength=len(lens)))]).astype(np.int64)     # first window of every sequence
+    if all(torch.is_tensor(s) for s in seqs):
+        p2 = torch.cat([s.to(dev, torch.float32) for s in seqs], dim=0).contiguous()
+    else:
+        host = [s.detach().cpu().numpy() if torch.is_tensor(s) else np.asarray(s) for s in seqs]
+        p2 = torch.from_numpy(np.concatenate([h.astype(np.float32, copy=False) for h in host], axis=0)).to(dev).contiguous()
+    off = np.zeros(len(lens) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lens)
+    out_lens = [int(first[s + 1] - first[s]) * T if opt.keep_padding else lens[s] for s in range(len(lens))]
+    out_off = np.zeros(len(lens) + 1, dtype=np.int64)
+    out_off[1:] = np.cumsum(out_lens)
+    merge_off = np.zeros((len(lens), 2), dtype=np.int64)
+    merge_off[:, 1] = out_lens
+    d_off, d_merge_off = torch.from_numpy(off).to(dev), torch.from_numpy(merge_off).to(dev)
+    d_seq, d_start = torch.from_numpy(win_seq).to(dev), torch.from_numpy(win_start).to(dev)
+    max_nw = int(np.max(first[1:] - first[:-1]))
+    d_zero = torch.zeros(max_nw, dtype=torch.int32, device=dev)
+    d_flip = torch.ones(opt.batch, dtype=torch.uint8, device=dev)
+    mirror = _mirror(model, J)
+    bone_mirror = torch.tensor([int(mirror[j]) - 1 for j in range(1, J)], device=dev) if opt.lengths == "model" else None
+    out_all = torch.empty(sum(out_lens), J, 3, dtype=torch.float32, device=dev)
+    hyp_all = torch.empty(sum(out_lens), opt.K, J, 4, dtype=torch.float32, device=dev) if opt.return_hyps else None
+    return _Plan(p2=p2, lens=lens, out_lens=out_lens, out_off=out_off, first=first, win_start=win_start, merge_off=merge_off,
+                 h_zero=np.zeros(max_nw, dtype=np.int32), d_off=d_off, d_merge_off=d_merge_off, d_seq=d_seq, d_start=d_start, d_zero=d_zero,
+                 d_flip=d_flip, mirror=mirror, bone_mirror=bone_mirror, out_all=out_all, hyp_all=hyp_all)
+
+
+def _lift_one(model, opt, plan, s, model_rows):
+    """Sequence ``s`` on its own: its windows in forwards of ``batch`` (the mirrored copies of a forward's windows follow them, as evaluate()
+    batches them; no forward mixes two sequences), every forward's hypotheses staged until all are there, then ONE merge into the sequence's
+    rows of ``out_all`` / ``hyp_all``.  ``lengths="model"``: the bone lengths every forward left in the engine are appended to ``model_rows``."""
+    lib, dev, T, J, K, tta = _lib.load(), opt.dev, opt.T, opt.J, opt.K, opt.tta
+    F = 2 if tta else 1
+    a0, nw = int(plan.first[s]), int(plan.first[s + 1] - plan.first[s])
+    buf_p = buf_s = None
+    for a in range(0, nw, opt.batch):
+        n = min(opt.batch, nw - a)
+        X = torch.empty(F * n, T, J, 2, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            for h in range(F):
+                _lib.check(lib.mp_lift_windows_2d(_lib.ptr(plan.p2), _lib.ptr(plan.d_off), len(plan.lens), _lib.ptr(plan.d_seq[a0 + a:]),
+                                                  _lib.ptr(plan.d_start[a0 + a:]), _lib.ptr(plan.d_flip) if h else None, plan.mirror, n, T, J,
+                                                  _lib.ptr(X[h * n:]), _lib.stream_ptr()), "mp_lift_windows_2d")
+        res = model(X)
+        poses, scores = res if isinstance(res, tuple) else (res, None)
+        poses = poses.reshape(F * n, K, T, J, 3)
+        if opt.lengths == "model":                   # the (F n, J - 1) lengths this forward left in the engine
+            lw = model._engine.peek(1).view(F * n, J - 1).abs()
+            model_rows.append((lw[:n] + lw[n:][:, plan.bone_mirror]) / 2 if tta else lw)
+        if n == nw:                                  # the whole sequence in one forward: merged where the engine left it
+            buf_p, buf_s = poses, scores
+            break
+        if buf_p is None:
+            buf_p = torch.empty(F * nw, K, T, J, 3, dtype=torch.float32, device=dev)
+            buf_s = torch.empty(F * nw, K, T, 1, dtype=torch.float32, device=dev) if scores is not None else None
+        for h in range(F):
+            buf_p[h * nw + a:h * nw + a + n] = poses[h * n:(h + 1) * n]
+            if scores is not None:
+                buf_s[h * nw + a:h * nw + a + n] = scores[h * n:(h + 1) * n]
+    o0, o1 = int(plan.out_off[s]), int(plan.out_off[s + 1])
+    merge_windows(buf_p, buf_s, plan.h_zero[:nw], plan.win_start[a0:a0 + nw], plan.merge_off[s], T=T, tta=tta, mirror=plan.mirror, agg=opt.agg,
+                  blend=opt.blend, scale=opt.scale, return_hyps=opt.return_hyps, out=plan.out_all[o0:o1],
+                  hyps=plan.hyp_all[o0:o1] if opt.return_hyps else None,
+                  device_tables=(plan.d_zero[:nw], plan.d_start[a0:a0 + nw], plan.d_merge_off[s]))
+
+
+def _rigid_stage(opt, plan, model_rows):
+    """One (J - 1) table of bone lengths per sequence, and every merged pose and hypothesis re-assembled with it, in place.  Returns the
+    (S, J - 1) tables in metres."""
+    dev, S, sk, scale = opt.dev, len(plan.lens), opt.skeleton, float(opt.scale)
+    d_out_off = torch.from_numpy(plan.out_off).to(dev)
+    if opt.lengths == "model":                       # plain mean over each sequence's windows, in window order
+        rows = torch.cat(model_rows, dim=0)
+        bones = torch.stack([rows[int(plan.first[s]):int(plan.first[s + 1])].mean(dim=0) for s in range(S)])
+    elif opt.lengths == "measured":                  # of the merged poses, which mp_lift_merge has already multiplied by scale
+        bones = bone_length_means(plan.out_all, d_out_off, real_frames=np.asarray(plan.lens, dtype=np.int64) if opt.keep_padding else None, skeleton=sk)
+        if scale != 1.0:
+            bones = bones / scale
+    else:
+        bones = torch.from_numpy(opt.table).to(dev)
+    if opt.symmetric:
+        bl, br = list(sk.bones_left), list(sk.bones_right)
+        mean = (bones[:, bl] + bones[:, br]) / 2
+        bones = bones.clone()
+        bones[:, bl] = mean
+        bones[:, br] = mean
+    used = (bones * scale).contiguous()
+    _rigid(_lib.load(), plan.out_all.unsqueeze(1), d_out_off, S, used, opt.parents)
+    if opt.return_hyps:
+        _rigid(_lib.load(), plan.hyp_all, d_out_off, S, used, opt.parents)
+    return bones
+
+
+def _place_stage(opt, plan):
+    """The root trajectories of the merged poses and the hypotheses (``place``), then both into the world frame, in place, the hypotheses on
+    the merged poses' floor (``world``).  No padded frames here: a frame of ``out_all`` is the frame of ``p2`` with the same number.  Returns
+    the dict of per-frame results and the (S,) floor offsets or None."""
+    lib, dev, S, out4 = _lib.load(), opt.dev, len(plan.lens), plan.out_all.unsqueeze(1)
+    d_intr, d_quat = torch.from_numpy(opt.cam_tables[0]).to(dev), torch.from_numpy(opt.cam_tables[1]).to(dev)
+    d_trans = torch.from_numpy(opt.cam_tables[2] * np.float32(opt.scale)).to(dev) if opt.place else None
+    placed, d_floor = {}, None
+    if opt.place:
+        placed["traj"], placed["reproj"], placed["ok"] = (t[:, 0] for t in _place(lib, out4, plan.p2, plan.d_off, S, d_intr, None, True))
+        if opt.return_hyps:
+            placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"] = _place(lib, plan.hyp_all, plan.p2, plan.d_off, S, d_intr, None, True)
+    if opt.world:
+        d_floor = torch.empty(S, dtype=torch.float32, device=dev) if opt.floor else None
+        _world(lib, out4, placed["traj"].unsqueeze(1).contiguous() if opt.place else None, plan.d_off, S, d_quat, d_trans, 1 if opt.floor else 0,
+               d_floor)
+        if opt.return_hyps:
+            _world(lib, plan.hyp_all, placed.get("hyps_traj"), plan.d_off, S, d_quat, d_trans, 2 if opt.floor else 0, d_floor)
+    return placed, d_floor
+
+
+def _per_sequence(opt, plan, bones, placed, d_floor):
+    """the buffers of all sequences cut into the per-sequence lists of ``_Lifted``"""
+    info = None
+    if opt.return_place:
+        per_seq = {k: torch.split(v, plan.out_lens, dim=0) for k, v in placed.items()}
+        info = [dict({k: v[i] for k, v in per_seq.items()}, **({"floor": d_floor[i]} if opt.floor else {})) for i in range(len(plan.lens))]
+    return _Lifted(list(torch.split(plan.out_all, plan.out_lens, dim=0)),
+                   list(torch.split(plan.hyp_all, plan.out_lens, dim=0)) if opt.return_hyps else None,
+                   list(bones.unbind(0)) if opt.return_bones else None, info)
+
+
 @torch.no_grad()
+def _lift_sequences(model, poses_2d, **options):
+    """``lift_sequences`` with its results by name (``_Lifted``): check options -> upload -> every sequence lifted on its own -> rigid stage ->
+    place / world / floor stage -> per-sequence lists."""
+    opt = _check_options(model, poses_2d, **options)
+    if not opt.seqs:
+        return _Lifted([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place)))
+    plan = _upload(model, opt)
+    model_rows = []
+    was_training = model.training
+    model.eval()
+    try:
+        for s in range(len(plan.lens)):
+            _lift_one(model, opt, plan, s, model_rows)
+    finally:
+        model.train(was_training)
+    bones = _rigid_stage(opt, plan, model_rows) if opt.rigid else None
+    placed, d_floor = _place_stage(opt, plan) if opt.place or opt.world else (None, None)
+    return _per_sequence(opt, plan, bones, placed, d_floor)
+
+
 def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
                    floor=False, return_place=False):
@@ -376,187 +593,11 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
     rotation alone (the reference's prepare_prediction_for_viz before its floor line).  ``floor`` (needs ``frame="world"``): every sequence's
     lowest merged joint is put on z = 0, and the SAME offset is subtracted from the hypotheses - merged pose and hypotheses stand in one scene
     (the reference floors each array on its own).  Not with ``keep_padding``: padded frames have no keypoints of their own."""
-    if not rigid and (lengths is not None or symmetric or return_bones):
-        raise ValueError("lengths, symmetric and return_bones describe rigid lifting: pass rigid=True")
-    if frame not in ("camera", "world"):
-        raise ValueError(f"frame must be 'camera' or 'world', got {frame!r}")
-    if not isinstance(place, (bool, np.bool_)) or not isinstance(floor, (bool, np.bool_)):
-        raise ValueError("place and floor are switches (True / False); to_world takes given floor offsets")
-    world = frame == "world"
-    if place and cameras is None:
-        raise ValueError("place=True needs cameras: one camera per sequence (camera_table)")
-    if world and cameras is None:
-        raise ValueError("frame='world' needs cameras: one camera per sequence (camera_table)")
-    if floor and not world:
-        raise ValueError("floor=True puts the world frame's z on the floor: pass frame='world'")
-    if cameras is not None and not (place or world):
-        raise ValueError("cameras describe place=True and frame='world': pass one of them")
-    if return_place and not (place or floor):
-        raise ValueError("return_place returns what place=True (and floor=True) computed: pass place=True")
-    if (place or world) and keep_padding:
-        raise ValueError("place / frame='world' with keep_padding=True: padded frames have no keypoints of their own")
-    single = torch.is_tensor(poses_2d) or isinstance(poses_2d, np.ndarray)
-    seqs = [poses_2d] if single else list(poses_2d)
-    n_res = 1 + bool(return_hyps) + bool(return_bones) + bool(return_place)
-    if not seqs:
-        return tuple([] for _ in range(n_res)) if n_res > 1 else []
-    cam_tables = None
-    if place or world:
-        cam_tables = camera_table(cameras)
-        if cam_tables[0].shape[0] != len(seqs):
-            raise ValueError(f"cameras: {cam_tables[0].shape[0]} cameras for {len(seqs)} sequences")
-    table = None
-    if rigid:                                                # argument errors first: nothing has touched the device yet
-        T, J, K = _model_shape(model)
-        mixste = getattr(model, "_arch", None) == "mixste"
-        if lengths is None:
-            lengths = "measured" if mixste else "model"
-        if isinstance(lengths, str):
-            if lengths not in ("model", "measured"):
-                raise ValueError(f"lengths must be None, 'model', 'measured' or a table, got {lengths!r}")
-            if lengths == "model" and mixste:
-                raise ValueError("lengths='model': MixSTE predicts no bone lengths; use 'measured' or pass a table")
-        else:
-            table = _check_lengths_table(lengths, len(seqs), J)
-            lengths = "table"
-    params = list(model.parameters())
-    if not params or not params[0].is_cuda:
-        raise RuntimeError("manipose_amd: lift_sequences needs the model on a ROCm device; there is no CPU fallback")
-    dev = params[0].device
-    for s in seqs:
-        if torch.is_tensor(s) and not s.is_cuda:
-            raise RuntimeError("manipose_amd: lift_sequences takes device tensors or numpy arrays (got a CPU tensor); there is no CPU fallback")
-    T, J, K = _model_shape(model)
-    stride = T if stride is None else int(stride)
-    if agg not in AGG or blend not in BLEND:
-        raise ValueError(f"agg in {sorted(AGG)} and blend in {sorted(BLEND)} expected, got {agg!r}, {blend!r}")
-    if keep_padding and stride != T:
-        raise ValueError("keep_padding describes the reference's non-overlapping windows: stride must be T")
-    for s in seqs:
-        if s.ndim != 3 or s.shape[1] != J or s.shape[2] != 2:
-            raise ValueError(f"every sequence must be (N, {J}, 2), got {tuple(s.shape)}")
-    lens = [int(s.shape[0]) for s in seqs]
-    win_seq, win_start = plan_windows(lens, T, stride)
-    first = np.concatenate([[0], np.cumsum(np.bincount(win_seq, minlength=len(lens)))]).astype(np.int64)     # first window of every sequence
-    if batch is None:
-        batch = (int(getattr(model, "max_batch_hint", 0)) // (2 if tta else 1)) or 16
-    batch = max(1, int(batch))
-    # everything the kernels read is uploaded once, up front
-    if all(torch.is_tensor(s) for s in seqs):
-        p2 = torch.cat([s.to(dev, torch.float32) for s in seqs], dim=0).contiguous()
-    else:
-        host = [s.detach().cpu().numpy() if torch.is_tensor(s) else np.asarray(s) for s in seqs]
-        p2 = torch.from_numpy(np.concatenate([h.astype(np.float32, copy=False) for h in host], axis=0)).to(dev).contiguous()
-    off = np.zeros(len(lens) + 1, dtype=np.int64)
-    off[1:] = np.cumsum(lens)
-    out_lens = [int(first[s + 1] - first[s]) * T if keep_padding else lens[s] for s in range(len(lens))]
-    merge_off = np.zeros((len(lens), 2), dtype=np.int64)                     # per sequence: the (S + 1 = 2) offsets of a one-sequence merge
-    merge_off[:, 1] = out_lens
-    d_off, d_merge_off = torch.from_numpy(off).to(dev), torch.from_numpy(merge_off).to(dev)
-    d_seq, d_start = torch.from_numpy(win_seq).to(dev), torch.from_numpy(win_start).to(dev)
-    max_nw = int(np.max(first[1:] - first[:-1]))
-    d_zero = torch.zeros(max_nw, dtype=torch.int32, device=dev)
-    h_zero = np.zeros(max_nw, dtype=np.int32)
-    d_flip = torch.ones(batch, dtype=torch.uint8, device=dev)
-    mirror = _mirror(model, J)
-    out_all = torch.empty(sum(out_lens), J, 3, dtype=torch.float32, device=dev)
-    hyp_all = torch.empty(sum(out_lens), K, J, 4, dtype=torch.float32, device=dev) if return_hyps else None
-    lib = _lib.load()
-    F = 2 if tta else 1
-    if rigid:
-        sk = _skeleton_of(model)
-        parents = _parents_c(sk)
-        if len(parents) != J:
-            raise ValueError(f"the model has {J} joints, its skeleton {len(parents)}")
-        bone_mirror = torch.tensor([int(mirror[j]) - 1 for j in range(1, J)], device=dev)      # bone of joint j <- bone of joint mirror[j]
-        model_rows = []
-    was_training = model.training
-    model.eval()
-    try:
-        o0 = 0
-        for s in range(len(lens)):
-            a0, nw = int(first[s]), int(first[s + 1] - first[s])
-            buf_p = buf_s = None
-            for a in range(0, nw, batch):
-                n = min(batch, nw - a)
-                X = torch.empty(F * n, T, J, 2, dtype=torch.float32, device=dev)
-                with torch.cuda.device(dev):
-                    for h in range(F):           # the mirrored copies of the n windows follow them, as evaluate() batches them
-                        _lib.check(lib.mp_lift_windows_2d(_lib.ptr(p2), _lib.ptr(d_off), len(lens), _lib.ptr(d_seq[a0 + a:]), _lib.ptr(d_start[a0 + a:]),
-                                                          _lib.ptr(d_flip) if h else None, mirror, n, T, J, _lib.ptr(X[h * n:]), _lib.stream_ptr()),
-                                   "mp_lift_windows_2d")
-                res = model(X)
-                poses, scores = res if isinstance(res, tuple) else (res, None)
-                poses = poses.reshape(F * n, K, T, J, 3)
-                if rigid and lengths == "model":             # the (F n, J - 1) lengths this forward left in the engine
-                    lw = model._engine.peek(1).view(F * n, J - 1).abs()
-                    model_rows.append((lw[:n] + lw[n:][:, bone_mirror]) / 2 if tta else lw)
-                if n == nw:                      # the whole sequence in one forward: merged where the engine left it
-                    buf_p, buf_s = poses, scores
-                    break
-                if buf_p is None:
-                    buf_p = torch.empty(F * nw, K, T, J, 3, dtype=torch.float32, device=dev)
-                    buf_s = torch.empty(F * nw, K, T, 1, dtype=torch.float32, device=dev) if scores is not None else None
-                for h in range(F):
-                    buf_p[h * nw + a:h * nw + a + n] = poses[h * n:(h + 1) * n]
-                    if scores is not None:
-                        buf_s[h * nw + a:h * nw + a + n] = scores[h * n:(h + 1) * n]
-            merge_windows(buf_p, buf_s, h_zero[:nw], win_start[a0:a0 + nw], merge_off[s], T=T, tta=tta, mirror=mirror, agg=agg, blend=blend,
-                          scale=scale, return_hyps=return_hyps, out=out_all[o0:o0 + out_lens[s]],
-                          hyps=hyp_all[o0:o0 + out_lens[s]] if return_hyps else None,
-                          device_tables=(d_zero[:nw], d_start[a0:a0 + nw], d_merge_off[s]))
-            o0 += out_lens[s]
-    finally:
-        model.train(was_training)
-    bones = None
-    if rigid:
-        rigid_off = np.zeros(len(lens) + 1, dtype=np.int64)
-        rigid_off[1:] = np.cumsum(out_lens)
-        d_rigid_off = torch.from_numpy(rigid_off).to(dev)
-        if lengths == "model":                               # plain mean over each sequence's windows, in window order
-            rows = torch.cat(model_rows, dim=0)
-            bones = torch.stack([rows[int(first[s]):int(first[s + 1])].mean(dim=0) for s in range(len(lens))])
-        elif lengths == "measured":                          # of the merged poses, which mp_lift_merge has already multiplied by scale
-            bones = bone_length_means(out_all, d_rigid_off, real_frames=np.asarray(lens, dtype=np.int64) if keep_padding else None, skeleton=sk)
-            if float(scale) != 1.0:
-                bones = bones / float(scale)
-        else:
-            bones = torch.from_numpy(table).to(dev)
-        if symmetric:
-            bl, br = list(sk.bones_left), list(sk.bones_right)
-            mean = (bones[:, bl] + bones[:, br]) / 2
-            bones = bones.clone()
-            bones[:, bl] = mean
-            bones[:, br] = mean
-        used = (bones * float(scale)).contiguous()
-        _rigid(lib, out_all.unsqueeze(1), d_rigid_off, len(lens), used, parents)
-        if return_hyps:
-            _rigid(lib, hyp_all, d_rigid_off, len(lens), used, parents)
-    placed = None
-    if place or world:                                       # (no padded frames here: a frame of out_all is the frame of p2 with the same number)
-        S = len(lens)
-        d_intr, d_quat = torch.from_numpy(cam_tables[0]).to(dev), torch.from_numpy(cam_tables[1]).to(dev)
-        d_trans = torch.from_numpy(cam_tables[2] * np.float32(scale)).to(dev) if place else None
-        placed = {}
-        if place:
-            placed["traj"], placed["reproj"], placed["ok"] = (t[:, 0] for t in _place(lib, out_all.unsqueeze(1), p2, d_off, S, d_intr, None, True))
-            if return_hyps:
-                placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"] = _place(lib, hyp_all, p2, d_off, S, d_intr, None, True)
-        if world:
-            d_floor = torch.empty(S, dtype=torch.float32, device=dev) if floor else None
-            _world(lib, out_all.unsqueeze(1), placed["traj"].unsqueeze(1).contiguous() if place else None, d_off, S, d_quat, d_trans,
-                   1 if floor else 0, d_floor)
-            if return_hyps:                                  # the hypotheses stand on the merged poses' floor
-                _world(lib, hyp_all, placed.get("hyps_traj"), d_off, S, d_quat, d_trans, 2 if floor else 0, d_floor)
-    res = [list(torch.split(out_all, out_lens, dim=0))]
-    if return_hyps:
-        res.append(list(torch.split(hyp_all, out_lens, dim=0)))
-    if return_bones:
-        res.append(list(bones.unbind(0)))
-    if return_place:
-        per_seq = {k: torch.split(v, out_lens, dim=0) for k, v in placed.items()}
-        res.append([dict({k: v[i] for k, v in per_seq.items()}, **({"floor": d_floor[i]} if floor else {})) for i in range(len(lens))])
-    return res[0] if len(res) == 1 else tuple(res)
+    res = _lift_sequences(model, poses_2d, stride=stride, tta=tta, agg=agg, blend=blend, return_hyps=return_hyps, batch=batch, scale=scale,
+                          keep_padding=keep_padding, rigid=rigid, lengths=lengths, symmetric=symmetric, return_bones=return_bones, cameras=cameras,
+                          place=place, frame=frame, floor=floor, return_place=return_place)
+    asked = [r for r in res if r is not None]                # in the order poses, hyps, bones, place
+    return asked[0] if len(asked) == 1 else tuple(asked)
 
 
 def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
@@ -566,9 +607,8 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
     from .architectures import RMCLManifoldMixSTE
     tta = bool(config.train.tta) if hasattr(config, "train") else bool(config["train"]["tta"])
     hyps = bool(return_hyps) and isinstance(model, RMCLManifoldMixSTE)
-    res = lift_sequences(model, poses_2d, stride=None, tta=tta, return_hyps=hyps, keep_padding=True)
-    res = res[1] if hyps else res
-    return torch.cat(res, dim=0).cpu().numpy()
+    res = _lift_sequences(model, poses_2d, stride=None, tta=tta, return_hyps=hyps, keep_padding=True)
+    return torch.cat(res.hyps if hyps else res.poses, dim=0).cpu().numpy()
 
 
 __all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "to_world", "lift_sequences",

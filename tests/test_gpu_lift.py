@@ -12,6 +12,7 @@ import torch
 
 import manipose_ref as orc
 from helpers import fixture_state, load_fixture
+from lift_fixtures import FIXTURES, fixture_model as _model, sequences as _sequences
 from lift_ref import MIRROR, closed_form_tables, covering, cut_windows, oracle_lift, unflip
 
 pytestmark = pytest.mark.gpu
@@ -148,35 +149,15 @@ def test_lift_merge_is_deterministic_and_center_best_returns_input_hypotheses(li
             g += 1
 
 
-def _build_rmcl(name="rmcl_small"):
-    from manipose_amd import ManifoldMixSTE, RMCLManifoldMixSTE, h36m_skeleton
-    fx = load_fixture(name)
-    c = fx["cfg"]
-    kw = dict(skeleton=h36m_skeleton(), num_frame=c["T"], embed_dim_rot=c["C_rot"], depth_rot=c["depth_rot"], num_heads_rot=c["heads_rot"],
-              embed_dim_seg=c["C_seg"], depth_seg=c["depth_seg"], num_heads_seg=c["heads_seg"], drop_path_rate=0.0, rot_rep_dim=c.get("rot_dim", 6))
-    model = RMCLManifoldMixSTE(n_hyp=c["n_hyp"], **kw) if c["n_hyp"] > 0 else ManifoldMixSTE(**kw)
-    model.load_state_dict(fixture_state(fx), strict=True)
-    model.precision = "fp32"
-    return fx, model.cuda().eval()
-
-
-def _sequences(lens, seed):
-    g = np.random.default_rng(seed)
-    p2 = [np.clip(0.3 * g.standard_normal((n, 17, 2)), -1, 1).astype(np.float32) for n in lens]
-    p3 = [(0.3 * g.standard_normal((n, 17, 3))).astype(np.float32) for n in lens]
-    return p2, p3
-
-
 def test_lift_sequences_is_reproducible_and_sequences_do_not_interact(lib):
     from manipose_amd import lift_sequences
-    fx, model = _build_rmcl()
-    T = fx["cfg"]["T"]
+    model, T, K = _model("rmcl")
     p2, _ = _sequences([T - 7, 2 * T, 3 * T + 5], seed=4)
     for stride, batch in ((T, 2), (T // 2 + 1, 3)):
         a, ah = lift_sequences(model, p2, stride=stride, batch=batch, return_hyps=True)
         b, bh = lift_sequences(model, p2, stride=stride, batch=batch, return_hyps=True)
         for i in range(3):
-            assert a[i].shape == (len(p2[i]), 17, 3) and ah[i].shape == (len(p2[i]), fx["cfg"]["n_hyp"], 17, 4)
+            assert a[i].shape == (len(p2[i]), 17, 3) and ah[i].shape == (len(p2[i]), K, 17, 4)
             assert torch.equal(a[i], b[i]) and torch.equal(ah[i], bh[i])                      # two calls: identical bits
             alone, alone_h = lift_sequences(model, [torch.from_numpy(p2[i]).cuda()], stride=stride, batch=batch, return_hyps=True)
             assert torch.equal(a[i], alone[0]) and torch.equal(ah[i], alone_h[0])             # together == alone, bit for bit
@@ -214,19 +195,10 @@ def _oracle_forward(kind, fx):
 def test_lift_sequences_end_to_end_vs_oracle(lib, kind):
     """fp32 models on 3 synthetic sequences, TTA on, stride T and T // 2 + 1, against the CPU oracle per window + pose_flip + numpy stitching.
     Bound: the one test_rmcl_model_forward_loss_backward_vs_reference applies to `poses` (tests/test_gpu_parity.py:424: rtol 1e-4, atol 2e-5)."""
-    from manipose_amd import MixSTE, lift_sequences
-    if kind == "mixste":
-        fx = load_fixture("mixste_tiny")
-        T, C_, depth, heads = [int(v) for v in fx["cfg_mixste"]]
-        model = MixSTE(num_frame=T, num_joints=17, in_chans=2, out_dim=3, embed_dim=C_, depth=depth, num_heads=heads, drop_path_rate=0.0)
-        model.load_state_dict(fixture_state(fx), strict=True)
-        model.precision = "fp32"
-        model = model.cuda().eval()
-    else:
-        fx, model = _build_rmcl("rmcl_small" if kind == "rmcl" else "manifold_k1")
-        T = fx["cfg"]["T"]
+    from manipose_amd import lift_sequences
+    model, T, _ = _model(kind)
     p2, _ = _sequences([T - 5, 2 * T, 2 * T + 5], seed=12)
-    fwd = _oracle_forward(kind, fx)
+    fwd = _oracle_forward(kind, load_fixture(FIXTURES[kind]))
     for stride in (T, T // 2 + 1):
         got = lift_sequences(model, p2, stride=stride, tta=True, batch=2)
         with torch.no_grad():
@@ -251,8 +223,7 @@ def test_lift_action_agrees_with_the_evaluation_path(lib):
     from manipose_amd import lift_action, lift_sequences
     from manipose_amd.hydra_lite import Cfg
     from manipose_amd.metrics import mpjpe_error
-    fx, model = _build_rmcl()
-    T = fx["cfg"]["T"]
+    model, T, K = _model("rmcl")
     p2, p3 = _sequences([T - 7, 2 * T, 2 * T + 5], seed=8)
     win_seq, win_start = closed_form_tables([len(a) for a in p2], T, T)
     X = torch.from_numpy(cut_windows(p2, win_seq, win_start, T)).cuda()
@@ -264,7 +235,7 @@ def test_lift_action_agrees_with_the_evaluation_path(lib):
     got = 1000.0 * mpjpe_error(torch.from_numpy(pred).cuda(), y.reshape(-1, 17, 3), "average").item()
     assert abs(got - want["mpjpe"]) <= 1e-3 * want["mpjpe"] + 0.05, (got, want)
     hy = lift_action(model, p2, cfg, True)
-    assert hy.shape == (len(win_seq) * T, fx["cfg"]["n_hyp"], 17, 4)
+    assert hy.shape == (len(win_seq) * T, K, 17, 4)
     np.testing.assert_allclose(hy[..., 3].sum(1), 1.0, atol=1e-5)                            # the scores of a frame sum to one
     best = torch.cat(lift_sequences(model, p2, tta=True, agg="best_score", keep_padding=True))
     got_b = 1000.0 * mpjpe_error(best, y.reshape(-1, 17, 3), "average").item()
@@ -286,7 +257,7 @@ def test_lift_entry_point_and_argument_errors(lib, tmp_path, monkeypatch):
         assert z[f"synthetic_{i:03d}"].shape == (n, 17, 3) and z[f"synthetic_{i:03d}__hyps"].shape == (n, 3, 17, 4)
         assert np.isfinite(z[f"synthetic_{i:03d}"]).all()
     # CPU input / CPU model: RuntimeError, never a fallback
-    fx, model = _build_rmcl()
+    model = _model("rmcl")[0]
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         lift_sequences(model, [torch.zeros(30, 17, 2)])
     with pytest.raises(ValueError):

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import lift_rigid_ref as ref
-from helpers import fixture_state, load_fixture
+from lift_fixtures import bits as _bits, fixture_model as _model, sequences_2d as _sequences, to_numpy as _np
 from lift_ref import MIRROR, closed_form_tables, cut_windows
 
 pytestmark = pytest.mark.gpu
@@ -24,10 +24,6 @@ LENS = [1, 2, 30, 257]                                                    # a on
 OFF = np.concatenate([[0], np.cumsum(LENS)]).astype(np.int64)
 PARENTS_C = (C.c_int32 * 17)(*ref.PARENTS)
 BONE_MIRROR = MIRROR[1:] - 1                                              # bone of joint j is read from bone of joint MIRROR[j]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _random_poses(inner, ch, seed):
@@ -152,41 +148,7 @@ def test_rigid_entry_points_reject_bad_arguments_before_any_launch(lib):
     assert np.abs(t.cpu().numpy() - want).max() <= POS_TOL                # ... which all point up the z axis
 
 
-# ---- end to end: the tiny fp32 fixture models of test_gpu_lift.py, built the way that file builds them ------------------------------------------
-_MODELS = {}
-
-
-def _model(kind):
-    if kind in _MODELS:
-        return _MODELS[kind]
-    from manipose_amd import ManifoldMixSTE, MixSTE, RMCLManifoldMixSTE, h36m_skeleton
-    if kind == "mixste":
-        fx = load_fixture("mixste_tiny")
-        T, C_, depth, heads = [int(v) for v in fx["cfg_mixste"]]
-        model = MixSTE(num_frame=T, num_joints=17, in_chans=2, out_dim=3, embed_dim=C_, depth=depth, num_heads=heads, drop_path_rate=0.0)
-        K = 1
-    else:
-        fx = load_fixture("rmcl_small" if kind == "rmcl" else "manifold_k1")
-        c = fx["cfg"]
-        kw = dict(skeleton=h36m_skeleton(), num_frame=c["T"], embed_dim_rot=c["C_rot"], depth_rot=c["depth_rot"], num_heads_rot=c["heads_rot"],
-                  embed_dim_seg=c["C_seg"], depth_seg=c["depth_seg"], num_heads_seg=c["heads_seg"], drop_path_rate=0.0, rot_rep_dim=c.get("rot_dim", 6))
-        model = RMCLManifoldMixSTE(n_hyp=c["n_hyp"], **kw) if c["n_hyp"] > 0 else ManifoldMixSTE(**kw)
-        T, K = c["T"], max(1, c["n_hyp"])
-    model.load_state_dict(fixture_state(fx), strict=True)
-    model.precision = "fp32"
-    _MODELS[kind] = (model.cuda().eval(), T, K)
-    return _MODELS[kind]
-
-
-def _sequences(T, seed=12):
-    g = np.random.default_rng(seed)
-    return [np.clip(0.3 * g.standard_normal((n, 17, 2)), -1, 1).astype(np.float32) for n in (T - 5, 2 * T, 2 * T + 5)]
-
-
-def _np(ts):
-    return [t.cpu().numpy() for t in ts]
-
-
+# ---- end to end: the tiny fp32 fixture models of lift_fixtures.py ------------------------------------------------------------------------------
 def _check_projection(got, base, bones, tol=POS_TOL, scale=1.0):
     """every sequence of `got` is the float64 projection of the same sequence of `base` with its row of `bones` (metres) times scale"""
     for g, b, L in zip(got, base, bones):
