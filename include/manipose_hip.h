@@ -185,6 +185,16 @@ int mp_attention_fwd_bf16x3_ex(const void* qkv_hi, const void* qkv_lo, void* out
 /* mp_attention_bwd_bf16 with out_f16 = 1: O is the fp16 plane of an f16f8 output (temporal MFMA backward only; MP_ERR_ARG elsewhere) */
 int mp_attention_bwd_bf16_ex(const void* qkv, const void* out, const void* d_out, const float* lse, float* delta, void* d_qkv, int temporal, int B,
                              int T, int J, int C, int H, int out_f16, void* stream);
+/* The three calls above in the forms only a model reaches otherwise.  qk_scale: the softmax scale (mp_model_config::qk_scale; muP: 1 / head_dim),
+ * 0 = head_dim ** -0.5.  grad_scale (backward; NULL = bf16 outputs): the 8-float gradient-scale block {S, 1 / S, -, 1, clamped (u32), non-finite
+ * (u32), -, -} of an f16_backward model on the device - dQ / dK / dV leave as fp16 of S x value, stores beyond +-65504 are clamped, non-finite ones
+ * written as 0, and both are counted in the block.  Only the MFMA backward kernels have that store: MP_ERR_ARG for a shape the row kernels serve. */
+int mp_attention_fwd_bf16_scale_ex(const void* qkv, void* out, float* lse, int temporal, int B, int T, int J, int C, int H, float qk_scale,
+                                   void* stream);
+int mp_attention_bwd_bf16_scale_ex(const void* qkv, const void* out, const void* d_out, const float* lse, float* delta, void* d_qkv, int temporal,
+                                   int B, int T, int J, int C, int H, int out_f16, float qk_scale, const float* grad_scale, void* stream);
+int mp_attention_fwd_bf16x3_scale_ex(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, float* scratch, int temporal,
+                                     int B, int T, int J, int C, int H, int out_form, float qk_scale, void* stream);
 /* Backward GEMMs of the f16f8 layers.  dgrad (dx non-NULL): dx = dy W (bf16 out), times z = gelu' (bf16) when z is non-NULL; f16 = 1: dy and W
  * are fp16; gout non-NULL (device address): dx is written as saturating fp16 of *gout x value, clamped at +-65504, non-finite values as 0,
  * counted in gsat[0] (clamped) and gsat[1] (non-finite), which are added to.  Weight gradient (dW non-NULL): dW += dy^T x, db += colsum(dy);

@@ -73,6 +73,9 @@ _SIGNATURES = {
     "mp_layernorm_fwd_ex": (i32, [vp, i32, i32, vp, vp, f32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, i32, vp]),
     "mp_attention_fwd_bf16x3_ex": (i32, [vp] * 6 + [i32] * 7 + [vp]),
     "mp_attention_bwd_bf16_ex": (i32, [vp] * 6 + [i32] * 7 + [vp]),
+    "mp_attention_fwd_bf16_scale_ex": (i32, [vp] * 3 + [i32] * 6 + [f32, vp]),
+    "mp_attention_bwd_bf16_scale_ex": (i32, [vp] * 6 + [i32] * 7 + [f32, vp, vp]),
+    "mp_attention_fwd_bf16x3_scale_ex": (i32, [vp] * 6 + [i32] * 7 + [f32, vp]),
     "mp_linear_bwd_f16": (i32, [vp] * 9 + [i32] * 5 + [vp, vp, i64, vp]),
     "mp_layernorm_bwd_ex": (i32, [vp, i32, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, i64, vp, vp]),
     "mp_layernorm_bwd2_ex": (i32, [vp, i32, vp, vp, vp, f32] + [vp] * 7 + [i32] * 3 + [vp, i32, i32] + [vp] * 4 + [i32, i32, vp, i64, vp, vp]),

@@ -7,6 +7,8 @@
 namespace mp {
 const char* last_error();
 long wgrad_f32_slab_floats(int Mtok, int Nout, int Kin);
+bool attn_tmfma_supported(int T, int D);            // attention_mfma.hip
+bool attn_smfma_supported(int N, int D, int H);
 }
 using namespace mp;
 
@@ -249,6 +251,56 @@ int mp_attention_bwd_bf16_ex(const void* qkv, const void* out, const void* d_out
   MP_CHECK(!out_f16 || temporal, MP_ERR_ARG, "mp_attention_bwd_bf16_ex: only the temporal backward reads O");
   return temporal ? attn_temporal_bwd(qkv, out, d_out, lse, delta, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream, out_f16)
                   : attn_spatial_bwd(qkv, d_out, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream);
+}
+/* the attention forms only the engine reaches: a softmax scale of its own (attn_scale_override) and the scaled-fp16 gradient stores of the
+ * MFMA backward kernels (attn_grad_f16_override); both are thread-local settings of the launches issued next, reset on every exit path */
+namespace {
+struct AttnScaleScope {
+  explicit AttnScaleScope(float s) { attn_scale_override(s); }
+  ~AttnScaleScope() { attn_scale_override(0.f); }
+  AttnScaleScope(const AttnScaleScope&) = delete;
+  AttnScaleScope& operator=(const AttnScaleScope&) = delete;
+};
+struct AttnGradF16Scope {
+  explicit AttnGradF16Scope(const float* gsc) { attn_grad_f16_override(gsc); }
+  ~AttnGradF16Scope() { attn_grad_f16_override(nullptr); }
+  AttnGradF16Scope(const AttnGradF16Scope&) = delete;
+  AttnGradF16Scope& operator=(const AttnGradF16Scope&) = delete;
+};
+}  // namespace
+int mp_attention_fwd_bf16_scale_ex(const void* qkv, void* out, float* lse, int temporal, int B, int T, int J, int C, int H, float qk_scale,
+                                   void* stream) {
+  MP_CHECK(qkv && out && (!temporal || lse), MP_ERR_ARG, "mp_attention_fwd_bf16_scale_ex: null pointer");
+  MP_CHECK(qk_scale >= 0.f && qk_scale <= 3.0e38f, MP_ERR_ARG, "mp_attention_fwd_bf16_scale_ex: qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)");
+  AttnScaleScope scale(qk_scale);
+  return temporal ? attn_temporal_fwd(qkv, out, lse, 1, B, T, J, C, H, (hipStream_t)stream)
+                  : attn_spatial_fwd(qkv, out, 1, B, T, J, C, H, (hipStream_t)stream);
+}
+int mp_attention_bwd_bf16_scale_ex(const void* qkv, const void* out, const void* d_out, const float* lse, float* delta, void* d_qkv, int temporal,
+                                   int B, int T, int J, int C, int H, int out_f16, float qk_scale, const float* grad_scale, void* stream) {
+  MP_CHECK(qkv && d_out && d_qkv && (!temporal || (out && lse && delta)), MP_ERR_ARG, "mp_attention_bwd_bf16_scale_ex: null pointer");
+  MP_CHECK(!out_f16 || temporal, MP_ERR_ARG, "mp_attention_bwd_bf16_scale_ex: only the temporal backward reads O");
+  MP_CHECK(qk_scale >= 0.f && qk_scale <= 3.0e38f, MP_ERR_ARG, "mp_attention_bwd_bf16_scale_ex: qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)");
+  if (grad_scale != nullptr) {      // the row kernels know no fp16 store: they would write bf16 where the caller expects scaled fp16
+    const bool mfma = H > 0 && C % H == 0 && C % 8 == 0 && (temporal ? attn_tmfma_supported(T, C / H) : attn_smfma_supported(J, C / H, H));
+    MP_CHECK(mfma, MP_ERR_ARG, "mp_attention_bwd_bf16_scale_ex: scaled fp16 gradients need an MFMA backward (temporal %d, T=%d J=%d C=%d H=%d)", temporal,
+             T, J, C, H);
+  }
+  AttnScaleScope scale(qk_scale);
+  AttnGradF16Scope f16_out(grad_scale);
+  return temporal ? attn_temporal_bwd(qkv, out, d_out, lse, delta, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream, out_f16)
+                  : attn_spatial_bwd(qkv, d_out, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream);
+}
+int mp_attention_fwd_bf16x3_scale_ex(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, float* scratch, int temporal,
+                                     int B, int T, int J, int C, int H, int out_form, float qk_scale, void* stream) {
+  MP_CHECK(qkv_hi && qkv_lo && out_hi && out_lo && (!temporal || lse) && (out_form == 0 || out_form == 1), MP_ERR_ARG,
+           "mp_attention_fwd_bf16x3_scale_ex: bad argument");
+  MP_CHECK(qk_scale >= 0.f && qk_scale <= 3.0e38f, MP_ERR_ARG, "mp_attention_fwd_bf16x3_scale_ex: qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)");
+  AttnScaleScope scale(qk_scale);
+  return temporal ? attn_temporal_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, lse, scratch, B, T, J, C, H,
+                                         (hipStream_t)stream, out_form)
+                  : attn_spatial_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, scratch, B, T, J, C, H,
+                                        (hipStream_t)stream, out_form);
 }
 int mp_linear_bwd_f16(const void* dy, const void* x, const void* W, void* dx, const void* z, const float* gout, uint32_t* gsat, float* dW, float* db,
                       int M, int N, int K, int f16, int x_f16, const float* oscale, float* slab, int64_t slab_floats, void* stream) {

@@ -705,11 +705,11 @@ def test_bf16_attention_forward_backward(lib, temporal, B, T, J, C, H):
     ref = _attn_ref(qkv, B, T, J, C, H, temporal)
     (ref * dout_b.float()).sum().backward()
     qd, dod = qkv_b.cuda(), dout_b.cuda()
-    out = torch.empty(M, C, device="cuda", dtype=torch.bfloat16)
-    lse = torch.zeros(B * J * H * T, device="cuda")
+    out = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)      # (NaN, not zeros: an element never written must not read as a value)
+    lse = torch.full((B * J * H * T,), float("nan"), device="cuda")
     _lib.check(lib.mp_attention_fwd_bf16(qd.data_ptr(), out.data_ptr(), lse.data_ptr(), temporal, B, T, J, C, H, st()))
     close(out.float(), ref, rtol=2e-2, atol=2e-2)
-    dq = torch.zeros(M, 3 * C, device="cuda", dtype=torch.bfloat16)
+    dq = torch.full((M, 3 * C), float("nan"), device="cuda", dtype=torch.bfloat16)
     delta = torch.empty(B * J * H * T, device="cuda")
     _lib.check(lib.mp_attention_bwd_bf16(qd.data_ptr(), out.data_ptr(), dod.data_ptr(), lse.data_ptr(), delta.data_ptr(),
                                          dq.data_ptr(), temporal, B, T, J, C, H, st()))
