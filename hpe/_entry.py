@@ -271,7 +271,8 @@ def sk_device(model):
     return next(model.parameters()).device
 
 
-LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj", "__hyps_reproj", "__hyps_ok", "__floor", "__cam")
+LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj", "__hyps_reproj", "__hyps_ok", "__floor", "__cam", "__traj_fit", "__filled",
+                 "__hyps_traj_fit", "__hyps_filled")
 
 
 def lift_place_options(cfg):
@@ -284,6 +285,27 @@ def lift_place_options(cfg):
     if (place or frame == "world") and str(cfg.data.dataset) == "3dhp":
         raise ValueError("lift.place / lift.frame=world need the cameras' calibration, and the MPI-INF-3DHP files (data.dataset=3dhp) carry none")
     return place, frame == "world", floor
+
+
+def lift_smooth_options(cfg):
+    """(smooth_poses, smooth_traj, smooth_degree, smooth_taper) of the lift group; ValueError for a value or a combination that cannot run - before
+    any model is built."""
+    radii = []
+    for key in ("smooth_poses", "smooth_traj"):
+        r = cfg.lift.get(key, 0)
+        if isinstance(r, bool) or not isinstance(r, int) or not 0 <= r <= 64:
+            raise ValueError(f"lift.{key} is a radius in frames, an integer in 0..64 (0: off), got {r!r}")
+        radii.append(r)
+    degree, taper = cfg.lift.get("smooth_degree", 2), str(cfg.lift.get("smooth_taper", "uniform"))
+    if isinstance(degree, bool) or not isinstance(degree, int) or not 0 <= degree <= 2:
+        raise ValueError(f"lift.smooth_degree must be 0, 1 or 2, got {degree!r}")
+    if taper not in ("uniform", "biweight"):
+        raise ValueError(f"lift.smooth_taper must be uniform or biweight, got {taper!r}")
+    if not any(radii) and (degree != 2 or taper != "uniform"):
+        raise ValueError("lift.smooth_degree / lift.smooth_taper describe smoothing: set lift.smooth_poses or lift.smooth_traj")
+    if radii[1] and not bool(cfg.lift.get("place", False)):
+        raise ValueError("lift.smooth_traj smooths the trajectory that lift.place fits: set lift.place=true")
+    return radii[0], radii[1], degree, taper
 
 
 def synthetic_cameras(groups):
@@ -303,7 +325,9 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
     it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
     lengths per sequence; lift.lengths, lift.symmetric) also ``<key>__bones`` -> (16,), the sequence's bone lengths in metres.
     ``cameras`` = {name: [one camera per sequence]} (camera_table's forms) is needed by lift.place (also ``<key>__traj`` (N, 3), ``<key>__reproj``
-    (N,), ``<key>__ok`` (N,) uint8 and with lift.hyps ``<key>__hyps_traj`` (N, K, 3), ``<key>__hyps_reproj``, ``<key>__hyps_ok`` (N, K)) and by
+    (N,), ``<key>__ok`` (N,) uint8 and with lift.hyps ``<key>__hyps_traj`` (N, K, 3), ``<key>__hyps_reproj``, ``<key>__hyps_ok`` (N, K); with
+    lift.smooth_traj ``__traj`` / ``__hyps_traj`` are the smoothed trajectories and ``<key>__traj_fit`` (N, 3), ``<key>__filled`` (N,) uint8,
+    ``<key>__hyps_traj_fit`` (N, K, 3), ``<key>__hyps_filled`` (N, K) are added) and by
     lift.frame=world (poses and hypotheses in the world frame; with lift.floor on z = 0 and ``<key>__floor``, the offset subtracted); whenever
     cameras were used ``<key>__cam`` holds the 16 numbers (intrinsic 9, orientation 4, translation 3)."""
     from manipose_amd import camera_table
@@ -311,6 +335,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
     out = {}
     rigid = bool(cfg.lift.get("rigid", False))
     place, world, floor = lift_place_options(cfg)
+    smooth_p, smooth_t, smooth_degree, smooth_taper = lift_smooth_options(cfg)
     use_cams = place or world
     if use_cams and cameras is None:
         raise ValueError("lift.place / lift.frame=world need the sequences' cameras")
@@ -318,7 +343,8 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
         res = _lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=cfg.lift.agg, blend=cfg.lift.blend,
                               return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
                               symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid, cameras=cameras[name] if use_cams else None,
-                              place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor)
+                              place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor,
+                              smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper)
         cam_rows = np.concatenate(camera_table(cameras[name]), axis=1) if use_cams else None
         for i, p in enumerate(res.poses):
             key = name if len(res.poses) == 1 else f"{name}.{i}"
@@ -356,6 +382,7 @@ def run(argv, extra_defaults=None):
     from manipose_amd.training import LiftingTrainer
     cfg = load_config(argv, extra_defaults)
     lift_place_options(cfg)                    # a lift.place / lift.frame / lift.floor that cannot run fails here, before the model is built
+    lift_smooth_options(cfg)                   # ... and so does a lift.smooth_* that cannot run
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")

@@ -480,6 +480,28 @@ int mp_lift_place(const float* poses, int64_t Ntot, int inner, int J, int C, con
 int mp_lift_world(float* poses, int64_t Ntot, int inner, int J, int C, const float* traj, const int64_t* seq_offset, int S, const float* quat,
                   const float* trans, int floor_mode, float* floor, float* scratch, int64_t scratch_floats, void* stream);
 
+/* Smoothing lifted sequences in time: a weighted local polynomial fit (Savitzky-Golay with validity weights) along the frames of a sequence, which
+ * also fills frames that have no valid value of their own.  The reference has no counterpart.  in / out (Ntot, inner, M, C) device floats, out of
+ * place; C = 3 or 4, 1 <= M <= 32 (M = 1, C = 3: a trajectory; M = J: poses or hypotheses); valid and filled (Ntot, inner) device bytes, either may
+ * be null (null valid: every frame is valid); seq_offset (S + 1) device int64 as for mp_lift_rigid, its entries clamped to 0 .. Ntot.
+ * Per frame g of sequence s = frames [f0, f1), inner index i, with radius R, degree deg, taper:
+ *   taps tau in [-R, R] with f0 <= g + tau < f1 (a window never crosses a sequence boundary and is never padded);
+ *   w_tau = k(tau) [valid[g + tau, i] != 0],  k = 1 (taper 0, "uniform") or (1 - (tau / (R + 1))^2)^2 (taper 1, "biweight");
+ *   n = taps with w_tau > 0.  n = 0: every float of the frame is copied bit for bit and filled = 0; otherwise filled = 1 and
+ *   d = min(deg, n - 1), or d = 0 when no valid tap has tau <= 0 or none has tau >= 0 (not bracketed: held constant, never extrapolated);
+ *   u_tau = tau / R;  for each channel c < 3 of each of the M items out = p(0), p the polynomial of degree d that minimises
+ *   sum_tau w_tau (p(u_tau) - y_tau)^2:  out = sum_tau c_tau y_tau,  c_tau = w_tau (a0 + a1 u_tau + a2 u_tau^2),  (a0, a1, a2) the first row of
+ *   the inverse of the (d + 1) x (d + 1) normal matrix [sum w u^(j+k)].  c_tau is computed once per (g, i) and shared by the M x 3 channels.
+ *   Channel 3 of C = 4 (a hypothesis' score) is copied bit for bit.
+ * All arithmetic between the float32 loads and the one float32 store is fp64; sums run over the valid taps in increasing tau; no atomics: identical
+ * bits on every call.  A non-finite value on a valid tap gives IEEE results in the windows that hold it; an invalid tap's value is never looked at.
+ * MP_ERR_ARG before anything is launched: in, out or seq_offset null; in and out overlapping; radius outside 1..MP_LIFT_SMOOTH_MAXR, degree outside
+ * 0..2, taper outside 0..1; M outside 1..32, C outside {3, 4}; Ntot, inner or S <= 0, S > Ntot; more work than one grid holds.  The call does not
+ * synchronise. */
+#define MP_LIFT_SMOOTH_MAXR 64
+int mp_lift_smooth(const float* in, float* out, int64_t Ntot, int inner, int M, int C, const uint8_t* valid, const int64_t* seq_offset, int S,
+                   int radius, int degree, int taper, uint8_t* filled, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -17,6 +17,13 @@ the sequences' cameras (``camera_table``) ``mp_lift_place`` fits, per pose and p
 the 2-D keypoints the pose was lifted from, and reports the reprojection error under the full H36M camera model; ``mp_lift_world`` rotates
 everything into the world frame (the reference's ``camera_to_world``, hpe/viz.py:93-98) and, with ``floor``, puts the sequence on z = 0.
 
+Smoothing in time (``smooth_poses`` / ``smooth_traj``, radii, 0 = off, the default): every stage above treats every frame on its own.
+``mp_lift_smooth`` fits, per frame and coordinate, a polynomial of degree ``smooth_degree`` to the frames within the radius that belong to the same
+sequence and are valid (Savitzky-Golay with validity weights; include/manipose_hip.h has the rule) and stores its value at the frame.  The merged
+poses and the hypotheses are smoothed BEFORE the rigid stage (bone lengths stay constant, and placing fits the trajectory to the poses that are
+emitted); the fitted root trajectories AFTER ``mp_lift_place`` and before ``mp_lift_world``, with the fit's ``ok`` as validity, so a frame whose fit
+was degenerate is filled from its neighbours.  Whether this lowers MPJPE / MPJVE on real data has not been measured (no dataset here).
+
 Scheduling: a sequence is lifted on its own - its windows are cut into forwards of ``batch`` (``2 * batch`` with TTA), all of them
 stay resident until the sequence is merged, and no forward mixes two sequences.  A frame's covering windows are therefore always
 resident when it is merged (no partial sum is ever carried), and a sequence's result does not depend on what else is lifted with
@@ -24,7 +31,7 @@ it: the engine's GEMM tile plan depends on the batch, so a window's bits do.
 
 Structure: ``lift_sequences`` is a chain of private stages - ``_check_options`` (every argument error, then an immutable record of resolved
 options), ``_upload`` (keypoints, window tables, offsets and output buffers, once), ``_lift_one`` per sequence (forwards and ONE merge),
-``_rigid_stage``, ``_place_stage``, ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place.  The
+``_smooth_poses_stage``, ``_rigid_stage``, ``_place_stage`` (with ``_smooth_traj_stage`` between its fit and its world transform), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place.  The
 public function turns the record into its documented list / tuple in one place; ``lift_action`` and hpe/_entry.py read the fields by name.
 """
 from __future__ import annotations
@@ -40,6 +47,8 @@ from . import _lib
 
 AGG = {"weighted_ave": 0, "best_score": 1}
 BLEND = {"mean": 0, "center": 1}
+TAPER = {"uniform": 0, "biweight": 1}
+SMOOTH_MAXR = 64             # MP_LIFT_SMOOTH_MAXR of include/manipose_hip.h
 
 
 def plan_windows(lengths: Sequence[int], T: int, stride: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -134,6 +143,10 @@ def _seq_table(seq_offset, ntot, dev):
 def _poses4(poses, who):
     if not torch.is_tensor(poses) or not poses.is_cuda:
         raise RuntimeError(f"manipose_amd: {who} takes device tensors; there is no CPU fallback")
+    return _poses4_shape(poses)
+
+
+def _poses4_shape(poses):
     p4 = poses.unsqueeze(1) if poses.dim() == 3 else poses
     if p4.dim() != 4 or p4.shape[3] not in (3, 4) or (poses.dim() == 3 and poses.shape[2] != 3) or poses.dtype != torch.float32 \
             or not poses.is_contiguous():
@@ -182,6 +195,69 @@ def project_rigid(poses, lengths, seq_offset=None, skeleton=None):
     if ntot > 0:
         _rigid(_lib.load(), p4, d_off, S, table, parents)
     return poses
+
+
+def _is_radius(r, lowest):
+    return isinstance(r, (int, np.integer)) and not isinstance(r, (bool, np.bool_)) and lowest <= int(r) <= SMOOTH_MAXR
+
+
+def _smooth_options(radius, degree, taper):
+    if not _is_radius(radius, 1):
+        raise ValueError(f"radius must be an integer in 1..{SMOOTH_MAXR}, got {radius!r}")
+    if not isinstance(degree, (int, np.integer)) or isinstance(degree, (bool, np.bool_)) or not 0 <= int(degree) <= 2:
+        raise ValueError(f"degree must be 0, 1 or 2, got {degree!r}")
+    if taper not in TAPER:
+        raise ValueError(f"taper must be one of {sorted(TAPER)}, got {taper!r}")
+
+
+def _smooth(lib, x4, valid, d_off, S, radius, degree, taper, want_filled=False):
+    """``mp_lift_smooth`` on x4 (Ntot, inner, M, C) with valid (Ntot, inner) uint8 or None: (a new tensor, filled (Ntot, inner) uint8 or None)"""
+    ntot, inner, M, ch = (int(v) for v in x4.shape)
+    out = torch.empty_like(x4)
+    filled = torch.empty(ntot, inner, dtype=torch.uint8, device=x4.device) if want_filled else None
+    if ntot > 0:
+        with torch.cuda.device(x4.device):
+            _lib.check(lib.mp_lift_smooth(_lib.ptr(x4), _lib.ptr(out), ntot, inner, M, ch, _lib.ptr(valid), _lib.ptr(d_off), S, int(radius), int(degree),
+                                          TAPER[taper], _lib.ptr(filled), _lib.stream_ptr()), "mp_lift_smooth")
+    return out, filled
+
+
+def smooth_poses(poses, seq_offset=None, radius=4, degree=2, taper="uniform"):
+    """``mp_lift_smooth`` on a device tensor, OUT of place: poses (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32 (channel 3, a hypothesis' score,
+    is copied) -> a new tensor of the same shape in which every coordinate of frame g is p(0) of the polynomial p of degree ``degree`` (0..2)
+    fitted by least squares to the frames g - radius .. g + radius of the same sequence (radius 1..64; at the ends of a sequence the window is
+    shorter, never padded, and the degree falls to the number of frames - 1), in the variable (frame - g) / radius.  ``taper``: "uniform"
+    (all taps weigh 1: the classical Savitzky-Golay filter) or "biweight" ((1 - (tau / (radius + 1))^2)^2).  ``seq_offset`` (S + 1): first frame
+    of every sequence, HOST table or device int64 tensor (default: one sequence).  Every frame counts as valid; fp64 inside, identical bits on
+    every call."""
+    _smooth_options(radius, degree, taper)
+    if torch.is_tensor(poses):
+        _poses4_shape(poses)                             # (the ValueErrors come before the refusal of a CPU tensor)
+    p4 = _poses4(poses, "smooth_poses")
+    d_off, S = _seq_table(seq_offset, int(p4.shape[0]), poses.device)
+    return _smooth(_lib.load(), p4, None, d_off, S, radius, degree, taper)[0].view(poses.shape)
+
+
+def smooth_traj(traj, ok=None, seq_offset=None, radius=4, degree=2, taper="uniform"):
+    """``mp_lift_smooth`` on root trajectories, OUT of place: traj (Ntot, 3) or (Ntot, inner, 3) float32 device tensor as ``place_poses`` returns it,
+    ``ok`` uint8 of shape (Ntot[, inner]) or None (every frame is valid): a frame with ok = 0 does not enter any fit, and gets the value the fit
+    through its valid neighbours has at it - constant where valid frames lie on one side only.  Returns ``(smoothed, filled)``: filled uint8
+    (Ntot[, inner]) is 0 where no frame within the radius in the same sequence is valid; such a frame keeps its input bits.  The other arguments
+    as for ``smooth_poses``."""
+    _smooth_options(radius, degree, taper)
+    if torch.is_tensor(traj):
+        if traj.dim() not in (2, 3) or traj.shape[-1] != 3 or traj.dtype != torch.float32 or not traj.is_contiguous():
+            raise ValueError(f"traj must be contiguous float32 (Ntot, 3) or (Ntot, inner, 3), got {tuple(traj.shape)} {traj.dtype}")
+        if ok is not None and (not torch.is_tensor(ok) or tuple(ok.shape) != tuple(traj.shape[:-1]) or ok.dtype != torch.uint8):
+            raise ValueError(f"ok must be a uint8 tensor of shape {tuple(traj.shape[:-1])}, got "
+                             f"{(tuple(ok.shape), ok.dtype) if torch.is_tensor(ok) else type(ok).__name__}")
+    if not torch.is_tensor(traj) or not traj.is_cuda or (ok is not None and not ok.is_cuda):
+        raise RuntimeError("manipose_amd: smooth_traj takes device tensors; there is no CPU fallback")
+    ntot = int(traj.shape[0])
+    d_off, S = _seq_table(seq_offset, ntot, traj.device)
+    out, filled = _smooth(_lib.load(), traj.view(ntot, -1, 1, 3), None if ok is None else ok.contiguous().view(ntot, -1), d_off, S, radius, degree,
+                          taper, want_filled=True)
+    return out.view(traj.shape), filled.view(traj.shape[:-1])
 
 
 FLOOR_SHARES = 16            # MP_LIFT_WORLD_SHARES of include/manipose_hip.h: partial minima per sequence in mp_lift_world's scratch
@@ -332,8 +408,9 @@ def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirr
 # What a lift was asked for, checked and resolved by _check_options; no stage after it validates anything.  seqs: the 2-D sequences;
 # cam_tables: camera_table(cameras) with place / world; lengths: "model", "measured" or "table" with rigid, and table: the caller's checked
 # (S, J - 1) one; skeleton, parents: the model's, with rigid; windows: plan_windows' (win_seq, win_start)
+# smooth_poses, smooth_traj: the two radii (0: off), smooth_degree, smooth_taper: shared by both
 _Options = namedtuple("_Options", "seqs tta agg blend scale return_hyps keep_padding rigid symmetric return_bones place world floor return_place "
-                                  "cam_tables T J K lengths table skeleton parents windows batch dev", defaults=(None,) * 11)
+                                  "smooth_poses smooth_traj smooth_degree smooth_taper cam_tables T J K lengths table skeleton parents windows batch dev", defaults=(None,) * 11)
 # Everything the kernels of a lift read, uploaded once by _upload, and the buffers they write.  p2: (sum N_i, J, 2) keypoints of all sequences,
 # lens: N_i; out_lens: frames emitted per sequence (whole windows with keep_padding), out_off: their (S + 1) offsets in out_all (., J, 3) and
 # hyp_all (., K, J, 4); first: (S + 1) first window of every sequence; merge_off (S, 2), h_zero / d_zero: the offsets (0, out_lens[s]) and the
@@ -346,7 +423,7 @@ _Lifted = namedtuple("_Lifted", "poses hyps bones place", defaults=(None,) * 3)
 
 def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
-                   floor=False, return_place=False):
+                   floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform"):
     """Every argument error of ``lift_sequences``, in a fixed order and before anything touches a device: the ValueErrors first, the "no CPU
     fallback" RuntimeErrors last.  No sequences: the record ends after ``return_place``."""
     if not rigid and (lengths is not None or symmetric or return_bones):
@@ -368,10 +445,22 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
         raise ValueError("return_place returns what place=True (and floor=True) computed: pass place=True")
     if (place or world) and keep_padding:
         raise ValueError("place / frame='world' with keep_padding=True: padded frames have no keypoints of their own")
+    for name, r in (("smooth_poses", smooth_poses), ("smooth_traj", smooth_traj)):
+        if not _is_radius(r, 0):
+            raise ValueError(f"{name} is a radius in frames, an integer in 0..{SMOOTH_MAXR} (0: off), got {r!r}")
+    smoothing = int(smooth_poses) > 0 or int(smooth_traj) > 0
+    if not smoothing and (smooth_degree != 2 or smooth_taper != "uniform"):
+        raise ValueError("smooth_degree and smooth_taper describe smoothing: pass smooth_poses or smooth_traj (a radius > 0)")
+    if smoothing:
+        _smooth_options(max(int(smooth_poses), int(smooth_traj)), smooth_degree, smooth_taper)
+    if int(smooth_traj) > 0 and not place:
+        raise ValueError("smooth_traj smooths the trajectory that place=True fits: pass place=True")
+    if smoothing and keep_padding:
+        raise ValueError("smooth_poses / smooth_traj with keep_padding=True: padded frames repeat the last frame and would enter the fits")
     single = torch.is_tensor(poses_2d) or isinstance(poses_2d, np.ndarray)
     seqs = [poses_2d] if single else list(poses_2d)
     opt = _Options(seqs, tta, agg, blend, scale, bool(return_hyps), keep_padding, rigid, symmetric, bool(return_bones), place, world, floor,
-                   bool(return_place))
+                   bool(return_place), int(smooth_poses), int(smooth_traj), int(smooth_degree), smooth_taper)
     if not seqs:
         return opt
     cam_tables = None
@@ -486,6 +575,28 @@ def _lift_one(model, opt, plan, s, model_rows):
                   device_tables=(plan.d_zero[:nw], plan.d_start[a0:a0 + nw], plan.d_merge_off[s]))
 
 
+def _smooth_poses_stage(opt, plan):
+    """The merged poses and, with ``return_hyps``, the hypotheses (hypothesis k is a track over time; its scores are untouched) smoothed along
+    the frames of their sequence; every frame is valid.  ``mp_lift_smooth`` is out of place: returns the plan with the new buffers.  (No padded
+    frames here: ``d_off`` describes ``out_all``.)"""
+    lib, S, args = _lib.load(), len(plan.lens), (opt.smooth_poses, opt.smooth_degree, opt.smooth_taper)
+    out = _smooth(lib, plan.out_all.unsqueeze(1), None, plan.d_off, S, *args)[0][:, 0]
+    hyps = _smooth(lib, plan.hyp_all, None, plan.d_off, S, *args)[0] if opt.return_hyps else None
+    return plan._replace(out_all=out, hyp_all=hyps)
+
+
+def _smooth_traj_stage(opt, plan, placed):
+    """The fitted trajectories of the merged poses and of the hypotheses smoothed along the frames of their sequence with the fit's ``ok`` as
+    validity: ``traj`` / ``hyps_traj`` become the smoothed ones (which the world stage uses), the fitted ones stay as ``traj_fit`` /
+    ``hyps_traj_fit``, and ``filled`` / ``hyps_filled`` say where a value could be given; ``ok`` and ``reproj`` stay what the fit reported."""
+    lib, S, ntot = _lib.load(), len(plan.lens), int(plan.out_all.shape[0])
+    for pre in ("", "hyps_") if opt.return_hyps else ("",):
+        fit, ok = placed[pre + "traj"], placed[pre + "ok"]
+        out, filled = _smooth(lib, fit.view(ntot, -1, 1, 3), ok.view(ntot, -1), plan.d_off, S, opt.smooth_traj, opt.smooth_degree, opt.smooth_taper,
+                              want_filled=True)
+        placed[pre + "traj_fit"], placed[pre + "traj"], placed[pre + "filled"] = fit, out.view(fit.shape), filled.view(ok.shape)
+
+
 def _rigid_stage(opt, plan, model_rows):
     """One (J - 1) table of bone lengths per sequence, and every merged pose and hypothesis re-assembled with it, in place.  Returns the
     (S, J - 1) tables in metres."""
@@ -525,6 +636,8 @@ def _place_stage(opt, plan):
         placed["traj"], placed["reproj"], placed["ok"] = (t[:, 0] for t in _place(lib, out4, plan.p2, plan.d_off, S, d_intr, None, True))
         if opt.return_hyps:
             placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"] = _place(lib, plan.hyp_all, plan.p2, plan.d_off, S, d_intr, None, True)
+        if opt.smooth_traj:
+            _smooth_traj_stage(opt, plan, placed)
     if opt.world:
         d_floor = torch.empty(S, dtype=torch.float32, device=dev) if opt.floor else None
         _world(lib, out4, placed["traj"].unsqueeze(1).contiguous() if opt.place else None, plan.d_off, S, d_quat, d_trans, 1 if opt.floor else 0,
@@ -547,8 +660,8 @@ def _per_sequence(opt, plan, bones, placed, d_floor):
 
 @torch.no_grad()
 def _lift_sequences(model, poses_2d, **options):
-    """``lift_sequences`` with its results by name (``_Lifted``): check options -> upload -> every sequence lifted on its own -> rigid stage ->
-    place / world / floor stage -> per-sequence lists."""
+    """``lift_sequences`` with its results by name (``_Lifted``): check options -> upload -> every sequence lifted on its own -> smoothed poses ->
+    rigid stage -> place (-> smoothed trajectories) / world / floor stage -> per-sequence lists."""
     opt = _check_options(model, poses_2d, **options)
     if not opt.seqs:
         return _Lifted([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place)))
@@ -561,6 +674,8 @@ def _lift_sequences(model, poses_2d, **options):
             _lift_one(model, opt, plan, s, model_rows)
     finally:
         model.train(was_training)
+    if opt.smooth_poses:
+        plan = _smooth_poses_stage(opt, plan)
     bones = _rigid_stage(opt, plan, model_rows) if opt.rigid else None
     placed, d_floor = _place_stage(opt, plan) if opt.place or opt.world else (None, None)
     return _per_sequence(opt, plan, bones, placed, d_floor)
@@ -568,7 +683,7 @@ def _lift_sequences(model, poses_2d, **options):
 
 def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
-                   floor=False, return_place=False):
+                   floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform"):
     """One 3-D pose per frame of every sequence.  ``poses_2d``: a list of (N_i, 17, 2) device tensors or numpy arrays (or one such
     array); returns a list of (N_i, 17, 3) device tensors, and with ``return_hyps`` also a list of (N_i, K, 17, 4) (every hypothesis
     and its score, from the un-mirrored pass).  ``stride`` (default T: non-overlapping windows) in 1..T; ``blend`` "mean" averages the
@@ -592,10 +707,22 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
     first and the camera's translation (times ``scale``, so ``traj`` and the world poses are in the poses' unit) afterwards, without it the
     rotation alone (the reference's prepare_prediction_for_viz before its floor line).  ``floor`` (needs ``frame="world"``): every sequence's
     lowest merged joint is put on z = 0, and the SAME offset is subtracted from the hypotheses - merged pose and hypotheses stand in one scene
-    (the reference floors each array on its own).  Not with ``keep_padding``: padded frames have no keypoints of their own."""
+    (the reference floors each array on its own).  Not with ``keep_padding``: padded frames have no keypoints of their own.
+
+    Smoothing in time (both off by default: nothing changes by a bit): ``smooth_poses`` and ``smooth_traj`` are radii in frames, 0..64, 0 = off;
+    ``smooth_degree`` (0..2) and ``smooth_taper`` ("uniform" | "biweight") are shared by both and need one of them (``smooth_poses()`` has the
+    rule: a least-squares polynomial over the frames within the radius, inside the sequence).  ``smooth_poses``: the merged poses and, with
+    ``return_hyps``, every hypothesis as a track over time (scores untouched) are smoothed after the merge and BEFORE the rigid stage, so bone
+    lengths stay constant and placing fits the poses that are emitted.  ``smooth_traj`` (needs ``place``): the fitted trajectories are smoothed
+    after the fit and before the world frame, with the fit's ``ok`` as validity: a frame with ok = 0 (``traj`` = 0) is filled from its valid
+    neighbours.  The place dicts then hold the smoothed ``traj`` / ``hyps_traj`` (what the world frame uses) and gain ``traj_fit`` /
+    ``hyps_traj_fit`` (the fitted values, bit for bit) and ``filled`` / ``hyps_filled`` (uint8; 0: no valid frame within the radius, the fitted
+    value is kept); ``ok`` and ``reproj`` stay what the fit reported (no reprojection error of the smoothed trajectory is computed).  Not with
+    ``keep_padding``."""
     res = _lift_sequences(model, poses_2d, stride=stride, tta=tta, agg=agg, blend=blend, return_hyps=return_hyps, batch=batch, scale=scale,
                           keep_padding=keep_padding, rigid=rigid, lengths=lengths, symmetric=symmetric, return_bones=return_bones, cameras=cameras,
-                          place=place, frame=frame, floor=floor, return_place=return_place)
+                          place=place, frame=frame, floor=floor, return_place=return_place, smooth_poses=smooth_poses, smooth_traj=smooth_traj,
+                          smooth_degree=smooth_degree, smooth_taper=smooth_taper)
     asked = [r for r in res if r is not None]                # in the order poses, hyps, bones, place
     return asked[0] if len(asked) == 1 else tuple(asked)
 
@@ -611,5 +738,6 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
     return torch.cat(res.hyps if hyps else res.poses, dim=0).cpu().numpy()
 
 
-__all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "to_world", "lift_sequences",
+__all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "to_world", "smooth_poses", "smooth_traj",
+           "lift_sequences",
            "lift_action"]

@@ -6,7 +6,10 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py [W=158] [T=243] [K=5] [precision=bf16x3] [reps=50]
     python tools/lift_bench.py --place [frames=3000] [K=5] [reps=50]
 --place times only the two kernels that put a lifted sequence in the scene (mp_lift_place: root translation and reprojection error of every
-hypothesis; mp_lift_world: world frame, with and without the floor) on `frames` frames x K hypotheses of one sequence with S11's first camera."""
+hypothesis; mp_lift_world: world frame, with and without the floor) on `frames` frames x K hypotheses of one sequence with S11's first camera,
+and then, in the same process, mp_lift_smooth (radius 4 and 32, degree 2, uniform) on the merged poses (frames, 17, 3), the hypotheses
+(frames, K, 17, 4) and the trajectories (frames, K, 3) next to its yardstick mp_lift_rigid on the same arrays (which reads and writes the same
+bytes once; it needs 2 joints, so the trajectory has none): both times, their ratio and the bytes/s of "read once, write once"."""
 import os
 import sys
 
@@ -58,6 +61,29 @@ def place_bench(argv):
                      ("mp_lift_world + floor (3 kernels)", lambda: to_world(work, quat, trans, traj, floor=True))):
         us = timed_us(fn, reps)            # (the public functions: their table uploads are inside the time)
         print(f"{name}: {us:,.1f} us  {frames * K / us:,.2f} M poses/s", flush=True)
+    smooth_bench(hyps, traj, reps)
+
+
+def smooth_bench(hyps, traj, reps):
+    """mp_lift_smooth and mp_lift_rigid through their private launchers on tables uploaded once: kernel against kernel"""
+    from manipose_amd import _lib
+    from manipose_amd.lifting import _parents_c, _rigid, _skeleton_of, _smooth
+    lib, dev, frames = _lib.load(), hyps.device, int(hyps.shape[0])
+    d_off = torch.tensor([0, frames], dtype=torch.int64, device=dev)
+    lengths = torch.full((1, 16), 0.25, device=dev)
+    parents = _parents_c(_skeleton_of(), 17)
+    merged = hyps[:, :1, :, :3].contiguous()                              # (frames, 1, 17, 3)
+    arrays = (("poses", merged), ("hypotheses", hyps.clone()), ("trajectory", traj.reshape(frames, -1, 1, 3).contiguous()))
+    print(f"mp_lift_smooth (degree 2, uniform) against mp_lift_rigid on the same arrays, {reps} launches each after 5 of warm-up:", flush=True)
+    for name, x in arrays:
+        moved = 2 * x.numel() * 4                                         # read once, write once
+        rigid_us = timed_us(lambda: _rigid(lib, x, d_off, 1, lengths, parents), reps) if x.shape[2] >= 2 else None
+        for R in (4, 32):
+            us = timed_us(lambda: _smooth(lib, x, None, d_off, 1, R, 2, "uniform"), reps)
+            against = f"mp_lift_rigid {rigid_us:,.1f} us ({moved / rigid_us / 1e3:,.1f} GB/s), ratio {us / rigid_us:.2f}" if rigid_us else \
+                "mp_lift_rigid needs 2 joints: no yardstick"
+            print(f"mp_lift_smooth {name} {tuple(x.shape)} R={R}: {us:,.1f} us  {moved / us / 1e3:,.1f} GB/s of the {moved / 1e6:.2f} MB read once + written once; "
+                  f"{against}", flush=True)
 
 
 if "--place" in sys.argv:
