@@ -221,6 +221,39 @@ int mp_layernorm_bwd2_ex(const void* dy1, int dy_bf16, const float* stats1, cons
                          float* scratch, int64_t scratch_floats, void* param_stream, void* stream);
 int mp_scale_rows_ex(const float* g, const float* mask, int mask_mode, void* out, int out_bf16, int M, int C, int T, int J, void* stream);
 
+/* The kernels at the two ends of the network, each through the engine's own launcher, all fp32.  Bad arguments (null pointers, non-positive
+ * dimensions, the limits named below, short scratch): MP_ERR_ARG before any launch.  Every gradient of a parameter is ACCUMULATED into.
+ * Input embedding of the rotation backbone (mix_ste.py:134-138): out[m][c] = W[c][0] x[m][0] + W[c][1] x[m][1] + b[c] + spos[m % J][c];
+ *   x [M][2], W [C][2], b [C], spos [J][C], out [M][C]; C % 4 == 0.  Backward: dW += g^T x, db += colsum(g), dspos[j] += sum of the rows m with
+ *   m % J == j, over the M / J WHOLE frames only: rows past the last whole frame (M % J != 0) enter no sum.  J == 17 with C % 4 == 0 and M % 17 == 0
+ *   runs the four-channel kernel, everything else the channel-per-thread kernel.  scratch: mp_embed_bwd_scratch_floats(C, J).
+ * Input embedding of the bones net (manifold_mix_ste.py:133-150): out[f][o] = sum_i W[o][i] x[f][i] + b[o] + spos[o], IN == 34;
+ *   x [BT][34], W [O][34], b, spos [O], out [BT][O].  Backward: dW += g^T x, db += colsum(g), dspos += colsum(g);
+ *   scratch >= (min(32, BT) + 1) * O * 35 floats.
+ * mp_tpos_grad_ex: dtpos[t][c] += sum_{b,j} g[((b T + t) J + j)][c]; g [B T J][C], dtpos [T][C]; C % 4 == 0 and J >= 4 (the kernel walks the
+ *   (b, j) rows of a frame four at a time; a smaller J is refused, dtpos untouched). */
+int mp_embed_fwd_ex(const float* x, const float* W, const float* b, const float* spos, float* out, int M, int C, int J, void* stream);
+int64_t mp_embed_bwd_scratch_floats(int C, int J);
+int mp_embed_bwd_ex(const float* g, const float* x, float* dW, float* db, float* dspos, int M, int C, int J, float* scratch, int64_t scratch_floats,
+                    void* stream);
+int mp_bones_embed_fwd_ex(const float* x, const float* W, const float* b, const float* spos, float* out, int BT, int IN, int O, void* stream);
+int mp_bones_embed_bwd_ex(const float* g, const float* x, float* dW, float* db, float* dspos, int BT, int IN, int O, float* scratch,
+                          int64_t scratch_floats, void* stream);
+int mp_tpos_grad_ex(const float* g, float* dtpos, int B, int T, int J, int C, void* stream);
+/* Score head (rmcl_manifold_mix_ste.py:291-298): logit[b][k][t] = sum_j w[k][j] headout[k][(b T + t) J + j][O - 1] + b[k], scores = softmax over k;
+ *   headout [K][B T J][O], packed w [K][J], b [K], scores [B][K][T]; 1 <= K <= 8, 1 <= J <= 32.  Backward: dlogit = s (ds - sum_k s ds); channel
+ *   O - 1 of dheadout is WRITTEN with dlogit w[k][j] (the other channels are not touched), dw[k][j] += sum_f dlogit emb, db[k] += sum_f dlogit;
+ *   scratch: mp_scores_bwd_scratch_floats(K, B, T).  param_stream (may be NULL): the two parameter-gradient kernels run there, behind an event
+ *   this call creates and destroys (the caller keeps scratch until that stream has run).
+ * Bone lengths (manifold_mix_ste.py:154): lengths[b][s] = mean_t headout[(b T + t) S + s].  Backward: dlengths[b][s] (may be NULL; WRITTEN) = the
+ *   sum over the KT decoded poses of window b of dlen_pose[(b KT + i) S + s], dheadout[(b T + t) S + s] = that sum / T; 1 <= S <= 32. */
+int mp_scores_fwd_ex(const float* headout, const float* w, const float* b, int K, int O, float* scores, int B, int T, int J, void* stream);
+int64_t mp_scores_bwd_scratch_floats(int K, int B, int T);
+int mp_scores_bwd_ex(const float* headout, const float* scores, const float* d_scores, const float* w, const float* b, float* dw, float* db, int K,
+                     int O, float* d_headout, int B, int T, int J, float* scratch, int64_t scratch_floats, void* param_stream, void* stream);
+int mp_bones_mean_fwd_ex(const float* headout, float* lengths, int B, int T, int S, void* stream);
+int mp_bones_mean_bwd_ex(const float* d_len_pose, int KT, float* d_lengths, float* d_headout, int B, int T, int S, void* stream);
+
 /* K output heads, head k = LayerNorm(C, eps 1e-5) -> Linear(C, O)  (MCLHead stack, rmcl_manifold_mix_ste.py:291-298; MixSTE.head,
  * mix_ste.py:123-126), all fp32.  Packed parameters: gamma, beta [K][C]; W [K][O][C]; b [K][O].  out [K][M][O]; stats [M][2] (mean, rstd
  * of x, shared by the heads) and fold (mp_heads_fold_floats(C) floats: the LayerNorm affine folded into the weights) are written by the

@@ -80,6 +80,17 @@ _SIGNATURES = {
     "mp_layernorm_bwd_ex": (i32, [vp, i32, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, i64, vp, vp]),
     "mp_layernorm_bwd2_ex": (i32, [vp, i32, vp, vp, vp, f32] + [vp] * 7 + [i32] * 3 + [vp, i32, i32] + [vp] * 4 + [i32, i32, vp, i64, vp, vp]),
     "mp_scale_rows_ex": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "mp_embed_fwd_ex": (i32, [vp] * 5 + [i32] * 3 + [vp]),
+    "mp_embed_bwd_scratch_floats": (i64, [i32, i32]),
+    "mp_embed_bwd_ex": (i32, [vp] * 5 + [i32] * 3 + [vp, i64, vp]),
+    "mp_bones_embed_fwd_ex": (i32, [vp] * 5 + [i32] * 3 + [vp]),
+    "mp_bones_embed_bwd_ex": (i32, [vp] * 5 + [i32] * 3 + [vp, i64, vp]),
+    "mp_tpos_grad_ex": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "mp_scores_fwd_ex": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp]),
+    "mp_scores_bwd_scratch_floats": (i64, [i32, i32, i32]),
+    "mp_scores_bwd_ex": (i32, [vp] * 7 + [i32, i32, vp, i32, i32, i32, vp, i64, vp, vp]),
+    "mp_bones_mean_fwd_ex": (i32, [vp, vp, i32, i32, i32, vp]),
+    "mp_bones_mean_bwd_ex": (i32, [vp, i32, vp, vp, i32, i32, i32, vp]),
     "mp_model_create": (i32, [C.POINTER(ModelConfig), C.POINTER(vp)]),
     "mp_model_destroy": (None, [vp]),
     "mp_model_workspace_bytes": (i64, [vp]),

@@ -378,6 +378,80 @@ int mp_scale_rows_ex(const float* g, const float* mask, int mask_mode, void* out
   return scale_rows(g, mask, mask_mode, out, out_bf16, M, C, T, J, (hipStream_t)stream);
 }
 
+/* unit-test entry points of the kernels at the two ends of the network (include/manipose_hip.h): the launchers' unstated limits are checked
+ * here, everything else is the engine's call */
+int mp_embed_fwd_ex(const float* x, const float* W, const float* b, const float* spos, float* out, int M, int C, int J, void* stream) {
+  MP_CHECK(x && W && b && spos && out, MP_ERR_ARG, "mp_embed_fwd_ex: null pointer");
+  MP_CHECK(M > 0 && J > 0 && C > 0 && C % 4 == 0, MP_ERR_ARG, "mp_embed_fwd_ex: M=%d C=%d J=%d unsupported (positive, C %% 4 == 0)", M, C, J);
+  return embed_fwd(x, W, b, spos, out, M, C, J, (hipStream_t)stream);
+}
+int64_t mp_embed_bwd_scratch_floats(int C, int J) { return (C > 0 && J > 0) ? (int64_t)embed_bwd_scratch_floats(C, J) : 0; }
+/* M % J != 0: the launcher takes the channel-per-thread kernel (also for J == 17) and sums the M / J whole frames only */
+int mp_embed_bwd_ex(const float* g, const float* x, float* dW, float* db, float* dspos, int M, int C, int J, float* scratch, int64_t scratch_floats,
+                    void* stream) {
+  MP_CHECK(g && x && dW && db && dspos && scratch, MP_ERR_ARG, "mp_embed_bwd_ex: null pointer");
+  MP_CHECK(M > 0 && J > 0 && C > 0 && C % 4 == 0, MP_ERR_ARG, "mp_embed_bwd_ex: M=%d C=%d J=%d unsupported (positive, C %% 4 == 0)", M, C, J);
+  MP_CHECK(scratch_floats >= embed_bwd_scratch_floats(C, J), MP_ERR_ARG, "mp_embed_bwd_ex: scratch needs mp_embed_bwd_scratch_floats(C, J) floats");
+  return embed_bwd(g, x, dW, db, dspos, M, C, J, scratch, (long)scratch_floats, (hipStream_t)stream);
+}
+int mp_bones_embed_fwd_ex(const float* x, const float* W, const float* b, const float* spos, float* out, int BT, int IN, int O, void* stream) {
+  MP_CHECK(x && W && b && spos && out, MP_ERR_ARG, "mp_bones_embed_fwd_ex: null pointer");
+  MP_CHECK(BT > 0 && O > 0 && IN == 34, MP_ERR_ARG, "mp_bones_embed_fwd_ex: BT=%d IN=%d O=%d unsupported (positive, IN == 34)", BT, IN, O);
+  return bones_embed_fwd(x, W, b, spos, out, BT, IN, O, (hipStream_t)stream);
+}
+int mp_bones_embed_bwd_ex(const float* g, const float* x, float* dW, float* db, float* dspos, int BT, int IN, int O, float* scratch,
+                          int64_t scratch_floats, void* stream) {
+  MP_CHECK(g && x && dW && db && dspos && scratch, MP_ERR_ARG, "mp_bones_embed_bwd_ex: null pointer");
+  MP_CHECK(BT > 0 && O > 0 && IN == 34, MP_ERR_ARG, "mp_bones_embed_bwd_ex: BT=%d IN=%d O=%d unsupported (positive, IN == 34)", BT, IN, O);
+  MP_CHECK(scratch_floats >= (int64_t)((BT < 32 ? BT : 32) + 1) * O * 35, MP_ERR_ARG, "mp_bones_embed_bwd_ex: scratch needs (min(32, BT) + 1) * O * 35 floats");
+  return bones_embed_bwd(g, x, dW, db, dspos, BT, IN, O, scratch, (long)scratch_floats, (hipStream_t)stream);
+}
+int mp_tpos_grad_ex(const float* g, float* dtpos, int B, int T, int J, int C, void* stream) {
+  MP_CHECK(g && dtpos, MP_ERR_ARG, "mp_tpos_grad_ex: null pointer");
+  MP_CHECK(B > 0 && T > 0 && J > 0 && C > 0, MP_ERR_ARG, "mp_tpos_grad_ex: B=%d T=%d J=%d C=%d must be positive", B, T, J, C);
+  return tpos_grad(g, dtpos, B, T, J, C, (hipStream_t)stream);      // refuses C % 4 != 0 and J < 4 itself
+}
+
+static int score_dims(const char* who, int K, int O, int B, int T, int J) {
+  MP_CHECK(K >= 1 && K <= 8 && J >= 1 && J <= 32, MP_ERR_ARG, "%s: K=%d J=%d unsupported (1 <= K <= 8, 1 <= J <= 32)", who, K, J);
+  MP_CHECK(O > 0 && B > 0 && T > 0, MP_ERR_ARG, "%s: O=%d B=%d T=%d must be positive", who, O, B, T);
+  return MP_OK;
+}
+int mp_scores_fwd_ex(const float* headout, const float* w, const float* b, int K, int O, float* scores, int B, int T, int J, void* stream) {
+  MP_CHECK(headout && w && b && scores, MP_ERR_ARG, "mp_scores_fwd_ex: null pointer");
+  if (int rc = score_dims("mp_scores_fwd_ex", K, O, B, T, J)) return rc;
+  ScoreParams p = {};
+  for (int k = 0; k < K; ++k) { p.w[k] = w + (long)k * J; p.b[k] = b + k; }
+  return scores_fwd(headout, p, K, O, scores, B, T, J, (hipStream_t)stream);
+}
+int64_t mp_scores_bwd_scratch_floats(int K, int B, int T) { return (K > 0 && B > 0 && T > 0) ? (int64_t)scores_bwd_scratch_floats(K, B, T) : 0; }
+int mp_scores_bwd_ex(const float* headout, const float* scores, const float* d_scores, const float* w, const float* b, float* dw, float* db, int K,
+                     int O, float* d_headout, int B, int T, int J, float* scratch, int64_t scratch_floats, void* param_stream, void* stream) {
+  MP_CHECK(headout && scores && d_scores && w && b && dw && db && d_headout && scratch, MP_ERR_ARG, "mp_scores_bwd_ex: null pointer");
+  if (int rc = score_dims("mp_scores_bwd_ex", K, O, B, T, J)) return rc;
+  MP_CHECK(scratch_floats >= scores_bwd_scratch_floats(K, B, T), MP_ERR_ARG, "mp_scores_bwd_ex: scratch needs mp_scores_bwd_scratch_floats(K, B, T) floats");
+  ScoreParams p = {};
+  ScoreGrads gp = {};
+  for (int k = 0; k < K; ++k) { p.w[k] = w + (long)k * J; p.b[k] = b + k; gp.w[k] = dw + (long)k * J; gp.b[k] = db + k; }
+  hipEvent_t ev = nullptr;
+  if (param_stream != nullptr) MP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  const int rc = scores_bwd(headout, scores, d_scores, p, gp, K, O, d_headout, B, T, J, scratch, (long)scratch_floats, (hipStream_t)stream,
+                            (hipStream_t)param_stream, ev);
+  if (ev != nullptr) (void)hipEventDestroy(ev);      // the wait already enqueued on param_stream keeps what it needs
+  return rc;
+}
+int mp_bones_mean_fwd_ex(const float* headout, float* lengths, int B, int T, int S, void* stream) {
+  MP_CHECK(headout && lengths, MP_ERR_ARG, "mp_bones_mean_fwd_ex: null pointer");
+  MP_CHECK(B > 0 && T > 0 && S >= 1 && S <= 32, MP_ERR_ARG, "mp_bones_mean_fwd_ex: B=%d T=%d S=%d unsupported (positive, S <= 32)", B, T, S);
+  return bones_mean_fwd(headout, lengths, B, T, S, (hipStream_t)stream);
+}
+int mp_bones_mean_bwd_ex(const float* d_len_pose, int KT, float* d_lengths, float* d_headout, int B, int T, int S, void* stream) {
+  MP_CHECK(d_len_pose && d_headout, MP_ERR_ARG, "mp_bones_mean_bwd_ex: null pointer");
+  MP_CHECK(B > 0 && T > 0 && KT > 0 && S >= 1 && S <= 32, MP_ERR_ARG, "mp_bones_mean_bwd_ex: B=%d T=%d KT=%d S=%d unsupported (positive, S <= 32)", B, T,
+           KT, S);
+  return bones_mean_bwd(d_len_pose, KT, d_lengths, d_headout, B, T, S, (hipStream_t)stream);
+}
+
 static int heads_pick(int impl, int K, int O, int C, const char* who, bool* mfma) {
   MP_CHECK(impl >= 0 && impl <= 2, MP_ERR_ARG, "%s: impl %d", who, impl);
   MP_CHECK(K >= 1 && K <= 8 && O >= 1, MP_ERR_ARG, "%s: K=%d O=%d unsupported", who, K, O);

@@ -858,6 +858,7 @@ __global__ __launch_bounds__(256) void tpos_grad_kernel(const float* __restrict_
 
 int tpos_grad(const float* g, float* dtpos, int B, int T, int J, int C, hipStream_t st) {
   MP_CHECK(C % 4 == 0, MP_ERR_ARG, "tpos_grad: C %% 4");
+  MP_CHECK(J >= 4, MP_ERR_ARG, "tpos_grad: J=%d < 4 (the kernel walks the (b, j) rows of a frame four at a time)", J);
   hipLaunchKernelGGL(tpos_grad_kernel, dim3(T, cdiv(C, 256)), dim3(256), 0, st, g, dtpos, B, T, J, C);
   MP_LAUNCH_CHECK();
   return MP_OK;
