@@ -272,7 +272,7 @@ def sk_device(model):
 
 
 LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj", "__hyps_reproj", "__hyps_ok", "__floor", "__cam", "__traj_fit", "__filled",
-                 "__hyps_traj_fit", "__hyps_filled")
+                 "__hyps_traj_fit", "__hyps_filled", "__path", "__path_cost")
 
 
 def lift_place_options(cfg):
@@ -308,6 +308,32 @@ def lift_smooth_options(cfg):
     return radii[0], radii[1], degree, taper
 
 
+def lift_path_options(cfg):
+    """(agg, path_sigma, path_switch) of lift.agg / lift.path_sigma / lift.path_switch; ValueError for a value or a combination that cannot run -
+    before any model is built."""
+    agg = str(cfg.lift.get("agg", "weighted_ave"))
+    sigma, switch = cfg.lift.get("path_sigma", 0.02), cfg.lift.get("path_switch", 0.0)
+    if agg not in ("weighted_ave", "best_score", "path"):
+        raise ValueError(f"lift.agg must be weighted_ave, best_score or path, got {agg!r}")
+    for key, v in (("path_sigma", sigma), ("path_switch", switch)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"lift.{key} is a number, got {v!r}")
+    if not sigma > 0:
+        raise ValueError(f"lift.path_sigma must be > 0 (metres), got {sigma!r}")
+    if not 0 <= switch < float("inf"):
+        raise ValueError(f"lift.path_switch must be finite and >= 0, got {switch!r}")
+    if agg != "path":
+        if sigma != 0.02 or switch != 0.0:
+            raise ValueError("lift.path_sigma / lift.path_switch describe the hypothesis path: set lift.agg=path")
+        return agg, float(sigma), float(switch)
+    if bool(cfg.train.tta):
+        raise ValueError("lift.agg=path with train.tta=true: the path runs through the hypotheses of the un-mirrored pass, and head k of a mirrored "
+                         "input is not head k of the plain one: set train.tta=false")
+    if str(cfg.model.arch) != "rmcl_manifold" or not 2 <= int(cfg.multi_hyp.n_hyp) <= 8:
+        raise ValueError("lift.agg=path chooses among a model's hypotheses: it needs model.arch=rmcl_manifold with multi_hyp.n_hyp in 2..8")
+    return agg, float(sigma), float(switch)
+
+
 def synthetic_cameras(groups):
     """Synthetic-data mode has no calibration of its own: sequence i (in the order of ``groups``) gets camera i % 4 of subject S11 (h36m_cameras())."""
     from manipose_amd.data.ingest import h36m_cameras
@@ -329,22 +355,26 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
     lift.smooth_traj ``__traj`` / ``__hyps_traj`` are the smoothed trajectories and ``<key>__traj_fit`` (N, 3), ``<key>__filled`` (N,) uint8,
     ``<key>__hyps_traj_fit`` (N, K, 3), ``<key>__hyps_filled`` (N, K) are added) and by
     lift.frame=world (poses and hypotheses in the world frame; with lift.floor on z = 0 and ``<key>__floor``, the offset subtracted); whenever
-    cameras were used ``<key>__cam`` holds the 16 numbers (intrinsic 9, orientation 4, translation 3)."""
+    cameras were used ``<key>__cam`` holds the 16 numbers (intrinsic 9, orientation 4, translation 3).  With lift.agg=path (one of the model's
+    hypotheses per frame, chosen over the whole sequence; lift.path_sigma, lift.path_switch) also ``<key>__path`` (N,) uint8, the hypothesis of
+    every frame, and ``<key>__path_cost``, the cost of the sequence's path (a float64 scalar)."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
     out = {}
     rigid = bool(cfg.lift.get("rigid", False))
     place, world, floor = lift_place_options(cfg)
     smooth_p, smooth_t, smooth_degree, smooth_taper = lift_smooth_options(cfg)
+    agg, path_sigma, path_switch = lift_path_options(cfg)
+    path_kw = dict(path_sigma=path_sigma, path_switch=path_switch, return_path=True) if agg == "path" else {}
     use_cams = place or world
     if use_cams and cameras is None:
         raise ValueError("lift.place / lift.frame=world need the sequences' cameras")
     for name, seqs in groups.items():
-        res = _lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=cfg.lift.agg, blend=cfg.lift.blend,
+        res = _lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=agg, blend=cfg.lift.blend,
                               return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
                               symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid, cameras=cameras[name] if use_cams else None,
                               place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor,
-                              smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper)
+                              smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper, **path_kw)
         cam_rows = np.concatenate(camera_table(cameras[name]), axis=1) if use_cams else None
         for i, p in enumerate(res.poses):
             key = name if len(res.poses) == 1 else f"{name}.{i}"
@@ -358,6 +388,8 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
                     out[f"{key}__{k}"] = v.cpu().numpy()
             if cam_rows is not None:
                 out[key + "__cam"] = cam_rows[i]
+            if res.path is not None:
+                out[key + "__path"], out[key + "__path_cost"] = (v.cpu().numpy() for v in res.path[i])
     np.savez(path, **out)
     return out
 
@@ -383,6 +415,7 @@ def run(argv, extra_defaults=None):
     cfg = load_config(argv, extra_defaults)
     lift_place_options(cfg)                    # a lift.place / lift.frame / lift.floor that cannot run fails here, before the model is built
     lift_smooth_options(cfg)                   # ... and so does a lift.smooth_* that cannot run
+    lift_path_options(cfg)                     # ... and a lift.agg=path that cannot (with the default train.tta=true: set train.tta=false)
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")

@@ -535,6 +535,33 @@ int mp_lift_world(float* poses, int64_t Ntot, int inner, int J, int C, const flo
 int mp_lift_smooth(const float* in, float* out, int64_t Ntot, int inner, int M, int C, const uint8_t* valid, const int64_t* seq_offset, int S,
                    int radius, int degree, int taper, uint8_t* filled, void* stream);
 
+/* Lifting a sequence along ONE hypothesis path: per frame exactly one of the model's K hypotheses, chosen jointly over the whole sequence - the
+ * maximum a posteriori path of a hidden Markov model whose states are the hypotheses, found with the Viterbi algorithm.  Nothing is averaged (every
+ * emitted pose is one the model made, on its manifold) and nothing is chosen frame by frame (mp_lift_merge's "best_score" jumps from head to head
+ * whenever two scores cross).  The reference has no counterpart: its aggregate is per frame.
+ * hyps (Ntot, K, J, 4) device floats as mp_lift_merge emits them: xyz in the poses' unit, the hypothesis' score replicated in channel 3 (read from
+ * joint 0); 1 <= K <= 8, 2 <= J <= 32; seq_offset (S + 1) device int64 as for mp_lift_rigid, its entries clamped to 0 .. Ntot.  Everything between
+ * the float32 loads and the stores is fp64.  Per sequence with frames [f0, f1):
+ *   unary cost       U[g][k] = -log(s), s the score of (g, k); a score that is not > 1e-12 (zero, negative, NaN) is taken as 1e-12;
+ *   transition cost  for g > f0, from state a at g - 1 to state b at g:
+ *                    D[g][a][b] = (1 / (2 sigma^2)) ((sum_j |x[g][b][j] - x[g-1][a][j]|^2) / J) + (a != b ? switch_cost : 0),
+ *                    the sum in joint order, then channel order; sigma > 0 in the poses' unit (+inf: the factor is exactly 0), switch_cost >= 0 and
+ *                    finite; a transition cost that is not finite (a NaN coordinate) is taken as 1e30;
+ *   forward pass     f[f0][k] = U[f0][k];  f[g][b] = min_a (f[g-1][a] + D[g][a][b]) + U[g][b], the back-pointer the FIRST (lowest) arg-min a;
+ *   end, backtrack   the last frame takes the first arg-min of f[f1-1][.], the frames before it follow the back-pointers.
+ * path (Ntot) bytes: the chosen hypothesis of every frame; out (Ntot, J, 3) or null: out[g] = hyps[g][path[g]][:, :3], copied bit for bit; cost (S)
+ * doubles or null: f at the chosen end state.  A sequence of one frame takes the first arg-min of its unary costs; an empty clamped range writes
+ * cost[s] = 0 and nothing else; a frame that no sequence's clamped range holds is not written.  hyps is not modified.
+ * scratch: at least mp_lift_path_scratch_floats(Ntot, K) floats = Ntot (8 K^2 + 9 K) bytes (D, U and the back-pointers), 8-byte aligned.  The backtrack
+ * walks the back-pointers out of LDS, MP_LIFT_PATH_CHUNK frames at a time.  No atomics, fixed order of operations: identical bits on every call, and a
+ * sequence's results do not depend on the other sequences of the call.
+ * MP_ERR_ARG before anything is launched: hyps, path, seq_offset or scratch null; K outside 1..8; J outside 2..32; Ntot or S <= 0, S > Ntot; sigma not
+ * > 0; switch_cost negative or not finite; scratch too small or misaligned.  The call does not synchronise. */
+#define MP_LIFT_PATH_CHUNK 512
+int64_t mp_lift_path_scratch_floats(int64_t Ntot, int K);
+int mp_lift_path(const float* hyps, int64_t Ntot, int K, int J, const int64_t* seq_offset, int S, float sigma, float switch_cost, uint8_t* path,
+                 float* out, double* cost, float* scratch, int64_t scratch_floats, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

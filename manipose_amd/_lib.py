@@ -126,6 +126,8 @@ _SIGNATURES = {
     "mp_lift_place": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
     "mp_lift_world": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i64, vp]),
     "mp_lift_smooth": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "mp_lift_path_scratch_floats": (i64, [i64, i32]),
+    "mp_lift_path": (i32, [vp, i64, i32, i32, vp, i32, f32, f32, vp, vp, vp, vp, i64, vp]),
     "mp_ingest_pose3d": (i32, [vp, i32, vp, i64, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(f32), i32, i32, f32, vp, vp]),
     "mp_ingest_pose2d": (i32, [vp, i32, i32, vp, i64, C.POINTER(i32), i32, f32, f32, vp, vp]),
     "mp_procrustes_errors": (i32, [vp, vp, vp, i64, i32, f32, f32, f32, f32, i32, vp, vp, i64, vp]),

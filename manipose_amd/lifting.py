@@ -24,6 +24,14 @@ poses and the hypotheses are smoothed BEFORE the rigid stage (bone lengths stay 
 emitted); the fitted root trajectories AFTER ``mp_lift_place`` and before ``mp_lift_world``, with the fit's ``ok`` as validity, so a frame whose fit
 was degenerate is filled from its neighbours.  Whether this lowers MPJPE / MPJVE on real data has not been measured (no dataset here).
 
+One hypothesis path (``agg="path"``): ``weighted_ave`` averages K poses that share their bone lengths but differ in rotation (the result lies off
+the manifold the model stays on), and ``best_score`` keeps a real hypothesis in every frame but chooses each frame on its own, so the sequence jumps
+from head to head whenever two scores cross.  ``mp_lift_path`` emits exactly one of the model's own hypotheses per frame, chosen jointly over the
+whole sequence: the most probable path of a hidden Markov model whose states are the hypotheses (unary cost -log score, transition cost the mean
+squared joint step over 2 sigma^2 plus a cost per switch), found with the Viterbi algorithm (include/manipose_hip.h has the rule).  It runs right
+after the merge, on the hypotheses of the un-mirrored pass, and every later stage starts from the selected poses.  Whether it lowers MPJPE / MPJVE
+on real data has not been measured (no dataset here), and the default sigma is not tuned.
+
 Scheduling: a sequence is lifted on its own - its windows are cut into forwards of ``batch`` (``2 * batch`` with TTA), all of them
 stay resident until the sequence is merged, and no forward mixes two sequences.  A frame's covering windows are therefore always
 resident when it is merged (no partial sum is ever carried), and a sequence's result does not depend on what else is lifted with
@@ -31,7 +39,7 @@ it: the engine's GEMM tile plan depends on the batch, so a window's bits do.
 
 Structure: ``lift_sequences`` is a chain of private stages - ``_check_options`` (every argument error, then an immutable record of resolved
 options), ``_upload`` (keypoints, window tables, offsets and output buffers, once), ``_lift_one`` per sequence (forwards and ONE merge),
-``_smooth_poses_stage``, ``_rigid_stage``, ``_place_stage`` (with ``_smooth_traj_stage`` between its fit and its world transform), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place.  The
+``_path_stage``, ``_smooth_poses_stage``, ``_rigid_stage``, ``_place_stage`` (with ``_smooth_traj_stage`` between its fit and its world transform), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place, path.  The
 public function turns the record into its documented list / tuple in one place; ``lift_action`` and hpe/_entry.py read the fields by name.
 """
 from __future__ import annotations
@@ -49,6 +57,8 @@ AGG = {"weighted_ave": 0, "best_score": 1}
 BLEND = {"mean": 0, "center": 1}
 TAPER = {"uniform": 0, "biweight": 1}
 SMOOTH_MAXR = 64             # MP_LIFT_SMOOTH_MAXR of include/manipose_hip.h
+PATH_MAXK = 8                # hypotheses mp_lift_path takes
+PATH_SIGMA, PATH_SWITCH = 0.02, 0.0      # defaults of agg="path": the step's standard deviation in metres (not tuned), the cost of a switch
 
 
 def plan_windows(lengths: Sequence[int], T: int, stride: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -260,6 +270,61 @@ def smooth_traj(traj, ok=None, seq_offset=None, radius=4, degree=2, taper="unifo
     return out.view(traj.shape), filled.view(traj.shape[:-1])
 
 
+def _path_options(sigma, switch_cost, names=("sigma", "switch_cost")):
+    for v in (sigma, switch_cost):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{names[0]} and {names[1]} are numbers, got {v!r}")
+    if not float(np.float32(sigma)) > 0:                     # (as the kernel takes it: a float32; +inf is allowed)
+        raise ValueError(f"{names[0]} must be > 0 (inf: the step costs nothing), got {sigma!r}")
+    if not 0 <= float(switch_cost) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"{names[1]} must be finite and >= 0, got {switch_cost!r}")
+
+
+def _hyps4_shape(hyps):
+    if hyps.dim() != 4 or hyps.shape[3] != 4 or hyps.dtype != torch.float32 or not hyps.is_contiguous():
+        raise ValueError(f"hyps must be contiguous float32 (Ntot, K, J, 4), got {tuple(hyps.shape)} {hyps.dtype}")
+    if not 1 <= int(hyps.shape[1]) <= PATH_MAXK:
+        raise ValueError(f"hyps have {int(hyps.shape[1])} hypotheses: 1..{PATH_MAXK} expected")
+    if not 2 <= int(hyps.shape[2]) <= 32:
+        raise ValueError(f"hyps have {int(hyps.shape[2])} joints: 2..32 expected")
+    return hyps
+
+
+def _path(lib, hyps, d_off, S, sigma, switch_cost):
+    """``mp_lift_path`` on hyps (Ntot, K, J, 4): (poses (Ntot, J, 3), path (Ntot,) uint8, cost (S,) float64), new tensors"""
+    ntot, K, J, _ = (int(v) for v in hyps.shape)
+    dev = hyps.device
+    out = torch.empty(ntot, J, 3, dtype=torch.float32, device=dev)
+    path = torch.empty(ntot, dtype=torch.uint8, device=dev)
+    cost = torch.zeros(S, dtype=torch.float64, device=dev)
+    if ntot > 0:
+        n = int(lib.mp_lift_path_scratch_floats(ntot, K))
+        scratch = torch.empty(n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_path(_lib.ptr(hyps), ntot, K, J, _lib.ptr(d_off), S, float(sigma), float(switch_cost), _lib.ptr(path), _lib.ptr(out),
+                                        _lib.ptr(cost), _lib.ptr(scratch), n, _lib.stream_ptr()), "mp_lift_path")
+    return out, path, cost
+
+
+def select_path(hyps, seq_offset=None, sigma=PATH_SIGMA, switch_cost=PATH_SWITCH):
+    """``mp_lift_path`` on a device tensor: hyps (Ntot, K, J, 4) float32 as ``lift_sequences(return_hyps=True)`` returns them (xyz, and the
+    hypothesis' score in channel 3), K in 1..8 -> ``(poses (Ntot, J, 3), path (Ntot,) uint8, cost (S,) float64)``, new device tensors: per frame
+    exactly one hypothesis, poses[g] = hyps[g, path[g], :, :3] bit for bit, the path being the cheapest one through the sequence under the unary cost
+    -log(score) (a score that is not > 1e-12 counts as 1e-12) and, from hypothesis a of a frame to hypothesis b of the next, the transition cost
+    mean_j |x_b[j] - x_a[j]|^2 / (2 sigma^2) + (switch_cost if a != b): the maximum a posteriori path of that hidden Markov model, by the Viterbi
+    algorithm in fp64, ties to the lowest index.  ``sigma`` > 0 in the unit of the hypotheses (inf: steps cost nothing, and with switch_cost = 0 the
+    path is the best score of every frame); ``switch_cost`` >= 0.  ``seq_offset`` (S + 1): first frame of every sequence, HOST table or device int64
+    tensor (default: one sequence); a path never crosses a sequence boundary, and a frame that no sequence of the table holds is left unwritten.  ``cost``: the cost of each sequence's path.  hyps is not modified;
+    identical bits on every call."""
+    _path_options(sigma, switch_cost)
+    if torch.is_tensor(hyps):
+        _hyps4_shape(hyps)                               # (the ValueErrors come before the refusal of a CPU tensor)
+    if not torch.is_tensor(hyps) or not hyps.is_cuda:
+        raise RuntimeError("manipose_amd: select_path takes device tensors; there is no CPU fallback")
+    d_off, S = _seq_table(seq_offset, int(hyps.shape[0]), hyps.device)
+    return _path(_lib.load(), hyps, d_off, S, sigma, switch_cost)
+
+
 FLOOR_SHARES = 16            # MP_LIFT_WORLD_SHARES of include/manipose_hip.h: partial minima per sequence in mp_lift_world's scratch
 
 
@@ -408,9 +473,11 @@ def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirr
 # What a lift was asked for, checked and resolved by _check_options; no stage after it validates anything.  seqs: the 2-D sequences;
 # cam_tables: camera_table(cameras) with place / world; lengths: "model", "measured" or "table" with rigid, and table: the caller's checked
 # (S, J - 1) one; skeleton, parents: the model's, with rigid; windows: plan_windows' (win_seq, win_start)
-# smooth_poses, smooth_traj: the two radii (0: off), smooth_degree, smooth_taper: shared by both
+# smooth_poses, smooth_traj: the two radii (0: off), smooth_degree, smooth_taper: shared by both; agg: "path" included, path_sigma (metres),
+# path_switch, return_path: its options
 _Options = namedtuple("_Options", "seqs tta agg blend scale return_hyps keep_padding rigid symmetric return_bones place world floor return_place "
-                                  "smooth_poses smooth_traj smooth_degree smooth_taper cam_tables T J K lengths table skeleton parents windows batch dev", defaults=(None,) * 11)
+                                  "smooth_poses smooth_traj smooth_degree smooth_taper path_sigma path_switch return_path cam_tables T J K lengths table skeleton parents "
+                                  "windows batch dev", defaults=(None,) * 11)
 # Everything the kernels of a lift read, uploaded once by _upload, and the buffers they write.  p2: (sum N_i, J, 2) keypoints of all sequences,
 # lens: N_i; out_lens: frames emitted per sequence (whole windows with keep_padding), out_off: their (S + 1) offsets in out_all (., J, 3) and
 # hyp_all (., K, J, 4); first: (S + 1) first window of every sequence; merge_off (S, 2), h_zero / d_zero: the offsets (0, out_lens[s]) and the
@@ -418,12 +485,13 @@ _Options = namedtuple("_Options", "seqs tta agg blend scale return_hyps keep_pad
 _Plan = namedtuple("_Plan", "p2 lens out_lens out_off first win_start merge_off h_zero d_off d_merge_off d_seq d_start d_zero d_flip mirror "
                             "bone_mirror out_all hyp_all")
 # Per-sequence lists of what a lift returns; a field that was not asked for is None
-_Lifted = namedtuple("_Lifted", "poses hyps bones place", defaults=(None,) * 3)
+_Lifted = namedtuple("_Lifted", "poses hyps bones place path", defaults=(None,) * 4)
 
 
 def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
-                   floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform"):
+                   floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform", path_sigma=PATH_SIGMA,
+                   path_switch=PATH_SWITCH, return_path=False):
     """Every argument error of ``lift_sequences``, in a fixed order and before anything touches a device: the ValueErrors first, the "no CPU
     fallback" RuntimeErrors last.  No sequences: the record ends after ``return_place``."""
     if not rigid and (lengths is not None or symmetric or return_bones):
@@ -457,10 +525,20 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
         raise ValueError("smooth_traj smooths the trajectory that place=True fits: pass place=True")
     if smoothing and keep_padding:
         raise ValueError("smooth_poses / smooth_traj with keep_padding=True: padded frames repeat the last frame and would enter the fits")
+    if agg == "path":
+        _path_options(path_sigma, path_switch, ("path_sigma", "path_switch"))
+        if tta:
+            raise ValueError("agg='path' with tta=True: the path runs through the hypotheses of the un-mirrored pass, and head k of a mirrored input "
+                             "is not head k of the plain one, so the mirrored pass has nothing to add to them: pass tta=False")
+        if keep_padding:
+            raise ValueError("agg='path' with keep_padding=True: padded frames repeat the last frame and would enter the path")
+    elif return_path or isinstance(path_sigma, bool) or isinstance(path_switch, bool) or path_sigma != PATH_SIGMA or path_switch != PATH_SWITCH:
+        raise ValueError("path_sigma, path_switch and return_path describe the hypothesis path: pass agg='path'")
     single = torch.is_tensor(poses_2d) or isinstance(poses_2d, np.ndarray)
     seqs = [poses_2d] if single else list(poses_2d)
     opt = _Options(seqs, tta, agg, blend, scale, bool(return_hyps), keep_padding, rigid, symmetric, bool(return_bones), place, world, floor,
-                   bool(return_place), int(smooth_poses), int(smooth_traj), int(smooth_degree), smooth_taper)
+                   bool(return_place), int(smooth_poses), int(smooth_traj), int(smooth_degree), smooth_taper, float(path_sigma), float(path_switch),
+                   bool(return_path))
     if not seqs:
         return opt
     cam_tables = None
@@ -469,6 +547,8 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
         if cam_tables[0].shape[0] != len(seqs):
             raise ValueError(f"cameras: {cam_tables[0].shape[0]} cameras for {len(seqs)} sequences")
     T, J, K = _model_shape(model)
+    if agg == "path" and not 2 <= K <= PATH_MAXK:
+        raise ValueError(f"agg='path' chooses among a model's hypotheses: this model has {K} (2..{PATH_MAXK} expected)")
     table = sk = parents = None
     if rigid:
         mixste = getattr(model, "_arch", None) == "mixste"
@@ -484,8 +564,8 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
         sk = _skeleton_of(model)
         parents = _parents_c(sk, J)
     stride = T if stride is None else int(stride)
-    if agg not in AGG or blend not in BLEND:
-        raise ValueError(f"agg in {sorted(AGG)} and blend in {sorted(BLEND)} expected, got {agg!r}, {blend!r}")
+    if (agg not in AGG and agg != "path") or blend not in BLEND:
+        raise ValueError(f"agg in {sorted(AGG) + ['path']} and blend in {sorted(BLEND)} expected, got {agg!r}, {blend!r}")
     if keep_padding and stride != T:
         raise ValueError("keep_padding describes the reference's non-overlapping windows: stride must be T")
     for s in seqs:
@@ -530,7 +610,7 @@ def _upload(model, opt):
     mirror = _mirror(model, J)
     bone_mirror = torch.tensor([int(mirror[j]) - 1 for j in range(1, J)], device=dev) if opt.lengths == "model" else None
     out_all = torch.empty(sum(out_lens), J, 3, dtype=torch.float32, device=dev)
-    hyp_all = torch.empty(sum(out_lens), opt.K, J, 4, dtype=torch.float32, device=dev) if opt.return_hyps else None
+    hyp_all = torch.empty(sum(out_lens), opt.K, J, 4, dtype=torch.float32, device=dev) if opt.return_hyps or opt.agg == "path" else None
     return _Plan(p2=p2, lens=lens, out_lens=out_lens, out_off=out_off, first=first, win_start=win_start, merge_off=merge_off,
                  h_zero=np.zeros(max_nw, dtype=np.int32), d_off=d_off, d_merge_off=d_merge_off, d_seq=d_seq, d_start=d_start, d_zero=d_zero,
                  d_flip=d_flip, mirror=mirror, bone_mirror=bone_mirror, out_all=out_all, hyp_all=hyp_all)
@@ -569,10 +649,19 @@ def _lift_one(model, opt, plan, s, model_rows):
             if scores is not None:
                 buf_s[h * nw + a:h * nw + a + n] = scores[h * n:(h + 1) * n]
     o0, o1 = int(plan.out_off[s]), int(plan.out_off[s + 1])
-    merge_windows(buf_p, buf_s, plan.h_zero[:nw], plan.win_start[a0:a0 + nw], plan.merge_off[s], T=T, tta=tta, mirror=plan.mirror, agg=opt.agg,
-                  blend=opt.blend, scale=opt.scale, return_hyps=opt.return_hyps, out=plan.out_all[o0:o1],
-                  hyps=plan.hyp_all[o0:o1] if opt.return_hyps else None,
+    hyps_on = plan.hyp_all is not None               # asked for, or what agg="path" chooses from (the merged poses are then replaced: _path_stage)
+    merge_windows(buf_p, buf_s, plan.h_zero[:nw], plan.win_start[a0:a0 + nw], plan.merge_off[s], T=T, tta=tta, mirror=plan.mirror,
+                  agg="weighted_ave" if opt.agg == "path" else opt.agg, blend=opt.blend, scale=opt.scale, return_hyps=hyps_on, out=plan.out_all[o0:o1],
+                  hyps=plan.hyp_all[o0:o1] if hyps_on else None,
                   device_tables=(plan.d_zero[:nw], plan.d_start[a0:a0 + nw], plan.d_merge_off[s]))
+
+
+def _path_stage(opt, plan):
+    """``agg="path"``: ONE call chooses every sequence's path through its merged hypotheses (``path_sigma`` is in metres, the hypotheses in the
+    poses' unit); the selected poses replace the merged ones, and the hypotheses stay in the plan only if they were asked for.  Returns the plan
+    and the (path (Ntot,), cost (S,)) of all sequences.  (No padded frames here: ``d_off`` describes ``hyp_all``.)"""
+    out, path, cost = _path(_lib.load(), plan.hyp_all, plan.d_off, len(plan.lens), opt.path_sigma * float(opt.scale), opt.path_switch)
+    return plan._replace(out_all=out, hyp_all=plan.hyp_all if opt.return_hyps else None), (path, cost)
 
 
 def _smooth_poses_stage(opt, plan):
@@ -647,7 +736,7 @@ def _place_stage(opt, plan):
     return placed, d_floor
 
 
-def _per_sequence(opt, plan, bones, placed, d_floor):
+def _per_sequence(opt, plan, bones, placed, d_floor, chosen=None):
     """the buffers of all sequences cut into the per-sequence lists of ``_Lifted``"""
     info = None
     if opt.return_place:
@@ -655,16 +744,17 @@ def _per_sequence(opt, plan, bones, placed, d_floor):
         info = [dict({k: v[i] for k, v in per_seq.items()}, **({"floor": d_floor[i]} if opt.floor else {})) for i in range(len(plan.lens))]
     return _Lifted(list(torch.split(plan.out_all, plan.out_lens, dim=0)),
                    list(torch.split(plan.hyp_all, plan.out_lens, dim=0)) if opt.return_hyps else None,
-                   list(bones.unbind(0)) if opt.return_bones else None, info)
+                   list(bones.unbind(0)) if opt.return_bones else None, info,
+                   list(zip(torch.split(chosen[0], plan.out_lens, dim=0), chosen[1].unbind(0))) if opt.return_path else None)
 
 
 @torch.no_grad()
 def _lift_sequences(model, poses_2d, **options):
-    """``lift_sequences`` with its results by name (``_Lifted``): check options -> upload -> every sequence lifted on its own -> smoothed poses ->
+    """``lift_sequences`` with its results by name (``_Lifted``): check options -> upload -> every sequence lifted on its own -> hypothesis path -> smoothed poses ->
     rigid stage -> place (-> smoothed trajectories) / world / floor stage -> per-sequence lists."""
     opt = _check_options(model, poses_2d, **options)
     if not opt.seqs:
-        return _Lifted([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place)))
+        return _Lifted([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place, opt.return_path)))
     plan = _upload(model, opt)
     model_rows = []
     was_training = model.training
@@ -674,16 +764,20 @@ def _lift_sequences(model, poses_2d, **options):
             _lift_one(model, opt, plan, s, model_rows)
     finally:
         model.train(was_training)
+    chosen = None
+    if opt.agg == "path":
+        plan, chosen = _path_stage(opt, plan)
     if opt.smooth_poses:
         plan = _smooth_poses_stage(opt, plan)
     bones = _rigid_stage(opt, plan, model_rows) if opt.rigid else None
     placed, d_floor = _place_stage(opt, plan) if opt.place or opt.world else (None, None)
-    return _per_sequence(opt, plan, bones, placed, d_floor)
+    return _per_sequence(opt, plan, bones, placed, d_floor, chosen)
 
 
 def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
-                   floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform"):
+                   floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform", path_sigma=PATH_SIGMA,
+                   path_switch=PATH_SWITCH, return_path=False):
     """One 3-D pose per frame of every sequence.  ``poses_2d``: a list of (N_i, 17, 2) device tensors or numpy arrays (or one such
     array); returns a list of (N_i, 17, 3) device tensors, and with ``return_hyps`` also a list of (N_i, K, 17, 4) (every hypothesis
     and its score, from the un-mirrored pass).  ``stride`` (default T: non-overlapping windows) in 1..T; ``blend`` "mean" averages the
@@ -718,12 +812,24 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
     neighbours.  The place dicts then hold the smoothed ``traj`` / ``hyps_traj`` (what the world frame uses) and gain ``traj_fit`` /
     ``hyps_traj_fit`` (the fitted values, bit for bit) and ``filled`` / ``hyps_filled`` (uint8; 0: no valid frame within the radius, the fitted
     value is kept); ``ok`` and ``reproj`` stay what the fit reported (no reprojection error of the smoothed trajectory is computed).  Not with
-    ``keep_padding``."""
+    ``keep_padding``.
+
+    One hypothesis path (``agg="path"``; with the default ``agg`` nothing changes by a bit): instead of averaging the K hypotheses of a frame
+    ("weighted_ave": a pose off the model's manifold) or taking every frame's best score on its own ("best_score": jumps from head to head), every
+    frame gets exactly ONE of the model's hypotheses, chosen jointly over the sequence (``select_path()`` has the rule: unary cost -log score,
+    transition cost mean squared joint step / (2 ``path_sigma``^2) + ``path_switch`` per change of head, cheapest path by the Viterbi algorithm).
+    ``path_sigma`` > 0 is in metres (``scale`` multiplies it like the poses; the default 0.02 is not tuned), ``path_switch`` >= 0.  The stage runs
+    right after the merge and before ``smooth_poses``: merge -> path -> smooth poses -> rigid -> place -> smooth trajectories -> world, each later
+    stage starting from the selected poses (so bone lengths are the model's own until something smooths them).  ``return_path`` appends a list of
+    per-sequence ``(path (N,) uint8, cost)`` pairs, cost a float64 scalar tensor; the results come in the order poses, hyps, bones, place, path.
+    The hypotheses are those ``return_hyps`` returns (the un-mirrored pass), so ``tta`` must be False: head k of a mirrored input is not head k
+    of the plain one.  Needs a model of 2..8 hypotheses; not with ``keep_padding``."""
     res = _lift_sequences(model, poses_2d, stride=stride, tta=tta, agg=agg, blend=blend, return_hyps=return_hyps, batch=batch, scale=scale,
                           keep_padding=keep_padding, rigid=rigid, lengths=lengths, symmetric=symmetric, return_bones=return_bones, cameras=cameras,
                           place=place, frame=frame, floor=floor, return_place=return_place, smooth_poses=smooth_poses, smooth_traj=smooth_traj,
-                          smooth_degree=smooth_degree, smooth_taper=smooth_taper)
-    asked = [r for r in res if r is not None]                # in the order poses, hyps, bones, place
+                          smooth_degree=smooth_degree, smooth_taper=smooth_taper, path_sigma=path_sigma, path_switch=path_switch,
+                          return_path=return_path)
+    asked = [r for r in res if r is not None]                # in the order poses, hyps, bones, place, path
     return asked[0] if len(asked) == 1 else tuple(asked)
 
 
@@ -739,5 +845,5 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
 
 
 __all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "to_world", "smooth_poses", "smooth_traj",
-           "lift_sequences",
+           "select_path", "lift_sequences",
            "lift_action"]

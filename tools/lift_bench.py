@@ -5,11 +5,15 @@
 Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py [W=158] [T=243] [K=5] [precision=bf16x3] [reps=50]
     python tools/lift_bench.py --place [frames=3000] [K=5] [reps=50]
+    python tools/lift_bench.py --path [frames=3000] [K=5] [reps=50]
 --place times only the two kernels that put a lifted sequence in the scene (mp_lift_place: root translation and reprojection error of every
 hypothesis; mp_lift_world: world frame, with and without the floor) on `frames` frames x K hypotheses of one sequence with S11's first camera,
 and then, in the same process, mp_lift_smooth (radius 4 and 32, degree 2, uniform) on the merged poses (frames, 17, 3), the hypotheses
 (frames, K, 17, 4) and the trajectories (frames, K, 3) next to its yardstick mp_lift_rigid on the same arrays (which reads and writes the same
-bytes once; it needs 2 joints, so the trajectory has none): both times, their ratio and the bytes/s of "read once, write once"."""
+bytes once; it needs 2 joints, so the trajectory has none): both times, their ratio and the bytes/s of "read once, write once".
+--path times mp_lift_path (one hypothesis per frame, chosen over the whole sequence: cost, scan and gather kernels) through its private launcher
+on `frames` frames x K hypotheses of 17 joints, as ONE sequence (the scan is one wave: the serial case) and cut into 16, next to mp_lift_rigid
+on the same hypotheses."""
 import os
 import sys
 
@@ -86,6 +90,38 @@ def smooth_bench(hyps, traj, reps):
                   f"{against}", flush=True)
 
 
+def path_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.lifting import _parents_c, _path, _rigid, _skeleton_of
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    K = int(argv[1]) if len(argv) > 1 else 5
+    reps = int(argv[2]) if len(argv) > 2 else 50
+    assert torch.cuda.is_available(), "needs an MI355X"
+    lib = _lib.load()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    f = torch.arange(frames, device="cuda", dtype=torch.float32)[:, None, None, None]
+    hyps = torch.empty(frames, K, 17, 4, device="cuda")
+    hyps[..., :3] = 0.3 * torch.sin(f / 9.0 + torch.rand(1, 1, 17, 3, device="cuda", generator=g) * 6.28) \
+        + 0.03 * torch.randn(1, K, 17, 3, device="cuda", generator=g) + 0.01 * torch.randn(frames, K, 17, 3, device="cuda", generator=g)
+    hyps[..., 3] = torch.softmax(1.5 * torch.randn(frames, K, device="cuda", generator=g), dim=1)[:, :, None]
+    lengths, parents = torch.full((1, 16), 0.25, device="cuda"), _parents_c(_skeleton_of(), 17)
+    one = torch.tensor([0, frames], dtype=torch.int64, device="cuda")
+    print(f"--path: {frames} frames x {K} hypotheses, {hyps.numel() * 4 / 1e6:.2f} MB of hypotheses, scratch {frames * (8 * K * K + 9 * K) / 1e6:.2f} MB; "
+          f"{reps} calls each after 5 of warm-up (the output and scratch allocations are inside the time)", flush=True)
+    for S in (1, 16):
+        d_off = torch.linspace(0, frames, S + 1, device="cuda").round().to(torch.int64)
+        us = timed_us(lambda: _path(lib, hyps, d_off, S, 0.02, 0.0), reps)
+        path = _path(lib, hyps, d_off, S, 0.02, 0.0)[1]
+        switches = int((path[1:] != path[:-1]).sum().item())
+        print(f"mp_lift_path, {S} sequence(s): {us:,.1f} us  {frames / us:,.2f} M frames/s; {switches} switches", flush=True)
+    work = hyps.clone()
+    us = timed_us(lambda: _rigid(lib, work, one, 1, lengths, parents), reps)
+    print(f"mp_lift_rigid on the same hypotheses: {us:,.1f} us", flush=True)
+
+
+if "--path" in sys.argv:
+    path_bench([a for a in sys.argv[1:] if a != "--path"])
+    sys.exit(0)
 if "--place" in sys.argv:
     place_bench([a for a in sys.argv[1:] if a != "--place"])
     sys.exit(0)
