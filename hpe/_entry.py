@@ -334,6 +334,16 @@ def lift_path_options(cfg):
     return agg, float(sigma), float(switch)
 
 
+def lift_score_options(cfg):
+    """lift.score as a bool; ValueError for a value or a combination that cannot run - before any model is built."""
+    score = cfg.lift.get("score", False)
+    if not isinstance(score, bool):
+        raise ValueError(f"lift.score must be true or false, got {score!r}")
+    if score and not bool(cfg.run.lift):
+        raise ValueError("lift.score scores what run.lift lifts: set run.lift=true")
+    return score
+
+
 def synthetic_cameras(groups):
     """Synthetic-data mode has no calibration of its own: sequence i (in the order of ``groups``) gets camera i % 4 of subject S11 (h36m_cameras())."""
     from manipose_amd.data.ingest import h36m_cameras
@@ -345,7 +355,7 @@ def synthetic_cameras(groups):
     return cams
 
 
-def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
+def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None):
     """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
     hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
     it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
@@ -357,7 +367,9 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
     lift.frame=world (poses and hypotheses in the world frame; with lift.floor on z = 0 and ``<key>__floor``, the offset subtracted); whenever
     cameras were used ``<key>__cam`` holds the 16 numbers (intrinsic 9, orientation 4, translation 3).  With lift.agg=path (one of the model's
     hypotheses per frame, chosen over the whole sequence; lift.path_sigma, lift.path_switch) also ``<key>__path`` (N,) uint8, the hypothesis of
-    every frame, and ``<key>__path_cost``, the cost of the sequence's path (a float64 scalar)."""
+    every frame, and ``<key>__path_cost``, the cost of the sequence's path (a float64 scalar).
+    ``targets`` = {name: [ground truth (N, 17, 3) in metres per sequence]} (lift.score): every sequence is scored against it on the device and the dict
+    ``scores`` receives {key: the score dict of lift_sequences(return_score=True) as numpy values, in metres}; the .npz keeps its keys."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
     out = {}
@@ -367,6 +379,8 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
     agg, path_sigma, path_switch = lift_path_options(cfg)
     path_kw = dict(path_sigma=path_sigma, path_switch=path_switch, return_path=True) if agg == "path" else {}
     use_cams = place or world
+    score_kw = lambda name: dict(targets=targets[name], return_score=True) if targets is not None else {}
+    to_host = lambda v: {k: to_host(x) for k, x in v.items()} if isinstance(v, dict) else v.cpu().numpy()
     if use_cams and cameras is None:
         raise ValueError("lift.place / lift.frame=world need the sequences' cameras")
     for name, seqs in groups.items():
@@ -374,7 +388,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
                               return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
                               symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid, cameras=cameras[name] if use_cams else None,
                               place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor,
-                              smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper, **path_kw)
+                              smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper, **path_kw, **score_kw(name))
         cam_rows = np.concatenate(camera_table(cameras[name]), axis=1) if use_cams else None
         for i, p in enumerate(res.poses):
             key = name if len(res.poses) == 1 else f"{name}.{i}"
@@ -390,6 +404,8 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None):
                 out[key + "__cam"] = cam_rows[i]
             if res.path is not None:
                 out[key + "__path"], out[key + "__path_cost"] = (v.cpu().numpy() for v in res.path[i])
+            if res.score is not None and scores is not None:
+                scores[key] = to_host(res.score[i])
     np.savez(path, **out)
     return out
 
@@ -400,6 +416,20 @@ def synthetic_sequences_2d(cfg, seed):
     n_seq = int(cfg.data.get("synthetic_sequences", 16))
     lens = [int(cfg.data.seq_len) * 4 + 37 * (i % 5) + 11 for i in range(n_seq)]
     return {f"synthetic_{i:03d}": [np.clip(0.3 * rng.standard_normal((n, 17, 2)), -1, 1).astype(np.float32)] for i, n in enumerate(lens)}
+
+
+def synthetic_sequences_3d(cfg, seed):
+    """The 3-D side of synthetic_sequences_2d, in the form fetch() prepares ground truth (joint 0: the root's position in the camera's frame, a few
+    metres in front of it; the other joints relative to the root).  It draws from a generator stream of its own, so the 2-D sequences keep their bits."""
+    rng = np.random.default_rng([int(seed), 3])
+    n_seq = int(cfg.data.get("synthetic_sequences", 16))
+    lens = [int(cfg.data.seq_len) * 4 + 37 * (i % 5) + 11 for i in range(n_seq)]
+    out = {}
+    for i, n in enumerate(lens):
+        a = (0.3 * rng.standard_normal((n, 17, 3))).astype(np.float32)
+        a[:, 0, 2] += np.float32(4.0)
+        out[f"synthetic_{i:03d}"] = [a]
+    return out
 
 
 def save_state(model, trainer, scheduler_state, epoch, folder, tag=None):
@@ -416,6 +446,7 @@ def run(argv, extra_defaults=None):
     lift_place_options(cfg)                    # a lift.place / lift.frame / lift.floor that cannot run fails here, before the model is built
     lift_smooth_options(cfg)                   # ... and so does a lift.smooth_* that cannot run
     lift_path_options(cfg)                     # ... and a lift.agg=path that cannot (with the default train.tta=true: set train.tta=false)
+    lift_score_options(cfg)                    # ... and a lift.score without run.lift
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")
@@ -586,6 +617,16 @@ def run(argv, extra_defaults=None):
         cams = None
         if any(lift_place_options(cfg)[:2]):
             cams = seqs["test_cams"] if real else synthetic_cameras(groups)
-        lifted = lift_sequences_to_file(model, cfg, groups, path, cams)
+        targets, scores = None, {}
+        if lift_score_options(cfg):            # the 3-D ground truth beside the 2-D sequences that are lifted
+            targets = {name: sq[0] for name, sq in seqs["test"].items()} if real else synthetic_sequences_3d(cfg, cfg.run.seed)
+        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores)
         print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if not k.endswith(LIFT_SUFFIXES))} frames of {len(groups)} groups -> {path}", flush=True)
+        if targets is not None:
+            from manipose_amd import report
+            written = report.write_lift_score_report(out_dir, scores)
+            n = np.array([float(v["frames"]) for v in scores.values()])
+            mean = lambda key: 1000.0 * float(np.nansum(n * np.array([float(v[key]) for v in scores.values()])) / max(1.0, n.sum()))
+            print(f"lift score (mm, {int(n.sum())} frames of {len(scores)} sequences): mpjpe {mean('mpjpe'):.3f}, p-mpjpe {mean('p_mpjpe'):.3f}, "
+                  f"mpjve {mean('mpjve'):.3f}, accel {mean('accel'):.3f} -> {written[0]}", flush=True)
     return best_val

@@ -562,6 +562,48 @@ int64_t mp_lift_path_scratch_floats(int64_t Ntot, int K);
 int mp_lift_path(const float* hyps, int64_t Ntot, int K, int J, const int64_t* seq_offset, int S, float sigma, float switch_cost, uint8_t* path,
                  float* out, double* cost, float* scratch, int64_t scratch_floats, void* stream);
 
+/* Scoring a lift against ground truth, per sequence: what the lifting stages emit (merged, smoothed, re-assembled or selected poses, hypotheses,
+ * fitted trajectories) held against the 3-D sequences of the dataset - the sums behind MPJPE, its root mean square, the velocity and acceleration
+ * errors, P-MPJPE (the reference's p_mpjpe, hpe/mh_so3_hpe/metrics/mean_joint_errors.py:148-189), per-joint errors and bone-length statistics.  The
+ * evaluation loop (mp_pose_metrics) scores windows per batch item; this scores sequences of any length, never across a sequence boundary.
+ * pred (Ntot, inner, M, C) device floats, C = 3 or 4 (channel 3, a hypothesis' score, is not read); gt (Ntot, M, 3), shared by the inner poses of a
+ * frame; valid (Ntot, inner) bytes or null (every frame is valid); seq_offset (S + 1) device int64 as for mp_lift_rigid, its entries clamped to
+ * 0 .. Ntot; parents (M) HOST ints, parents[0] = -1 and parents before children, or null (no bone statistics); 1 <= M <= 32 (M = 1: a root
+ * trajectory); pred_scale, gt_scale finite and > 0; flags: bit 0 = root-relative, bit 1 = Procrustes (needs M >= 3).  Everything between the float32
+ * loads and the stores is fp64, without contraction into fused multiply-adds.  For one sequence with frames [f0, f1) and one inner index i:
+ *   P[g][j] = pred_scale * (double)pred, G[g][j] = gt_scale * (double)gt; with bit 0, joint 0 of the same pose is subtracted from every joint of P,
+ *   and likewise of G;
+ *   a frame is COUNTED if valid is null or non-zero there and all 3 M coordinates of P and of G are finite; a frame that is not counted contributes
+ *   to nothing, and its frame_err is -1;
+ *   e[g][j] = sqrt(|P[g][j] - G[g][j]|^2), the squares added in channel order;  frame_err[g][i] = (float)(sum_j e[g][j] / M), j in order.
+ * rows (S, inner, mp_lift_score_row_doubles(M)) doubles:
+ *   [0] counted frames   [1] sum_g sum_j e   [2] sum_g sum_j e^2
+ *   [3] pairs (g-1, g), both in the sequence and counted   [4] over them sum_j |(P[g] - P[g-1]) - (G[g] - G[g-1])|
+ *   [5] triples (g-2, g-1, g), all in the sequence and counted   [6] over them sum_j |(P[g] - 2 P[g-1] + P[g-2]) - (G[g] - 2 G[g-1] + G[g-2])|
+ *   [7] bit 1: sum_g sum_j of the error after the similarity alignment (scale, proper rotation, translation) of P[g] onto G[g], else 0: Horn's closed
+ *       form as in mp_procrustes_errors, in fp64, the cyclic Jacobi sweeps run until the off-diagonal mass is at most 2^-52 times the matrix norm
+ *       (30 sweeps at most)
+ *   [8] counted frames the alignment skipped (the centred P or the centred G has zero squared norm); they add nothing to [7]
+ *   [9, 9 + M) per joint sum_g e[g][j]
+ *   [9 + M + 3 (b - 1) + {0, 1, 2}], b = 1 .. M - 1, with L = |P[b] - P[parents[b]]| and LG likewise of G: sum L, sum L^2, sum |LG - L|; zeros with
+ *       null parents.
+ * A velocity or acceleration term never crosses a sequence boundary; a sequence whose clamped range is empty gets an all-zero row.  frame_err
+ * (Ntot, inner) floats or null; a frame that no sequence's clamped range holds is not written.
+ * Schedule: MP_LIFT_SCORE_SHARES workgroups per (sequence, inner), each on a contiguous slice of the sequence's own range (a whole number of tiles),
+ * each writing one partial row to scratch (the alignment, one lane per pose, in a kernel of its own on the same slices); a last kernel adds the shares
+ * in share order.  No atomics; the order of every sum depends on the
+ * sequence's own frames only: identical bits on every call, and a sequence scored alone has the bits it has in a call with others.
+ * scratch: at least mp_lift_score_scratch_doubles(S, inner, M) doubles = S inner MP_LIFT_SCORE_SHARES row doubles, 8-byte aligned.
+ * MP_ERR_ARG before anything is launched: pred, gt, seq_offset, rows or scratch null; C not 3 or 4; M outside 1..32; Procrustes with M < 3; Ntot,
+ * inner or S <= 0, S > Ntot; flags outside 0..3; a scale that is not finite and > 0; a parent table that breaks the order; scratch too small or
+ * misaligned.  The call does not synchronise. */
+#define MP_LIFT_SCORE_SHARES 32
+int mp_lift_score_row_doubles(int M);                    /* 9 + M + 3 (M - 1) */
+int64_t mp_lift_score_scratch_doubles(int S, int inner, int M);
+int mp_lift_score(const float* pred, int64_t Ntot, int inner, int M, int C, const float* gt, const uint8_t* valid, const int64_t* seq_offset, int S,
+                  const int32_t* parents, double pred_scale, double gt_scale, int flags, double* rows, float* frame_err, double* scratch,
+                  int64_t scratch_doubles, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

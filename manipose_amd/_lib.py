@@ -17,7 +17,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "manipose_hip.h")
 _lib: Optional[C.CDLL] = None
 ABI_VERSION = 8
 
-vp, i32, i64, f32, u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
+vp, i32, i64, f32, u64, f64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_double
 
 
 class LossConfig(C.Structure):
@@ -128,6 +128,9 @@ _SIGNATURES = {
     "mp_lift_smooth": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]),
     "mp_lift_path_scratch_floats": (i64, [i64, i32]),
     "mp_lift_path": (i32, [vp, i64, i32, i32, vp, i32, f32, f32, vp, vp, vp, vp, i64, vp]),
+    "mp_lift_score_row_doubles": (i32, [i32]),
+    "mp_lift_score_scratch_doubles": (i64, [i32, i32, i32]),
+    "mp_lift_score": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, i32, C.POINTER(i32), f64, f64, i32, vp, vp, vp, i64, vp]),
     "mp_ingest_pose3d": (i32, [vp, i32, vp, i64, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(f32), i32, i32, f32, vp, vp]),
     "mp_ingest_pose2d": (i32, [vp, i32, i32, vp, i64, C.POINTER(i32), i32, f32, f32, vp, vp]),
     "mp_procrustes_errors": (i32, [vp, vp, vp, i64, i32, f32, f32, f32, f32, i32, vp, vp, i64, vp]),

@@ -32,6 +32,11 @@ squared joint step over 2 sigma^2 plus a cost per switch), found with the Viterb
 after the merge, on the hypotheses of the un-mirrored pass, and every later stage starts from the selected poses.  Whether it lowers MPJPE / MPJVE
 on real data has not been measured (no dataset here), and the default sigma is not tuned.
 
+Scoring (``targets`` / ``return_score``, off by default): ``mp_lift_score`` holds what the stages emit against the dataset's 3-D sequences, per
+sequence and on the device - MPJPE, P-MPJPE, velocity and acceleration errors, per-joint errors, bone-length statistics, and the trajectory's error
+with ``place`` (include/manipose_hip.h has the rule; ``score_poses`` / ``score_traj`` are the stand-alone forms).  It is the instrument for the
+sentences above that say "has not been measured"; no number is claimed here.
+
 Scheduling: a sequence is lifted on its own - its windows are cut into forwards of ``batch`` (``2 * batch`` with TTA), all of them
 stay resident until the sequence is merged, and no forward mixes two sequences.  A frame's covering windows are therefore always
 resident when it is merged (no partial sum is ever carried), and a sequence's result does not depend on what else is lifted with
@@ -39,7 +44,7 @@ it: the engine's GEMM tile plan depends on the batch, so a window's bits do.
 
 Structure: ``lift_sequences`` is a chain of private stages - ``_check_options`` (every argument error, then an immutable record of resolved
 options), ``_upload`` (keypoints, window tables, offsets and output buffers, once), ``_lift_one`` per sequence (forwards and ONE merge),
-``_path_stage``, ``_smooth_poses_stage``, ``_rigid_stage``, ``_place_stage`` (with ``_smooth_traj_stage`` between its fit and its world transform), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place, path.  The
+``_path_stage``, ``_smooth_poses_stage``, ``_rigid_stage``, ``_score_stage`` (with ``targets``), ``_place_stage`` (with ``_smooth_traj_stage`` and ``_score_traj_stage`` between its fit and its world transform), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place, path, and the score.  The
 public function turns the record into its documented list / tuple in one place; ``lift_action`` and hpe/_entry.py read the fields by name.
 """
 from __future__ import annotations
@@ -325,6 +330,130 @@ def select_path(hyps, seq_offset=None, sigma=PATH_SIGMA, switch_cost=PATH_SWITCH
     return _path(_lib.load(), hyps, d_off, S, sigma, switch_cost)
 
 
+SCORE_SHARES = 32            # MP_LIFT_SCORE_SHARES of include/manipose_hip.h: partial rows per (sequence, inner) in mp_lift_score's scratch
+SCORE_ROOT_RELATIVE, SCORE_PROCRUSTES = 1, 2     # mp_lift_score's flags
+# What score_poses returns: device float64 tensors of shape (S,), or (S, inner) for 4-D poses; per_joint (.., M); bone_* (.., M - 1) or None without a
+# skeleton; rows: mp_lift_score's raw sums (.., 9 + M + 3 (M - 1)); frame_err (Ntot[, inner]) float32 with return_frames, else None
+PoseScore = namedtuple("PoseScore", "frames mpjpe rmse mpjve accel p_mpjpe per_joint bone_mean bone_std bone_err rows frame_err")
+# What score_traj returns: (S,) or (S, inner) device float64 tensors
+TrajScore = namedtuple("TrajScore", "frames ate rmse velocity accel")
+
+
+def _is_scale(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and np.isfinite(float(v)) and float(v) > 0
+
+
+def _score(lib, p4, gt, valid, d_off, S, parents, pred_scale, gt_scale, flags, want_frames=False):
+    """``mp_lift_score`` on p4 (Ntot, inner, M, C) against gt (Ntot, M, 3), valid (Ntot, inner) uint8 or None: (rows (S, inner, R) float64, frame_err
+    (Ntot, inner) float32 or None), new tensors.  A frame that no sequence holds keeps frame_err = -1."""
+    ntot, inner, M, ch = (int(v) for v in p4.shape)
+    dev = p4.device
+    rows = torch.zeros(S, inner, 6 + 4 * M, dtype=torch.float64, device=dev)
+    frame_err = torch.full((ntot, inner), -1.0, dtype=torch.float32, device=dev) if want_frames else None
+    if ntot > 0:
+        n = int(lib.mp_lift_score_scratch_doubles(S, inner, M))
+        scratch = torch.empty(n, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_score(_lib.ptr(p4), ntot, inner, M, ch, _lib.ptr(gt), _lib.ptr(valid), _lib.ptr(d_off), S, parents, float(pred_scale),
+                                         float(gt_scale), int(flags), _lib.ptr(rows), _lib.ptr(frame_err), _lib.ptr(scratch), n, _lib.stream_ptr()),
+                       "mp_lift_score")
+    return rows, frame_err
+
+
+def _ratio(num, den):
+    """num / den in float64, NaN where the count den is 0"""
+    return torch.where(den > 0, num / den.clamp(min=1.0), torch.full_like(num, float("nan")))
+
+
+def _pose_record(rows, M, procrustes, bones, frame_err=None):
+    """mp_lift_score's rows (.., R) as a PoseScore"""
+    n, nm = rows[..., 0], rows[..., 0] * M
+    bone_mean = bone_std = bone_err = None
+    if bones:
+        b = rows[..., 9 + M:].reshape(*rows.shape[:-1], M - 1, 3)
+        cnt = n.unsqueeze(-1).expand(b.shape[:-1])
+        bone_mean, bone_err = _ratio(b[..., 0], cnt), _ratio(b[..., 2], cnt)
+        bone_std = torch.sqrt((_ratio(b[..., 1], cnt) - bone_mean * bone_mean).clamp(min=0.0))      # (NaN stays NaN under clamp)
+    p = _ratio(rows[..., 7], (n - rows[..., 8]) * M) if procrustes else torch.full_like(n, float("nan"))
+    return PoseScore(n, _ratio(rows[..., 1], nm), torch.sqrt(_ratio(rows[..., 2], nm)), _ratio(rows[..., 4], rows[..., 3] * M),
+                     _ratio(rows[..., 6], rows[..., 5] * M), p, _ratio(rows[..., 9:9 + M], n.unsqueeze(-1).expand(*n.shape, M)), bone_mean, bone_std,
+                     bone_err, rows, frame_err)
+
+
+def _score_valid(valid, shape, name):
+    if valid is not None and (not torch.is_tensor(valid) or tuple(valid.shape) != tuple(shape) or valid.dtype != torch.uint8):
+        raise ValueError(f"{name} must be a uint8 tensor of shape {tuple(shape)}, got "
+                         f"{(tuple(valid.shape), valid.dtype) if torch.is_tensor(valid) else type(valid).__name__}")
+
+
+def score_poses(poses, target, seq_offset=None, valid=None, skeleton=None, root_relative=False, procrustes=True, pose_scale=1.0, target_scale=1.0,
+                return_frames=False):
+    """``mp_lift_score`` on device tensors: lifted poses against ground truth, per sequence.  ``poses`` (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32
+    (channel 3, a hypothesis' score, is not read); ``target`` (Ntot, J, 3) float32, shared by the ``inner`` poses of a frame; ``seq_offset`` (S + 1):
+    first frame of every sequence, HOST table or device int64 tensor (default: one sequence); ``valid`` uint8 (Ntot[, inner]) or None (every frame is
+    valid).  With P = pose_scale * poses and G = target_scale * target in fp64 (``root_relative``: joint 0 of the same pose subtracted from both), a
+    frame is COUNTED if it is valid and all its coordinates of P and G are finite, and e[g][j] = |P[g][j] - G[g][j]|.  Returns a ``PoseScore`` of
+    device float64 tensors of shape (S,) - (S, inner) for 4-D poses: ``frames`` counted; ``mpjpe`` the mean of e; ``rmse`` the root of the mean of
+    e^2; ``mpjve`` the mean over the pairs of consecutive counted frames of |(P[g] - P[g-1]) - (G[g] - G[g-1])|; ``accel`` the same of the second
+    differences over triples; ``p_mpjpe`` (``procrustes``, needs J >= 3; NaN without it) the mean of e after the similarity alignment of every P[g]
+    onto G[g], the reference's p_mpjpe, over the counted frames whose centred poses are not single points; ``per_joint`` (.., J); ``bone_mean``,
+    ``bone_std`` (population standard deviation over the frames) and ``bone_err`` (mean |target's length - pose's length|), each (.., J - 1), of
+    the bones of ``skeleton`` (default: the 17-joint H36M tree for 17 joints, else None: no bone statistics); ``rows``: the kernel's raw sums
+    (include/manipose_hip.h has the slots); ``frame_err`` (Ntot[, inner]) float32 with ``return_frames``: the mean of e over the joints, -1 for a
+    frame that is not counted or that no sequence holds.  A ratio whose count is 0 is NaN.  No term crosses a sequence boundary; fp64 inside,
+    identical bits on every call."""
+    if not _is_scale(pose_scale) or not _is_scale(target_scale):
+        raise ValueError(f"pose_scale and target_scale must be finite numbers > 0, got {pose_scale!r}, {target_scale!r}")
+    parents = None
+    if torch.is_tensor(poses):
+        p4 = _poses4_shape(poses)                        # (the ValueErrors come before the refusal of a CPU tensor)
+        ntot, inner, J = int(p4.shape[0]), int(p4.shape[1]), int(p4.shape[2])
+        if not torch.is_tensor(target) or tuple(target.shape) != (ntot, J, 3) or target.dtype != torch.float32 or not target.is_contiguous():
+            raise ValueError(f"target must be a contiguous float32 tensor ({ntot}, {J}, 3), got "
+                             f"{(tuple(target.shape), target.dtype) if torch.is_tensor(target) else type(target).__name__}")
+        _score_valid(valid, poses.shape[:-2], "valid")
+        if procrustes and J < 3:
+            raise ValueError(f"procrustes=True aligns poses of at least 3 joints, got {J}")
+        if skeleton is not None or J == 17:
+            parents = _parents_c(_skeleton_of(skeleton=skeleton), J)
+    if not torch.is_tensor(poses) or not poses.is_cuda or not target.is_cuda or (valid is not None and not valid.is_cuda):
+        raise RuntimeError("manipose_amd: score_poses takes device tensors; there is no CPU fallback")
+    d_off, S = _seq_table(seq_offset, ntot, poses.device)
+    flags = (SCORE_ROOT_RELATIVE if root_relative else 0) | (SCORE_PROCRUSTES if procrustes else 0)
+    rows, fe = _score(_lib.load(), p4, target, None if valid is None else valid.contiguous().view(ntot, inner), d_off, S, parents, pose_scale,
+                      target_scale, flags, return_frames)
+    if poses.dim() == 3:
+        rows, fe = rows[:, 0], (fe[:, 0] if fe is not None else None)
+    return _pose_record(rows, J, bool(procrustes), parents is not None, fe)
+
+
+def score_traj(traj, target, ok=None, seq_offset=None):
+    """``mp_lift_score`` on root trajectories (its M = 1 form: no alignment, no bones): ``traj`` (Ntot, 3) or (Ntot, inner, 3) float32 device tensor
+    as ``place_poses`` returns it, ``target`` (Ntot, 3) float32 in the same unit, ``ok`` uint8 (Ntot[, inner]) or None: a frame with ok = 0 or a
+    non-finite coordinate is not counted.  Returns a ``TrajScore`` of device float64 tensors (S,) or (S, inner): ``frames`` counted, ``ate`` the mean
+    distance, ``rmse`` the root of the mean squared distance, ``velocity`` / ``accel`` the mean norms of the first / second differences of the error
+    over consecutive counted frames of one sequence.  A ratio whose count is 0 is NaN.  ``seq_offset`` as for ``score_poses``."""
+    if torch.is_tensor(traj):
+        if traj.dim() not in (2, 3) or traj.shape[-1] != 3 or traj.dtype != torch.float32 or not traj.is_contiguous():
+            raise ValueError(f"traj must be contiguous float32 (Ntot, 3) or (Ntot, inner, 3), got {tuple(traj.shape)} {traj.dtype}")
+        if not torch.is_tensor(target) or tuple(target.shape) != (int(traj.shape[0]), 3) or target.dtype != torch.float32 or not target.is_contiguous():
+            raise ValueError(f"target must be a contiguous float32 tensor ({int(traj.shape[0])}, 3), got "
+                             f"{(tuple(target.shape), target.dtype) if torch.is_tensor(target) else type(target).__name__}")
+        _score_valid(ok, traj.shape[:-1], "ok")
+    if not torch.is_tensor(traj) or not traj.is_cuda or not target.is_cuda or (ok is not None and not ok.is_cuda):
+        raise RuntimeError("manipose_amd: score_traj takes device tensors; there is no CPU fallback")
+    ntot = int(traj.shape[0])
+    d_off, S = _seq_table(seq_offset, ntot, traj.device)
+    rows = _score(_lib.load(), traj.view(ntot, -1, 1, 3), target.view(ntot, 1, 3), None if ok is None else ok.contiguous().view(ntot, -1), d_off, S, None,
+                  1.0, 1.0, 0)[0]
+    return _traj_record(rows[:, 0] if traj.dim() == 2 else rows)
+
+
+def _traj_record(rows):
+    n = rows[..., 0]
+    return TrajScore(n, _ratio(rows[..., 1], n), torch.sqrt(_ratio(rows[..., 2], n)), _ratio(rows[..., 4], rows[..., 3]), _ratio(rows[..., 6], rows[..., 5]))
+
+
 FLOOR_SHARES = 16            # MP_LIFT_WORLD_SHARES of include/manipose_hip.h: partial minima per sequence in mp_lift_world's scratch
 
 
@@ -474,24 +603,27 @@ def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirr
 # cam_tables: camera_table(cameras) with place / world; lengths: "model", "measured" or "table" with rigid, and table: the caller's checked
 # (S, J - 1) one; skeleton, parents: the model's, with rigid; windows: plan_windows' (win_seq, win_start)
 # smooth_poses, smooth_traj: the two radii (0: off), smooth_degree, smooth_taper: shared by both; agg: "path" included, path_sigma (metres),
-# path_switch, return_path: its options
+# path_switch, return_path: its options; targets: the checked (N_i, J, 3) ground truth in metres or None, return_score
 _Options = namedtuple("_Options", "seqs tta agg blend scale return_hyps keep_padding rigid symmetric return_bones place world floor return_place "
                                   "smooth_poses smooth_traj smooth_degree smooth_taper path_sigma path_switch return_path cam_tables T J K lengths table skeleton parents "
-                                  "windows batch dev", defaults=(None,) * 11)
+                                  "windows batch dev targets return_score", defaults=(None,) * 11 + (None, False))
 # Everything the kernels of a lift read, uploaded once by _upload, and the buffers they write.  p2: (sum N_i, J, 2) keypoints of all sequences,
 # lens: N_i; out_lens: frames emitted per sequence (whole windows with keep_padding), out_off: their (S + 1) offsets in out_all (., J, 3) and
-# hyp_all (., K, J, 4); first: (S + 1) first window of every sequence; merge_off (S, 2), h_zero / d_zero: the offsets (0, out_lens[s]) and the
+# hyp_all (., K, J, 4); gt: (sum N_i, J, 3) targets of all sequences in metres, joint 0 (the root's position) as given; first: (S + 1) first window of every sequence; merge_off (S, 2), h_zero / d_zero: the offsets (0, out_lens[s]) and the
 # win_seq (zeros) of a one-sequence merge; bone_mirror (lengths="model"): bone of joint j <- bone of joint mirror[j]; d_*: device copies
 _Plan = namedtuple("_Plan", "p2 lens out_lens out_off first win_start merge_off h_zero d_off d_merge_off d_seq d_start d_zero d_flip mirror "
-                            "bone_mirror out_all hyp_all")
+                            "bone_mirror out_all hyp_all gt", defaults=(None,))
 # Per-sequence lists of what a lift returns; a field that was not asked for is None
 _Lifted = namedtuple("_Lifted", "poses hyps bones place path", defaults=(None,) * 4)
+# ... and what _lift_sequences returns: the same with the per-sequence score dicts of ``targets`` / ``return_score``
+_Scored = namedtuple("_Scored", _Lifted._fields + ("score",), defaults=(None,) * 5)
+SCORE_FIELDS = ("frames", "mpjpe", "rmse", "mpjve", "accel", "p_mpjpe", "per_joint", "bone_mean", "bone_std", "bone_err")   # of a score dict
 
 
 def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
                    floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform", path_sigma=PATH_SIGMA,
-                   path_switch=PATH_SWITCH, return_path=False):
+                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False):
     """Every argument error of ``lift_sequences``, in a fixed order and before anything touches a device: the ValueErrors first, the "no CPU
     fallback" RuntimeErrors last.  No sequences: the record ends after ``return_place``."""
     if not rigid and (lengths is not None or symmetric or return_bones):
@@ -536,9 +668,24 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
         raise ValueError("path_sigma, path_switch and return_path describe the hypothesis path: pass agg='path'")
     single = torch.is_tensor(poses_2d) or isinstance(poses_2d, np.ndarray)
     seqs = [poses_2d] if single else list(poses_2d)
+    if return_score and targets is None:
+        raise ValueError("return_score returns the score against ground truth: pass targets (one (N, J, 3) array per sequence)")
+    if targets is not None:
+        if keep_padding:
+            raise ValueError("targets with keep_padding=True: padded frames have no ground truth of their own")
+        targets = [targets] if torch.is_tensor(targets) or isinstance(targets, np.ndarray) else list(targets)
+        if len(targets) != len(seqs):
+            raise ValueError(f"targets: {len(targets)} arrays for {len(seqs)} sequences")
+        for i, (t, q) in enumerate(zip(targets, seqs)):
+            h = t if torch.is_tensor(t) else np.asarray(t)                   # (a device tensor stays where it is: only its shape is looked at)
+            numbers = (h.dtype.is_floating_point or h.dtype in (torch.int32, torch.int64)) if torch.is_tensor(t) else h.dtype.kind in "fiu"
+            want = (int(q.shape[0]), int(q.shape[1]), 3) if getattr(q, "ndim", 0) == 3 else None
+            if not numbers or want is None or tuple(h.shape) != want:
+                raise ValueError(f"targets[{i}] must be {want if want else '(N, J, 3)'} numbers like its sequence, got shape {tuple(h.shape)} {h.dtype}")
+            targets[i] = h
     opt = _Options(seqs, tta, agg, blend, scale, bool(return_hyps), keep_padding, rigid, symmetric, bool(return_bones), place, world, floor,
                    bool(return_place), int(smooth_poses), int(smooth_traj), int(smooth_degree), smooth_taper, float(path_sigma), float(path_switch),
-                   bool(return_path))
+                   bool(return_path), targets=targets, return_score=bool(return_score))
     if not seqs:
         return opt
     cam_tables = None
@@ -613,7 +760,15 @@ def _upload(model, opt):
     hyp_all = torch.empty(sum(out_lens), opt.K, J, 4, dtype=torch.float32, device=dev) if opt.return_hyps or opt.agg == "path" else None
     return _Plan(p2=p2, lens=lens, out_lens=out_lens, out_off=out_off, first=first, win_start=win_start, merge_off=merge_off,
                  h_zero=np.zeros(max_nw, dtype=np.int32), d_off=d_off, d_merge_off=d_merge_off, d_seq=d_seq, d_start=d_start, d_zero=d_zero,
-                 d_flip=d_flip, mirror=mirror, bone_mirror=bone_mirror, out_all=out_all, hyp_all=hyp_all)
+                 d_flip=d_flip, mirror=mirror, bone_mirror=bone_mirror, out_all=out_all, hyp_all=hyp_all,
+                 gt=_upload_targets(opt.targets, dev) if opt.return_score else None)
+
+
+def _upload_targets(targets, dev):
+    if all(torch.is_tensor(t) for t in targets):
+        return torch.cat([t.to(dev, torch.float32) for t in targets], dim=0).contiguous()
+    host = [t.detach().cpu().numpy() if torch.is_tensor(t) else t for t in targets]
+    return torch.from_numpy(np.concatenate([h.astype(np.float32, copy=False) for h in host], axis=0)).to(dev).contiguous()
 
 
 def _lift_one(model, opt, plan, s, model_rows):
@@ -713,7 +868,41 @@ def _rigid_stage(opt, plan, model_rows):
     return bones
 
 
-def _place_stage(opt, plan):
+def _score_stage(opt, plan, model):
+    """The emitted poses and, with ``return_hyps``, every hypothesis against the targets with joint 0 zeroed (the poses are root-relative; joint 0 of
+    a target holds the root's position), ``pred_scale = 1 / scale``: every number in metres.  After the rigid stage and before placing: what follows
+    moves a pose rigidly, so the score is that of the placed pose and of the world frame's too.  Returns the dict of PoseScore fields of all
+    sequences ((S,) tensors; under "hyps" the same of the hypotheses, (S, K), and "oracle_mpjpe" (S,): the mean over the frames with a counted
+    hypothesis of min_k frame_err - plain torch on the device).  (No padded frames here: ``d_off`` describes ``out_all``.)"""
+    lib, S, J, inv = _lib.load(), len(plan.lens), opt.J, 1.0 / float(opt.scale)
+    parents = _parents_c(_skeleton_of(model), J)
+    gt = plan.gt.clone()
+    gt[:, 0] = 0.0
+    flags = SCORE_PROCRUSTES
+    rec = _pose_record(_score(lib, plan.out_all.unsqueeze(1), gt, None, plan.d_off, S, parents, inv, 1.0, flags)[0][:, 0], J, True, True)
+    score = {f: getattr(rec, f) for f in SCORE_FIELDS}
+    if opt.return_hyps:
+        rows, fe = _score(lib, plan.hyp_all, gt, None, plan.d_off, S, parents, inv, 1.0, flags, want_frames=True)
+        hrec = _pose_record(rows, J, True, True)
+        score["hyps"] = {f: getattr(hrec, f) for f in SCORE_FIELDS}
+        best = torch.where(fe >= 0, fe.double(), torch.full_like(fe, float("inf"), dtype=torch.float64)).min(dim=1).values
+        seen = torch.isfinite(best)
+        per = [(b[m].mean() if bool(m.any()) else b.new_full((), float("nan"))) for b, m in zip(torch.split(best, plan.out_lens), torch.split(seen, plan.out_lens))]
+        score["oracle_mpjpe"] = torch.stack(per)
+    return score
+
+
+def _score_traj_stage(opt, plan, placed, score):
+    """The trajectory the world stage uses (smoothed with ``smooth_traj``) against the targets' joint 0, in metres; a frame counts where the fit was
+    ``ok`` or, smoothed, where a value could be ``filled`` in."""
+    valid = placed["filled"] if opt.smooth_traj else placed["ok"]
+    ntot = int(plan.out_all.shape[0])
+    rows = _score(_lib.load(), placed["traj"].contiguous().view(ntot, 1, 1, 3), plan.gt[:, :1].contiguous(), valid.contiguous().view(ntot, 1), plan.d_off,
+                  len(plan.lens), None, 1.0 / float(opt.scale), 1.0, 0)[0][:, 0]
+    score["traj"] = dict(_traj_record(rows)._asdict())
+
+
+def _place_stage(opt, plan, score=None):
     """The root trajectories of the merged poses and the hypotheses (``place``), then both into the world frame, in place, the hypotheses on
     the merged poses' floor (``world``).  No padded frames here: a frame of ``out_all`` is the frame of ``p2`` with the same number.  Returns
     the dict of per-frame results and the (S,) floor offsets or None."""
@@ -727,6 +916,8 @@ def _place_stage(opt, plan):
             placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"] = _place(lib, plan.hyp_all, plan.p2, plan.d_off, S, d_intr, None, True)
         if opt.smooth_traj:
             _smooth_traj_stage(opt, plan, placed)
+        if score is not None:
+            _score_traj_stage(opt, plan, placed, score)
     if opt.world:
         d_floor = torch.empty(S, dtype=torch.float32, device=dev) if opt.floor else None
         _world(lib, out4, placed["traj"].unsqueeze(1).contiguous() if opt.place else None, plan.d_off, S, d_quat, d_trans, 1 if opt.floor else 0,
@@ -736,25 +927,31 @@ def _place_stage(opt, plan):
     return placed, d_floor
 
 
-def _per_sequence(opt, plan, bones, placed, d_floor, chosen=None):
+def _cut_score(score, s):
+    return {k: (_cut_score(v, s) if isinstance(v, dict) else v[s]) for k, v in score.items()}
+
+
+def _per_sequence(opt, plan, bones, placed, d_floor, chosen=None, score=None):
     """the buffers of all sequences cut into the per-sequence lists of ``_Lifted``"""
     info = None
     if opt.return_place:
         per_seq = {k: torch.split(v, plan.out_lens, dim=0) for k, v in placed.items()}
         info = [dict({k: v[i] for k, v in per_seq.items()}, **({"floor": d_floor[i]} if opt.floor else {})) for i in range(len(plan.lens))]
-    return _Lifted(list(torch.split(plan.out_all, plan.out_lens, dim=0)),
+    return _Scored(list(torch.split(plan.out_all, plan.out_lens, dim=0)),
                    list(torch.split(plan.hyp_all, plan.out_lens, dim=0)) if opt.return_hyps else None,
                    list(bones.unbind(0)) if opt.return_bones else None, info,
-                   list(zip(torch.split(chosen[0], plan.out_lens, dim=0), chosen[1].unbind(0))) if opt.return_path else None)
+                   list(zip(torch.split(chosen[0], plan.out_lens, dim=0), chosen[1].unbind(0))) if opt.return_path else None,
+                   [_cut_score(score, s) for s in range(len(plan.lens))] if opt.return_score else None)
 
 
 @torch.no_grad()
 def _lift_sequences(model, poses_2d, **options):
-    """``lift_sequences`` with its results by name (``_Lifted``): check options -> upload -> every sequence lifted on its own -> hypothesis path -> smoothed poses ->
-    rigid stage -> place (-> smoothed trajectories) / world / floor stage -> per-sequence lists."""
+    """``lift_sequences`` with its results by name (``_Scored``: ``_Lifted`` and the score): check options -> upload -> every sequence lifted on its own ->
+    hypothesis path -> smoothed poses -> rigid stage -> score -> place (-> smoothed trajectories -> their score) / world / floor stage -> per-sequence lists."""
     opt = _check_options(model, poses_2d, **options)
     if not opt.seqs:
-        return _Lifted([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place, opt.return_path)))
+        return _Scored([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place, opt.return_path,
+                                                                   opt.return_score)))
     plan = _upload(model, opt)
     model_rows = []
     was_training = model.training
@@ -770,14 +967,15 @@ def _lift_sequences(model, poses_2d, **options):
     if opt.smooth_poses:
         plan = _smooth_poses_stage(opt, plan)
     bones = _rigid_stage(opt, plan, model_rows) if opt.rigid else None
-    placed, d_floor = _place_stage(opt, plan) if opt.place or opt.world else (None, None)
-    return _per_sequence(opt, plan, bones, placed, d_floor, chosen)
+    score = _score_stage(opt, plan, model) if opt.return_score else None
+    placed, d_floor = _place_stage(opt, plan, score) if opt.place or opt.world else (None, None)
+    return _per_sequence(opt, plan, bones, placed, d_floor, chosen, score)
 
 
 def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
                    floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform", path_sigma=PATH_SIGMA,
-                   path_switch=PATH_SWITCH, return_path=False):
+                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False):
     """One 3-D pose per frame of every sequence.  ``poses_2d``: a list of (N_i, 17, 2) device tensors or numpy arrays (or one such
     array); returns a list of (N_i, 17, 3) device tensors, and with ``return_hyps`` also a list of (N_i, K, 17, 4) (every hypothesis
     and its score, from the un-mirrored pass).  ``stride`` (default T: non-overlapping windows) in 1..T; ``blend`` "mean" averages the
@@ -823,13 +1021,24 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
     stage starting from the selected poses (so bone lengths are the model's own until something smooths them).  ``return_path`` appends a list of
     per-sequence ``(path (N,) uint8, cost)`` pairs, cost a float64 scalar tensor; the results come in the order poses, hyps, bones, place, path.
     The hypotheses are those ``return_hyps`` returns (the un-mirrored pass), so ``tta`` must be False: head k of a mirrored input is not head k
-    of the plain one.  Needs a model of 2..8 hypotheses; not with ``keep_padding``."""
+    of the plain one.  Needs a model of 2..8 hypotheses; not with ``keep_padding``.
+
+    Scoring against ground truth (``targets=None``, the default: nothing changes by a bit).  ``targets``: one (N_i, J, 3) array per sequence in metres,
+    as the dataset's ``fetch()`` prepares them: joint 0 holds the root's position in the camera's frame, the other joints are relative to the root.
+    ``return_score`` appends one dict per sequence (the results come in the order poses, hyps, bones, place, path, score): ``score_poses()``'s
+    ``frames``, ``mpjpe``, ``rmse``, ``mpjve``, ``accel``, ``p_mpjpe``, ``per_joint`` (J), ``bone_mean``, ``bone_std``, ``bone_err`` (J - 1), float64
+    device tensors in metres, of the poses that are emitted - after the path, the smoothing and the rigid stage, before placing, which moves poses
+    rigidly - against the targets with joint 0 zeroed (``scale`` is divided out).  With ``return_hyps`` the key ``hyps`` holds the same fields of
+    every hypothesis ((K,), (K, J), (K, J - 1)) and ``oracle_mpjpe`` the mean over the frames of the best hypothesis' error.  With ``place`` the key
+    ``traj`` holds ``score_traj()``'s ``frames``, ``ate``, ``rmse``, ``velocity``, ``accel`` of the trajectory the world frame uses (smoothed with
+    ``smooth_traj``) against the targets' joint 0, over the frames whose fit is ``ok`` (``filled`` when smoothed).  Whether any option lowers these
+    numbers on real data has not been measured here.  Not with ``keep_padding``."""
     res = _lift_sequences(model, poses_2d, stride=stride, tta=tta, agg=agg, blend=blend, return_hyps=return_hyps, batch=batch, scale=scale,
                           keep_padding=keep_padding, rigid=rigid, lengths=lengths, symmetric=symmetric, return_bones=return_bones, cameras=cameras,
                           place=place, frame=frame, floor=floor, return_place=return_place, smooth_poses=smooth_poses, smooth_traj=smooth_traj,
                           smooth_degree=smooth_degree, smooth_taper=smooth_taper, path_sigma=path_sigma, path_switch=path_switch,
-                          return_path=return_path)
-    asked = [r for r in res if r is not None]                # in the order poses, hyps, bones, place, path
+                          return_path=return_path, targets=targets, return_score=return_score)
+    asked = [r for r in res if r is not None]                # in the order poses, hyps, bones, place, path, score
     return asked[0] if len(asked) == 1 else tuple(asked)
 
 
@@ -845,5 +1054,5 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
 
 
 __all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "to_world", "smooth_poses", "smooth_traj",
-           "select_path", "lift_sequences",
+           "select_path", "score_poses", "score_traj", "lift_sequences",
            "lift_action"]

@@ -10,7 +10,9 @@ seg_max_strech.csv, seg_max_delta_strech.csv, cw_err.csv, jw_err.csv, all_seg_er
 3DHP (one row, no row label): seg_symmetry.csv, seg_consistency.csv, cw_err.csv, jw_err.csv.
 all_pred_hyps.pkl and the mlflow calls of the reference are not reproduced.
 run.hyp_report (no file of the reference: it does this study in follow-up scripts on the pickle): hyp_report.csv, hyp_heads.csv, hyp_joints.csv
-from ``HypothesisAccumulator.report()`` (write_hypothesis_report)."""
+from ``HypothesisAccumulator.report()`` (write_hypothesis_report).
+run.lift with lift.score (no file of the reference: it never scores a lifted sequence): lift_score.csv, lift_score_joints.csv from the score dicts
+of ``lift_sequences(targets=..., return_score=True)`` (write_lift_score_report)."""
 from __future__ import annotations
 
 import csv
@@ -172,4 +174,63 @@ def write_hypothesis_report(out_dir: str, groups: Mapping[str, Mapping], skeleto
             write_csv(paths[-1], h, [list(values[0])])
         else:
             write_csv(paths[-1], ["act", *h], _table(acts, values))
+    return paths
+
+
+LIFT_SCORE_HEAD = ("frames", "mpjpe", "p_mpjpe", "mpjve", "accel", "bone_std", "bone_err")       # then oracle_mpjpe, then traj_ate, traj_frames
+
+
+def _weighted_rows(labels, values, weights):
+    """Rows [label, *values] plus the last row "average": per column the mean weighted by ``weights`` (a column of ``values``' shape or one weight
+    per row) over the rows whose value is not NaN; NaN where no such row carries weight."""
+    v = np.asarray(values, dtype=np.float64).reshape(len(labels), -1)
+    w = np.broadcast_to(np.asarray(weights, dtype=np.float64).reshape(len(labels), -1), v.shape)
+    w = np.where(np.isnan(v), 0.0, w)
+    tot = w.sum(axis=0)
+    avg = np.where(tot > 0, (np.where(w > 0, v, 0.0) * w).sum(axis=0) / np.where(tot > 0, tot, 1.0), np.nan)
+    return [[lab, *row.tolist()] for lab, row in zip(list(labels) + ["average"], np.vstack([v, avg[None]]))]
+
+
+def write_lift_score_report(out_dir: str, scores: Mapping[str, Mapping], skeleton=None) -> List[str]:
+    """``scores``: {sequence key: the score dict of ``lift_sequences(targets=..., return_score=True)`` as numbers / numpy arrays, in metres} in the
+    order of the rows.  Two tables in the layout of the other report files (a label column "act", one row per key and a last row "average"),
+    the errors in millimetres:
+      lift_score.csv         frames, mpjpe, p_mpjpe, mpjve, accel, bone_std (the mean over the bones of a bone's standard deviation over the frames),
+                             bone_err (the mean over the bones of |target's length - pose's length|); with hypotheses oracle_mpjpe; with a placed
+                             trajectory traj_ate and traj_frames.  The "average" row weighs a row by its frames (traj_ate by traj_frames) and sums
+                             the two frame columns;
+      lift_score_joints.csv  the error per joint under the joints' names, averaged the same way.
+    Returns the paths written."""
+    keys = list(scores)
+    if not keys:
+        raise ValueError("write_lift_score_report: no sequence to report")
+    recs = [scores[k] for k in keys]
+    num = lambda v: float(np.asarray(v, dtype=np.float64).reshape(()))
+    mm = lambda v: 1000.0 * num(v)
+    mean_mm = lambda v: 1000.0 * float(np.asarray(v, dtype=np.float64).mean())
+    frames = [num(r["frames"]) for r in recs]
+    head = ["act", *LIFT_SCORE_HEAD]
+    cols = [[mm(r["mpjpe"]), mm(r["p_mpjpe"]), mm(r["mpjve"]), mm(r["accel"]), mean_mm(r["bone_std"]), mean_mm(r["bone_err"])] for r in recs]
+    weights = [[f] * 6 for f in frames]
+    if all("oracle_mpjpe" in r for r in recs):
+        head.append("oracle_mpjpe")
+        for c, w, r, f in zip(cols, weights, recs, frames):
+            c.append(mm(r["oracle_mpjpe"])); w.append(f)
+    traj = all("traj" in r for r in recs)
+    if traj:
+        head += ["traj_ate", "traj_frames"]
+        for c, w, r in zip(cols, weights, recs):
+            c.append(mm(r["traj"]["ate"])); w.append(num(r["traj"]["frames"]))
+    rows = _weighted_rows(keys, cols, weights)
+    rows = [[r[0], f, *r[1:]] for r, f in zip(rows, frames + [float(sum(frames))])]
+    if traj:
+        tf = [num(r["traj"]["frames"]) for r in recs]
+        rows = [[*r, f] for r, f in zip(rows, tf + [float(sum(tf))])]
+    jn = joints_names(skeleton)
+    per_joint = [1000.0 * np.asarray(r["per_joint"], dtype=np.float64).reshape(-1) for r in recs]
+    if any(len(v) != len(jn) for v in per_joint):
+        raise ValueError(f"write_lift_score_report: per_joint of {len(per_joint[0])} joints under {len(jn)} joint names")
+    paths = [os.path.join(out_dir, "lift_score.csv"), os.path.join(out_dir, "lift_score_joints.csv")]
+    write_csv(paths[0], head, rows)
+    write_csv(paths[1], ["act", *jn], _weighted_rows(keys, per_joint, frames))
     return paths

@@ -6,6 +6,7 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py [W=158] [T=243] [K=5] [precision=bf16x3] [reps=50]
     python tools/lift_bench.py --place [frames=3000] [K=5] [reps=50]
     python tools/lift_bench.py --path [frames=3000] [K=5] [reps=50]
+    python tools/lift_bench.py --score [frames=3000] [K=5] [reps=50]
 --place times only the two kernels that put a lifted sequence in the scene (mp_lift_place: root translation and reprojection error of every
 hypothesis; mp_lift_world: world frame, with and without the floor) on `frames` frames x K hypotheses of one sequence with S11's first camera,
 and then, in the same process, mp_lift_smooth (radius 4 and 32, degree 2, uniform) on the merged poses (frames, 17, 3), the hypotheses
@@ -13,7 +14,10 @@ and then, in the same process, mp_lift_smooth (radius 4 and 32, degree 2, unifor
 bytes once; it needs 2 joints, so the trajectory has none): both times, their ratio and the bytes/s of "read once, write once".
 --path times mp_lift_path (one hypothesis per frame, chosen over the whole sequence: cost, scan and gather kernels) through its private launcher
 on `frames` frames x K hypotheses of 17 joints, as ONE sequence (the scan is one wave: the serial case) and cut into 16, next to mp_lift_rigid
-on the same hypotheses."""
+on the same hypotheses.
+--score times mp_lift_score (the score of lifted poses against ground truth: score, alignment and finalize kernels) through its private launcher
+on `frames` frames x K hypotheses of 17 joints with bones, with and without the Procrustes alignment, as ONE sequence and cut into 16, and on the
+(frames, K, 3) trajectories, next to mp_lift_rigid on the same hypotheses."""
 import os
 import sys
 
@@ -119,6 +123,37 @@ def path_bench(argv):
     print(f"mp_lift_rigid on the same hypotheses: {us:,.1f} us", flush=True)
 
 
+def score_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.lifting import SCORE_PROCRUSTES, _parents_c, _rigid, _score, _skeleton_of
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    K = int(argv[1]) if len(argv) > 1 else 5
+    reps = int(argv[2]) if len(argv) > 2 else 50
+    assert torch.cuda.is_available(), "needs an MI355X"
+    lib = _lib.load()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    gt = 0.3 * torch.randn(frames, 17, 3, device="cuda", generator=g)
+    hyps = torch.rand(frames, K, 17, 4, device="cuda", generator=g)
+    hyps[..., :3] = 0.9 * gt[:, None] + 0.05 * torch.randn(frames, K, 17, 3, device="cuda", generator=g)
+    traj, root = hyps[:, :, :1, :3].contiguous(), gt[:, :1].contiguous()
+    lengths, parents = torch.full((1, 16), 0.25, device="cuda"), _parents_c(_skeleton_of(), 17)
+    print(f"--score: {frames} frames x {K} hypotheses, {hyps.numel() * 4 / 1e6:.2f} MB of hypotheses; {reps} calls each after 5 of warm-up (the output and "
+          f"scratch allocations are inside the time)", flush=True)
+    for S in (1, 16):
+        d_off = torch.linspace(0, frames, S + 1, device="cuda").round().to(torch.int64)
+        for name, flags in (("sums and alignment", SCORE_PROCRUSTES), ("sums only", 0)):
+            us = timed_us(lambda: _score(lib, hyps, gt, None, d_off, S, parents, 1.0, 1.0, flags, want_frames=True), reps)
+            print(f"mp_lift_score, {S} sequence(s), {name}: {us:,.1f} us  {frames * K / us:,.2f} M poses/s", flush=True)
+        us = timed_us(lambda: _score(lib, traj, root, None, d_off, S, None, 1.0, 1.0, 0), reps)
+        print(f"mp_lift_score, {S} sequence(s), trajectories (M = 1): {us:,.1f} us  {frames * K / us:,.2f} M poses/s", flush=True)
+    work = hyps.clone()
+    us = timed_us(lambda: _rigid(lib, work, torch.tensor([0, frames], dtype=torch.int64, device="cuda"), 1, lengths, parents), reps)
+    print(f"mp_lift_rigid on the same hypotheses: {us:,.1f} us", flush=True)
+
+
+if "--score" in sys.argv:
+    score_bench([a for a in sys.argv[1:] if a != "--score"])
+    sys.exit(0)
 if "--path" in sys.argv:
     path_bench([a for a in sys.argv[1:] if a != "--path"])
     sys.exit(0)
