@@ -272,7 +272,7 @@ def sk_device(model):
 
 
 LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj", "__hyps_reproj", "__hyps_ok", "__floor", "__cam", "__traj_fit", "__filled",
-                 "__hyps_traj_fit", "__hyps_filled", "__path", "__path_cost")
+                 "__hyps_traj_fit", "__hyps_filled", "__path", "__path_cost", "__steps", "__hyps_steps", "__reproj_smooth", "__hyps_reproj_smooth")
 
 
 def lift_place_options(cfg):
@@ -285,6 +285,17 @@ def lift_place_options(cfg):
     if (place or frame == "world") and str(cfg.data.dataset) == "3dhp":
         raise ValueError("lift.place / lift.frame=world need the cameras' calibration, and the MPI-INF-3DHP files (data.dataset=3dhp) carry none")
     return place, frame == "world", floor
+
+
+def lift_refine_options(cfg):
+    """lift.place_refine as an int: the Gauss-Newton steps after lift.place's linear fit (0: none); ValueError for a value or a combination that
+    cannot run - before any model is built."""
+    n = cfg.lift.get("place_refine", 0)
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 16:
+        raise ValueError(f"lift.place_refine counts Gauss-Newton steps, an integer in 0..16 (0: off), got {n!r}")
+    if n and not bool(cfg.lift.get("place", False)):
+        raise ValueError("lift.place_refine refines the trajectory that lift.place fits: set lift.place=true")
+    return n
 
 
 def lift_smooth_options(cfg):
@@ -363,7 +374,9 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     ``cameras`` = {name: [one camera per sequence]} (camera_table's forms) is needed by lift.place (also ``<key>__traj`` (N, 3), ``<key>__reproj``
     (N,), ``<key>__ok`` (N,) uint8 and with lift.hyps ``<key>__hyps_traj`` (N, K, 3), ``<key>__hyps_reproj``, ``<key>__hyps_ok`` (N, K); with
     lift.smooth_traj ``__traj`` / ``__hyps_traj`` are the smoothed trajectories and ``<key>__traj_fit`` (N, 3), ``<key>__filled`` (N,) uint8,
-    ``<key>__hyps_traj_fit`` (N, K, 3), ``<key>__hyps_filled`` (N, K) are added) and by
+    ``<key>__hyps_traj_fit`` (N, K, 3), ``<key>__hyps_filled`` (N, K) are added; with lift.place_refine the trajectories are refined under the full
+    camera model and ``<key>__steps`` (N,) uint8, ``<key>__hyps_steps`` (N, K) are added, with lift.smooth_traj also ``<key>__reproj_smooth`` (N,) and
+    ``<key>__hyps_reproj_smooth`` (N, K), the reprojection error of the smoothed trajectory) and by
     lift.frame=world (poses and hypotheses in the world frame; with lift.floor on z = 0 and ``<key>__floor``, the offset subtracted); whenever
     cameras were used ``<key>__cam`` holds the 16 numbers (intrinsic 9, orientation 4, translation 3).  With lift.agg=path (one of the model's
     hypotheses per frame, chosen over the whole sequence; lift.path_sigma, lift.path_switch) also ``<key>__path`` (N,) uint8, the hypothesis of
@@ -376,6 +389,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     rigid = bool(cfg.lift.get("rigid", False))
     place, world, floor = lift_place_options(cfg)
     smooth_p, smooth_t, smooth_degree, smooth_taper = lift_smooth_options(cfg)
+    refine_kw = dict(place_refine=lift_refine_options(cfg)) if lift_refine_options(cfg) else {}
     agg, path_sigma, path_switch = lift_path_options(cfg)
     path_kw = dict(path_sigma=path_sigma, path_switch=path_switch, return_path=True) if agg == "path" else {}
     use_cams = place or world
@@ -388,7 +402,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
                               return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
                               symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid, cameras=cameras[name] if use_cams else None,
                               place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor,
-                              smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper, **path_kw, **score_kw(name))
+                              smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper, **refine_kw, **path_kw, **score_kw(name))
         cam_rows = np.concatenate(camera_table(cameras[name]), axis=1) if use_cams else None
         for i, p in enumerate(res.poses):
             key = name if len(res.poses) == 1 else f"{name}.{i}"
@@ -445,6 +459,7 @@ def run(argv, extra_defaults=None):
     cfg = load_config(argv, extra_defaults)
     lift_place_options(cfg)                    # a lift.place / lift.frame / lift.floor that cannot run fails here, before the model is built
     lift_smooth_options(cfg)                   # ... and so does a lift.smooth_* that cannot run
+    lift_refine_options(cfg)                   # ... and a lift.place_refine without lift.place
     lift_path_options(cfg)                     # ... and a lift.agg=path that cannot (with the default train.tta=true: set train.tta=false)
     lift_score_options(cfg)                    # ... and a lift.score without run.lift
     rank, world, local = init_from_env()

@@ -513,6 +513,34 @@ int mp_lift_place(const float* poses, int64_t Ntot, int inner, int J, int C, con
 int mp_lift_world(float* poses, int64_t Ntot, int inner, int J, int C, const float* traj, const int64_t* seq_offset, int S, const float* quat,
                   const float* trans, int floor_mode, float* floor, float* scratch, int64_t scratch_floats, void* stream);
 
+/* Refining placed root trajectories under the FULL camera model.  mp_lift_place fits t with the pinhole part of the camera (linear in t) and
+ * measures the error with the full one; mp_lift_place_refine starts from that fit, or from a given trajectory, and takes up to `iters` undamped
+ * Gauss-Newton steps on  F(t) = sum_j w_j |pi(p_j + t) - u_j|^2,  pi as for mp_lift_place by `distort`.  The reference has no counterpart.  The
+ * conventions, checks and MP_ERR_ARG cases of mp_lift_place apply (poses read only); in addition 0 <= iters <= MP_LIFT_REFINE_MAXITERS, start
+ * (Ntot, inner, 3) device floats or null, start_ok (Ntot, inner) device bytes or null (it needs start), steps (Ntot, inner) device bytes or null.
+ * Per pose, in fp64 between the float32 loads and stores, joints of weight 0 never looked at, every sum in joint order:
+ * 1. Start.  start null: t, ok and the degenerate rule of mp_lift_place (ok = 0, t = 0, reproj = 0, steps = 0 for a degenerate fit).  start given:
+ *    t = start[i]; if start_ok[i] == 0, t is not finite or sum w is not > 0: t is stored as it came in, bit for bit, reproj = 0, ok = 0, steps = 0.
+ * 2. Evaluation at t, one pass over the joints:  P = p_j + t,  q = P.xy / P.z,  x = clamp(q, -1, 1),  s_x, s_y = 1 where -1 <= q <= 1 else 0 (the
+ *    derivative of the clamp),  r_j = pi(P) - u_j,  and the 2 x 3 Jacobian  J_j = diag(f) d(px, py)/d(x, y) d(x, y)/dt  with
+ *    dx/dt = s_x (1/Z, 0, -q_x/Z),  dy/dt = s_y (0, 1/Z, -q_y/Z);  distort = 0: d(px, py)/d(x, y) is the identity;  distort = 1: with m the bracket
+ *    of project_to_2d,  dm = k1 + 2 k2 r2 + 3 k3 r2^2,  m_x = 2 x dm + p1,  m_y = 2 y dm + p2:
+ *    dpx/dx = m + x m_x + 2 p1 x,  dpx/dy = x m_y + 2 p1 y,  dpy/dx = y m_x + 2 p2 x,  dpy/dy = m + y m_y + 2 p2 y.
+ *    Sums:  F = sum w |r|^2,  E = sum w |r|,  W = sum w,  H = sum w J^T J,  g = sum w J^T r,  deep = every weighted Z > 0.
+ * 3. Steps.  If the first evaluation has deep false or F not finite: ok = 0, t and E / W stored as computed, no step (mp_lift_place's rule for a
+ *    joint behind the camera).  Otherwise for k = 1 .. iters:  det H by cofactors,  d = -adj(H) g / det;  the step is taken iff det and
+ *    H00 H11 H22 are finite,  det > 1e-12 H00 H11 H22  (the ratio lies in [0, 1] for a positive semi-definite H),  t' = t + d is finite, the
+ *    evaluation at t' has deep true, and  F' <= (1 + 1e-6) F.  On the first step not taken the iteration ends and t stays.  No convergence test
+ *    and no damping: the start lies centimetres from the minimum, where Gauss-Newton converges in about three steps; the 1e-6 slack keeps
+ *    rounding from deciding at the minimum, where F' / F is 1.
+ * 4. Store.  traj = (float) t,  reproj = (float)(E / W) at the final t,  ok = 1,  steps = steps taken.
+ * iters = 0 with start null: every output has the bits of mp_lift_place.  iters = 0 with start given: the reprojection error of a given trajectory.
+ * One lane owns one pose and a pose depends on no other pose; no atomics: identical bits on every call.  The call does not synchronise. */
+#define MP_LIFT_REFINE_MAXITERS 16
+int mp_lift_place_refine(const float* poses, int64_t Ntot, int inner, int J, int C, const float* kp, const int64_t* seq_offset, int S, const float* intr,
+                         const float* weights, int distort, const float* start, const uint8_t* start_ok, int iters, float* traj, float* reproj,
+                         uint8_t* ok, uint8_t* steps, void* stream);
+
 /* Smoothing lifted sequences in time: a weighted local polynomial fit (Savitzky-Golay with validity weights) along the frames of a sequence, which
  * also fills frames that have no valid value of their own.  The reference has no counterpart.  in / out (Ntot, inner, M, C) device floats, out of
  * place; C = 3 or 4, 1 <= M <= 32 (M = 1, C = 3: a trajectory; M = J: poses or hypotheses); valid and filled (Ntot, inner) device bytes, either may

@@ -17,6 +17,13 @@ the sequences' cameras (``camera_table``) ``mp_lift_place`` fits, per pose and p
 the 2-D keypoints the pose was lifted from, and reports the reprojection error under the full H36M camera model; ``mp_lift_world`` rotates
 everything into the world frame (the reference's ``camera_to_world``, hpe/viz.py:93-98) and, with ``floor``, puts the sequence on z = 0.
 
+Refining the placement (``place_refine``, Gauss-Newton steps, 0 = off, the default): the fit above uses the pinhole part of the camera only, because
+that fit is linear in the translation, while the H36M cameras distort (k1 ~ -0.2, k2 ~ 0.25): on noise-free keypoints made with the full model the
+linear fit misses the true root by up to 0.17 m, almost all of it depth.  ``mp_lift_place_refine`` starts from the linear fit and takes up to
+``place_refine`` undamped Gauss-Newton steps on the squared reprojection error of the FULL projection (include/manipose_hip.h has the rule); three
+steps recover the translation of that construction to the float32 rounding of its keypoints.  The same entry point with zero steps and a given
+trajectory is ``reproject_poses``.  What this does to accuracy on real H36M data has not been measured (no dataset here).
+
 Smoothing in time (``smooth_poses`` / ``smooth_traj``, radii, 0 = off, the default): every stage above treats every frame on its own.
 ``mp_lift_smooth`` fits, per frame and coordinate, a polynomial of degree ``smooth_degree`` to the frames within the radius that belong to the same
 sequence and are valid (Savitzky-Golay with validity weights; include/manipose_hip.h has the rule) and stores its value at the frame.  The merged
@@ -44,7 +51,7 @@ it: the engine's GEMM tile plan depends on the batch, so a window's bits do.
 
 Structure: ``lift_sequences`` is a chain of private stages - ``_check_options`` (every argument error, then an immutable record of resolved
 options), ``_upload`` (keypoints, window tables, offsets and output buffers, once), ``_lift_one`` per sequence (forwards and ONE merge),
-``_path_stage``, ``_smooth_poses_stage``, ``_rigid_stage``, ``_score_stage`` (with ``targets``), ``_place_stage`` (with ``_smooth_traj_stage`` and ``_score_traj_stage`` between its fit and its world transform), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place, path, and the score.  The
+``_path_stage``, ``_smooth_poses_stage``, ``_rigid_stage``, ``_score_stage`` (with ``targets``), ``_place_stage`` (with ``_smooth_traj_stage``, ``_reproj_smooth_stage`` and ``_score_traj_stage`` between its fit and its world transform), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place, path, and the score.  The
 public function turns the record into its documented list / tuple in one place; ``lift_action`` and hpe/_entry.py read the fields by name.
 """
 from __future__ import annotations
@@ -454,6 +461,7 @@ def _traj_record(rows):
     return TrajScore(n, _ratio(rows[..., 1], n), torch.sqrt(_ratio(rows[..., 2], n)), _ratio(rows[..., 4], rows[..., 3]), _ratio(rows[..., 6], rows[..., 5]))
 
 
+REFINE_MAXITERS = 16         # MP_LIFT_REFINE_MAXITERS of include/manipose_hip.h: Gauss-Newton steps mp_lift_place_refine takes at most
 FLOOR_SHARES = 16            # MP_LIFT_WORLD_SHARES of include/manipose_hip.h: partial minima per sequence in mp_lift_world's scratch
 
 
@@ -502,6 +510,27 @@ def _place(lib, p4, kp, d_off, S, d_intr, d_w, distort):
     return traj, reproj, ok
 
 
+def _is_iters(n):
+    return isinstance(n, (int, np.integer)) and not isinstance(n, (bool, np.bool_)) and 0 <= int(n) <= REFINE_MAXITERS
+
+
+def _place_refine(lib, p4, kp, d_off, S, d_intr, d_w, distort, iters, start=None, start_ok=None):
+    """``mp_lift_place_refine`` on p4 (Ntot, inner, J, C): (traj, reproj, ok, steps), new tensors; start (Ntot, inner, 3) or None: the linear fit,
+    start_ok (Ntot, inner) uint8 or None"""
+    ntot, inner, J, ch = (int(v) for v in p4.shape)
+    dev = p4.device
+    traj = torch.empty(ntot, inner, 3, dtype=torch.float32, device=dev)
+    reproj = torch.empty(ntot, inner, dtype=torch.float32, device=dev)
+    ok = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
+    steps = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
+    if ntot > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_place_refine(_lib.ptr(p4), ntot, inner, J, ch, _lib.ptr(kp), _lib.ptr(d_off), S, _lib.ptr(d_intr), _lib.ptr(d_w),
+                                                int(bool(distort)), _lib.ptr(start), _lib.ptr(start_ok), int(iters), _lib.ptr(traj), _lib.ptr(reproj),
+                                                _lib.ptr(ok), _lib.ptr(steps), _lib.stream_ptr()), "mp_lift_place_refine")
+    return traj, reproj, ok, steps
+
+
 def _world(lib, p4, traj, d_off, S, d_quat, d_trans, floor_mode=0, d_floor=None):
     ntot, inner, J, ch = (int(v) for v in p4.shape)
     if ntot == 0:
@@ -513,7 +542,21 @@ def _world(lib, p4, traj, d_off, S, d_quat, d_trans, floor_mode=0, d_floor=None)
                                      _lib.stream_ptr()), "mp_lift_world")
 
 
-def place_poses(poses, keypoints_2d, intrinsics, seq_offset=None, weights=None, distort=True):
+def _place_inputs(poses, keypoints_2d, intrinsics, seq_offset, weights, who):
+    """the checks and uploads place_poses and reproject_poses share: (p4, keypoints, d_off, S, d_intr, d_w)"""
+    p4 = _poses4(poses, who)
+    dev, ntot, J = poses.device, int(p4.shape[0]), int(p4.shape[2])
+    if not torch.is_tensor(keypoints_2d) or not keypoints_2d.is_cuda:
+        raise RuntimeError(f"manipose_amd: {who} takes device tensors; there is no CPU fallback")
+    if tuple(keypoints_2d.shape) != (ntot, J, 2) or keypoints_2d.dtype != torch.float32:
+        raise ValueError(f"keypoints_2d must be float32 ({ntot}, {J}, 2), got {tuple(keypoints_2d.shape)} {keypoints_2d.dtype}")
+    d_off, S = _seq_table(seq_offset, ntot, dev)
+    d_intr = _device_f32(intrinsics, dev, (S, 9), "intrinsics", row=(9,) if S == 1 else None)
+    d_w = _device_f32(weights, dev, (J,), "weights", nonneg=True) if weights is not None else None
+    return p4, keypoints_2d.contiguous(), d_off, S, d_intr, d_w
+
+
+def place_poses(poses, keypoints_2d, intrinsics, seq_offset=None, weights=None, distort=True, refine=0, return_steps=False):
     """``mp_lift_place`` on device tensors: per pose the root translation that fits the frame's 2-D keypoints, and the reprojection error.
     ``poses`` (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32 (channel 3, a hypothesis' score, is not read); ``keypoints_2d`` (Ntot, J, 2) in
     normalised screen coordinates, shared by the ``inner`` poses of a frame; ``intrinsics`` (S, 9) or (9,), tensor or array, as
@@ -521,18 +564,39 @@ def place_poses(poses, keypoints_2d, intrinsics, seq_offset=None, weights=None, 
     tensor (default: one sequence); ``weights`` (J) non-negative or None (all ones; a joint of weight 0 is skipped).  The fit uses the pinhole
     part of the camera; the error the full model (``distort=True``, the reference's project_to_2d) or project_to_2d_linear, in normalised screen
     units (times res_w / 2: pixels).  Returns ``traj`` (Ntot[, inner], 3) in the poses' unit, ``reproj`` (Ntot[, inner]), ``ok`` uint8: 0 where the
-    fit is degenerate (no weight, a non-finite input, all keypoints on one spot: traj and reproj are 0) or puts a joint behind the camera."""
-    p4 = _poses4(poses, "place_poses")
-    dev, ntot, J = poses.device, int(p4.shape[0]), int(p4.shape[2])
-    if not torch.is_tensor(keypoints_2d) or not keypoints_2d.is_cuda:
-        raise RuntimeError("manipose_amd: place_poses takes device tensors; there is no CPU fallback")
-    if tuple(keypoints_2d.shape) != (ntot, J, 2) or keypoints_2d.dtype != torch.float32:
-        raise ValueError(f"keypoints_2d must be float32 ({ntot}, {J}, 2), got {tuple(keypoints_2d.shape)} {keypoints_2d.dtype}")
-    d_off, S = _seq_table(seq_offset, ntot, dev)
-    d_intr = _device_f32(intrinsics, dev, (S, 9), "intrinsics", row=(9,) if S == 1 else None)
-    d_w = _device_f32(weights, dev, (J,), "weights", nonneg=True) if weights is not None else None
-    traj, reproj, ok = _place(_lib.load(), p4, keypoints_2d.contiguous(), d_off, S, d_intr, d_w, distort)
-    return (traj[:, 0], reproj[:, 0], ok[:, 0]) if poses.dim() == 3 else (traj, reproj, ok)
+    fit is degenerate (no weight, a non-finite input, all keypoints on one spot: traj and reproj are 0) or puts a joint behind the camera.
+    ``refine`` (0..16, default 0: the linear fit alone, ``mp_lift_place``): ``mp_lift_place_refine`` starts from that fit and takes up to that many
+    undamped Gauss-Newton steps on the weighted squared reprojection error of the projection ``distort`` names - the fit then uses the model the
+    error is measured with; a step is taken only while the normal matrix is regular, the translation stays finite and in front of the camera, and
+    the cost does not rise (include/manipose_hip.h has the rule); ``reproj`` is the error at the refined translation.  ``return_steps`` appends
+    ``steps`` uint8 (Ntot[, inner]): the steps taken (0 everywhere without ``refine``)."""
+    if not _is_iters(refine):
+        raise ValueError(f"refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: the linear fit alone), got {refine!r}")
+    p4, kp, d_off, S, d_intr, d_w = _place_inputs(poses, keypoints_2d, intrinsics, seq_offset, weights, "place_poses")
+    if int(refine) == 0 and not return_steps:
+        res = _place(_lib.load(), p4, kp, d_off, S, d_intr, d_w, distort)
+    else:
+        res = _place_refine(_lib.load(), p4, kp, d_off, S, d_intr, d_w, distort, refine)[:4 if return_steps else 3]
+    return tuple(r[:, 0] for r in res) if poses.dim() == 3 else tuple(res)
+
+
+def reproject_poses(poses, traj, keypoints_2d, intrinsics, ok=None, seq_offset=None, weights=None, distort=True):
+    """``mp_lift_place_refine`` with zero steps on a GIVEN trajectory: the reprojection error of poses placed at ``traj`` - a smoothed trajectory,
+    a ground-truth one, another method's.  ``traj`` (Ntot[, inner], 3) float32 device tensor shaped like ``place_poses`` returns it, ``ok`` uint8
+    (Ntot[, inner]) or None (every frame is given); the other arguments as for ``place_poses``.  Returns ``(reproj, ok)``: reproj (Ntot[, inner])
+    float32 in normalised screen units, the weighted mean distance between the keypoints and the projection of pose + traj; ok uint8, 0 with
+    reproj = 0 where ``ok`` was 0 or traj is not finite, 0 with reproj as computed where a joint lies behind the camera or the error is not
+    finite, else 1."""
+    if torch.is_tensor(poses) and torch.is_tensor(traj):
+        _poses4_shape(poses)
+        if tuple(traj.shape) != tuple(poses.shape[:-2]) + (3,) or traj.dtype != torch.float32:
+            raise ValueError(f"traj must be float32 {tuple(poses.shape[:-2]) + (3,)}, got {tuple(traj.shape)} {traj.dtype}")
+        _score_valid(ok, traj.shape[:-1], "ok")
+    if not torch.is_tensor(traj) or not traj.is_cuda or (ok is not None and not ok.is_cuda):
+        raise RuntimeError("manipose_amd: reproject_poses takes device tensors; there is no CPU fallback")
+    p4, kp, d_off, S, d_intr, d_w = _place_inputs(poses, keypoints_2d, intrinsics, seq_offset, weights, "reproject_poses")
+    _, reproj, good, _ = _place_refine(_lib.load(), p4, kp, d_off, S, d_intr, d_w, distort, 0, traj.contiguous(), None if ok is None else ok.contiguous())
+    return (reproj[:, 0], good[:, 0]) if poses.dim() == 3 else (reproj, good)
 
 
 def to_world(poses, orientation, translation=None, traj=None, seq_offset=None, floor=False):
@@ -603,10 +667,11 @@ def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirr
 # cam_tables: camera_table(cameras) with place / world; lengths: "model", "measured" or "table" with rigid, and table: the caller's checked
 # (S, J - 1) one; skeleton, parents: the model's, with rigid; windows: plan_windows' (win_seq, win_start)
 # smooth_poses, smooth_traj: the two radii (0: off), smooth_degree, smooth_taper: shared by both; agg: "path" included, path_sigma (metres),
-# path_switch, return_path: its options; targets: the checked (N_i, J, 3) ground truth in metres or None, return_score
+# path_switch, return_path: its options; targets: the checked (N_i, J, 3) ground truth in metres or None, return_score; place_refine: Gauss-Newton
+# steps after the linear fit (0: none)
 _Options = namedtuple("_Options", "seqs tta agg blend scale return_hyps keep_padding rigid symmetric return_bones place world floor return_place "
                                   "smooth_poses smooth_traj smooth_degree smooth_taper path_sigma path_switch return_path cam_tables T J K lengths table skeleton parents "
-                                  "windows batch dev targets return_score", defaults=(None,) * 11 + (None, False))
+                                  "windows batch dev targets return_score place_refine", defaults=(None,) * 11 + (None, False, 0))
 # Everything the kernels of a lift read, uploaded once by _upload, and the buffers they write.  p2: (sum N_i, J, 2) keypoints of all sequences,
 # lens: N_i; out_lens: frames emitted per sequence (whole windows with keep_padding), out_off: their (S + 1) offsets in out_all (., J, 3) and
 # hyp_all (., K, J, 4); gt: (sum N_i, J, 3) targets of all sequences in metres, joint 0 (the root's position) as given; first: (S + 1) first window of every sequence; merge_off (S, 2), h_zero / d_zero: the offsets (0, out_lens[s]) and the
@@ -623,7 +688,7 @@ SCORE_FIELDS = ("frames", "mpjpe", "rmse", "mpjve", "accel", "p_mpjpe", "per_joi
 def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
                    floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform", path_sigma=PATH_SIGMA,
-                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False):
+                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False, place_refine=0):
     """Every argument error of ``lift_sequences``, in a fixed order and before anything touches a device: the ValueErrors first, the "no CPU
     fallback" RuntimeErrors last.  No sequences: the record ends after ``return_place``."""
     if not rigid and (lengths is not None or symmetric or return_bones):
@@ -645,6 +710,10 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
         raise ValueError("return_place returns what place=True (and floor=True) computed: pass place=True")
     if (place or world) and keep_padding:
         raise ValueError("place / frame='world' with keep_padding=True: padded frames have no keypoints of their own")
+    if not _is_iters(place_refine):
+        raise ValueError(f"place_refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: off), got {place_refine!r}")
+    if int(place_refine) > 0 and not place:
+        raise ValueError("place_refine refines the trajectory that place=True fits: pass place=True")
     for name, r in (("smooth_poses", smooth_poses), ("smooth_traj", smooth_traj)):
         if not _is_radius(r, 0):
             raise ValueError(f"{name} is a radius in frames, an integer in 0..{SMOOTH_MAXR} (0: off), got {r!r}")
@@ -685,7 +754,7 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
             targets[i] = h
     opt = _Options(seqs, tta, agg, blend, scale, bool(return_hyps), keep_padding, rigid, symmetric, bool(return_bones), place, world, floor,
                    bool(return_place), int(smooth_poses), int(smooth_traj), int(smooth_degree), smooth_taper, float(path_sigma), float(path_switch),
-                   bool(return_path), targets=targets, return_score=bool(return_score))
+                   bool(return_path), targets=targets, return_score=bool(return_score), place_refine=int(place_refine))
     if not seqs:
         return opt
     cam_tables = None
@@ -841,6 +910,17 @@ def _smooth_traj_stage(opt, plan, placed):
         placed[pre + "traj_fit"], placed[pre + "traj"], placed[pre + "filled"] = fit, out.view(fit.shape), filled.view(ok.shape)
 
 
+def _reproj_smooth_stage(opt, plan, placed, d_intr):
+    """``place_refine`` with ``smooth_traj``: the reprojection error of the smoothed trajectories over their ``filled`` frames, under the full camera
+    model (``reproj`` stays the error at the fitted translation): ``reproj_smooth`` / ``hyps_reproj_smooth``, 0 where nothing was filled in."""
+    lib, S, ntot = _lib.load(), len(plan.lens), int(plan.out_all.shape[0])
+    for pre, p4 in (("", plan.out_all.unsqueeze(1)), ("hyps_", plan.hyp_all)) if opt.return_hyps else (("", plan.out_all.unsqueeze(1)),):
+        traj, filled = placed[pre + "traj"], placed[pre + "filled"]
+        err = _place_refine(lib, p4, plan.p2, plan.d_off, S, d_intr, None, True, 0, traj.contiguous().view(ntot, -1, 3),
+                            filled.contiguous().view(ntot, -1))[1]
+        placed[pre + "reproj_smooth"] = err.view(filled.shape)
+
+
 def _rigid_stage(opt, plan, model_rows):
     """One (J - 1) table of bone lengths per sequence, and every merged pose and hypothesis re-assembled with it, in place.  Returns the
     (S, J - 1) tables in metres."""
@@ -911,11 +991,19 @@ def _place_stage(opt, plan, score=None):
     d_trans = torch.from_numpy(opt.cam_tables[2] * np.float32(opt.scale)).to(dev) if opt.place else None
     placed, d_floor = {}, None
     if opt.place:
-        placed["traj"], placed["reproj"], placed["ok"] = (t[:, 0] for t in _place(lib, out4, plan.p2, plan.d_off, S, d_intr, None, True))
-        if opt.return_hyps:
-            placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"] = _place(lib, plan.hyp_all, plan.p2, plan.d_off, S, d_intr, None, True)
+        if opt.place_refine:                             # the linear fit, then Gauss-Newton steps under the full camera model
+            fit = lambda p4: _place_refine(lib, p4, plan.p2, plan.d_off, S, d_intr, None, True, opt.place_refine)
+            placed["traj"], placed["reproj"], placed["ok"], placed["steps"] = (t[:, 0] for t in fit(out4))
+            if opt.return_hyps:
+                placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"], placed["hyps_steps"] = fit(plan.hyp_all)
+        else:
+            placed["traj"], placed["reproj"], placed["ok"] = (t[:, 0] for t in _place(lib, out4, plan.p2, plan.d_off, S, d_intr, None, True))
+            if opt.return_hyps:
+                placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"] = _place(lib, plan.hyp_all, plan.p2, plan.d_off, S, d_intr, None, True)
         if opt.smooth_traj:
             _smooth_traj_stage(opt, plan, placed)
+            if opt.place_refine:
+                _reproj_smooth_stage(opt, plan, placed, d_intr)
         if score is not None:
             _score_traj_stage(opt, plan, placed, score)
     if opt.world:
@@ -975,7 +1063,7 @@ def _lift_sequences(model, poses_2d, **options):
 def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
                    floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform", path_sigma=PATH_SIGMA,
-                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False):
+                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False, place_refine=0):
     """One 3-D pose per frame of every sequence.  ``poses_2d``: a list of (N_i, 17, 2) device tensors or numpy arrays (or one such
     array); returns a list of (N_i, 17, 3) device tensors, and with ``return_hyps`` also a list of (N_i, K, 17, 4) (every hypothesis
     and its score, from the un-mirrored pass).  ``stride`` (default T: non-overlapping windows) in 1..T; ``blend`` "mean" averages the
@@ -1001,6 +1089,13 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
     lowest merged joint is put on z = 0, and the SAME offset is subtracted from the hypotheses - merged pose and hypotheses stand in one scene
     (the reference floors each array on its own).  Not with ``keep_padding``: padded frames have no keypoints of their own.
 
+    Refining the placement (``place_refine=0``, the default: nothing changes by a bit, and no dict gains a key; needs ``place``): an integer in
+    0..16, the undamped Gauss-Newton steps ``mp_lift_place_refine`` takes from the linear fit on the reprojection error of the FULL camera model
+    (``place_poses(refine=)`` has the rule), for the merged poses and, with ``return_hyps``, for every hypothesis.  ``traj`` / ``hyps_traj`` are then
+    the refined trajectories - which ``smooth_traj``, the score's ``traj`` and the world frame use unchanged - ``reproj`` the error at them, and the
+    place dicts gain ``steps`` / ``hyps_steps`` (uint8: steps taken); with ``smooth_traj`` also ``reproj_smooth`` / ``hyps_reproj_smooth``, the
+    reprojection error of the smoothed trajectory where ``filled`` is 1 (0 elsewhere).  Three steps suffice on the H36M cameras.
+
     Smoothing in time (both off by default: nothing changes by a bit): ``smooth_poses`` and ``smooth_traj`` are radii in frames, 0..64, 0 = off;
     ``smooth_degree`` (0..2) and ``smooth_taper`` ("uniform" | "biweight") are shared by both and need one of them (``smooth_poses()`` has the
     rule: a least-squares polynomial over the frames within the radius, inside the sequence).  ``smooth_poses``: the merged poses and, with
@@ -1009,7 +1104,7 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
     after the fit and before the world frame, with the fit's ``ok`` as validity: a frame with ok = 0 (``traj`` = 0) is filled from its valid
     neighbours.  The place dicts then hold the smoothed ``traj`` / ``hyps_traj`` (what the world frame uses) and gain ``traj_fit`` /
     ``hyps_traj_fit`` (the fitted values, bit for bit) and ``filled`` / ``hyps_filled`` (uint8; 0: no valid frame within the radius, the fitted
-    value is kept); ``ok`` and ``reproj`` stay what the fit reported (no reprojection error of the smoothed trajectory is computed).  Not with
+    value is kept); ``ok`` and ``reproj`` stay what the fit reported (the reprojection error of the smoothed trajectory comes with ``place_refine``).  Not with
     ``keep_padding``.
 
     One hypothesis path (``agg="path"``; with the default ``agg`` nothing changes by a bit): instead of averaging the K hypotheses of a frame
@@ -1037,7 +1132,7 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
                           keep_padding=keep_padding, rigid=rigid, lengths=lengths, symmetric=symmetric, return_bones=return_bones, cameras=cameras,
                           place=place, frame=frame, floor=floor, return_place=return_place, smooth_poses=smooth_poses, smooth_traj=smooth_traj,
                           smooth_degree=smooth_degree, smooth_taper=smooth_taper, path_sigma=path_sigma, path_switch=path_switch,
-                          return_path=return_path, targets=targets, return_score=return_score)
+                          return_path=return_path, targets=targets, return_score=return_score, place_refine=place_refine)
     asked = [r for r in res if r is not None]                # in the order poses, hyps, bones, place, path, score
     return asked[0] if len(asked) == 1 else tuple(asked)
 
@@ -1053,6 +1148,6 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
     return torch.cat(res.hyps if hyps else res.poses, dim=0).cpu().numpy()
 
 
-__all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "to_world", "smooth_poses", "smooth_traj",
+__all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "reproject_poses", "to_world", "smooth_poses", "smooth_traj",
            "select_path", "score_poses", "score_traj", "lift_sequences",
            "lift_action"]
