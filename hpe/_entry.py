@@ -272,7 +272,8 @@ def sk_device(model):
 
 
 LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj", "__hyps_reproj", "__hyps_ok", "__floor", "__cam", "__traj_fit", "__filled",
-                 "__hyps_traj_fit", "__hyps_filled", "__path", "__path_cost", "__steps", "__hyps_steps", "__reproj_smooth", "__hyps_reproj_smooth")
+                 "__hyps_traj_fit", "__hyps_filled", "__path", "__path_cost", "__steps", "__hyps_steps", "__reproj_smooth", "__hyps_reproj_smooth",
+                 "__quat", "__quat_ok", "__hyps_quat", "__hyps_quat_ok")
 
 
 def lift_place_options(cfg):
@@ -355,6 +356,22 @@ def lift_score_options(cfg):
     return score
 
 
+def lift_rotations_options(cfg):
+    """(rotations, continuous) of lift.rotations / lift.rotations_continuous; ValueError for a value or a combination that cannot run - before any
+    model is built.  No camera is needed: it works wherever run.lift works."""
+    rotations, continuous = cfg.lift.get("rotations", False), cfg.lift.get("rotations_continuous", True)
+    if not isinstance(rotations, bool) or not isinstance(continuous, bool):
+        raise ValueError(f"lift.rotations and lift.rotations_continuous must be true or false, got {rotations!r}, {continuous!r}")
+    if rotations and not bool(cfg.run.lift):
+        raise ValueError("lift.rotations computes the joint rotations of what run.lift lifts: set run.lift=true")
+    if not continuous and not rotations:
+        raise ValueError("lift.rotations_continuous describes the joint rotations: set lift.rotations=true")
+    return rotations, continuous
+
+
+ROTATION_KEYS = {"quat": "__quat", "ok": "__quat_ok", "hyps_quat": "__hyps_quat", "hyps_ok": "__hyps_quat_ok"}      # of a rotations dict -> in lift.npz
+
+
 def synthetic_cameras(groups):
     """Synthetic-data mode has no calibration of its own: sequence i (in the order of ``groups``) gets camera i % 4 of subject S11 (h36m_cameras())."""
     from manipose_amd.data.ingest import h36m_cameras
@@ -380,7 +397,9 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     lift.frame=world (poses and hypotheses in the world frame; with lift.floor on z = 0 and ``<key>__floor``, the offset subtracted); whenever
     cameras were used ``<key>__cam`` holds the 16 numbers (intrinsic 9, orientation 4, translation 3).  With lift.agg=path (one of the model's
     hypotheses per frame, chosen over the whole sequence; lift.path_sigma, lift.path_switch) also ``<key>__path`` (N,) uint8, the hypothesis of
-    every frame, and ``<key>__path_cost``, the cost of the sequence's path (a float64 scalar).
+    every frame, and ``<key>__path_cost``, the cost of the sequence's path (a float64 scalar).  With lift.rotations (the joint rotations of the
+    poses as emitted, mp_lift_rotations; lift.rotations_continuous) also ``<key>__quat`` (N, 17, 4) float32 unit quaternions (w, x, y, z),
+    ``<key>__quat_ok`` (N,) uint8 and with lift.hyps ``<key>__hyps_quat`` (N, K, 17, 4), ``<key>__hyps_quat_ok`` (N, K).
     ``targets`` = {name: [ground truth (N, 17, 3) in metres per sequence]} (lift.score): every sequence is scored against it on the device and the dict
     ``scores`` receives {key: the score dict of lift_sequences(return_score=True) as numpy values, in metres}; the .npz keeps its keys."""
     from manipose_amd import camera_table
@@ -392,6 +411,8 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     refine_kw = dict(place_refine=lift_refine_options(cfg)) if lift_refine_options(cfg) else {}
     agg, path_sigma, path_switch = lift_path_options(cfg)
     path_kw = dict(path_sigma=path_sigma, path_switch=path_switch, return_path=True) if agg == "path" else {}
+    rotations, rot_continuous = lift_rotations_options(cfg)
+    rot_kw = dict(rotations=True, rotations_continuous=rot_continuous, return_rotations=True) if rotations else {}
     use_cams = place or world
     score_kw = lambda name: dict(targets=targets[name], return_score=True) if targets is not None else {}
     to_host = lambda v: {k: to_host(x) for k, x in v.items()} if isinstance(v, dict) else v.cpu().numpy()
@@ -402,7 +423,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
                               return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
                               symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid, cameras=cameras[name] if use_cams else None,
                               place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor,
-                              smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper, **refine_kw, **path_kw, **score_kw(name))
+                              smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper, **refine_kw, **path_kw, **rot_kw, **score_kw(name))
         cam_rows = np.concatenate(camera_table(cameras[name]), axis=1) if use_cams else None
         for i, p in enumerate(res.poses):
             key = name if len(res.poses) == 1 else f"{name}.{i}"
@@ -418,6 +439,9 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
                 out[key + "__cam"] = cam_rows[i]
             if res.path is not None:
                 out[key + "__path"], out[key + "__path_cost"] = (v.cpu().numpy() for v in res.path[i])
+            if res.rotations is not None:
+                for k, v in res.rotations[i].items():
+                    out[key + ROTATION_KEYS[k]] = v.cpu().numpy()
             if res.score is not None and scores is not None:
                 scores[key] = to_host(res.score[i])
     np.savez(path, **out)
@@ -462,6 +486,7 @@ def run(argv, extra_defaults=None):
     lift_refine_options(cfg)                   # ... and a lift.place_refine without lift.place
     lift_path_options(cfg)                     # ... and a lift.agg=path that cannot (with the default train.tta=true: set train.tta=false)
     lift_score_options(cfg)                    # ... and a lift.score without run.lift
+    lift_rotations_options(cfg)                # ... and a lift.rotations without run.lift
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")

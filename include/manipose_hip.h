@@ -541,6 +541,36 @@ int mp_lift_place_refine(const float* poses, int64_t Ntot, int inner, int J, int
                          const float* weights, int distort, const float* start, const uint8_t* start_ok, int iters, float* traj, float* reproj,
                          uint8_t* ok, uint8_t* steps, void* stream);
 
+/* Joint rotations of lifted poses: the inverse of the decoder's forward kinematics on the poses the pipeline emits.  The reference has no
+ * counterpart.  poses (Ntot, inner, J, C) device floats, read only, C = 3 or 4 (channel 3 is not read), 2 <= J <= 32; seq_offset (S + 1) device
+ * int64 (read by MP_LIFT_ROT_CONTINUOUS alone, every sequence's frames clamped to 0 .. Ntot-1); parents (J) HOST int32, parents[0] = -1,
+ * 0 <= parents[j] < j; rest (J, 3) HOST floats, row j >= 1 the T-pose direction of the bone parents[j] -> j (the skeleton's t_pose_operators),
+ * normalised here in fp64, row 0 ignored; a zero or non-finite row is MP_ERR_ARG.  Outputs: quat (Ntot, inner, J, 4) device floats (w, x, y, z),
+ * 16-byte aligned; rot6d (Ntot, inner, J, 6) device floats or null: columns 0 then 1 of the matrix of q[j] (fp64 q), what mp_fk_decode_fwd takes;
+ * ok (Ntot, inner) device bytes; a zero component of q[j] or rot6d is stored as +0.  The FK convention is the decoder's: Rw[0] = R[0], Rw[j] = Rw[parent] R[j], p[j] = p[parent] + Rw[j] (len_j
+ * rest_j), so fk(q, measured lengths) is the pose again.  Per pose, on its own, fp64 between the float32 loads and stores:
+ * 1. Bones.  b_j = p_j - p_parent is GOOD if its six coordinates are finite and |b_j| > 1e-12; then d_j = b_j / |b_j|.  If any coordinate of the
+ *    pose is not finite: every quaternion is (1, 0, 0, 0) and ok = 0.
+ * 2. Reference children of the root, chosen on the host: a = the lowest child of joint 0, b = the lowest child of joint 0 with
+ *    |rest_a x rest_b| > 1e-6, or none (H36M: a = 1, the right hip, +x; b = 7, the spine, +y).
+ * 3. Root.  E = [e1, e2, e1 x e2], e1 = rest_a, e2 = unit(rest_b - (rest_b . e1) e1); F the same frame of d_a, d_b; Rw[0] = F E^T.  Fallbacks with
+ *    ok = 0: d_b not good or |d_b - (d_b . f1) f1| <= 1e-9: Rw[0] = arc(rest_a -> d_a); d_a not good either: identity.  No b: arc(rest_a -> d_a),
+ *    ok untouched.  q[0] is the unit quaternion of Rw[0], taken from the largest of 4w^2 = 1 + tr, 4x^2 = 1 + m00 - m11 - m22, 4y^2, 4z^2 (the
+ *    first on a tie), normalised, with the sign that makes its first non-zero component positive.
+ * 4. Joints j = 1 .. J-1:  u = Rw[parent]^T d_j,  q[j] = arc(rest_j -> u),  Rw[j] = Rw[parent] q[j];  arc(r -> u) = normalize(1 + r . u, r x u),
+ *    the shortest, twist-free rotation; where 1 + r . u < 1e-12 it is the half turn (0, n), n = unit(e_k - (e_k . r) r), k the coordinate where
+ *    |r| is smallest (the lowest on a tie), n's first non-zero component positive, and ok = 0.  A bone that is not good: q[j] = (1, 0, 0, 0),
+ *    ok = 0.
+ * 5. MP_LIFT_ROT_CONTINUOUS, per (sequence, inner index, joint) over the sequence's frames f0 .. f1-1: with c[g] the float32 quaternion as stored
+ *    by 1-4, flip[f0] = 0, flip[g] = flip[g-1] XOR (dot(c[g], c[g-1]) < 0) (the dot in fp64), and -c[g] is stored where flip[g]; rot6d is
+ *    not touched, a frame no sequence holds keeps c[g].  An exclusive-or prefix over integer flags: the result does not depend on how the frames
+ *    are cut into chunks.
+ * The twist about a bone is zero by construction: a convention, not a measurement.  No atomics, a fixed order: identical bits on every call; a
+ * pose's result of 1-4 depends on no other pose, a sequence's signs on no other sequence.  The call does not synchronise. */
+#define MP_LIFT_ROT_CONTINUOUS 1
+int mp_lift_rotations(const float* poses, int64_t Ntot, int inner, int J, int C, const int64_t* seq_offset, int S, const int32_t* parents,
+                      const float* rest, int flags, float* quat, float* rot6d, uint8_t* ok, void* stream);
+
 /* Smoothing lifted sequences in time: a weighted local polynomial fit (Savitzky-Golay with validity weights) along the frames of a sequence, which
  * also fills frames that have no valid value of their own.  The reference has no counterpart.  in / out (Ntot, inner, M, C) device floats, out of
  * place; C = 3 or 4, 1 <= M <= 32 (M = 1, C = 3: a trajectory; M = J: poses or hypotheses); valid and filled (Ntot, inner) device bytes, either may

@@ -126,6 +126,7 @@ _SIGNATURES = {
     "mp_lift_place": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
     "mp_lift_world": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i64, vp]),
     "mp_lift_place_refine": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "mp_lift_rotations": (i32, [vp, i64, i32, i32, i32, vp, i32, C.POINTER(i32), C.POINTER(f32), i32, vp, vp, vp, vp]),
     "mp_lift_smooth": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]),
     "mp_lift_path_scratch_floats": (i64, [i64, i32]),
     "mp_lift_path": (i32, [vp, i64, i32, i32, vp, i32, f32, f32, vp, vp, vp, vp, i64, vp]),

@@ -24,6 +24,12 @@ linear fit misses the true root by up to 0.17 m, almost all of it depth.  ``mp_l
 steps recover the translation of that construction to the float32 rounding of its keypoints.  The same entry point with zero steps and a given
 trajectory is ``reproject_poses``.  What this does to accuracy on real H36M data has not been measured (no dataset here).
 
+Joint rotations (``rotations``, off by default): every stage here emits joint POSITIONS, while the model decodes (6-D rotation per joint, segment
+lengths) by forward kinematics.  ``mp_lift_rotations`` is the inverse on the poses as they are emitted: per pose the root orientation from the
+frame the hip and the spine span, per joint the shortest-arc (twist-free) rotation that turns the bone's T-pose direction into its measured one
+(include/manipose_hip.h has the rule), as unit quaternions (w, x, y, z) that are sign-continuous along every sequence, and as the 6-D form the
+decoder takes.  ``pose_rotations`` is the public form.  No accuracy of these rotations on real data has been measured (no dataset here).
+
 Smoothing in time (``smooth_poses`` / ``smooth_traj``, radii, 0 = off, the default): every stage above treats every frame on its own.
 ``mp_lift_smooth`` fits, per frame and coordinate, a polynomial of degree ``smooth_degree`` to the frames within the radius that belong to the same
 sequence and are valid (Savitzky-Golay with validity weights; include/manipose_hip.h has the rule) and stores its value at the frame.  The merged
@@ -51,7 +57,7 @@ it: the engine's GEMM tile plan depends on the batch, so a window's bits do.
 
 Structure: ``lift_sequences`` is a chain of private stages - ``_check_options`` (every argument error, then an immutable record of resolved
 options), ``_upload`` (keypoints, window tables, offsets and output buffers, once), ``_lift_one`` per sequence (forwards and ONE merge),
-``_path_stage``, ``_smooth_poses_stage``, ``_rigid_stage``, ``_score_stage`` (with ``targets``), ``_place_stage`` (with ``_smooth_traj_stage``, ``_reproj_smooth_stage`` and ``_score_traj_stage`` between its fit and its world transform), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place, path, and the score.  The
+``_path_stage``, ``_smooth_poses_stage``, ``_rigid_stage``, ``_score_stage`` (with ``targets``), ``_place_stage`` (with ``_smooth_traj_stage``, ``_reproj_smooth_stage`` and ``_score_traj_stage`` between its fit and its world transform), ``_rotations_stage`` (last, on the poses as emitted), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place, path, and the score and the rotations.  The
 public function turns the record into its documented list / tuple in one place; ``lift_action`` and hpe/_entry.py read the fields by name.
 """
 from __future__ import annotations
@@ -217,6 +223,76 @@ def project_rigid(poses, lengths, seq_offset=None, skeleton=None):
     if ntot > 0:
         _rigid(_lib.load(), p4, d_off, S, table, parents)
     return poses
+
+
+ROT_CONTINUOUS = 1           # MP_LIFT_ROT_CONTINUOUS of include/manipose_hip.h
+
+
+def _rest_c(sk, J):
+    """The (J, 3) T-pose directions of a skeleton's ``t_pose_operators`` (joint -> direction of the bone parent -> joint; the root has none) as a C
+    float table, row 0 zero; ValueError for a missing, non-finite or zero direction (the entry point normalises them)"""
+    ops = getattr(sk, "t_pose_operators", None)
+    if ops is None:
+        raise ValueError("joint rotations need the skeleton's t_pose_operators: the T-pose direction of every bone")
+    rest = np.zeros((J, 3), dtype=np.float32)
+    for j in range(1, J):
+        try:
+            v = ops[j]
+        except (KeyError, IndexError):
+            raise ValueError(f"t_pose_operators has no direction for joint {j}") from None
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        if v.shape != (3,) or v.dtype.kind not in "fiu":
+            raise ValueError(f"t_pose_operators[{j}] must be 3 numbers, got shape {tuple(v.shape)} {v.dtype}")
+        with np.errstate(over="ignore"):
+            v = v.astype(np.float32)
+        if not np.isfinite(v).all() or not (v != 0).any():
+            raise ValueError(f"t_pose_operators[{j}] = {v.tolist()}: a T-pose direction must be finite and not zero")
+        rest[j] = v
+    return (C.c_float * (3 * J))(*rest.ravel().tolist())
+
+
+def _rotations(lib, p4, d_off, S, parents, rest, continuous=True, want_rot6d=False):
+    """``mp_lift_rotations`` on p4 (Ntot, inner, J, C): (quat (Ntot, inner, J, 4), ok (Ntot, inner) uint8, rot6d (Ntot, inner, J, 6) or None), new
+    tensors; p4 is read only"""
+    ntot, inner, J, ch = (int(v) for v in p4.shape)
+    dev = p4.device
+    quat = torch.empty(ntot, inner, J, 4, dtype=torch.float32, device=dev)
+    ok = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
+    rot6d = torch.empty(ntot, inner, J, 6, dtype=torch.float32, device=dev) if want_rot6d else None
+    if ntot > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_rotations(_lib.ptr(p4), ntot, inner, J, ch, _lib.ptr(d_off), S, parents, rest, ROT_CONTINUOUS if continuous else 0,
+                                             _lib.ptr(quat), _lib.ptr(rot6d), _lib.ptr(ok), _lib.stream_ptr()), "mp_lift_rotations")
+    return quat, ok, rot6d
+
+
+def pose_rotations(poses, seq_offset=None, skeleton=None, continuous=True, return_rot6d=False):
+    """``mp_lift_rotations`` on a device tensor, OUT of place: the joint rotations that, with each pose's own bone lengths and root position, ARE the
+    pose under the decoder's forward kinematics (Rw[0] = R[0], Rw[j] = Rw[parent] R[j], p[j] = p[parent] + Rw[j] (len_j rest_j)).  ``poses``
+    (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32 (channel 3, a hypothesis' score, is not read); ``skeleton``: anything with ``parents`` and
+    ``t_pose_operators`` (default, for J = 17 only: the H36M tree); ``seq_offset`` (S + 1): first frame of every sequence, HOST table or device
+    int64 tensor (default: one sequence), used by ``continuous`` alone.  Returns ``(quat, ok)`` and with ``return_rot6d`` also ``rot6d``: quat
+    (Ntot[, inner], J, 4) float32 unit quaternions (w, x, y, z), quat[:, 0] the root's orientation (the frame of the bones to its first child and to
+    its first child in another direction - H36M: right hip and spine - against the T-pose's), quat[:, j] the shortest-arc rotation of bone j in
+    its parent's frame: the twist about a bone is zero by construction, a convention and not a measurement.  ok (Ntot[, inner]) uint8: 0 where a
+    bone has no direction (length 0, a non-finite coordinate: identity; any non-finite coordinate makes the whole pose identities), lies exactly
+    opposite its T-pose direction (a half turn about a fixed axis) or the root's two bones are collinear.  rot6d (Ntot[, inner], J, 6): columns 0
+    then 1 of each quaternion's matrix, what ``torch.ops.manipose.fk_decode`` / ``mp_fk_decode_fwd`` take.  A quaternion's sign is the one that
+    makes its first non-zero component positive; with ``continuous`` it is then flipped along every (sequence, inner index, joint) track wherever
+    that keeps consecutive frames in one hemisphere (dot >= 0), so the track can be filtered or interpolated; rot6d does not depend on the sign.
+    fp64 inside, identical bits on every call (include/manipose_hip.h has the rule)."""
+    if torch.is_tensor(poses):
+        _poses4_shape(poses)
+        J = int(poses.shape[-2])
+        if skeleton is None and J != 17:
+            raise ValueError(f"poses have {J} joints: the default skeleton is the 17-joint H36M tree; pass a skeleton with parents and t_pose_operators")
+        sk = _skeleton_of(skeleton=skeleton)
+        parents, rest = _parents_c(sk, J), _rest_c(sk, J)
+    p4 = _poses4(poses, "pose_rotations")
+    d_off, S = _seq_table(seq_offset, int(p4.shape[0]), poses.device)
+    quat, ok, rot6d = _rotations(_lib.load(), p4, d_off, S, parents, rest, bool(continuous), bool(return_rot6d))
+    res = (quat, ok, rot6d) if return_rot6d else (quat, ok)
+    return tuple(r[:, 0] for r in res) if poses.dim() == 3 else res
 
 
 def _is_radius(r, lowest):
@@ -668,10 +744,11 @@ def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirr
 # (S, J - 1) one; skeleton, parents: the model's, with rigid; windows: plan_windows' (win_seq, win_start)
 # smooth_poses, smooth_traj: the two radii (0: off), smooth_degree, smooth_taper: shared by both; agg: "path" included, path_sigma (metres),
 # path_switch, return_path: its options; targets: the checked (N_i, J, 3) ground truth in metres or None, return_score; place_refine: Gauss-Newton
-# steps after the linear fit (0: none)
+# steps after the linear fit (0: none); rotations, rotations_continuous, return_rotations and rot_tables: the (parents, rest) C tables of the stage
 _Options = namedtuple("_Options", "seqs tta agg blend scale return_hyps keep_padding rigid symmetric return_bones place world floor return_place "
                                   "smooth_poses smooth_traj smooth_degree smooth_taper path_sigma path_switch return_path cam_tables T J K lengths table skeleton parents "
-                                  "windows batch dev targets return_score place_refine", defaults=(None,) * 11 + (None, False, 0))
+                                  "windows batch dev targets return_score place_refine rotations rotations_continuous return_rotations rot_tables",
+                      defaults=(None,) * 11 + (None, False, 0, False, True, False, None))
 # Everything the kernels of a lift read, uploaded once by _upload, and the buffers they write.  p2: (sum N_i, J, 2) keypoints of all sequences,
 # lens: N_i; out_lens: frames emitted per sequence (whole windows with keep_padding), out_off: their (S + 1) offsets in out_all (., J, 3) and
 # hyp_all (., K, J, 4); gt: (sum N_i, J, 3) targets of all sequences in metres, joint 0 (the root's position) as given; first: (S + 1) first window of every sequence; merge_off (S, 2), h_zero / d_zero: the offsets (0, out_lens[s]) and the
@@ -682,13 +759,16 @@ _Plan = namedtuple("_Plan", "p2 lens out_lens out_off first win_start merge_off 
 _Lifted = namedtuple("_Lifted", "poses hyps bones place path", defaults=(None,) * 4)
 # ... and what _lift_sequences returns: the same with the per-sequence score dicts of ``targets`` / ``return_score``
 _Scored = namedtuple("_Scored", _Lifted._fields + ("score",), defaults=(None,) * 5)
+# ... and with the per-sequence rotation dicts of ``rotations`` / ``return_rotations``: what _lift_sequences returns
+_Rotated = namedtuple("_Rotated", _Scored._fields + ("rotations",), defaults=(None,) * 6)
 SCORE_FIELDS = ("frames", "mpjpe", "rmse", "mpjve", "accel", "p_mpjpe", "per_joint", "bone_mean", "bone_std", "bone_err")   # of a score dict
 
 
 def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
                    floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform", path_sigma=PATH_SIGMA,
-                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False, place_refine=0):
+                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False, place_refine=0, rotations=False,
+                   rotations_continuous=True, return_rotations=False):
     """Every argument error of ``lift_sequences``, in a fixed order and before anything touches a device: the ValueErrors first, the "no CPU
     fallback" RuntimeErrors last.  No sequences: the record ends after ``return_place``."""
     if not rigid and (lengths is not None or symmetric or return_bones):
@@ -714,6 +794,12 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
         raise ValueError(f"place_refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: off), got {place_refine!r}")
     if int(place_refine) > 0 and not place:
         raise ValueError("place_refine refines the trajectory that place=True fits: pass place=True")
+    if not all(isinstance(v, (bool, np.bool_)) for v in (rotations, rotations_continuous, return_rotations)):
+        raise ValueError("rotations, rotations_continuous and return_rotations are switches (True / False)")
+    if not rotations and (return_rotations or not rotations_continuous):
+        raise ValueError("rotations_continuous and return_rotations describe the joint rotations: pass rotations=True")
+    if rotations and keep_padding:
+        raise ValueError("rotations with keep_padding=True: padded frames repeat the last frame and would enter the sign-continuous tracks")
     for name, r in (("smooth_poses", smooth_poses), ("smooth_traj", smooth_traj)):
         if not _is_radius(r, 0):
             raise ValueError(f"{name} is a radius in frames, an integer in 0..{SMOOTH_MAXR} (0: off), got {r!r}")
@@ -754,7 +840,8 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
             targets[i] = h
     opt = _Options(seqs, tta, agg, blend, scale, bool(return_hyps), keep_padding, rigid, symmetric, bool(return_bones), place, world, floor,
                    bool(return_place), int(smooth_poses), int(smooth_traj), int(smooth_degree), smooth_taper, float(path_sigma), float(path_switch),
-                   bool(return_path), targets=targets, return_score=bool(return_score), place_refine=int(place_refine))
+                   bool(return_path), targets=targets, return_score=bool(return_score), place_refine=int(place_refine), rotations=bool(rotations),
+                   rotations_continuous=bool(rotations_continuous), return_rotations=bool(return_rotations))
     if not seqs:
         return opt
     cam_tables = None
@@ -779,6 +866,10 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
             table, lengths = _host_f32(lengths, (len(seqs), J - 1), "lengths", row=(J - 1,), nonneg=True), "table"
         sk = _skeleton_of(model)
         parents = _parents_c(sk, J)
+    rot_tables = None
+    if rotations:                                    # the tree and the T-pose the model decodes with (MixSTE carries none: the H36M ones)
+        rot_sk = _skeleton_of(model)
+        rot_tables = (_parents_c(rot_sk, J), _rest_c(rot_sk, J))
     stride = T if stride is None else int(stride)
     if (agg not in AGG and agg != "path") or blend not in BLEND:
         raise ValueError(f"agg in {sorted(AGG) + ['path']} and blend in {sorted(BLEND)} expected, got {agg!r}, {blend!r}")
@@ -796,7 +887,7 @@ def _check_options(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
             raise RuntimeError("manipose_amd: lift_sequences takes device tensors or numpy arrays (got a CPU tensor); there is no CPU fallback")
     if batch is None:
         batch = (int(getattr(model, "max_batch_hint", 0)) // (2 if tta else 1)) or 16
-    return opt._replace(cam_tables=cam_tables, T=T, J=J, K=K, lengths=lengths, table=table, skeleton=sk, parents=parents,
+    return opt._replace(cam_tables=cam_tables, T=T, J=J, K=K, lengths=lengths, table=table, skeleton=sk, parents=parents, rot_tables=rot_tables,
                         windows=windows, batch=max(1, int(batch)), dev=params[0].device)
 
 
@@ -1015,31 +1106,48 @@ def _place_stage(opt, plan, score=None):
     return placed, d_floor
 
 
+def _rotations_stage(opt, plan):
+    """The joint rotations of the poses AS EMITTED - after path, smoothing, rigid and place / world, so with ``frame="world"`` the root quaternion is
+    in the world frame; local rotations do not care - and, with ``return_hyps``, of every hypothesis: the dict quat (Ntot, J, 4), ok (Ntot,) and
+    hyps_quat (Ntot, K, J, 4), hyps_ok (Ntot, K) of all sequences.  The poses are read only.  (No padded frames here: ``d_off`` describes
+    ``out_all``.)"""
+    lib, S, (parents, rest) = _lib.load(), len(plan.lens), opt.rot_tables
+    quat, ok, _ = _rotations(lib, plan.out_all.unsqueeze(1), plan.d_off, S, parents, rest, opt.rotations_continuous)
+    rot = {"quat": quat[:, 0], "ok": ok[:, 0]}
+    if opt.return_hyps:
+        rot["hyps_quat"], rot["hyps_ok"], _ = _rotations(lib, plan.hyp_all, plan.d_off, S, parents, rest, opt.rotations_continuous)
+    return rot
+
+
 def _cut_score(score, s):
     return {k: (_cut_score(v, s) if isinstance(v, dict) else v[s]) for k, v in score.items()}
 
 
-def _per_sequence(opt, plan, bones, placed, d_floor, chosen=None, score=None):
+def _per_sequence(opt, plan, bones, placed, d_floor, chosen=None, score=None, rot=None):
     """the buffers of all sequences cut into the per-sequence lists of ``_Lifted``"""
     info = None
     if opt.return_place:
         per_seq = {k: torch.split(v, plan.out_lens, dim=0) for k, v in placed.items()}
         info = [dict({k: v[i] for k, v in per_seq.items()}, **({"floor": d_floor[i]} if opt.floor else {})) for i in range(len(plan.lens))]
-    return _Scored(list(torch.split(plan.out_all, plan.out_lens, dim=0)),
+    turns = None
+    if opt.return_rotations:
+        per_seq = {k: torch.split(v, plan.out_lens, dim=0) for k, v in rot.items()}
+        turns = [{k: v[i] for k, v in per_seq.items()} for i in range(len(plan.lens))]
+    return _Rotated(list(torch.split(plan.out_all, plan.out_lens, dim=0)),
                    list(torch.split(plan.hyp_all, plan.out_lens, dim=0)) if opt.return_hyps else None,
                    list(bones.unbind(0)) if opt.return_bones else None, info,
                    list(zip(torch.split(chosen[0], plan.out_lens, dim=0), chosen[1].unbind(0))) if opt.return_path else None,
-                   [_cut_score(score, s) for s in range(len(plan.lens))] if opt.return_score else None)
+                   [_cut_score(score, s) for s in range(len(plan.lens))] if opt.return_score else None, turns)
 
 
 @torch.no_grad()
 def _lift_sequences(model, poses_2d, **options):
-    """``lift_sequences`` with its results by name (``_Scored``: ``_Lifted`` and the score): check options -> upload -> every sequence lifted on its own ->
-    hypothesis path -> smoothed poses -> rigid stage -> score -> place (-> smoothed trajectories -> their score) / world / floor stage -> per-sequence lists."""
+    """``lift_sequences`` with its results by name (``_Rotated``: ``_Lifted``, the score and the rotations): check options -> upload -> every sequence lifted on its own ->
+    hypothesis path -> smoothed poses -> rigid stage -> score -> place (-> smoothed trajectories -> their score) / world / floor stage -> joint rotations -> per-sequence lists."""
     opt = _check_options(model, poses_2d, **options)
     if not opt.seqs:
-        return _Scored([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place, opt.return_path,
-                                                                   opt.return_score)))
+        return _Rotated([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place, opt.return_path,
+                                                                    opt.return_score, opt.return_rotations)))
     plan = _upload(model, opt)
     model_rows = []
     was_training = model.training
@@ -1057,13 +1165,15 @@ def _lift_sequences(model, poses_2d, **options):
     bones = _rigid_stage(opt, plan, model_rows) if opt.rigid else None
     score = _score_stage(opt, plan, model) if opt.return_score else None
     placed, d_floor = _place_stage(opt, plan, score) if opt.place or opt.world else (None, None)
-    return _per_sequence(opt, plan, bones, placed, d_floor, chosen, score)
+    rot = _rotations_stage(opt, plan) if opt.rotations else None
+    return _per_sequence(opt, plan, bones, placed, d_floor, chosen, score, rot)
 
 
 def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave", blend="mean", return_hyps=False, batch=None, scale=1.0,
                    keep_padding=False, rigid=False, lengths=None, symmetric=False, return_bones=False, cameras=None, place=False, frame="camera",
                    floor=False, return_place=False, smooth_poses=0, smooth_traj=0, smooth_degree=2, smooth_taper="uniform", path_sigma=PATH_SIGMA,
-                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False, place_refine=0):
+                   path_switch=PATH_SWITCH, return_path=False, targets=None, return_score=False, place_refine=0, rotations=False,
+                   rotations_continuous=True, return_rotations=False):
     """One 3-D pose per frame of every sequence.  ``poses_2d``: a list of (N_i, 17, 2) device tensors or numpy arrays (or one such
     array); returns a list of (N_i, 17, 3) device tensors, and with ``return_hyps`` also a list of (N_i, K, 17, 4) (every hypothesis
     and its score, from the un-mirrored pass).  ``stride`` (default T: non-overlapping windows) in 1..T; ``blend`` "mean" averages the
@@ -1127,13 +1237,25 @@ def lift_sequences(model, poses_2d, *, stride=None, tta=True, agg="weighted_ave"
     every hypothesis ((K,), (K, J), (K, J - 1)) and ``oracle_mpjpe`` the mean over the frames of the best hypothesis' error.  With ``place`` the key
     ``traj`` holds ``score_traj()``'s ``frames``, ``ate``, ``rmse``, ``velocity``, ``accel`` of the trajectory the world frame uses (smoothed with
     ``smooth_traj``) against the targets' joint 0, over the frames whose fit is ``ok`` (``filled`` when smoothed).  Whether any option lowers these
-    numbers on real data has not been measured here.  Not with ``keep_padding``."""
+    numbers on real data has not been measured here.  Not with ``keep_padding``.
+
+    Joint rotations (``rotations=False``, the default: nothing changes by a bit, and no dict gains a key).  ``rotations``: ``mp_lift_rotations``
+    (``pose_rotations()`` has the rule) runs LAST, on the poses as they are emitted - after the path, the smoothing, the rigid stage and placing / the
+    world frame, so with ``frame="world"`` the root quaternion is in the world frame (local rotations do not care) - and, with ``return_hyps``, on
+    every hypothesis; the poses are not modified.  ``return_rotations`` appends one dict per sequence (the results come in the order poses, hyps,
+    bones, place, path, score, rotations): ``quat`` (N, J, 4) float32 unit quaternions (w, x, y, z), ``ok`` (N,) uint8, and with hypotheses
+    ``hyps_quat`` (N, K, J, 4), ``hyps_ok`` (N, K).  ``rotations_continuous`` (default on) keeps every joint's quaternion track in one hemisphere
+    from frame to frame within its sequence.  With ``rigid`` the triple (root trajectory or origin, ``quat``, ``bones``) reproduces the emitted poses
+    through the decoder's forward kinematics; without ``rigid`` it reproduces them only with each frame's own measured bone lengths.  The twist about
+    a bone is fixed at zero by construction: a convention, not a measurement, and what these rotations are worth on real data has not been measured
+    here.  Not with ``keep_padding``."""
     res = _lift_sequences(model, poses_2d, stride=stride, tta=tta, agg=agg, blend=blend, return_hyps=return_hyps, batch=batch, scale=scale,
                           keep_padding=keep_padding, rigid=rigid, lengths=lengths, symmetric=symmetric, return_bones=return_bones, cameras=cameras,
                           place=place, frame=frame, floor=floor, return_place=return_place, smooth_poses=smooth_poses, smooth_traj=smooth_traj,
                           smooth_degree=smooth_degree, smooth_taper=smooth_taper, path_sigma=path_sigma, path_switch=path_switch,
-                          return_path=return_path, targets=targets, return_score=return_score, place_refine=place_refine)
-    asked = [r for r in res if r is not None]                # in the order poses, hyps, bones, place, path, score
+                          return_path=return_path, targets=targets, return_score=return_score, place_refine=place_refine, rotations=rotations,
+                          rotations_continuous=rotations_continuous, return_rotations=return_rotations)
+    asked = [r for r in res if r is not None]                # in the order poses, hyps, bones, place, path, score, rotations
     return asked[0] if len(asked) == 1 else tuple(asked)
 
 
@@ -1148,6 +1270,6 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
     return torch.cat(res.hyps if hyps else res.poses, dim=0).cpu().numpy()
 
 
-__all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "reproject_poses", "to_world", "smooth_poses", "smooth_traj",
+__all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "reproject_poses", "pose_rotations", "to_world", "smooth_poses", "smooth_traj",
            "select_path", "score_poses", "score_traj", "lift_sequences",
            "lift_action"]

@@ -7,6 +7,7 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --place [frames=3000] [K=5] [reps=50]
     python tools/lift_bench.py --path [frames=3000] [K=5] [reps=50]
     python tools/lift_bench.py --score [frames=3000] [K=5] [reps=50]
+    python tools/lift_bench.py --rotations [frames=3000] [K=5] [reps=50]
 --place times only the two kernels that put a lifted sequence in the scene (mp_lift_place: root translation and reprojection error of every
 hypothesis; mp_lift_world: world frame, with and without the floor) on `frames` frames x K hypotheses of one sequence with S11's first camera,
 and then, in the same process, mp_lift_smooth (radius 4 and 32, degree 2, uniform) on the merged poses (frames, 17, 3), the hypotheses
@@ -19,7 +20,10 @@ on `frames` frames x K hypotheses of 17 joints, as ONE sequence (the scan is one
 on the same hypotheses.
 --score times mp_lift_score (the score of lifted poses against ground truth: score, alignment and finalize kernels) through its private launcher
 on `frames` frames x K hypotheses of 17 joints with bones, with and without the Procrustes alignment, as ONE sequence and cut into 16, and on the
-(frames, K, 3) trajectories, next to mp_lift_rigid on the same hypotheses."""
+(frames, K, 3) trajectories, next to mp_lift_rigid on the same hypotheses.
+--rotations times mp_lift_rotations (the joint rotations of lifted poses: the rotation kernel and, with the continuity flag, the sign kernel) through
+its private launcher on `frames` frames x K hypotheses of 17 joints, canonical signs alone and sign-continuous as ONE sequence and cut into 16,
+with and without rot6d, next to mp_lift_rigid on the same hypotheses."""
 import os
 import sys
 
@@ -175,6 +179,39 @@ def score_bench(argv):
     print(f"mp_lift_rigid on the same hypotheses: {us:,.1f} us", flush=True)
 
 
+def rotations_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.lifting import _parents_c, _rest_c, _rigid, _rotations, _skeleton_of
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    K = int(argv[1]) if len(argv) > 1 else 5
+    reps = int(argv[2]) if len(argv) > 2 else 50
+    assert torch.cuda.is_available(), "needs an MI355X"
+    lib = _lib.load()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    hyps = torch.rand(frames, K, 17, 4, device="cuda", generator=g)
+    hyps[..., :3] = 0.3 * torch.randn(frames, K, 17, 3, device="cuda", generator=g)
+    lengths, parents, rest = torch.full((1, 16), 0.25, device="cuda"), _parents_c(_skeleton_of(), 17), _rest_c(_skeleton_of(), 17)
+    one = torch.tensor([0, frames], dtype=torch.int64, device="cuda")
+    moved = hyps.numel() * 4 + frames * K * (17 * 16 + 1)
+    print(f"--rotations: {frames} frames x {K} hypotheses, {hyps.numel() * 4 / 1e6:.2f} MB of hypotheses read, {frames * K * 17 * 16 / 1e6:.2f} MB of quaternions "
+          f"written; {reps} calls each after 5 of warm-up (the output allocations are inside the time)", flush=True)
+    us = timed_us(lambda: _rotations(lib, hyps, one, 1, parents, rest, False), reps)
+    print(f"mp_lift_rotations, canonical signs (one kernel): {us:,.1f} us  {frames * K / us:,.2f} M poses/s, {moved / us / 1e3:,.1f} GB/s of the "
+          f"{moved / 1e6:.2f} MB it must move", flush=True)
+    us = timed_us(lambda: _rotations(lib, hyps, one, 1, parents, rest, False, True), reps)
+    print(f"mp_lift_rotations, canonical signs, with rot6d: {us:,.1f} us  {frames * K / us:,.2f} M poses/s", flush=True)
+    for S in (1, 16):
+        d_off = torch.linspace(0, frames, S + 1, device="cuda").round().to(torch.int64)
+        us = timed_us(lambda: _rotations(lib, hyps, d_off, S, parents, rest, True), reps)
+        print(f"mp_lift_rotations, sign-continuous, {S} sequence(s) (two kernels): {us:,.1f} us  {frames * K / us:,.2f} M poses/s", flush=True)
+    work = hyps.clone()
+    us = timed_us(lambda: _rigid(lib, work, one, 1, lengths, parents), reps)
+    print(f"mp_lift_rigid on the same hypotheses: {us:,.1f} us", flush=True)
+
+
+if "--rotations" in sys.argv:
+    rotations_bench([a for a in sys.argv[1:] if a != "--rotations"])
+    sys.exit(0)
 if "--score" in sys.argv:
     score_bench([a for a in sys.argv[1:] if a != "--score"])
     sys.exit(0)
