@@ -501,6 +501,7 @@ int mp_bone_length_means(const float* poses, int64_t Ntot, int J, const int64_t*
  * traj (Ntot, inner, 3) and reproj (Ntot, inner) floats, ok (Ntot, inner) bytes.  ok = 0 with t = (0, 0, 0) and reproj = 0: W <= 0, a non-finite sum,
  * or D <= 1e-9 W Q (D / (W Q) lies in [0, 1]; 0: all weighted keypoints coincide).  ok = 0 with t and reproj stored as computed: a weighted joint
  * with Z_j + tz <= 0.  Otherwise ok = 1.  A pose's result depends on no other pose.
+ * The call is mp_lift_place_refine (below) with start = start_ok = steps = null and iters = 0: one kernel serves both.
  * mp_lift_world (poses updated IN PLACE): every joint p <- qrot(q_s, p + traj) + trans_s,  qrot(q, v) = v + 2 (w (q_xyz x v) + q_xyz x (q_xyz x v))
  * (the reference's qrot, data/quaternion.py:6-20: q is not normalised); quat (S, 4) = (w, x, y, z); traj (Ntot, inner, 3) or null, trans (S, 3) or
  * null: with both null this is camera_to_world(., R, t = 0).  floor_mode 0: nothing more.  1: after the float32 results are stored, floor[s] (S floats,
@@ -534,7 +535,8 @@ int mp_lift_world(float* poses, int64_t Ntot, int inner, int J, int C, const flo
  *    and no damping: the start lies centimetres from the minimum, where Gauss-Newton converges in about three steps; the 1e-6 slack keeps
  *    rounding from deciding at the minimum, where F' / F is 1.
  * 4. Store.  traj = (float) t,  reproj = (float)(E / W) at the final t,  ok = 1,  steps = steps taken.
- * iters = 0 with start null: every output has the bits of mp_lift_place.  iters = 0 with start given: the reprojection error of a given trajectory.
+ * iters = 0 with start null IS mp_lift_place: that entry point makes exactly this call (steps null), so the two share every bit by construction.
+ * iters = 0 with start given: the reprojection error of a given trajectory.
  * One lane owns one pose and a pose depends on no other pose; no atomics: identical bits on every call.  The call does not synchronise. */
 #define MP_LIFT_REFINE_MAXITERS 16
 int mp_lift_place_refine(const float* poses, int64_t Ntot, int inner, int J, int C, const float* kp, const int64_t* seq_offset, int S, const float* intr,

@@ -15,13 +15,15 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 # library: 171.6 / 170.9 -> 170.2 / 169.9 ms per step).  The feature flag also reaches the host pass, which says it does not know it: filtered.
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -fno-slp-vectorize -Xclang -target-feature -Xclang -packed-fp32-ops -Wall -Wno-unused-function $EXTRA"
 pids=()
+objs=()
 for f in "$HERE"/*.hip; do
   o="$OBJ/$(basename "${f%.hip}").o"
+  objs+=("$o")                 # the link takes the objects of the sources that are present, not a stale one of a deleted source
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/common.h" -nt "$o" ] || [ "$HERE/kernels.h" -nt "$o" ] || [ "$HERE/hazard.h" -nt "$o" ] || [ "$HERE/kloop_asm.inc" -nt "$o" ] || [ "$HERE/lift_common.h" -nt "$o" ] || [ "$HERE/../../include/manipose_hip.h" -nt "$o" ]; then
     $HIPCC $FLAGS -c "$f" -o "$o" 2> >(grep -v "is not a recognized feature for this target" >&2) &
     pids+=($!)
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ"/*.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "${objs[@]}"
 echo "built $OUT"

@@ -1,14 +1,29 @@
-// Placing lifted sequences in the scene (include/manipose_hip.h: mp_lift_place, mp_lift_world): what mp_lift_merge / mp_lift_rigid leave is
-// root-relative and in the camera's frame.  mp_lift_place fits, per pose, the root translation whose pinhole projection meets the sequence's own
-// 2-D keypoints, and reports the reprojection error under the full H36M camera model (the reference's project_to_2d,
-// hpe/mh_so3_hpe/data/camera.py:35-70; project_to_2d_linear :73-95); mp_lift_world is the reference's camera_to_world (:31-32, qrot of
-// data/quaternion.py:6-20) with the fitted translation added first, and the floor line of its prepare_prediction_for_viz (z -= min z).
+// Placing lifted sequences in the scene (include/manipose_hip.h: mp_lift_place, mp_lift_place_refine, mp_lift_world): what mp_lift_merge /
+// mp_lift_rigid leave is root-relative and in the camera's frame.  The fit kernel finds, per pose, the root translation whose pinhole projection
+// meets the sequence's own 2-D keypoints - that fit is linear in t - and reports the reprojection error under the full H36M camera model (the
+// reference's project_to_2d, hpe/mh_so3_hpe/data/camera.py:35-70; project_to_2d_linear :73-95); mp_lift_world is the reference's camera_to_world
+// (:31-32, qrot of data/quaternion.py:6-20) with the fitted translation added first, and the floor line of its prepare_prediction_for_viz
+// (z -= min z).
+//
+// ONE FIT KERNEL serves both entry points: mp_lift_place is mp_lift_place_refine with start = start_ok = steps = null and iters = 0.  Under the
+// H36M calibration (k1 ~ -0.2, k2 ~ 0.25) the pinhole fit and the full model disagree by centimetres of depth, so from that fit (or from a given
+// trajectory) the kernel takes up to `iters` undamped Gauss-Newton steps on the weighted squared reprojection error of the FULL projection, with the
+// analytic 2 x 3 Jacobian per joint and a 3 x 3 solve by cofactors.  With iters = 0 it is the linear fit alone (start null) or the pure reprojection
+// of a given trajectory (start given).  The rule is in the header; tests/lift_place_ref.py and tests/lift_refine_ref.py state it in float64.
 //
 // ONE LANE OWNS ONE POSE, as in lift_rigid.hip; a pose is (C = 3 or 4) x J floats and channel 3 (a hypothesis' score) is neither read nor
-// written.  Everything between the float32 loads and the float32 stores is fp64: 17 joints and a few dozen operations per pose, so the only
-// error against a float64 statement on the same inputs is the final rounding (the fit's condition number is a few hundred; a float32 solve of
-// the same construction misses by 2e-5 m).  The joints are read twice (sums, then reprojection) instead of being kept in a register array.
-// The workload is a few MB (3000 frames x 5 hypotheses x 272 B), nobody has measured it, and no rate is claimed.
+// written.  Everything between the float32 loads and the float32 stores is fp64: 17 joints and a few dozen operations per pose and pass, so the
+// only error against a float64 statement on the same inputs is the final rounding (the linear fit's condition number is a few hundred; a float32
+// solve of the same construction misses by 2e-5 m).  Sums run in joint order; a pose depends on no other pose; no atomics: the same bits on every
+// call.  The fit kernel runs in workgroups of one wave and reads a pose's joints iters + 2 times (the linear sums, the first evaluation, one
+// evaluation per step) straight from global memory, where a lane sits J C floats (204 or 272 bytes) from its neighbour; nothing is kept in a
+// register array indexed at run time.  Copying the workgroup's 64 poses and their frames' keypoints into LDS first (consecutive lanes on
+// consecutive floats, odd rows, as lift_score_align_kernel does) was built and measured on an MI355X on 3000 frames x 5 hypotheses (4 MB of poses,
+// which stay in L2): staged 18.4 / 47.8 / 90.7 us at iters 0 / 3 / 8, this form 15.8 / 42.6 / 88.8 us, this form in workgroups of 256 lanes
+// 15.4 / 47.9 / 99.4 us.  Staging does not pay: the time goes to the fp64 arithmetic of a pass (five divisions and a square root per joint), not to
+// the loads.  (mp_lift_place once had a kernel of its own, the linear fit and one error pass in workgroups of 256 lanes: into outputs allocated
+// once it took 14.9 us on the same poses, this kernel at iters = 0 takes 11.7 us - 59 workgroups against 235 on 256 CUs.  One kernel is also one
+// place to change the camera model and the degenerate-fit rule.  DESIGN.md, "Refining the placement", has both measurements.)
 //
 // Floor (mode 1): the minimum is taken from the STORED float32 values by a second kernel - MP_LIFT_WORLD_SHARES workgroups per sequence, each
 // over one contiguous share of the sequence's poses, DPP inside a wave, LDS across the 4 waves, one partial per workgroup - and the third
@@ -19,75 +34,167 @@
 namespace mp {
 
 constexpr int FLOOR_SHARES = MP_LIFT_WORLD_SHARES;
+constexpr int REFINE_THREADS = 64;   // lanes of a workgroup of the fit kernel: one wave (235 workgroups for 15,000 poses; 256 lanes measured slower)
 
 // torch.clamp(x, -1, 1): a NaN stays a NaN
-__device__ __forceinline__ double place_clamp1(double x) { return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x); }
+__device__ __forceinline__ double refine_clamp1(double x) { return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x); }
 
-struct PlaceArgs {
+struct RefineArgs {
   const float* poses;            // (Ntot, inner, J, C)
   const float* kp;               // (Ntot, J, 2)
   const long* seq_offset;        // (S + 1) device
   const float* intr;             // (S, 9) device
   const float* weights;          // (J) device or null
+  const float* start;            // (Ntot, inner, 3) or null: the linear fit
+  const unsigned char* start_ok; // (Ntot, inner) or null
   float* traj;                   // (Ntot, inner, 3)
   float* reproj;                 // (Ntot, inner)
   unsigned char* ok;             // (Ntot, inner)
+  unsigned char* steps;          // (Ntot, inner) or null
   long npose;                    // Ntot * inner
-  int inner, J, C, S, distort;
+  int inner, J, C, S, distort, iters;
 };
 
-__global__ __launch_bounds__(POSE_THREADS) void lift_place_kernel(PlaceArgs A) {
-  const long i = (long)blockIdx.x * POSE_THREADS + threadIdx.x;        // pose (frame, inner index)
+struct RefineCam { double fx, fy, cx, cy, k1, k2, k3, p1, p2; };
+
+// what one pass over the weighted joints at a translation gives: F = sum w |r|^2, E = sum w |r|, W = sum w, H = sum w J^T J (upper triangle),
+// g = sum w J^T r, deep = every weighted Z > 0
+struct RefineEval {
+  double F, E, W, H00, H01, H02, H11, H12, H22, g0, g1, g2;
+  bool deep;
+};
+
+// P: the lane's pose (J rows of C floats), U: its frame's keypoints (J rows of 2 floats).  JAC = false leaves H and g at zero
+// (iters = 0: the reprojection error alone)
+template <bool JAC>
+__device__ __forceinline__ RefineEval refine_eval(const float* P, const float* U, const float* weights, int J, int C, int distort, const RefineCam& cam,
+                                                  double tx, double ty, double tz) {
+  RefineEval e = {};
+  e.deep = true;
+  const double fx = cam.fx, fy = cam.fy, cx = cam.cx, cy = cam.cy, k1 = cam.k1, k2 = cam.k2, k3 = cam.k3, p1 = cam.p1, p2 = cam.p2;
+  for (int j = 0; j < J; ++j) {                                        // sums in joint order
+    const double w = weights != nullptr ? (double)weights[j] : 1.0;
+    if (w == 0.0) continue;                                            // a joint of weight 0 is not looked at
+    const double X = (double)P[j * C] + tx, Y = (double)P[j * C + 1] + ty, Z = (double)P[j * C + 2] + tz;
+    if (!(Z > 0.0)) e.deep = false;
+    const double qx = X / Z, qy = Y / Z;
+    const double xx = refine_clamp1(qx), yy = refine_clamp1(qy);
+    double px = xx, py = yy;
+    double a = 1.0, b = 0.0, c = 0.0, d = 1.0;                         // d(px, py) / d(x, y)
+    if (distort) {
+      const double r2 = xx * xx + yy * yy;
+      const double m = 1.0 + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2)) + (p1 * xx + p2 * yy);
+      px = xx * m + p1 * r2;
+      py = yy * m + p2 * r2;
+      if (JAC) {
+        const double dm = k1 + 2.0 * k2 * r2 + 3.0 * k3 * (r2 * r2);
+        const double mx = 2.0 * xx * dm + p1, my = 2.0 * yy * dm + p2;
+        a = m + xx * mx + 2.0 * p1 * xx;
+        b = xx * my + 2.0 * p1 * yy;
+        c = yy * mx + 2.0 * p2 * xx;
+        d = m + yy * my + 2.0 * p2 * yy;
+      }
+    }
+    const double du = fx * px + cx - (double)U[2 * j], dv = fy * py + cy - (double)U[2 * j + 1];
+    const double rr = du * du + dv * dv;
+    e.W += w;
+    e.E += w * sqrt(rr);
+    e.F += w * rr;
+    if (JAC) {
+      const double sx = (qx >= -1.0 && qx <= 1.0) ? 1.0 : 0.0, sy = (qy >= -1.0 && qy <= 1.0) ? 1.0 : 0.0;   // the derivative of the clamp
+      const double iz = 1.0 / Z;
+      const double xz = sx * iz, yz = sy * iz, xq = sx * (-qx / Z), yq = sy * (-qy / Z);   // dx/dt = (xz, 0, xq), dy/dt = (0, yz, yq)
+      const double j00 = fx * (a * xz), j01 = fx * (b * yz), j02 = fx * (a * xq + b * yq);
+      const double j10 = fy * (c * xz), j11 = fy * (d * yz), j12 = fy * (c * xq + d * yq);
+      e.H00 += w * (j00 * j00 + j10 * j10);
+      e.H01 += w * (j00 * j01 + j10 * j11);
+      e.H02 += w * (j00 * j02 + j10 * j12);
+      e.H11 += w * (j01 * j01 + j11 * j11);
+      e.H12 += w * (j01 * j02 + j11 * j12);
+      e.H22 += w * (j02 * j02 + j12 * j12);
+      e.g0 += w * (j00 * du + j10 * dv);
+      e.g1 += w * (j01 * du + j11 * dv);
+      e.g2 += w * (j02 * du + j12 * dv);
+    }
+  }
+  return e;
+}
+
+__global__ __launch_bounds__(REFINE_THREADS) void lift_place_refine_kernel(RefineArgs A) {
+  const int J = A.J, C = A.C;
+  const long i = (long)blockIdx.x * REFINE_THREADS + threadIdx.x;      // pose (frame, inner index)
   if (i >= A.npose) return;
   const long g = i / A.inner;                                          // frame
   const int s = lift_seq_of(A.seq_offset, A.S, g);
   const float* cam = A.intr + (long)s * 9;
-  const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
-  const float* P = A.poses + i * A.J * A.C;
-  const float* U = A.kp + g * A.J * 2;
-  double W = 0.0, Sa = 0.0, Sb = 0.0, Q = 0.0, Sx = 0.0, Sy = 0.0, Sc = 0.0;
-  for (int j = 0; j < A.J; ++j) {                                      // sums in joint order
-    const double w = A.weights != nullptr ? (double)A.weights[j] : 1.0;
-    if (w == 0.0) continue;                                            // a joint of weight 0 is not looked at
-    const double X = P[j * A.C], Y = P[j * A.C + 1], Z = P[j * A.C + 2];
-    const double a = ((double)U[2 * j] - cx) / fx, b = ((double)U[2 * j + 1] - cy) / fy;
-    const double ex = X - a * Z, ey = Y - b * Z;
-    W += w; Sa += w * a; Sb += w * b; Q += w * (a * a + b * b);
-    Sx += w * ex; Sy += w * ey; Sc += w * (a * ex + b * ey);
-  }
-  // [[W, 0, -Sa], [0, W, -Sb], [-Sa, -Sb, Q]] t = [-Sx, -Sy, Sc]; its determinant is W (W Q - Sa^2 - Sb^2)
-  const double WQ = W * Q, det = WQ - Sa * Sa - Sb * Sb;
-  const bool finite = __builtin_isfinite(W) && __builtin_isfinite(Sa) && __builtin_isfinite(Sb) && __builtin_isfinite(Q) && __builtin_isfinite(Sx) &&
-                      __builtin_isfinite(Sy) && __builtin_isfinite(Sc);
-  double tx = 0.0, ty = 0.0, tz = 0.0, err = 0.0;
-  unsigned char ok = 0;
-  if (W > 0.0 && finite && det > 1e-9 * WQ) {
-    tz = (W * Sc - Sa * Sx - Sb * Sy) / det;
-    tx = (Sa * tz - Sx) / W;
-    ty = (Sb * tz - Sy) / W;
-    const double k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[7], p2 = cam[8];
-    ok = 1;
-    for (int j = 0; j < A.J; ++j) {
+  const RefineCam K = {cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7], cam[8]};
+  const float* P = A.poses + i * J * C;
+  const float* U = A.kp + g * J * 2;
+  double tx = 0.0, ty = 0.0, tz = 0.0;
+  bool have = false;                                                   // a translation to evaluate at
+  if (A.start == nullptr) {                                            // the linear fit
+    const double fx = K.fx, fy = K.fy, cx = K.cx, cy = K.cy;
+    double W = 0.0, Sa = 0.0, Sb = 0.0, Q = 0.0, Sx = 0.0, Sy = 0.0, Sc = 0.0;
+    for (int j = 0; j < J; ++j) {                                      // sums in joint order
       const double w = A.weights != nullptr ? (double)A.weights[j] : 1.0;
       if (w == 0.0) continue;
-      const double X = (double)P[j * A.C] + tx, Y = (double)P[j * A.C + 1] + ty, Z = (double)P[j * A.C + 2] + tz;
-      if (!(Z > 0.0)) ok = 0;                                          // behind the camera: t and the error are stored as computed
-      const double xx = place_clamp1(X / Z), yy = place_clamp1(Y / Z);
-      double px = xx, py = yy;
-      if (A.distort) {
-        const double r2 = xx * xx + yy * yy;
-        const double m = 1.0 + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2)) + (p1 * xx + p2 * yy);
-        px = xx * m + p1 * r2;
-        py = yy * m + p2 * r2;
-      }
-      const double du = fx * px + cx - (double)U[2 * j], dv = fy * py + cy - (double)U[2 * j + 1];
-      err += w * sqrt(du * du + dv * dv);
+      const double X = P[j * C], Y = P[j * C + 1], Z = P[j * C + 2];
+      const double a = ((double)U[2 * j] - cx) / fx, b = ((double)U[2 * j + 1] - cy) / fy;
+      const double ex = X - a * Z, ey = Y - b * Z;
+      W += w; Sa += w * a; Sb += w * b; Q += w * (a * a + b * b);
+      Sx += w * ex; Sy += w * ey; Sc += w * (a * ex + b * ey);
     }
-    err /= W;
+    const double WQ = W * Q, det = WQ - Sa * Sa - Sb * Sb;
+    const bool finite = __builtin_isfinite(W) && __builtin_isfinite(Sa) && __builtin_isfinite(Sb) && __builtin_isfinite(Q) && __builtin_isfinite(Sx) &&
+                        __builtin_isfinite(Sy) && __builtin_isfinite(Sc);
+    if (W > 0.0 && finite && det > 1e-9 * WQ) {
+      tz = (W * Sc - Sa * Sx - Sb * Sy) / det;
+      tx = (Sa * tz - Sx) / W;
+      ty = (Sb * tz - Sy) / W;
+      have = true;
+    }
+  } else {
+    const float sx = A.start[i * 3], sy = A.start[i * 3 + 1], sz = A.start[i * 3 + 2];
+    tx = sx; ty = sy; tz = sz;
+    have = (A.start_ok == nullptr || A.start_ok[i] != 0) && __builtin_isfinite(tx) && __builtin_isfinite(ty) && __builtin_isfinite(tz);
+    if (have) {                                                        // ... and a weighted joint to evaluate it on
+      double W = 0.0;
+      for (int j = 0; j < J; ++j) W += A.weights != nullptr ? (double)A.weights[j] : 1.0;
+      have = W > 0.0;
+    }
+    if (!have) {                                                       // copied through, bit for bit
+      A.traj[i * 3] = sx; A.traj[i * 3 + 1] = sy; A.traj[i * 3 + 2] = sz;
+    }
   }
-  A.traj[i * 3] = (float)tx; A.traj[i * 3 + 1] = (float)ty; A.traj[i * 3 + 2] = (float)tz;
+  unsigned char ok = 0, taken = 0;
+  double err = 0.0;
+  if (have) {
+    RefineEval e = A.iters > 0 ? refine_eval<true>(P, U, A.weights, J, C, A.distort, K, tx, ty, tz)
+                               : refine_eval<false>(P, U, A.weights, J, C, A.distort, K, tx, ty, tz);
+    if (e.deep && __builtin_isfinite(e.F)) {
+      ok = 1;
+      for (int k = 0; k < A.iters; ++k) {
+        const double c00 = e.H11 * e.H22 - e.H12 * e.H12, c01 = e.H02 * e.H12 - e.H01 * e.H22, c02 = e.H01 * e.H12 - e.H02 * e.H11;
+        const double det = e.H00 * c00 + e.H01 * c01 + e.H02 * c02, scale = e.H00 * e.H11 * e.H22;
+        if (!(__builtin_isfinite(det) && __builtin_isfinite(scale) && det > 1e-12 * scale)) break;
+        const double c11 = e.H00 * e.H22 - e.H02 * e.H02, c12 = e.H01 * e.H02 - e.H00 * e.H12, c22 = e.H00 * e.H11 - e.H01 * e.H01;
+        const double nx = tx - (c00 * e.g0 + c01 * e.g1 + c02 * e.g2) / det;       // t + d, d = -adj(H) g / det
+        const double ny = ty - (c01 * e.g0 + c11 * e.g1 + c12 * e.g2) / det;
+        const double nz = tz - (c02 * e.g0 + c12 * e.g1 + c22 * e.g2) / det;
+        if (!(__builtin_isfinite(nx) && __builtin_isfinite(ny) && __builtin_isfinite(nz))) break;
+        const RefineEval n = refine_eval<true>(P, U, A.weights, J, C, A.distort, K, nx, ny, nz);
+        if (!(n.deep && n.F <= (1.0 + 1e-6) * e.F)) break;             // (a NaN cost is not taken either)
+        tx = nx; ty = ny; tz = nz; e = n; ++taken;
+      }
+    }
+    err = e.E / e.W;
+    A.traj[i * 3] = (float)tx; A.traj[i * 3 + 1] = (float)ty; A.traj[i * 3 + 2] = (float)tz;
+  } else if (A.start == nullptr) {
+    A.traj[i * 3] = 0.f; A.traj[i * 3 + 1] = 0.f; A.traj[i * 3 + 2] = 0.f;
+  }
   A.reproj[i] = (float)err;
   A.ok[i] = ok;
+  if (A.steps != nullptr) A.steps[i] = taken;
 }
 
 struct WorldArgs {
@@ -166,6 +273,28 @@ __global__ __launch_bounds__(POSE_THREADS) void floor_apply_kernel(WorldArgs A) 
   if (A.floor_mode == 1 && i < A.S) A.floor[i] = floor_merge(A.partial, (int)i);                  // (S <= Ntot <= npose: every sequence has its lane)
 }
 
+// the one launcher of the fit kernel; `who` is the entry point, in whose name the arguments are refused
+static int lift_place_launch(const char* who, const float* poses, int64_t Ntot, int inner, int J, int C, const float* kp, const int64_t* seq_offset, int S,
+                             const float* intr, const float* weights, int distort, const float* start, const uint8_t* start_ok, int iters, float* traj,
+                             float* reproj, uint8_t* ok, uint8_t* steps, void* stream) {
+  static_assert(sizeof(long) == sizeof(int64_t), "LP64");
+  MP_CHECK(poses && kp && seq_offset && intr && traj && reproj && ok, MP_ERR_ARG, "%s: null pointer", who);
+  MP_CHECK(distort == 0 || distort == 1, MP_ERR_ARG, "%s: distort=%d (0: project_to_2d_linear, 1: project_to_2d)", who, distort);
+  MP_CHECK(iters >= 0 && iters <= MP_LIFT_REFINE_MAXITERS, MP_ERR_ARG, "%s: iters=%d outside 0..%d", who, iters, MP_LIFT_REFINE_MAXITERS);
+  MP_CHECK(start_ok == nullptr || start != nullptr, MP_ERR_ARG, "%s: start_ok without start: null pointer", who);
+  long blocks = 0;
+  if (int rc = lift_pose_shape(who, (long)Ntot, inner, J, C, S, &blocks)) return rc;
+  blocks = (Ntot * inner + REFINE_THREADS - 1) / REFINE_THREADS;
+  MP_CHECK(blocks <= 0x7fffffffL, MP_ERR_ARG, "%s: %ld poses: too many for one launch", who, (long)Ntot * inner);
+  RefineArgs a = {};
+  a.poses = poses; a.kp = kp; a.seq_offset = (const long*)seq_offset; a.intr = intr; a.weights = weights; a.start = start; a.start_ok = start_ok;
+  a.traj = traj; a.reproj = reproj; a.ok = ok; a.steps = steps; a.npose = (long)Ntot * inner;
+  a.inner = inner; a.J = J; a.C = C; a.S = S; a.distort = distort; a.iters = iters;
+  hipLaunchKernelGGL(lift_place_refine_kernel, dim3((unsigned)blocks), dim3(REFINE_THREADS), 0, (hipStream_t)stream, a);
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
 }  // namespace mp
 using namespace mp;
 
@@ -173,18 +302,15 @@ extern "C" {
 
 int mp_lift_place(const float* poses, int64_t Ntot, int inner, int J, int C, const float* kp, const int64_t* seq_offset, int S, const float* intr,
                   const float* weights, int distort, float* traj, float* reproj, uint8_t* ok, void* stream) {
-  static_assert(sizeof(long) == sizeof(int64_t), "LP64");
-  MP_CHECK(poses && kp && seq_offset && intr && traj && reproj && ok, MP_ERR_ARG, "mp_lift_place: null pointer");
-  MP_CHECK(distort == 0 || distort == 1, MP_ERR_ARG, "mp_lift_place: distort=%d (0: project_to_2d_linear, 1: project_to_2d)", distort);
-  long blocks = 0;
-  if (int rc = lift_pose_shape("mp_lift_place", (long)Ntot, inner, J, C, S, &blocks)) return rc;
-  PlaceArgs a = {};
-  a.poses = poses; a.kp = kp; a.seq_offset = (const long*)seq_offset; a.intr = intr; a.weights = weights;
-  a.traj = traj; a.reproj = reproj; a.ok = ok; a.npose = (long)Ntot * inner;
-  a.inner = inner; a.J = J; a.C = C; a.S = S; a.distort = distort;
-  hipLaunchKernelGGL(lift_place_kernel, dim3((unsigned)blocks), dim3(POSE_THREADS), 0, (hipStream_t)stream, a);
-  MP_LAUNCH_CHECK();
-  return MP_OK;
+  return lift_place_launch("mp_lift_place", poses, Ntot, inner, J, C, kp, seq_offset, S, intr, weights, distort, nullptr, nullptr, 0, traj, reproj, ok,
+                           nullptr, stream);
+}
+
+int mp_lift_place_refine(const float* poses, int64_t Ntot, int inner, int J, int C, const float* kp, const int64_t* seq_offset, int S, const float* intr,
+                         const float* weights, int distort, const float* start, const uint8_t* start_ok, int iters, float* traj, float* reproj,
+                         uint8_t* ok, uint8_t* steps, void* stream) {
+  return lift_place_launch("mp_lift_place_refine", poses, Ntot, inner, J, C, kp, seq_offset, S, intr, weights, distort, start, start_ok, iters, traj,
+                           reproj, ok, steps, stream);
 }
 
 int mp_lift_world(float* poses, int64_t Ntot, int inner, int J, int C, const float* traj, const int64_t* seq_offset, int S, const float* quat,

@@ -57,8 +57,10 @@ it: the engine's GEMM tile plan depends on the batch, so a window's bits do.
 
 Structure: ``lift_sequences`` is a chain of private stages - ``_check_options`` (every argument error, then an immutable record of resolved
 options), ``_upload`` (keypoints, window tables, offsets and output buffers, once), ``_lift_one`` per sequence (forwards and ONE merge),
-``_path_stage``, ``_smooth_poses_stage``, ``_rigid_stage``, ``_score_stage`` (with ``targets``), ``_place_stage`` (with ``_smooth_traj_stage``, ``_reproj_smooth_stage`` and ``_score_traj_stage`` between its fit and its world transform), ``_rotations_stage`` (last, on the poses as emitted), ``_per_sequence`` - whose result is a ``_Lifted`` record with the fields poses, hyps, bones, place, path, and the score and the rotations.  The
+``_path_stage``, ``_smooth_poses_stage``, ``_rigid_stage``, ``_score_stage`` (with ``targets``), ``_place_stage`` (with ``_smooth_traj_stage``, ``_reproj_smooth_stage`` and ``_score_traj_stage`` between its fit and its world transform), ``_rotations_stage`` (last, on the poses as emitted), ``_per_sequence`` - whose result is ONE record, ``_Lifted``, with the fields poses, hyps, bones, place, path, score, rotations.  The
 public function turns the record into its documented list / tuple in one place; ``lift_action`` and hpe/_entry.py read the fields by name.
+Placing has ONE launcher, ``_place_refine``, as the library has one fit kernel: ``place_poses``, ``reproject_poses`` and ``_place_stage`` all go
+through it, and zero steps from the linear fit is what ``mp_lift_place`` computes.
 """
 from __future__ import annotations
 
@@ -336,6 +338,11 @@ def smooth_poses(poses, seq_offset=None, radius=4, degree=2, taper="uniform"):
     return _smooth(_lib.load(), p4, None, d_off, S, radius, degree, taper)[0].view(poses.shape)
 
 
+def _traj_shape(traj):
+    if traj.dim() not in (2, 3) or traj.shape[-1] != 3 or traj.dtype != torch.float32 or not traj.is_contiguous():
+        raise ValueError(f"traj must be contiguous float32 (Ntot, 3) or (Ntot, inner, 3), got {tuple(traj.shape)} {traj.dtype}")
+
+
 def smooth_traj(traj, ok=None, seq_offset=None, radius=4, degree=2, taper="uniform"):
     """``mp_lift_smooth`` on root trajectories, OUT of place: traj (Ntot, 3) or (Ntot, inner, 3) float32 device tensor as ``place_poses`` returns it,
     ``ok`` uint8 of shape (Ntot[, inner]) or None (every frame is valid): a frame with ok = 0 does not enter any fit, and gets the value the fit
@@ -344,8 +351,7 @@ def smooth_traj(traj, ok=None, seq_offset=None, radius=4, degree=2, taper="unifo
     as for ``smooth_poses``."""
     _smooth_options(radius, degree, taper)
     if torch.is_tensor(traj):
-        if traj.dim() not in (2, 3) or traj.shape[-1] != 3 or traj.dtype != torch.float32 or not traj.is_contiguous():
-            raise ValueError(f"traj must be contiguous float32 (Ntot, 3) or (Ntot, inner, 3), got {tuple(traj.shape)} {traj.dtype}")
+        _traj_shape(traj)
         if ok is not None and (not torch.is_tensor(ok) or tuple(ok.shape) != tuple(traj.shape[:-1]) or ok.dtype != torch.uint8):
             raise ValueError(f"ok must be a uint8 tensor of shape {tuple(traj.shape[:-1])}, got "
                              f"{(tuple(ok.shape), ok.dtype) if torch.is_tensor(ok) else type(ok).__name__}")
@@ -517,8 +523,7 @@ def score_traj(traj, target, ok=None, seq_offset=None):
     distance, ``rmse`` the root of the mean squared distance, ``velocity`` / ``accel`` the mean norms of the first / second differences of the error
     over consecutive counted frames of one sequence.  A ratio whose count is 0 is NaN.  ``seq_offset`` as for ``score_poses``."""
     if torch.is_tensor(traj):
-        if traj.dim() not in (2, 3) or traj.shape[-1] != 3 or traj.dtype != torch.float32 or not traj.is_contiguous():
-            raise ValueError(f"traj must be contiguous float32 (Ntot, 3) or (Ntot, inner, 3), got {tuple(traj.shape)} {traj.dtype}")
+        _traj_shape(traj)
         if not torch.is_tensor(target) or tuple(target.shape) != (int(traj.shape[0]), 3) or target.dtype != torch.float32 or not target.is_contiguous():
             raise ValueError(f"target must be a contiguous float32 tensor ({int(traj.shape[0])}, 3), got "
                              f"{(tuple(target.shape), target.dtype) if torch.is_tensor(target) else type(target).__name__}")
@@ -573,26 +578,13 @@ def camera_table(cameras):
     return rows[:, :9].copy(), rows[:, 9:13].copy(), rows[:, 13:16].copy()
 
 
-def _place(lib, p4, kp, d_off, S, d_intr, d_w, distort):
-    ntot, inner, J, ch = (int(v) for v in p4.shape)
-    dev = p4.device
-    traj = torch.empty(ntot, inner, 3, dtype=torch.float32, device=dev)
-    reproj = torch.empty(ntot, inner, dtype=torch.float32, device=dev)
-    ok = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
-    if ntot > 0:
-        with torch.cuda.device(dev):
-            _lib.check(lib.mp_lift_place(_lib.ptr(p4), ntot, inner, J, ch, _lib.ptr(kp), _lib.ptr(d_off), S, _lib.ptr(d_intr), _lib.ptr(d_w),
-                                         int(bool(distort)), _lib.ptr(traj), _lib.ptr(reproj), _lib.ptr(ok), _lib.stream_ptr()), "mp_lift_place")
-    return traj, reproj, ok
-
-
 def _is_iters(n):
     return isinstance(n, (int, np.integer)) and not isinstance(n, (bool, np.bool_)) and 0 <= int(n) <= REFINE_MAXITERS
 
 
 def _place_refine(lib, p4, kp, d_off, S, d_intr, d_w, distort, iters, start=None, start_ok=None):
-    """``mp_lift_place_refine`` on p4 (Ntot, inner, J, C): (traj, reproj, ok, steps), new tensors; start (Ntot, inner, 3) or None: the linear fit,
-    start_ok (Ntot, inner) uint8 or None"""
+    """``mp_lift_place_refine`` on p4 (Ntot, inner, J, C), the one launcher of the fit: (traj, reproj, ok, steps), new tensors; start (Ntot, inner, 3)
+    or None: the linear fit (with iters = 0: what ``mp_lift_place`` computes, by the same kernel), start_ok (Ntot, inner) uint8 or None"""
     ntot, inner, J, ch = (int(v) for v in p4.shape)
     dev = p4.device
     traj = torch.empty(ntot, inner, 3, dtype=torch.float32, device=dev)
@@ -632,6 +624,11 @@ def _place_inputs(poses, keypoints_2d, intrinsics, seq_offset, weights, who):
     return p4, keypoints_2d.contiguous(), d_off, S, d_intr, d_w
 
 
+def _traj_of_poses(traj, poses):
+    if tuple(traj.shape) != tuple(poses.shape[:-2]) + (3,) or traj.dtype != torch.float32:
+        raise ValueError(f"traj must be float32 {tuple(poses.shape[:-2]) + (3,)}, got {tuple(traj.shape)} {traj.dtype}")
+
+
 def place_poses(poses, keypoints_2d, intrinsics, seq_offset=None, weights=None, distort=True, refine=0, return_steps=False):
     """``mp_lift_place`` on device tensors: per pose the root translation that fits the frame's 2-D keypoints, and the reprojection error.
     ``poses`` (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32 (channel 3, a hypothesis' score, is not read); ``keypoints_2d`` (Ntot, J, 2) in
@@ -649,10 +646,7 @@ def place_poses(poses, keypoints_2d, intrinsics, seq_offset=None, weights=None, 
     if not _is_iters(refine):
         raise ValueError(f"refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: the linear fit alone), got {refine!r}")
     p4, kp, d_off, S, d_intr, d_w = _place_inputs(poses, keypoints_2d, intrinsics, seq_offset, weights, "place_poses")
-    if int(refine) == 0 and not return_steps:
-        res = _place(_lib.load(), p4, kp, d_off, S, d_intr, d_w, distort)
-    else:
-        res = _place_refine(_lib.load(), p4, kp, d_off, S, d_intr, d_w, distort, refine)[:4 if return_steps else 3]
+    res = _place_refine(_lib.load(), p4, kp, d_off, S, d_intr, d_w, distort, refine)[:4 if return_steps else 3]
     return tuple(r[:, 0] for r in res) if poses.dim() == 3 else tuple(res)
 
 
@@ -665,8 +659,7 @@ def reproject_poses(poses, traj, keypoints_2d, intrinsics, ok=None, seq_offset=N
     finite, else 1."""
     if torch.is_tensor(poses) and torch.is_tensor(traj):
         _poses4_shape(poses)
-        if tuple(traj.shape) != tuple(poses.shape[:-2]) + (3,) or traj.dtype != torch.float32:
-            raise ValueError(f"traj must be float32 {tuple(poses.shape[:-2]) + (3,)}, got {tuple(traj.shape)} {traj.dtype}")
+        _traj_of_poses(traj, poses)
         _score_valid(ok, traj.shape[:-1], "ok")
     if not torch.is_tensor(traj) or not traj.is_cuda or (ok is not None and not ok.is_cuda):
         raise RuntimeError("manipose_amd: reproject_poses takes device tensors; there is no CPU fallback")
@@ -690,8 +683,7 @@ def to_world(poses, orientation, translation=None, traj=None, seq_offset=None, f
     if traj is not None:
         if not torch.is_tensor(traj) or not traj.is_cuda:
             raise RuntimeError("manipose_amd: to_world takes device tensors; there is no CPU fallback")
-        if tuple(traj.shape) != tuple(poses.shape[:-2]) + (3,) or traj.dtype != torch.float32:
-            raise ValueError(f"traj must be float32 {tuple(poses.shape[:-2]) + (3,)}, got {tuple(traj.shape)} {traj.dtype}")
+        _traj_of_poses(traj, poses)
         traj = traj.contiguous()
     if floor is True:
         d_floor = torch.empty(S, dtype=torch.float32, device=dev)
@@ -755,12 +747,9 @@ _Options = namedtuple("_Options", "seqs tta agg blend scale return_hyps keep_pad
 # win_seq (zeros) of a one-sequence merge; bone_mirror (lengths="model"): bone of joint j <- bone of joint mirror[j]; d_*: device copies
 _Plan = namedtuple("_Plan", "p2 lens out_lens out_off first win_start merge_off h_zero d_off d_merge_off d_seq d_start d_zero d_flip mirror "
                             "bone_mirror out_all hyp_all gt", defaults=(None,))
-# Per-sequence lists of what a lift returns; a field that was not asked for is None
-_Lifted = namedtuple("_Lifted", "poses hyps bones place path", defaults=(None,) * 4)
-# ... and what _lift_sequences returns: the same with the per-sequence score dicts of ``targets`` / ``return_score``
-_Scored = namedtuple("_Scored", _Lifted._fields + ("score",), defaults=(None,) * 5)
-# ... and with the per-sequence rotation dicts of ``rotations`` / ``return_rotations``: what _lift_sequences returns
-_Rotated = namedtuple("_Rotated", _Scored._fields + ("rotations",), defaults=(None,) * 6)
+# What _lift_sequences returns: per-sequence lists of the poses, the hypotheses, the bone tables, the place dicts, the (path, cost) pairs, the score
+# dicts and the rotation dicts; a field that was not asked for is None
+_Lifted = namedtuple("_Lifted", "poses hyps bones place path score rotations", defaults=(None,) * 6)
 SCORE_FIELDS = ("frames", "mpjpe", "rmse", "mpjve", "accel", "p_mpjpe", "per_joint", "bone_mean", "bone_std", "bone_err")   # of a score dict
 
 
@@ -1082,15 +1071,11 @@ def _place_stage(opt, plan, score=None):
     d_trans = torch.from_numpy(opt.cam_tables[2] * np.float32(opt.scale)).to(dev) if opt.place else None
     placed, d_floor = {}, None
     if opt.place:
-        if opt.place_refine:                             # the linear fit, then Gauss-Newton steps under the full camera model
-            fit = lambda p4: _place_refine(lib, p4, plan.p2, plan.d_off, S, d_intr, None, True, opt.place_refine)
-            placed["traj"], placed["reproj"], placed["ok"], placed["steps"] = (t[:, 0] for t in fit(out4))
-            if opt.return_hyps:
-                placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"], placed["hyps_steps"] = fit(plan.hyp_all)
-        else:
-            placed["traj"], placed["reproj"], placed["ok"] = (t[:, 0] for t in _place(lib, out4, plan.p2, plan.d_off, S, d_intr, None, True))
-            if opt.return_hyps:
-                placed["hyps_traj"], placed["hyps_reproj"], placed["hyps_ok"] = _place(lib, plan.hyp_all, plan.p2, plan.d_off, S, d_intr, None, True)
+        keys = ("traj", "reproj", "ok", "steps") if opt.place_refine else ("traj", "reproj", "ok")      # (zip stops at the keys: no steps without refine)
+        fit = lambda p4: _place_refine(lib, p4, plan.p2, plan.d_off, S, d_intr, None, True, opt.place_refine)     # the linear fit, then Gauss-Newton steps
+        placed.update((k, t[:, 0]) for k, t in zip(keys, fit(out4)))
+        if opt.return_hyps:
+            placed.update(("hyps_" + k, t) for k, t in zip(keys, fit(plan.hyp_all)))
         if opt.smooth_traj:
             _smooth_traj_stage(opt, plan, placed)
             if opt.place_refine:
@@ -1133,7 +1118,7 @@ def _per_sequence(opt, plan, bones, placed, d_floor, chosen=None, score=None, ro
     if opt.return_rotations:
         per_seq = {k: torch.split(v, plan.out_lens, dim=0) for k, v in rot.items()}
         turns = [{k: v[i] for k, v in per_seq.items()} for i in range(len(plan.lens))]
-    return _Rotated(list(torch.split(plan.out_all, plan.out_lens, dim=0)),
+    return _Lifted(list(torch.split(plan.out_all, plan.out_lens, dim=0)),
                    list(torch.split(plan.hyp_all, plan.out_lens, dim=0)) if opt.return_hyps else None,
                    list(bones.unbind(0)) if opt.return_bones else None, info,
                    list(zip(torch.split(chosen[0], plan.out_lens, dim=0), chosen[1].unbind(0))) if opt.return_path else None,
@@ -1142,12 +1127,12 @@ def _per_sequence(opt, plan, bones, placed, d_floor, chosen=None, score=None, ro
 
 @torch.no_grad()
 def _lift_sequences(model, poses_2d, **options):
-    """``lift_sequences`` with its results by name (``_Rotated``: ``_Lifted``, the score and the rotations): check options -> upload -> every sequence lifted on its own ->
+    """``lift_sequences`` with its results by name (``_Lifted``): check options -> upload -> every sequence lifted on its own ->
     hypothesis path -> smoothed poses -> rigid stage -> score -> place (-> smoothed trajectories -> their score) / world / floor stage -> joint rotations -> per-sequence lists."""
     opt = _check_options(model, poses_2d, **options)
     if not opt.seqs:
-        return _Rotated([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place, opt.return_path,
-                                                                    opt.return_score, opt.return_rotations)))
+        return _Lifted([], *([] if wanted else None for wanted in (opt.return_hyps, opt.return_bones, opt.return_place, opt.return_path,
+                                                                   opt.return_score, opt.return_rotations)))
     plan = _upload(model, opt)
     model_rows = []
     was_training = model.training

@@ -1,5 +1,5 @@
 """Refining placed root trajectories under the full camera model on the device: mp_lift_place_refine against the float64 statement of its rule
-(lift_refine_ref.py), against mp_lift_place (zero steps: identical bits), the recovery of a known translation that the linear fit misses, weights, the
+(lift_refine_ref.py), against mp_lift_place and the recorded bits of both from before they shared a kernel (zero steps: identical bits), the recovery of a known translation that the linear fit misses, weights, the
 guards of the iteration, the start mode (reproject_poses, warm starts), sequences alone and together, argument errors, and lift_sequences /
 run.lift with place_refine.
 
@@ -79,18 +79,53 @@ def test_refine_against_fp64(lib, inner, ch, distort, iters):
     assert len(three) == 3 and all(_same(a.cpu().numpy(), b) for a, b in zip(three, got))
 
 
+def _raw_place(lib, poses, kp, intr, off, weights, distort):
+    """mp_lift_place itself (no Python launcher calls it any more) on (Ntot, inner, J, C) poses: (traj, reproj, ok) as numpy"""
+    from manipose_amd import _lib
+    p4, k, o, cam, w = _dev(poses), _dev(kp), _dev(np.asarray(off, np.int64)), _dev(intr), None if weights is None else _dev(weights)
+    ntot, inner, J, ch = p4.shape
+    traj, reproj = torch.empty(ntot, inner, 3, device="cuda"), torch.empty(ntot, inner, device="cuda")
+    ok = torch.empty(ntot, inner, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.mp_lift_place(_lib.ptr(p4), ntot, inner, J, ch, _lib.ptr(k), _lib.ptr(o), len(off) - 1, _lib.ptr(cam), _lib.ptr(w), int(distort),
+                                 _lib.ptr(traj), _lib.ptr(reproj), _lib.ptr(ok), _lib.stream_ptr()), "mp_lift_place")
+    torch.cuda.synchronize()
+    return [r.cpu().numpy() for r in (traj, reproj, ok)]
+
+
 def test_zero_steps_have_the_bits_of_mp_lift_place(lib):
+    """mp_lift_place and mp_lift_place_refine are one kernel behind two entry points, so comparing them with each other no longer guards the fit.
+    tests/golden/lift_place_bits.npz holds the outputs of the commit BEFORE the two kernels were merged, recorded on gfx950 with this toolchain:
+    of its own mp_lift_place kernel on the three scenes below (distort both ways, weights none and uneven), and of mp_lift_place_refine on
+    fp64_scene(5, 4) at iters 0, 4 and 16 from the linear fit and at iters 0 from a given start / start_ok.  Both entry points must reproduce
+    those bits: a change to the camera model, the degenerate-fit rule or the order of a sum shows here."""
     from manipose_amd import place_poses
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "lift_place_bits.npz"))
     intr = ref.s11_intrinsics()
     poses, kp, _, off = ref.fp64_scene(5, 4)
     uneven = np.random.default_rng(9).uniform(0.25, 4.0, 17).astype(np.float32)
-    for given, k, cam, o in ((poses, kp, intr, off), (poses[:, 0, :, :3].copy(), kp, intr, off), ref.guards_scene()[2:] + (None,)):
+    scenes = (("full", poses, kp, intr, off), ("slice", poses[:, 0, :, :3].copy(), kp, intr, off), ("guards",) + ref.guards_scene()[2:] + (None,))
+    for name, given, k, cam, o in scenes:
         for distort in (True, False):
-            for w in (None, uneven):
+            for wname, w in (("none", None), ("uneven", uneven)):
                 want = [r.cpu().numpy() for r in place_poses(_dev(given), _dev(k), cam, o, w, distort)]
                 got = _refine(given, k, cam, o, w, distort, 0)
                 assert all(_same(a, b) for a, b in zip(got[:3], want)) and not got[3].any()
+                rec = [gold[f"place_{name}_d{int(distort)}_{wname}_{field}"] for field in ("traj", "reproj", "ok")]
+                assert rec[0].dtype == np.float32 and rec[1].dtype == np.float32 and rec[2].dtype == np.uint8
+                p4 = given[:, None] if given.ndim == 3 else given
+                one = _raw_place(lib, p4, k, cam, [0, len(given)] if o is None else o, w, distort)
+                for a, b, r in zip(one, got, rec):                        # mp_lift_place, mp_lift_place_refine at zero steps, the recording
+                    assert _same(a, r) and _same(b.reshape(r.shape), r), (name, distort, wname)
     assert not want[2].all() and want[2].any()                            # (the last scene holds degenerate fits and a joint behind the camera)
+    fields = ("traj", "reproj", "ok", "steps")
+    for iters in (0, 4, 16):                                              # the steps too: the same instructions as before the merge
+        got = _raw(lib, poses, kp, intr, off, iters)
+        assert all(_same(a, gold[f"refine_i{iters}_{field}"]) for a, field in zip(got, fields)), iters
+        assert (got[3] == iters).all()
+    start, start_ok = gold["refine_start_in"], gold["refine_start_ok_in"]
+    got = _raw(lib, poses, kp, intr, off, 0, start, start_ok)
+    assert all(_same(a, gold[f"refine_start_{field}"]) for a, field in zip(got, fields))
+    assert not start_ok.all() and not np.isfinite(start).all() and got[2].any() and not got[2].all()      # (skipped poses are in the recording)
 
 
 def test_recovery_of_a_translation_the_linear_fit_misses(lib):

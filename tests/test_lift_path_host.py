@@ -111,7 +111,7 @@ def test_new_abi_symbols_are_declared_everywhere():
     assert 1 <= chunk <= 1024
     assert lifting.AGG == {"weighted_ave": 0, "best_score": 1}                   # mp_lift_merge's two: the path is not an aggregation of the merge
     assert manipose_amd.select_path is lifting.select_path and "select_path" in lifting.__all__
-    assert lifting._Lifted._fields == ("poses", "hyps", "bones", "place", "path")
+    assert lifting._Lifted._fields == ("poses", "hyps", "bones", "place", "path", "score", "rotations")
     assert os.path.exists(os.path.join(ROOT, "manipose_amd", "csrc", "lift_path.hip"))
     if os.path.exists(_lib.LIB_PATH):
         lib = _lib.load()

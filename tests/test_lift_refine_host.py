@@ -177,7 +177,7 @@ def test_new_abi_symbol_is_declared_everywhere():
     assert _lib.ABI_VERSION == 8 and int(re.search(r"#define MP_ABI_VERSION (\d+)", header).group(1)) == 8        # purely additive
     assert int(re.search(r"#define MP_LIFT_REFINE_MAXITERS (\d+)", header).group(1)) == lifting.REFINE_MAXITERS == ref.MAXITERS
     assert manipose_amd.reproject_poses is lifting.reproject_poses and "reproject_poses" in lifting.__all__
-    assert os.path.exists(os.path.join(ROOT, "manipose_amd", "csrc", "lift_refine.hip"))
+    assert os.path.exists(os.path.join(ROOT, "manipose_amd", "csrc", "lift_place.hip"))
     if os.path.exists(_lib.LIB_PATH):
         assert hasattr(_lib.load(), "mp_lift_place_refine")
 

@@ -113,7 +113,7 @@ def test_new_abi_symbol_is_declared_everywhere():
     assert int(re.search(r"#define MP_LIFT_ROT_CONTINUOUS (\d+)", header).group(1)) == lifting.ROT_CONTINUOUS == 1
     assert manipose_amd.pose_rotations is lifting.pose_rotations and "pose_rotations" in lifting.__all__
     assert os.path.exists(os.path.join(ROOT, "manipose_amd", "csrc", "lift_rot.hip"))
-    assert lifting._Rotated._fields == lifting._Scored._fields + ("rotations",)
+    assert lifting._Lifted._fields == ("poses", "hyps", "bones", "place", "path", "score", "rotations")
     if os.path.exists(_lib.LIB_PATH):
         assert hasattr(_lib.load(), "mp_lift_rotations")
 

@@ -108,7 +108,7 @@ def test_new_abi_symbols_are_declared_everywhere():
     assert shares == lifting.SCORE_SHARES and shares > 1                    # more than one workgroup per sequence
     assert manipose_amd.score_poses is lifting.score_poses and manipose_amd.score_traj is lifting.score_traj
     assert "score_poses" in lifting.__all__ and "score_traj" in lifting.__all__
-    assert lifting._Scored._fields == lifting._Lifted._fields + ("score",)
+    assert lifting._Lifted._fields == ("poses", "hyps", "bones", "place", "path", "score", "rotations")
     assert os.path.exists(os.path.join(ROOT, "manipose_amd", "csrc", "lift_score.hip"))
     if os.path.exists(_lib.LIB_PATH):
         lib = _lib.load()

@@ -13,8 +13,9 @@ hypothesis; mp_lift_world: world frame, with and without the floor) on `frames` 
 and then, in the same process, mp_lift_smooth (radius 4 and 32, degree 2, uniform) on the merged poses (frames, 17, 3), the hypotheses
 (frames, K, 17, 4) and the trajectories (frames, K, 3) next to its yardstick mp_lift_rigid on the same arrays (which reads and writes the same
 bytes once; it needs 2 joints, so the trajectory has none): both times, their ratio and the bytes/s of "read once, write once".  Between the two,
-mp_lift_place_refine (Gauss-Newton steps under the full camera model) at iters 0, 3 and 8 and as the pure reprojection of a given trajectory, next
-to its yardstick mp_lift_place on the same arrays, both through their private launchers on tables uploaded once.
+mp_lift_place_refine (Gauss-Newton steps under the full camera model) at iters 0, 3 and 8 and as the pure reprojection of a given trajectory,
+through the private launcher on tables uploaded once; its iters = 0 row is what mp_lift_place runs (one kernel serves both) and the yardstick of the
+others.  One row before them calls mp_lift_place itself into outputs allocated once: the kernel without the launcher's allocations.
 --path times mp_lift_path (one hypothesis per frame, chosen over the whole sequence: cost, scan and gather kernels) through its private launcher
 on `frames` frames x K hypotheses of 17 joints, as ONE sequence (the scan is one wave: the serial case) and cut into 16, next to mp_lift_rigid
 on the same hypotheses.
@@ -80,18 +81,22 @@ def place_bench(argv):
 
 
 def refine_bench(hyps, kp, intr, reps):
-    """mp_lift_place_refine and mp_lift_place through their private launchers on tables uploaded once: kernel against kernel (the allocation of
-    the outputs from torch's caching allocator is inside both times)"""
+    """mp_lift_place_refine through its private launcher on tables uploaded once; ratios against its iters = 0 row, which is mp_lift_place's kernel
+    and arguments (the allocation of the outputs from torch's caching allocator is inside every time)"""
     from manipose_amd import _lib
-    from manipose_amd.lifting import _place, _place_refine
+    from manipose_amd.lifting import _place_refine
     lib, dev, frames, K = _lib.load(), hyps.device, int(hyps.shape[0]), int(hyps.shape[1])
     d_off = torch.tensor([0, frames], dtype=torch.int64, device=dev)
     d_intr = torch.from_numpy(intr).to(dev)
-    print(f"mp_lift_place_refine against mp_lift_place on the same {frames} x {K} poses (full camera model), {reps} launches each after 5 of warm-up:", flush=True)
-    base = timed_us(lambda: _place(lib, hyps, kp, d_off, 1, d_intr, None, True), reps)
-    print(f"mp_lift_place: {base:,.1f} us  {frames * K / base:,.2f} M poses/s", flush=True)
+    print(f"mp_lift_place_refine on {frames} x {K} poses (full camera model), {reps} launches each after 5 of warm-up; ratios against iters=0:", flush=True)
+    out = _place_refine(lib, hyps, kp, d_off, 1, d_intr, None, True, 0)
+    us = timed_us(lambda: lib.mp_lift_place(_lib.ptr(hyps), frames, K, 17, 4, _lib.ptr(kp), _lib.ptr(d_off), 1, _lib.ptr(d_intr), None, 1, _lib.ptr(out[0]),
+                                            _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream_ptr()), reps)
+    print(f"mp_lift_place into outputs allocated once (the kernel alone: a row below that is not well above it is bound by its allocations): {us:,.1f} us", flush=True)
+    base = None
     for iters in (0, 3, 8):
         us = timed_us(lambda: _place_refine(lib, hyps, kp, d_off, 1, d_intr, None, True, iters), reps)
+        base = us if base is None else base
         steps = _place_refine(lib, hyps, kp, d_off, 1, d_intr, None, True, iters)[3].float().mean().item()
         print(f"mp_lift_place_refine iters={iters}: {us:,.1f} us  {frames * K / us:,.2f} M poses/s, ratio {us / base:.2f}; {steps:.2f} steps taken per pose",
               flush=True)
