@@ -273,7 +273,7 @@ def sk_device(model):
 
 LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj", "__hyps_reproj", "__hyps_ok", "__floor", "__cam", "__traj_fit", "__filled",
                  "__hyps_traj_fit", "__hyps_filled", "__path", "__path_cost", "__steps", "__hyps_steps", "__reproj_smooth", "__hyps_reproj_smooth",
-                 "__quat", "__quat_ok", "__hyps_quat", "__hyps_quat_ok")
+                 "__quat", "__quat_ok", "__hyps_quat", "__hyps_quat_ok", "__root", "__choice", "__spread", "__cost", "__views")
 
 
 def lift_place_options(cfg):
@@ -369,6 +369,136 @@ def lift_rotations_options(cfg):
     return rotations, continuous
 
 
+def lift_fuse_options(cfg):
+    """(fuse, sigma, score_weight, refine) of lift.fuse / lift.fuse_sigma / lift.fuse_score_weight / lift.fuse_refine; ValueError for a value or a
+    combination that cannot run - before any model is built."""
+    fuse = cfg.lift.get("fuse", False)
+    sigma, weight, refine = cfg.lift.get("fuse_sigma", 0.02), cfg.lift.get("fuse_score_weight", 1.0), cfg.lift.get("fuse_refine", 3)
+    if not isinstance(fuse, bool):
+        raise ValueError(f"lift.fuse must be true or false, got {fuse!r}")
+    for key, v in (("fuse_sigma", sigma), ("fuse_score_weight", weight)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"lift.{key} is a number, got {v!r}")
+    if not sigma > 0:
+        raise ValueError(f"lift.fuse_sigma must be > 0 (metres), got {sigma!r}")
+    if not 0 <= weight < float("inf"):
+        raise ValueError(f"lift.fuse_score_weight must be finite and >= 0, got {weight!r}")
+    if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
+        raise ValueError(f"lift.fuse_refine counts Gauss-Newton steps, an integer in 0..16, got {refine!r}")
+    if not fuse:
+        if sigma != 0.02 or weight != 1.0 or refine != 3:
+            raise ValueError("lift.fuse_sigma / lift.fuse_score_weight / lift.fuse_refine describe the fusion of a take's views: set lift.fuse=true")
+        return False, float(sigma), float(weight), refine
+    if not bool(cfg.run.lift):
+        raise ValueError("lift.fuse fuses what run.lift lifts: set run.lift=true")
+    if str(cfg.data.dataset) == "3dhp":
+        raise ValueError("lift.fuse needs the cameras' calibration, and the MPI-INF-3DHP files (data.dataset=3dhp) carry none")
+    if bool(cfg.lift.get("keep_padding", False)):
+        raise ValueError("lift.fuse with keep_padding: padded frames have no keypoints of their own")
+    if bool(cfg.data.data_dir) and (str(cfg.model.arch) != "rmcl_manifold" or not 2 <= int(cfg.multi_hyp.n_hyp) <= 8):
+        raise ValueError("lift.fuse chooses among the hypotheses of a take's views: it needs model.arch=rmcl_manifold with multi_hyp.n_hyp in 2..8 "
+                         "(a model without hypotheses can be fused only where every take has one view: synthetic-data mode)")
+    if int(cfg.multi_hyp.n_hyp) > 8 and str(cfg.model.arch) == "rmcl_manifold":
+        raise ValueError("lift.fuse takes at most 8 hypotheses per view: set multi_hyp.n_hyp <= 8")
+    return True, float(sigma), float(weight), refine
+
+
+def _camera_index(cam):
+    """fetch()'s 17th number, a camera dict's "index", or None"""
+    if isinstance(cam, dict):
+        return cam.get("index")
+    a = cam.detach().cpu().numpy() if torch.is_tensor(cam) else np.asarray(cam)
+    return float(a[16]) if a.ndim == 1 and a.shape[0] >= 17 else None
+
+
+def split_takes(cams):
+    """The takes of a group: lists of sequence indices; a new take starts wherever the camera index does not increase (a camera without an index:
+    a take of its own)."""
+    takes, last = [], None
+    for i, cam in enumerate(cams):
+        idx = _camera_index(cam)
+        if not takes or idx is None or last is None or not idx > last:
+            takes.append([])
+        takes[-1].append(i)
+        last = idx
+    return takes
+
+
+def _qrot(q, v):
+    """the dataset's camera-to-world rotation of (N, 3) points in float64 (qrot: q is not normalised)"""
+    q, v = np.asarray(q, np.float64), np.asarray(v, np.float64)
+    uv = np.cross(np.broadcast_to(q[1:], v.shape), v)
+    return v + 2.0 * (q[0] * uv + np.cross(np.broadcast_to(q[1:], v.shape), uv))
+
+
+def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
+    """lift.fuse on one group: its sequences are cut into takes (split_takes), every take's views are fused (fuse_views: one hypothesis per view,
+    chosen jointly; their mean, root-relative in the world's orientation), with lift.rigid re-assembled with the mean of the views' bone tables, and
+    placed with ONE world root per frame (place_views); with lift.floor the take stands on z = 0.  ``res``: the group's _Lifted with hypotheses, taken
+    after the smoothing and rigid stages.  Writes ``<name>.fused<t>`` and its ``__root``, ``__choice``, ``__spread``, ``__cost``, ``__ok`` (consensus
+    and root fit both ok), ``__reproj`` (V, N), ``__steps``, ``__views`` (and ``__floor``) into ``out``; with ``targets`` the take's score into ``scores``."""
+    from manipose_amd import camera_table, fuse_views, place_views, project_rigid, score_poses, score_traj, to_world
+    from manipose_amd.lifting import SCORE_FIELDS
+    _, sigma, weight, refine = lift_fuse_options(cfg)
+    _, world, floor = lift_place_options(cfg)
+    takes = split_takes(cams)
+    for t, views in enumerate(takes):
+        lens = [int(res.hyps[i].shape[0]) for i in views]
+        if len(set(lens)) > 1:
+            raise ValueError(f"lift.fuse: the views {views} of take {t} of {name!r} have {lens} frames: the views of a take show the same frames")
+        if len(views) > 4:
+            raise ValueError(f"lift.fuse: take {t} of {name!r} has {len(views)} views, at most 4 can be fused")
+    V, dev = max(len(v) for v in takes), res.hyps[0].device
+    if all(len(v) == 1 for v in takes):
+        print(f"lift.fuse [{name}]: every take has one view: nothing to agree on, the root is fitted from that view alone", flush=True)
+    K, J = int(res.hyps[0].shape[1]), int(res.hyps[0].shape[2])
+    frames = [int(res.hyps[v[0]].shape[0]) for v in takes]
+    off = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+    hyps = torch.zeros(V, int(off[-1]), K, J, 4, dtype=torch.float32, device=dev)
+    kp = torch.zeros(V, int(off[-1]), J, 2, dtype=torch.float32, device=dev)
+    valid = torch.zeros(V, int(off[-1]), dtype=torch.uint8, device=dev)
+    quat = np.zeros((len(takes), V, 4), np.float32)
+    quat[..., 0] = 1.0
+    for t, views in enumerate(takes):
+        for v, i in enumerate(views):
+            hyps[v, off[t]:off[t + 1]] = res.hyps[i]
+            kp[v, off[t]:off[t + 1]] = torch.as_tensor(seqs[i], dtype=torch.float32).to(dev)
+            valid[v, off[t]:off[t + 1]] = 1
+            quat[t, v] = camera_table([cams[i]])[1][0]
+    nested = [[cams[i] for i in views] + [None] * (V - len(views)) for views in takes]
+    pose, choice, cost, spread, ok = fuse_views(hyps, None if world else quat, valid, off, sigma, weight)
+    if res.bones is not None:                  # lift.rigid: one table per take, the mean of its views'
+        project_rigid(pose, torch.stack([torch.stack([res.bones[i] for i in views]).mean(dim=0) for views in takes]), seq_offset=off)
+    root, reproj, placed, steps = place_views(pose, kp, nested, valid, off, refine=refine, return_steps=True)
+    unit = np.tile(np.array([1, 0, 0, 0], np.float32), (len(takes), 1))
+    scene = to_world(pose.clone(), unit, traj=root, seq_offset=off, floor=True if floor else False)
+    scene, d_floor = scene if floor else (scene, None)
+    if targets is not None:
+        gt_pose, gt_root = [], []
+        for views in takes:                    # the first view's ground truth, rotated into the world
+            cam = np.concatenate(camera_table([cams[views[0]]]), axis=1)[0].astype(np.float64)
+            gt = torch.as_tensor(targets[views[0]]).detach().cpu().numpy().astype(np.float64)
+            gt_pose.append(_qrot(cam[9:13], (gt - gt[:, :1]).reshape(-1, 3)).reshape(gt.shape))
+            gt_root.append(_qrot(cam[9:13], gt[:, 0]) + cam[13:16])
+        d_pose = torch.from_numpy(np.concatenate(gt_pose).astype(np.float32)).to(dev)
+        d_root = torch.from_numpy(np.concatenate(gt_root).astype(np.float32)).to(dev)
+        rec = score_poses(pose, d_pose, seq_offset=off, root_relative=True)
+        ate = score_traj(root, d_root, ok=placed, seq_offset=off)
+    for t, views in enumerate(takes):
+        key, sl = f"{name}.fused{t}", slice(int(off[t]), int(off[t + 1]))
+        out[key] = scene[sl].cpu().numpy()
+        out[key + "__root"], out[key + "__choice"] = root[sl].cpu().numpy(), choice[sl, :len(views)].cpu().numpy()
+        out[key + "__spread"], out[key + "__cost"] = spread[sl].cpu().numpy(), cost[sl].cpu().numpy()
+        out[key + "__ok"] = (ok[sl] & placed[sl]).cpu().numpy()
+        out[key + "__reproj"], out[key + "__steps"] = reproj[:len(views), sl].cpu().numpy(), steps[sl].cpu().numpy()
+        out[key + "__views"] = np.array(views, dtype=np.int64)
+        if floor:
+            out[key + "__floor"] = d_floor[t].cpu().numpy()
+        if targets is not None and scores is not None:
+            scores[key] = {f: getattr(rec, f)[t].cpu().numpy() for f in SCORE_FIELDS}
+            scores[key]["traj"] = {"ate": ate.ate[t].cpu().numpy(), "frames": ate.frames[t].cpu().numpy()}
+
+
 ROTATION_KEYS = {"quat": "__quat", "ok": "__quat_ok", "hyps_quat": "__hyps_quat", "hyps_ok": "__hyps_quat_ok"}      # of a rotations dict -> in lift.npz
 
 
@@ -383,7 +513,7 @@ def synthetic_cameras(groups):
     return cams
 
 
-def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None):
+def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None, fused_scores=None):
     """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
     hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
     it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
@@ -401,7 +531,12 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     poses as emitted, mp_lift_rotations; lift.rotations_continuous) also ``<key>__quat`` (N, 17, 4) float32 unit quaternions (w, x, y, z),
     ``<key>__quat_ok`` (N,) uint8 and with lift.hyps ``<key>__hyps_quat`` (N, K, 17, 4), ``<key>__hyps_quat_ok`` (N, K).
     ``targets`` = {name: [ground truth (N, 17, 3) in metres per sequence]} (lift.score): every sequence is scored against it on the device and the dict
-    ``scores`` receives {key: the score dict of lift_sequences(return_score=True) as numpy values, in metres}; the .npz keeps its keys."""
+    ``scores`` receives {key: the score dict of lift_sequences(return_score=True) as numpy values, in metres}; the .npz keeps its keys.
+    With lift.fuse (``cameras`` needed; lift.fuse_sigma, lift.fuse_score_weight, lift.fuse_refine) the sequences of a group are cut into takes - a
+    new take wherever the camera index, fetch()'s 17th number, does not increase - and every take ``t`` also gets ``<name>.fused<t>`` (N, 17, 3), the
+    views' consensus pose at ONE world root, with ``__root`` (N, 3), ``__choice`` (N, V) uint8, ``__spread``, ``__cost``, ``__ok``, ``__steps`` (N,),
+    ``__reproj`` (V, N), ``__views`` (the sequences' indices within the group) and with lift.floor ``__floor`` (fuse_group); with ``targets`` the dict
+    ``fused_scores`` receives {fused key: score dict} of the fused pose and root against the first view's ground truth in the world."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
     out = {}
@@ -414,13 +549,17 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     rotations, rot_continuous = lift_rotations_options(cfg)
     rot_kw = dict(rotations=True, rotations_continuous=rot_continuous, return_rotations=True) if rotations else {}
     use_cams = place or world
+    fuse, want_hyps = lift_fuse_options(cfg)[0], bool(cfg.lift.hyps)       # the fusion reads the hypotheses whether or not lift.hyps writes them
     score_kw = lambda name: dict(targets=targets[name], return_score=True) if targets is not None else {}
     to_host = lambda v: {k: to_host(x) for k, x in v.items()} if isinstance(v, dict) else v.cpu().numpy()
+    asked = lambda d: d if want_hyps else {k: v for k, v in d.items() if k != "oracle_mpjpe" and not k.startswith("hyps")}
     if use_cams and cameras is None:
         raise ValueError("lift.place / lift.frame=world need the sequences' cameras")
+    if fuse and cameras is None:
+        raise ValueError("lift.fuse needs the sequences' cameras")
     for name, seqs in groups.items():
         res = _lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=agg, blend=cfg.lift.blend,
-                              return_hyps=bool(cfg.lift.hyps), batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
+                              return_hyps=want_hyps or fuse, batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
                               symmetric=bool(cfg.lift.get("symmetric", False)), return_bones=rigid, cameras=cameras[name] if use_cams else None,
                               place=place, frame="world" if world else "camera", floor=floor, return_place=place or floor,
                               smooth_poses=smooth_p, smooth_traj=smooth_t, smooth_degree=smooth_degree, smooth_taper=smooth_taper, **refine_kw, **path_kw, **rot_kw, **score_kw(name))
@@ -428,22 +567,24 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
         for i, p in enumerate(res.poses):
             key = name if len(res.poses) == 1 else f"{name}.{i}"
             out[key] = p.cpu().numpy()
-            if res.hyps is not None:
+            if res.hyps is not None and want_hyps:
                 out[key + "__hyps"] = res.hyps[i].cpu().numpy()
             if res.bones is not None:
                 out[key + "__bones"] = res.bones[i].cpu().numpy()
             if res.place is not None:
-                for k, v in res.place[i].items():
+                for k, v in asked(res.place[i]).items():
                     out[f"{key}__{k}"] = v.cpu().numpy()
             if cam_rows is not None:
                 out[key + "__cam"] = cam_rows[i]
             if res.path is not None:
                 out[key + "__path"], out[key + "__path_cost"] = (v.cpu().numpy() for v in res.path[i])
             if res.rotations is not None:
-                for k, v in res.rotations[i].items():
+                for k, v in asked(res.rotations[i]).items():
                     out[key + ROTATION_KEYS[k]] = v.cpu().numpy()
             if res.score is not None and scores is not None:
-                scores[key] = to_host(res.score[i])
+                scores[key] = to_host(asked(res.score[i]))
+        if fuse:
+            fuse_group(out, name, res, seqs, cameras[name], cfg, targets[name] if targets is not None else None, fused_scores)
     np.savez(path, **out)
     return out
 
@@ -487,6 +628,7 @@ def run(argv, extra_defaults=None):
     lift_path_options(cfg)                     # ... and a lift.agg=path that cannot (with the default train.tta=true: set train.tta=false)
     lift_score_options(cfg)                    # ... and a lift.score without run.lift
     lift_rotations_options(cfg)                # ... and a lift.rotations without run.lift
+    lift_fuse_options(cfg)                     # ... and a lift.fuse without run.lift, without calibration or without hypotheses
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")
@@ -655,13 +797,17 @@ def run(argv, extra_defaults=None):
         groups = {name: sq[1] for name, sq in seqs["test"].items()} if real else synthetic_sequences_2d(cfg, cfg.run.seed)
         path = cfg.lift.output if os.path.isabs(str(cfg.lift.output)) else os.path.join(out_dir, str(cfg.lift.output))
         cams = None
-        if any(lift_place_options(cfg)[:2]):
+        if any(lift_place_options(cfg)[:2]) or lift_fuse_options(cfg)[0]:
             cams = seqs["test_cams"] if real else synthetic_cameras(groups)
-        targets, scores = None, {}
+        targets, scores, fused_scores = None, {}, {}
         if lift_score_options(cfg):            # the 3-D ground truth beside the 2-D sequences that are lifted
             targets = {name: sq[0] for name, sq in seqs["test"].items()} if real else synthetic_sequences_3d(cfg, cfg.run.seed)
-        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores)
-        print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if not k.endswith(LIFT_SUFFIXES))} frames of {len(groups)} groups -> {path}", flush=True)
+        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores)
+        is_pose = lambda k: not k.endswith(LIFT_SUFFIXES) and ".fused" not in k
+        print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if is_pose(k))} frames of {len(groups)} groups -> {path}", flush=True)
+        if lift_fuse_options(cfg)[0]:
+            takes = [k for k in lifted if ".fused" in k and not k.endswith(LIFT_SUFFIXES)]
+            print(f"lift.fuse: {len(takes)} takes fused, {sum(lifted[k].shape[0] for k in takes)} frames", flush=True)
         if targets is not None:
             from manipose_amd import report
             written = report.write_lift_score_report(out_dir, scores)
@@ -669,4 +815,7 @@ def run(argv, extra_defaults=None):
             mean = lambda key: 1000.0 * float(np.nansum(n * np.array([float(v[key]) for v in scores.values()])) / max(1.0, n.sum()))
             print(f"lift score (mm, {int(n.sum())} frames of {len(scores)} sequences): mpjpe {mean('mpjpe'):.3f}, p-mpjpe {mean('p_mpjpe'):.3f}, "
                   f"mpjve {mean('mpjve'):.3f}, accel {mean('accel'):.3f} -> {written[0]}", flush=True)
+            if fused_scores:
+                print(f"lift score, fused takes -> {report.write_lift_score_report(out_dir, fused_scores, name='lift_score_fused', joints=False)[0]}",
+                      flush=True)
     return best_val

@@ -664,6 +664,55 @@ int mp_lift_score(const float* pred, int64_t Ntot, int inner, int M, int C, cons
                   const int32_t* parents, double pred_scale, double gt_scale, int flags, double* rows, float* frame_err, double* scratch,
                   int64_t scratch_doubles, void* stream);
 
+/* Fusing the camera views of a take: Human3.6M records every motion with four calibrated cameras at once, and a second camera sees the first one's
+ * depth axis as an image axis - the views resolve each other's ambiguity, in the choice of a hypothesis and in the depth of the root.  The reference
+ * has no counterpart.  A TAKE is a group of up to V views of one motion, 1 <= V <= MP_LIFT_FUSE_MAXV, all with the same number of frames; the views
+ * of all takes lie side by side: a per-view array is (V, Ftot, ...), Ftot the sum of the takes' frame counts.  take_offset (G + 1) device int64 is
+ * used like seq_offset (frame f belongs to the last take g with take_offset[g] <= f; entries clamped to 0 .. Ftot).  valid (V, Ftot) device bytes
+ * or null (every view is valid): a take with fewer than V views marks the missing ones 0 in all of its frames; an invalid view's data is never
+ * looked at.  Per-take camera tables, device floats: quat (G, V, 4) = (w, x, y, z), trans (G, V, 3), intr (G, V, 9) as for mp_lift_place.  A view
+ * whose |q|^2 is not finite or < 1e-12 counts as invalid in every frame of its take.  R is the rotation matrix of q / |q|, normalised in fp64
+ * (mp_lift_world keeps the dataset's quaternion un-normalised, as the reference's qrot does; H36M's are unit to 6e-8); camera to world is
+ * x_world = R x_cam + T.  quat null: R is the identity, nothing is multiplied and the differences are exact.  Everything between the float32 loads
+ * and the float32 stores is fp64; no atomics, fixed orders: identical bits on every call; a frame's result depends on no other frame; neither
+ * call synchronises.
+ * mp_lift_fuse: hyps (V, Ftot, K, J, C) read only, 1 <= K <= MP_LIFT_FUSE_MAXK, 2 <= J <= 32, C = 3 or 4 (channel 3 of joint 0: the hypothesis'
+ * score; C = 3: every unary cost is 0); sigma > 0 in the poses' unit (+inf: the pair factor is exactly 0); score_weight >= 0 and finite.  Per
+ * frame f of take g:
+ * 1. Rotate.  w[v][k][j] = R_gv (x[v][f][k][j] - x[v][f][k][0]): root-relative, placed or floored poses may be passed.
+ * 2. Pair cost, views a < b:  d(a, i; b, l) = (sum_j |w[a][i][j] - w[b][l][j]|^2) / J, the sum in joint order, then channel order; a d that is not
+ *    finite is taken as 1e30.
+ * 3. Unary cost.  u(v, k) = -log(s); an s that is not > 1e-12 is taken as 1e-12 (mp_lift_path's rule).
+ * 4. Combinations c = (k_v) over the frame's valid views:  E(c) = (1 / (2 sigma^2)) sum_{a < b valid} d(a, k_a; b, k_b) + score_weight sum_{v valid}
+ *    u(v, k_v), the pairs in lexicographic order of (a, b), then the unary terms in view order.  The choice is the FIRST minimum in lexicographic
+ *    order of c, view 0 most significant (at most 8^4 = 4096 combinations).
+ * 5. pose[f][j] = (sum_{v valid} w[v][k_v][j]) / n in view order, n the number of valid views; joint 0 is stored as +0.
+ * 6. spread[f] = sqrt(sum_v sum_j |w[v][k_v][j] - pose64[f][j]|^2 / (n J)), in the poses' unit: how well the views agree.
+ * 7. cost[f] = E;  choice[f][v] = k_v, 255 for an invalid view;  ok[f] = 1, 0 if E >= 1e30.  n = 0: pose 0, every choice 255, cost = spread = 0, ok = 0.
+ * pose (Ftot, J, 3) floats, root-relative in the world's orientation; choice (Ftot, V) bytes; cost, spread (Ftot) floats; ok (Ftot) bytes.
+ * MP_ERR_ARG before anything is launched: hyps, take_offset or an output null; V, K, J or C out of range; Ftot or G <= 0, G > Ftot; sigma not > 0;
+ * score_weight negative or not finite; more frames than one grid holds.
+ * mp_lift_fuse_place: ONE world root per frame from all views.  pose (Ftot, J, 3) as mp_lift_fuse wrote it, kp (V, Ftot, J, 2) normalised screen
+ * coordinates, weights (J) or null, distort and 0 <= iters <= MP_LIFT_REFINE_MAXITERS as for mp_lift_place_refine.  Joint j seen by view v with the
+ * root at r is the camera-space point P = R^T (pose_j + r - T_v).
+ * 1. Start, linear under the pinhole part: with a, b as for mp_lift_place and rho_x, rho_y, rho_z the rows of R^T,  m_x = rho_x - a rho_z,
+ *    m_y = rho_y - b rho_z,  H = sum_v sum_j w_j (m_x m_x^T + m_y m_y^T),  h = sum w_j (m_x (m_x . (T_v - pose_j)) + m_y (m_y . (T_v - pose_j))),
+ *    over the valid views in order, then the joints in order, a joint of weight 0 skipped;  r = adj(H) h / det by cofactors.  Degenerate - no valid
+ *    view, sum w not > 0, a non-finite sum, det not > 1e-12 H00 H11 H22, r not finite:  ok = 0, root = 0, reproj = 0, steps = 0.
+ * 2. Evaluation and steps: steps 2 to 4 of mp_lift_place_refine with F, E, W, H, g and deep summed over the valid views, then the joints; the
+ *    Jacobian with respect to r is J_j R^T; the acceptance rule and its constants are the same; deep asks every weighted joint of every valid view
+ *    to lie in front of its camera.
+ * 3. root (Ftot, 3) floats;  reproj (V, Ftot) floats: view v's own E_v / W_v at the final r (its weighted mean distance, as mp_lift_place_refine's
+ *    reproj), 0 for an invalid view;  ok (Ftot) bytes;  steps (Ftot) bytes or null.
+ * One lane owns one frame.  MP_ERR_ARG: those of mp_lift_place_refine, and pose, kp, take_offset, trans or intr null, V outside 1..4, G out of range. */
+#define MP_LIFT_FUSE_MAXV 4
+#define MP_LIFT_FUSE_MAXK 8
+int mp_lift_fuse(const float* hyps, int V, int64_t Ftot, int K, int J, int C, const uint8_t* valid, const int64_t* take_offset, int G, const float* quat,
+                 float sigma, float score_weight, float* pose, uint8_t* choice, float* cost, float* spread, uint8_t* ok, void* stream);
+int mp_lift_fuse_place(const float* pose, const float* kp, int V, int64_t Ftot, int J, const uint8_t* valid, const int64_t* take_offset, int G,
+                       const float* quat, const float* trans, const float* intr, const float* weights, int distort, int iters, float* root,
+                       float* reproj, uint8_t* ok, uint8_t* steps, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -61,6 +61,9 @@ options), ``_upload`` (keypoints, window tables, offsets and output buffers, onc
 public function turns the record into its documented list / tuple in one place; ``lift_action`` and hpe/_entry.py read the fields by name.
 Placing has ONE launcher, ``_place_refine``, as the library has one fit kernel: ``place_poses``, ``reproject_poses`` and ``_place_stage`` all go
 through it, and zero steps from the linear fit is what ``mp_lift_place`` computes.
+Fusing the camera views of a take (``fuse_views``: one hypothesis per view, chosen jointly, and their mean; ``place_views``: one world root per frame
+from all views) is NOT a stage of the chain: both work on what ``lift_sequences`` returns for the views, and hpe/_entry.py (``lift.fuse``) cuts a
+group's sequences into takes and calls them.
 """
 from __future__ import annotations
 
@@ -697,6 +700,170 @@ def to_world(poses, orientation, translation=None, traj=None, seq_offset=None, f
     return poses
 
 
+FUSE_MAXV, FUSE_MAXK = 4, 8  # MP_LIFT_FUSE_MAXV, MP_LIFT_FUSE_MAXK of include/manipose_hip.h: views of a take, hypotheses of a view
+FUSE_SIGMA, FUSE_SCORE_WEIGHT = 0.02, 1.0    # defaults of fuse_views: the views' disagreement in metres (not tuned), the weight of -log(score)
+
+
+def _fuse_options(sigma, score_weight, names=("sigma", "score_weight")):
+    _path_options(sigma, score_weight, names)              # the same two rules: sigma > 0 (inf allowed), the other finite and >= 0
+
+
+def _fuse_quat(orientation, G, V):
+    """(G, V, 4) float32 host quaternions, (V, 4) standing for one take; a zero quaternion is refused here (the kernel would ignore the view)"""
+    h = _host_f32(orientation, (G, V, 4), "orientation", row=(V, 4) if G == 1 else None)
+    if not ((h.astype(np.float64) ** 2).sum(-1) >= 1e-12).all():
+        raise ValueError("orientation holds a zero quaternion: mark a missing view in valid and give it any unit quaternion")
+    return h
+
+
+def _fuse_valid(valid, V, ftot, who):
+    if valid is None:
+        return None
+    _score_valid(valid, (V, ftot), "valid")
+    if not valid.is_cuda:
+        raise RuntimeError(f"manipose_amd: {who} takes device tensors; there is no CPU fallback")
+    return valid.contiguous()
+
+
+def _fuse(lib, hyps, valid, d_off, G, d_quat, sigma, score_weight):
+    """``mp_lift_fuse`` on hyps (V, Ftot, K, J, C): (pose, choice, cost, spread, ok), new tensors"""
+    V, ftot, K, J, ch = (int(v) for v in hyps.shape)
+    dev = hyps.device
+    pose = torch.empty(ftot, J, 3, dtype=torch.float32, device=dev)
+    choice = torch.empty(ftot, V, dtype=torch.uint8, device=dev)
+    cost = torch.empty(ftot, dtype=torch.float32, device=dev)
+    spread = torch.empty(ftot, dtype=torch.float32, device=dev)
+    ok = torch.empty(ftot, dtype=torch.uint8, device=dev)
+    if ftot > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_fuse(_lib.ptr(hyps), V, ftot, K, J, ch, _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(d_quat), float(sigma),
+                                        float(score_weight), _lib.ptr(pose), _lib.ptr(choice), _lib.ptr(cost), _lib.ptr(spread), _lib.ptr(ok),
+                                        _lib.stream_ptr()), "mp_lift_fuse")
+    return pose, choice, cost, spread, ok
+
+
+def _fuse_place(lib, pose, kp, valid, d_off, G, d_quat, d_trans, d_intr, d_w, distort, iters):
+    """``mp_lift_fuse_place`` on pose (Ftot, J, 3), kp (V, Ftot, J, 2): (root, reproj, ok, steps), new tensors"""
+    V, ftot, J = int(kp.shape[0]), int(kp.shape[1]), int(kp.shape[2])
+    dev = pose.device
+    root = torch.empty(ftot, 3, dtype=torch.float32, device=dev)
+    reproj = torch.empty(V, ftot, dtype=torch.float32, device=dev)
+    ok = torch.empty(ftot, dtype=torch.uint8, device=dev)
+    steps = torch.empty(ftot, dtype=torch.uint8, device=dev)
+    if ftot > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_fuse_place(_lib.ptr(pose), _lib.ptr(kp), V, ftot, J, _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(d_quat),
+                                              _lib.ptr(d_trans), _lib.ptr(d_intr), _lib.ptr(d_w), int(bool(distort)), int(iters), _lib.ptr(root),
+                                              _lib.ptr(reproj), _lib.ptr(ok), _lib.ptr(steps), _lib.stream_ptr()), "mp_lift_fuse_place")
+    return root, reproj, ok, steps
+
+
+def _fuse_hyps_shape(hyps):
+    if hyps.dim() != 5 or hyps.shape[4] not in (3, 4) or hyps.dtype != torch.float32 or not hyps.is_contiguous():
+        raise ValueError(f"hyps must be contiguous float32 (V, Ftot, K, J, 3 | 4), got {tuple(hyps.shape)} {hyps.dtype}")
+    V, _, K, J, _ = (int(v) for v in hyps.shape)
+    if not 1 <= V <= FUSE_MAXV:
+        raise ValueError(f"hyps have {V} views: 1..{FUSE_MAXV} expected")
+    if not 1 <= K <= FUSE_MAXK:
+        raise ValueError(f"hyps have {K} hypotheses: 1..{FUSE_MAXK} expected")
+    if not 2 <= J <= 32:
+        raise ValueError(f"hyps have {J} joints: 2..32 expected")
+
+
+def fuse_views(hyps, orientation=None, valid=None, take_offset=None, sigma=FUSE_SIGMA, score_weight=FUSE_SCORE_WEIGHT):
+    """``mp_lift_fuse`` on device tensors: the camera views of a take fused into one pose per frame.  ``hyps`` (V, Ftot, K, J, 3 | 4) float32, the
+    K hypotheses of each of V <= 4 views of the same frames, each in its camera's frame (channel 3 of joint 0: the hypothesis' score; without it
+    every hypothesis is equally likely); ``orientation`` (G, V, 4) or, for one take, (V, 4) camera quaternions (w, x, y, z), tensor or array,
+    normalised in the kernel, or None: the views are in the world's orientation already; ``valid`` (V, Ftot) uint8 device tensor or None: 0 where a
+    view is missing (a take with fewer than V views: all of its frames); ``take_offset`` (G + 1): first frame of every take, HOST table or device
+    int64 tensor (default: one take).  Per frame the ONE combination of a hypothesis per valid view is chosen that minimises
+    sum_{a < b} mean_j |w_a - w_b|^2 / (2 sigma^2) + score_weight sum_v -log(score_v), w the root-relative hypothesis rotated into the world - the
+    first minimum in lexicographic order - and the chosen hypotheses are averaged (include/manipose_hip.h has the rule).  ``sigma`` > 0 in the
+    poses' unit (inf: the views do not see each other and every view takes its best score), ``score_weight`` >= 0.  Returns ``(pose (Ftot, J, 3)
+    root-relative in the world's orientation, choice (Ftot, V) uint8 (255: invalid view), cost (Ftot), spread (Ftot) the chosen hypotheses' RMS
+    distance from their mean, ok (Ftot) uint8)``, new device tensors.  hyps is not modified; identical bits on every call."""
+    _fuse_options(sigma, score_weight)
+    if torch.is_tensor(hyps):
+        _fuse_hyps_shape(hyps)                            # (the ValueErrors come before the refusal of a CPU tensor)
+        V, ftot = int(hyps.shape[0]), int(hyps.shape[1])
+        _score_valid(valid, (V, ftot), "valid")
+        G = 1 if take_offset is None else max(int(take_offset.numel() if torch.is_tensor(take_offset) else np.asarray(take_offset).size) - 1, 1)
+        h_quat = _fuse_quat(orientation, G, V) if orientation is not None else None
+    if not torch.is_tensor(hyps) or not hyps.is_cuda:
+        raise RuntimeError("manipose_amd: fuse_views takes device tensors; there is no CPU fallback")
+    valid = _fuse_valid(valid, V, ftot, "fuse_views")
+    d_off, G = _seq_table(take_offset, ftot, hyps.device)
+    d_quat = torch.from_numpy(h_quat).to(hyps.device) if h_quat is not None else None
+    return _fuse(_lib.load(), hyps, valid, d_off, G, d_quat, sigma, score_weight)
+
+
+def _take_cameras(cameras, V):
+    """cameras[take][view] (camera_table's forms, None: a missing view) -> host (intr (G, V, 9), quat (G, V, 4), trans (G, V, 3), present (G, V) bool);
+    a missing view gets the identity camera, which is never read"""
+    if isinstance(cameras, dict) or not hasattr(cameras, "__len__") or len(cameras) == 0:
+        raise ValueError("cameras must be a nested list [take][view] of cameras (None: a missing view)")
+    G = len(cameras)
+    intr, quat, trans = np.zeros((G, V, 9), np.float32), np.zeros((G, V, 4), np.float32), np.zeros((G, V, 3), np.float32)
+    present = np.zeros((G, V), bool)
+    intr[..., 0:2], quat[..., 0] = 1.0, 1.0
+    for g, take in enumerate(cameras):
+        if isinstance(take, dict) or not hasattr(take, "__len__") or len(take) != V:
+            raise ValueError(f"cameras[{g}] must list {V} views (None: a missing view)")
+        for v, cam in enumerate(take):
+            if cam is None:
+                continue
+            try:
+                i, q, t = camera_table([cam])
+            except ValueError as e:
+                raise ValueError(f"take {g}, view {v}: {e}") from None
+            if not float((q.astype(np.float64) ** 2).sum()) >= 1e-12:
+                raise ValueError(f"take {g}, view {v}: zero quaternion")
+            intr[g, v], quat[g, v], trans[g, v], present[g, v] = i[0], q[0], t[0], True
+    return intr, quat, trans, present
+
+
+def place_views(pose, keypoints_2d, cameras, valid=None, take_offset=None, weights=None, distort=True, refine=3, return_steps=False):
+    """``mp_lift_fuse_place`` on device tensors: ONE world root per frame from all views of its take.  ``pose`` (Ftot, J, 3) float32, root-relative
+    in the world's orientation, as ``fuse_views`` returns it; ``keypoints_2d`` (V, Ftot, J, 2) float32, every view's keypoints in normalised screen
+    coordinates; ``cameras``: nested list [take][view] of cameras in ``camera_table``'s forms (a dict of ``h36m_cameras()`` with its
+    ``translation``, or ``fetch()``'s 16 numbers), None for a view the take does not have; ``valid`` (V, Ftot) uint8 device tensor or None;
+    ``take_offset`` (G + 1) as for ``fuse_views``; ``weights`` (J) or None.  The root starts at the linear fit of all views' pinhole projections
+    (condition number about 6 with H36M's four cameras, against 6e2 for one view) and takes up to ``refine`` (0..16) Gauss-Newton steps under the
+    camera model ``distort`` names, with ``place_poses``' acceptance rule.  Returns ``(root (Ftot, 3), reproj (V, Ftot): every view's own mean
+    reprojection error at the root, 0 for an invalid view, ok (Ftot) uint8[, steps (Ftot) uint8])``."""
+    if not _is_iters(refine):
+        raise ValueError(f"refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: the linear fit alone), got {refine!r}")
+    if torch.is_tensor(pose) and torch.is_tensor(keypoints_2d):
+        if pose.dim() != 3 or pose.shape[2] != 3 or pose.dtype != torch.float32 or not pose.is_contiguous() or not 2 <= int(pose.shape[1]) <= 32:
+            raise ValueError(f"pose must be contiguous float32 (Ftot, J, 3) with 2..32 joints, got {tuple(pose.shape)} {pose.dtype}")
+        ftot, J = int(pose.shape[0]), int(pose.shape[1])
+        kp = keypoints_2d
+        if kp.dim() != 4 or not 1 <= int(kp.shape[0]) <= FUSE_MAXV or tuple(kp.shape[1:]) != (ftot, J, 2) or kp.dtype != torch.float32:
+            raise ValueError(f"keypoints_2d must be float32 (V <= {FUSE_MAXV}, {ftot}, {J}, 2), got {tuple(kp.shape)} {kp.dtype}")
+        V = int(kp.shape[0])
+        if valid is not None:
+            _score_valid(valid, (V, ftot), "valid")
+        intr, quat, trans, present = _take_cameras(cameras, V)
+        h_w = _host_f32(weights, (J,), "weights", nonneg=True) if weights is not None else None
+    if not torch.is_tensor(pose) or not pose.is_cuda or not torch.is_tensor(keypoints_2d) or not keypoints_2d.is_cuda:
+        raise RuntimeError("manipose_amd: place_views takes device tensors; there is no CPU fallback")
+    dev = pose.device
+    valid = _fuse_valid(valid, V, ftot, "place_views")
+    d_off, G = _seq_table(take_offset, ftot, dev)
+    if G != intr.shape[0]:
+        raise ValueError(f"cameras lists {intr.shape[0]} takes, take_offset {G}")
+    if not present.all():                                  # a missing view is invalid in every frame of its take
+        off = d_off.cpu().numpy().clip(0, ftot)
+        mask = np.ones((V, ftot), np.uint8)
+        for g, v in zip(*np.nonzero(~present)):
+            mask[v, off[g]:max(off[g], off[g + 1])] = 0
+        mask = torch.from_numpy(mask).to(dev)
+        valid = mask if valid is None else valid & mask
+    res = _fuse_place(_lib.load(), pose, keypoints_2d.contiguous(), valid, d_off, G, torch.from_numpy(quat).to(dev), torch.from_numpy(trans).to(dev),
+                      torch.from_numpy(intr).to(dev), torch.from_numpy(h_w).to(dev) if h_w is not None else None, distort, refine)
+    return res if return_steps else res[:3]
+
+
 def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirror, agg="weighted_ave", blend="mean", scale=1.0,
                   return_hyps=False, out=None, hyps=None, device_tables=None):
     """``mp_lift_merge`` on device tensors: poses (F*W, K, T, J, 3), scores (F*W, K, T, 1) or None (K == 1); win_seq / win_start (W)
@@ -1256,5 +1423,5 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
 
 
 __all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "reproject_poses", "pose_rotations", "to_world", "smooth_poses", "smooth_traj",
-           "select_path", "score_poses", "score_traj", "lift_sequences",
+           "select_path", "score_poses", "score_traj", "fuse_views", "place_views", "lift_sequences",
            "lift_action"]

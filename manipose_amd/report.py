@@ -191,7 +191,7 @@ def _weighted_rows(labels, values, weights):
     return [[lab, *row.tolist()] for lab, row in zip(list(labels) + ["average"], np.vstack([v, avg[None]]))]
 
 
-def write_lift_score_report(out_dir: str, scores: Mapping[str, Mapping], skeleton=None) -> List[str]:
+def write_lift_score_report(out_dir: str, scores: Mapping[str, Mapping], skeleton=None, name: str = "lift_score", joints: bool = True) -> List[str]:
     """``scores``: {sequence key: the score dict of ``lift_sequences(targets=..., return_score=True)`` as numbers / numpy arrays, in metres} in the
     order of the rows.  Two tables in the layout of the other report files (a label column "act", one row per key and a last row "average"),
     the errors in millimetres:
@@ -200,6 +200,7 @@ def write_lift_score_report(out_dir: str, scores: Mapping[str, Mapping], skeleto
                              trajectory traj_ate and traj_frames.  The "average" row weighs a row by its frames (traj_ate by traj_frames) and sums
                              the two frame columns;
       lift_score_joints.csv  the error per joint under the joints' names, averaged the same way.
+    ``name``: the files' stem (run.lift's fused takes go to lift_score_fused.csv); ``joints=False`` leaves the per-joint table out.
     Returns the paths written."""
     keys = list(scores)
     if not keys:
@@ -230,7 +231,8 @@ def write_lift_score_report(out_dir: str, scores: Mapping[str, Mapping], skeleto
     per_joint = [1000.0 * np.asarray(r["per_joint"], dtype=np.float64).reshape(-1) for r in recs]
     if any(len(v) != len(jn) for v in per_joint):
         raise ValueError(f"write_lift_score_report: per_joint of {len(per_joint[0])} joints under {len(jn)} joint names")
-    paths = [os.path.join(out_dir, "lift_score.csv"), os.path.join(out_dir, "lift_score_joints.csv")]
+    paths = [os.path.join(out_dir, f"{name}.csv"), os.path.join(out_dir, f"{name}_joints.csv")][:2 if joints else 1]
     write_csv(paths[0], head, rows)
-    write_csv(paths[1], ["act", *jn], _weighted_rows(keys, per_joint, frames))
+    if joints:
+        write_csv(paths[1], ["act", *jn], _weighted_rows(keys, per_joint, frames))
     return paths

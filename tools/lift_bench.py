@@ -8,6 +8,10 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --path [frames=3000] [K=5] [reps=50]
     python tools/lift_bench.py --score [frames=3000] [K=5] [reps=50]
     python tools/lift_bench.py --rotations [frames=3000] [K=5] [reps=50]
+    python tools/lift_bench.py --fuse [frames=3000] [K=5] [reps=200]
+--fuse times mp_lift_fuse (one hypothesis per view chosen jointly over S11's four cameras, and their mean) and mp_lift_fuse_place (one world root
+per frame from all views, at iters 0 and 3) through their private launchers on 4 views x `frames` frames x K hypotheses of ONE take, next to
+mp_lift_path on one view's hypotheses of the same frames, for scale.
 --place times only the two kernels that put a lifted sequence in the scene (mp_lift_place: root translation and reprojection error of every
 hypothesis; mp_lift_world: world frame, with and without the floor) on `frames` frames x K hypotheses of one sequence with S11's first camera,
 and then, in the same process, mp_lift_smooth (radius 4 and 32, degree 2, uniform) on the merged poses (frames, 17, 3), the hypotheses
@@ -214,6 +218,50 @@ def rotations_bench(argv):
     print(f"mp_lift_rigid on the same hypotheses: {us:,.1f} us", flush=True)
 
 
+def fuse_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.data.ingest import h36m_cameras
+    from manipose_amd.lifting import _fuse, _fuse_place, _path
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    K = int(argv[1]) if len(argv) > 1 else 5
+    reps = int(argv[2]) if len(argv) > 2 else 200
+    assert torch.cuda.is_available(), "needs an MI355X"
+    lib, V = _lib.load(), 4
+    cams = h36m_cameras()["S11"]
+    quat, trans, intr = (torch.from_numpy(np.stack([c[k] for c in cams])[None].astype(np.float32)).cuda() for k in ("orientation", "translation", "intrinsic"))
+    qn = quat[0] / quat[0].norm(dim=1, keepdim=True)
+    w, x, y, z = qn.unbind(1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                     2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).view(V, 3, 3)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    pose = 0.3 * torch.randn(frames, 17, 3, device="cuda", generator=g)
+    pose[:, 0] = 0
+    root = torch.cat([2 * torch.rand(frames, 2, device="cuda", generator=g) - 1, 0.8 + 0.2 * torch.rand(frames, 1, device="cuda", generator=g)], dim=1)
+    cam = torch.einsum("fjc,vcd->vfjd", pose, R)                          # R^T p: every view's camera-frame pose
+    hyps = torch.empty(V, frames, K, 17, 4, device="cuda")
+    hyps[..., :3] = cam[:, :, None] + 0.005 * torch.randn(V, frames, K, 17, 3, device="cuda", generator=g)
+    hyps[:, :, 1:, :, 2] += 0.08 * torch.randn(V, frames, K - 1, 17, device="cuda", generator=g)      # all but one moved along the camera's depth axis
+    hyps[..., 3] = torch.softmax(1.5 * torch.randn(V, frames, K, device="cuda", generator=g), dim=2)[..., None]
+    P = torch.einsum("vfjc,vcd->vfjd", (pose + root[:, None])[None] - trans[0][:, None, None], R)
+    kp = (intr[0, :, None, None, 0:2] * P[..., :2] / P[..., 2:3] + intr[0, :, None, None, 2:4] + 0.01 * torch.randn(V, frames, 17, 2, device="cuda", generator=g)).contiguous()
+    one = torch.tensor([0, frames], dtype=torch.int64, device="cuda")
+    fused = _fuse(lib, hyps, None, one, 1, quat, 0.02, 1.0)
+    print(f"--fuse: {V} views x {frames} frames x {K} hypotheses, {hyps.numel() * 4 / 1e6:.2f} MB of hypotheses, {K ** V} combinations a frame; {reps} calls each "
+          f"after 5 of warm-up (the output allocations are inside the time); hypothesis 0 chosen in {(fused[1] == 0).float().mean().item():.3f} of the views",
+          flush=True)
+    us = timed_us(lambda: _fuse(lib, hyps, None, one, 1, quat, 0.02, 1.0), reps)
+    print(f"mp_lift_fuse: {us:,.1f} us  {frames / us:,.2f} M frames/s", flush=True)
+    for iters in (0, 3):
+        us = timed_us(lambda: _fuse_place(lib, fused[0], kp, None, one, 1, quat, trans, intr, None, True, iters), reps)
+        steps = _fuse_place(lib, fused[0], kp, None, one, 1, quat, trans, intr, None, True, iters)[3].float().mean().item()
+        print(f"mp_lift_fuse_place iters={iters}: {us:,.1f} us  {frames / us:,.2f} M frames/s; {steps:.2f} steps taken per frame", flush=True)
+    us = timed_us(lambda: _path(lib, hyps[0], one, 1, 0.02, 0.0), reps)
+    print(f"mp_lift_path on one view's {frames} frames x {K} hypotheses, for scale: {us:,.1f} us", flush=True)
+
+
+if "--fuse" in sys.argv:
+    fuse_bench([a for a in sys.argv[1:] if a != "--fuse"])
+    sys.exit(0)
 if "--rotations" in sys.argv:
     rotations_bench([a for a in sys.argv[1:] if a != "--rotations"])
     sys.exit(0)
