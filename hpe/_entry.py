@@ -403,6 +403,29 @@ def lift_fuse_options(cfg):
     return True, float(sigma), float(weight), refine
 
 
+def lift_fuse_path_options(cfg):
+    """(fuse_path, path_sigma, switch_cost) of lift.fuse_path / lift.fuse_path_sigma / lift.fuse_path_switch; ValueError for a value or a
+    combination that cannot run - before any model is built."""
+    path = cfg.lift.get("fuse_path", False)
+    sigma, switch = cfg.lift.get("fuse_path_sigma", 0.02), cfg.lift.get("fuse_path_switch", 0.0)
+    if not isinstance(path, bool):
+        raise ValueError(f"lift.fuse_path must be true or false, got {path!r}")
+    for key, v in (("fuse_path_sigma", sigma), ("fuse_path_switch", switch)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"lift.{key} is a number, got {v!r}")
+    if not sigma > 0:
+        raise ValueError(f"lift.fuse_path_sigma must be > 0 (metres), got {sigma!r}")
+    if not 0 <= switch < float("inf"):
+        raise ValueError(f"lift.fuse_path_switch must be finite and >= 0, got {switch!r}")
+    if not path:
+        if sigma != 0.02 or switch != 0.0:
+            raise ValueError("lift.fuse_path_sigma / lift.fuse_path_switch describe the path through a take's fused views: set lift.fuse_path=true")
+        return False, float(sigma), float(switch)
+    if not lift_fuse_options(cfg)[0]:
+        raise ValueError("lift.fuse_path chooses the fused views' hypotheses along time: set lift.fuse=true")
+    return True, float(sigma), float(switch)
+
+
 def _camera_index(cam):
     """fetch()'s 17th number, a camera dict's "index", or None"""
     if isinstance(cam, dict):
@@ -437,9 +460,10 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
     placed with ONE world root per frame (place_views); with lift.floor the take stands on z = 0.  ``res``: the group's _Lifted with hypotheses, taken
     after the smoothing and rigid stages.  Writes ``<name>.fused<t>`` and its ``__root``, ``__choice``, ``__spread``, ``__cost``, ``__ok`` (consensus
     and root fit both ok), ``__reproj`` (V, N), ``__steps``, ``__views`` (and ``__floor``) into ``out``; with ``targets`` the take's score into ``scores``."""
-    from manipose_amd import camera_table, fuse_views, place_views, project_rigid, score_poses, score_traj, to_world
+    from manipose_amd import camera_table, fuse_views, fuse_views_path, place_views, project_rigid, score_poses, score_traj, to_world
     from manipose_amd.lifting import SCORE_FIELDS
     _, sigma, weight, refine = lift_fuse_options(cfg)
+    along, path_sigma, path_switch = lift_fuse_path_options(cfg)
     _, world, floor = lift_place_options(cfg)
     takes = split_takes(cams)
     for t, views in enumerate(takes):
@@ -466,7 +490,10 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
             valid[v, off[t]:off[t + 1]] = 1
             quat[t, v] = camera_table([cams[i]])[1][0]
     nested = [[cams[i] for i in views] + [None] * (V - len(views)) for views in takes]
-    pose, choice, cost, spread, ok = fuse_views(hyps, None if world else quat, valid, off, sigma, weight)
+    if along:                                  # lift.fuse_path: the same choice, made jointly over the whole take
+        pose, choice, cost, spread, ok, path_cost = fuse_views_path(hyps, None if world else quat, valid, off, sigma, weight, path_sigma, path_switch)
+    else:
+        pose, choice, cost, spread, ok = fuse_views(hyps, None if world else quat, valid, off, sigma, weight)
     if res.bones is not None:                  # lift.rigid: one table per take, the mean of its views'
         project_rigid(pose, torch.stack([torch.stack([res.bones[i] for i in views]).mean(dim=0) for views in takes]), seq_offset=off)
     root, reproj, placed, steps = place_views(pose, kp, nested, valid, off, refine=refine, return_steps=True)
@@ -492,6 +519,8 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
         out[key + "__ok"] = (ok[sl] & placed[sl]).cpu().numpy()
         out[key + "__reproj"], out[key + "__steps"] = reproj[:len(views), sl].cpu().numpy(), steps[sl].cpu().numpy()
         out[key + "__views"] = np.array(views, dtype=np.int64)
+        if along:
+            out[key + "__path_cost"] = path_cost[t].cpu().numpy()
         if floor:
             out[key + "__floor"] = d_floor[t].cpu().numpy()
         if targets is not None and scores is not None:
@@ -535,7 +564,8 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     With lift.fuse (``cameras`` needed; lift.fuse_sigma, lift.fuse_score_weight, lift.fuse_refine) the sequences of a group are cut into takes - a
     new take wherever the camera index, fetch()'s 17th number, does not increase - and every take ``t`` also gets ``<name>.fused<t>`` (N, 17, 3), the
     views' consensus pose at ONE world root, with ``__root`` (N, 3), ``__choice`` (N, V) uint8, ``__spread``, ``__cost``, ``__ok``, ``__steps`` (N,),
-    ``__reproj`` (V, N), ``__views`` (the sequences' indices within the group) and with lift.floor ``__floor`` (fuse_group); with ``targets`` the dict
+    ``__reproj`` (V, N), ``__views`` (the sequences' indices within the group), with lift.floor ``__floor`` and with lift.fuse_path (lift.fuse_path_sigma,
+    lift.fuse_path_switch) ``__path_cost``, a scalar (fuse_group); with ``targets`` the dict
     ``fused_scores`` receives {fused key: score dict} of the fused pose and root against the first view's ground truth in the world."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
@@ -629,6 +659,7 @@ def run(argv, extra_defaults=None):
     lift_score_options(cfg)                    # ... and a lift.score without run.lift
     lift_rotations_options(cfg)                # ... and a lift.rotations without run.lift
     lift_fuse_options(cfg)                     # ... and a lift.fuse without run.lift, without calibration or without hypotheses
+    lift_fuse_path_options(cfg)                # ... and a lift.fuse_path without lift.fuse
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")

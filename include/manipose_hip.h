@@ -713,6 +713,49 @@ int mp_lift_fuse_place(const float* pose, const float* kp, int V, int64_t Ftot, 
                        const float* quat, const float* trans, const float* intr, const float* weights, int distort, int iters, float* root,
                        float* reproj, uint8_t* ok, uint8_t* steps, void* stream);
 
+/* Fusing the views of a take ALONG TIME: one hypothesis per view and frame, chosen jointly over the views AND over the whole take.  mp_lift_fuse
+ * decides every frame on its own, so an ambiguity that all views share - a left/right-mirrored body is consistent in every camera, the pair cost
+ * cannot reject it - is taken in every frame where its score happens to be higher, and the fused motion flickers; mp_lift_path removes that
+ * flicker for one view.  This is the Viterbi path over the COMBINATIONS of a take: K^V states, at most 4096.  The conventions are mp_lift_fuse's:
+ * takes, take_offset (entries clamped to 0 .. Ftot), valid, quat and its fp64 normalisation, a view with a zero quaternion counts as invalid;
+ * fp64 between the float32 loads and the float32 stores, without contraction into fused multiply-adds; no atomics, fixed orders: identical bits
+ * on every call; a take's result does not depend on the other takes of the call; the call does not synchronise.  Not measured on real data.
+ * hyps (V, Ftot, K, J, C) read only, 1 <= V <= MP_LIFT_FUSE_MAXV, 1 <= K <= MP_LIFT_FUSE_MAXK, 2 <= J <= 32, C = 3 or 4; sigma and score_weight as
+ * for mp_lift_fuse; path_sigma > 0 in the poses' unit (+inf: the motion factor is exactly 0); switch_cost >= 0 and finite.
+ * A STATE is c = (k_0 .. k_{V-1}), every view a digit 0 .. K - 1, view 0 most significant; it always has V digits.  For frame g of a take with
+ * frames [f0, f1):
+ * 1. w, d(a, i; b, l), u(v, k): exactly steps 1 to 3 of mp_lift_fuse (for C = 3, u = 0).
+ * 2. Frame cost  E_g(c) = (1 / (2 sigma^2)) sum_{a < b valid at g} d(a, k_a; b, k_b) + score_weight sum_{v valid at g} u(v, k_v), step 4 of
+ *    mp_lift_fuse with its order of additions.  A view invalid at g contributes nothing: its digit is free.  No valid view: E_g = 0.
+ * 3. Transition of view v from a at g - 1 to b at g:
+ *    t_v(g; a -> b) = (1 / (2 path_sigma^2)) ((sum_j |w[v][g][b][j] - w[v][g-1][a][j]|^2) / J) + (a != b ? switch_cost : 0), the sum in joint
+ *    order, then channel order; a value that is not finite is taken as 1e30; if view v is invalid at g or at g - 1, t_v = 0 for every (a, b): a
+ *    view's chain is cut across a gap.
+ * 4. Forward pass, STAGED per view (the transition is a sum over the views; the staged order of additions is the definition):
+ *    f[f0][c] = E_f0(c);  for g > f0:  h_0 = f[g-1];  for v = 0 .. V - 1:  h_{v+1}[c with digit v = b] = min_a (h_v[c with digit v = a] +
+ *    t_v(g; a -> b)), the back-pointer digit bp_v[g][c] the FIRST (lowest) arg-min a;  f[g][c] = h_V[c] + E_g(c).  This is min over all
+ *    predecessor states of f[g-1][c'] + sum_v t_v up to the rounding of another order of additions, in V K^(V+1) operations instead of K^(2V).
+ * 5. End and backtrack.  The last frame takes the first minimum of f[f1-1][.] in lexicographic order; from g to g - 1 the back-pointer digits are
+ *    applied for v = V - 1 down to 0, c_v <- bp_v[g][c] with c updated in between (the inverse of the staging).  path_cost[take] (double) = f at
+ *    the chosen end state; an empty clamped range writes path_cost = 0 and nothing else.
+ * 6. Emit, per frame with its chosen c, steps 5 to 7 of mp_lift_fuse over the views valid at the frame: pose (Ftot, J, 3) the mean in view order,
+ *    joint 0 stored as +0; spread (Ftot); cost[f] = (float)E_f(c); choice (Ftot, V) bytes, 255 for a view invalid at f (whatever its free digit);
+ *    ok[f] = 1, 0 if E_f(c) >= 1e30; no valid view: pose, cost and spread 0, every choice 255, ok 0.  A frame outside every take's clamped range
+ *    is not written.
+ * With path_sigma = +inf and switch_cost = 0 the choice is mp_lift_fuse's wherever its minimum is unique; with V = 1, quat null, score_weight = 1
+ * and joint 0 at the origin the path and path_cost are mp_lift_path's.
+ * scratch: at least mp_lift_fuse_path_scratch_bytes(V, Ftot, K) bytes = Ftot (8 R + 2 K^V + 2) rounded up to 8, R = (V (V - 1) / 2 + V) K^2 + V K
+ * (per frame the row of pair, transition and unary tables in doubles, one 16-bit word of V 3-bit back-pointer digits per state, the chosen state),
+ * 8-byte aligned; 0 for arguments out of range.  The backtrack walks the back-pointers out of LDS, at most MP_LIFT_FUSE_PATH_CHUNK frames at a
+ * time.
+ * MP_ERR_ARG before anything is launched: those of mp_lift_fuse; path_sigma not > 0; switch_cost negative or not finite; path_cost null; scratch
+ * null, too small or misaligned. */
+#define MP_LIFT_FUSE_PATH_CHUNK 512
+int64_t mp_lift_fuse_path_scratch_bytes(int V, int64_t Ftot, int K);
+int mp_lift_fuse_path(const float* hyps, int V, int64_t Ftot, int K, int J, int C, const uint8_t* valid, const int64_t* take_offset, int G,
+                      const float* quat, float sigma, float score_weight, float path_sigma, float switch_cost, float* pose, uint8_t* choice, float* cost,
+                      float* spread, uint8_t* ok, double* path_cost, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -61,8 +61,9 @@ options), ``_upload`` (keypoints, window tables, offsets and output buffers, onc
 public function turns the record into its documented list / tuple in one place; ``lift_action`` and hpe/_entry.py read the fields by name.
 Placing has ONE launcher, ``_place_refine``, as the library has one fit kernel: ``place_poses``, ``reproject_poses`` and ``_place_stage`` all go
 through it, and zero steps from the linear fit is what ``mp_lift_place`` computes.
-Fusing the camera views of a take (``fuse_views``: one hypothesis per view, chosen jointly, and their mean; ``place_views``: one world root per frame
-from all views) is NOT a stage of the chain: both work on what ``lift_sequences`` returns for the views, and hpe/_entry.py (``lift.fuse``) cuts a
+Fusing the camera views of a take (``fuse_views_path``: ``fuse_views``' choice made jointly over the whole take, a Viterbi path over the combinations,
+so that a hypothesis all views agree on - a mirrored body - cannot make the fused motion flicker; ``fuse_views``: one hypothesis per view, chosen jointly, and their mean; ``place_views``: one world root per frame
+from all views) is NOT a stage of the chain: they work on what ``lift_sequences`` returns for the views, and hpe/_entry.py (``lift.fuse``) cuts a
 group's sequences into takes and calls them.
 """
 from __future__ import annotations
@@ -797,6 +798,55 @@ def fuse_views(hyps, orientation=None, valid=None, take_offset=None, sigma=FUSE_
     return _fuse(_lib.load(), hyps, valid, d_off, G, d_quat, sigma, score_weight)
 
 
+def _fuse_path(lib, hyps, valid, d_off, G, d_quat, sigma, score_weight, path_sigma, switch_cost):
+    """``mp_lift_fuse_path`` on hyps (V, Ftot, K, J, C): (pose, choice, cost, spread, ok, path_cost (G,) float64), new tensors"""
+    V, ftot, K, J, ch = (int(v) for v in hyps.shape)
+    dev = hyps.device
+    pose = torch.empty(ftot, J, 3, dtype=torch.float32, device=dev)
+    choice = torch.empty(ftot, V, dtype=torch.uint8, device=dev)
+    cost = torch.empty(ftot, dtype=torch.float32, device=dev)
+    spread = torch.empty(ftot, dtype=torch.float32, device=dev)
+    ok = torch.empty(ftot, dtype=torch.uint8, device=dev)
+    path_cost = torch.zeros(G, dtype=torch.float64, device=dev)
+    if ftot > 0:
+        n = int(lib.mp_lift_fuse_path_scratch_bytes(V, ftot, K))
+        scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_fuse_path(_lib.ptr(hyps), V, ftot, K, J, ch, _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(d_quat), float(sigma),
+                                             float(score_weight), float(path_sigma), float(switch_cost), _lib.ptr(pose), _lib.ptr(choice),
+                                             _lib.ptr(cost), _lib.ptr(spread), _lib.ptr(ok), _lib.ptr(path_cost), _lib.ptr(scratch), n,
+                                             _lib.stream_ptr()), "mp_lift_fuse_path")
+    return pose, choice, cost, spread, ok, path_cost
+
+
+def fuse_views_path(hyps, orientation=None, valid=None, take_offset=None, sigma=FUSE_SIGMA, score_weight=FUSE_SCORE_WEIGHT, path_sigma=PATH_SIGMA,
+                    switch_cost=PATH_SWITCH):
+    """``mp_lift_fuse_path`` on device tensors: the camera views of a take fused along time.  The arguments are ``fuse_views``'; the choice is not
+    made frame by frame but jointly over the whole take: the cheapest PATH through the combinations (one hypothesis per view: K^V states, at most
+    4096) under ``fuse_views``' cost per frame and, per view, ``select_path``'s cost per step - mean_j |w_b[j] - w_a[j]|^2 / (2 path_sigma^2) +
+    (switch_cost if a != b) from hypothesis a of a frame to hypothesis b of the next, w the rotated root-relative hypothesis; by the Viterbi
+    algorithm in fp64, staged per view, ties to the first combination (include/manipose_hip.h has the rule).  ``fuse_views`` takes a hypothesis
+    that all views agree on - a left/right-mirrored body - in every frame where its score is higher, and the fused motion flickers; the path does
+    not jump.  A view missing at a frame (``valid``) has no say there and its chain is cut.  ``path_sigma`` > 0 in the poses' unit (inf: steps cost
+    nothing, and with switch_cost = 0 the choice is ``fuse_views``'), ``switch_cost`` >= 0.  Returns ``(pose, choice, cost, spread, ok, path_cost
+    (G,) float64: the cost of every take's path)``, the first five as ``fuse_views`` returns them, new device tensors.  A frame that no take of
+    ``take_offset`` holds is left unwritten.  hyps is not modified; identical bits on every call.  Not measured on real data."""
+    _fuse_options(sigma, score_weight)
+    _path_options(path_sigma, switch_cost, ("path_sigma", "switch_cost"))
+    if torch.is_tensor(hyps):
+        _fuse_hyps_shape(hyps)                            # (the ValueErrors come before the refusal of a CPU tensor)
+        V, ftot = int(hyps.shape[0]), int(hyps.shape[1])
+        _score_valid(valid, (V, ftot), "valid")
+        G = 1 if take_offset is None else max(int(take_offset.numel() if torch.is_tensor(take_offset) else np.asarray(take_offset).size) - 1, 1)
+        h_quat = _fuse_quat(orientation, G, V) if orientation is not None else None
+    if not torch.is_tensor(hyps) or not hyps.is_cuda:
+        raise RuntimeError("manipose_amd: fuse_views_path takes device tensors; there is no CPU fallback")
+    valid = _fuse_valid(valid, V, ftot, "fuse_views_path")
+    d_off, G = _seq_table(take_offset, ftot, hyps.device)
+    d_quat = torch.from_numpy(h_quat).to(hyps.device) if h_quat is not None else None
+    return _fuse_path(_lib.load(), hyps, valid, d_off, G, d_quat, sigma, score_weight, path_sigma, switch_cost)
+
+
 def _take_cameras(cameras, V):
     """cameras[take][view] (camera_table's forms, None: a missing view) -> host (intr (G, V, 9), quat (G, V, 4), trans (G, V, 3), present (G, V) bool);
     a missing view gets the identity camera, which is never read"""
@@ -1423,5 +1473,5 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
 
 
 __all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "reproject_poses", "pose_rotations", "to_world", "smooth_poses", "smooth_traj",
-           "select_path", "score_poses", "score_traj", "fuse_views", "place_views", "lift_sequences",
+           "select_path", "score_poses", "score_traj", "fuse_views", "fuse_views_path", "place_views", "lift_sequences",
            "lift_action"]

@@ -9,6 +9,10 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --score [frames=3000] [K=5] [reps=50]
     python tools/lift_bench.py --rotations [frames=3000] [K=5] [reps=50]
     python tools/lift_bench.py --fuse [frames=3000] [K=5] [reps=200]
+    python tools/lift_bench.py --fuse-path [frames=3000] [K=5] [reps=20]
+--fuse-path times mp_lift_fuse_path (the views' hypotheses chosen jointly over the whole take: tables, scan and emit kernels) through its private
+launcher on --fuse's scene - 4 views x `frames` frames x K hypotheses - as ONE take (the scan is one workgroup walking the frames in order: the serial
+case) and cut into 16, next to mp_lift_fuse on the same scene.
 --fuse times mp_lift_fuse (one hypothesis per view chosen jointly over S11's four cameras, and their mean) and mp_lift_fuse_place (one world root
 per frame from all views, at iters 0 and 3) through their private launchers on 4 views x `frames` frames x K hypotheses of ONE take, next to
 mp_lift_path on one view's hypotheses of the same frames, for scale.
@@ -218,13 +222,10 @@ def rotations_bench(argv):
     print(f"mp_lift_rigid on the same hypotheses: {us:,.1f} us", flush=True)
 
 
-def fuse_bench(argv):
+def fuse_scene(frames, K):
+    """--fuse's scene: (lib, V, (quat, trans, intr), pose, hyps (V, frames, K, 17, 4), kp) on S11's four cameras"""
     from manipose_amd import _lib
     from manipose_amd.data.ingest import h36m_cameras
-    from manipose_amd.lifting import _fuse, _fuse_place, _path
-    frames = int(argv[0]) if len(argv) > 0 else 3000
-    K = int(argv[1]) if len(argv) > 1 else 5
-    reps = int(argv[2]) if len(argv) > 2 else 200
     assert torch.cuda.is_available(), "needs an MI355X"
     lib, V = _lib.load(), 4
     cams = h36m_cameras()["S11"]
@@ -244,6 +245,17 @@ def fuse_bench(argv):
     hyps[..., 3] = torch.softmax(1.5 * torch.randn(V, frames, K, device="cuda", generator=g), dim=2)[..., None]
     P = torch.einsum("vfjc,vcd->vfjd", (pose + root[:, None])[None] - trans[0][:, None, None], R)
     kp = (intr[0, :, None, None, 0:2] * P[..., :2] / P[..., 2:3] + intr[0, :, None, None, 2:4] + 0.01 * torch.randn(V, frames, 17, 2, device="cuda", generator=g)).contiguous()
+    return lib, V, (quat, trans, intr), pose, hyps, kp
+
+
+def fuse_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.data.ingest import h36m_cameras
+    from manipose_amd.lifting import _fuse, _fuse_place, _path
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    K = int(argv[1]) if len(argv) > 1 else 5
+    reps = int(argv[2]) if len(argv) > 2 else 200
+    lib, V, (quat, trans, intr), pose, hyps, kp = fuse_scene(frames, K)
     one = torch.tensor([0, frames], dtype=torch.int64, device="cuda")
     fused = _fuse(lib, hyps, None, one, 1, quat, 0.02, 1.0)
     print(f"--fuse: {V} views x {frames} frames x {K} hypotheses, {hyps.numel() * 4 / 1e6:.2f} MB of hypotheses, {K ** V} combinations a frame; {reps} calls each "
@@ -259,6 +271,30 @@ def fuse_bench(argv):
     print(f"mp_lift_path on one view's {frames} frames x {K} hypotheses, for scale: {us:,.1f} us", flush=True)
 
 
+def fuse_path_bench(argv):
+    from manipose_amd.lifting import _fuse, _fuse_path
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    K = int(argv[1]) if len(argv) > 1 else 5
+    reps = int(argv[2]) if len(argv) > 2 else 20
+    lib, V, (quat, _, _), _, hyps, _ = fuse_scene(frames, K)
+    print(f"--fuse-path: {V} views x {frames} frames x {K} hypotheses, {K ** V} states a frame, {lib.mp_lift_fuse_path_scratch_bytes(V, frames, K) / 1e6:.2f} MB of "
+          f"scratch; {reps} calls each after 5 of warm-up (the allocations of outputs and scratch are inside the time)", flush=True)
+    for G in (1, 16):
+        off = torch.tensor([frames * i // G for i in range(G + 1)], dtype=torch.int64, device="cuda")
+        q = quat.expand(G, V, 4).contiguous()
+        res = _fuse_path(lib, hyps, None, off, G, q, 0.02, 1.0, 0.02, 0.0)
+        per = _fuse(lib, hyps, None, off, G, q, 0.02, 1.0)
+        us = timed_us(lambda: _fuse_path(lib, hyps, None, off, G, q, 0.02, 1.0, 0.02, 0.0), reps)
+        print(f"mp_lift_fuse_path, {G} take(s): {us:,.1f} us  {frames / us:,.3f} M frames/s  {us / (frames / G) * 1e3:,.0f} ns per frame of a take; choice differs from "
+              f"mp_lift_fuse's in {(res[1] != per[1]).any(dim=1).float().mean().item():.3f} of the frames", flush=True)
+    one = torch.tensor([0, frames], dtype=torch.int64, device="cuda")
+    us = timed_us(lambda: _fuse(lib, hyps, None, one, 1, quat, 0.02, 1.0), 10 * reps)
+    print(f"mp_lift_fuse on the same scene, for scale: {us:,.1f} us", flush=True)
+
+
+if "--fuse-path" in sys.argv:
+    fuse_path_bench([a for a in sys.argv[1:] if a != "--fuse-path"])
+    sys.exit(0)
 if "--fuse" in sys.argv:
     fuse_bench([a for a in sys.argv[1:] if a != "--fuse"])
     sys.exit(0)
