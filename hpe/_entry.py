@@ -273,7 +273,8 @@ def sk_device(model):
 
 LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj", "__hyps_reproj", "__hyps_ok", "__floor", "__cam", "__traj_fit", "__filled",
                  "__hyps_traj_fit", "__hyps_filled", "__path", "__path_cost", "__steps", "__hyps_steps", "__reproj_smooth", "__hyps_reproj_smooth",
-                 "__quat", "__quat_ok", "__hyps_quat", "__hyps_quat_ok", "__root", "__choice", "__spread", "__cost", "__views")
+                 "__quat", "__quat_ok", "__hyps_quat", "__hyps_quat_ok", "__root", "__choice", "__spread", "__cost", "__views", "__cam_quat", "__cam_trans",
+                 "__cam_rms", "__cam_trans_rms", "__cam_used", "__cam_ok", "__cam_err_deg", "__cam_err_m")
 
 
 def lift_place_options(cfg):
@@ -392,7 +393,9 @@ def lift_fuse_options(cfg):
     if not bool(cfg.run.lift):
         raise ValueError("lift.fuse fuses what run.lift lifts: set run.lift=true")
     if str(cfg.data.dataset) == "3dhp":
-        raise ValueError("lift.fuse needs the cameras' calibration, and the MPI-INF-3DHP files (data.dataset=3dhp) carry none")
+        raise ValueError("lift.fuse needs the cameras' calibration, and the MPI-INF-3DHP files (data.dataset=3dhp) carry none - nor do they say which "
+                         "sequences are one take, so lift.fuse_cameras=estimate cannot help here: cut the takes yourself and give their views' poses to "
+                         "manipose_amd.align_views, whose quat and trans are fuse_views' and place_views' extrinsics")
     if bool(cfg.lift.get("keep_padding", False)):
         raise ValueError("lift.fuse with keep_padding: padded frames have no keypoints of their own")
     if bool(cfg.data.data_dir) and (str(cfg.model.arch) != "rmcl_manifold" or not 2 <= int(cfg.multi_hyp.n_hyp) <= 8):
@@ -426,6 +429,28 @@ def lift_fuse_path_options(cfg):
     return True, float(sigma), float(switch)
 
 
+def lift_fuse_align_options(cfg):
+    """(estimate, sigma, iters) of lift.fuse_cameras / lift.fuse_align_sigma / lift.fuse_align_iters; ValueError for a value or a combination that
+    cannot run - before any model is built."""
+    cameras = cfg.lift.get("fuse_cameras", "dataset")
+    sigma, iters = cfg.lift.get("fuse_align_sigma", 0.05), cfg.lift.get("fuse_align_iters", 5)
+    if cameras not in ("dataset", "estimate"):
+        raise ValueError(f"lift.fuse_cameras must be dataset or estimate, got {cameras!r}")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
+        raise ValueError(f"lift.fuse_align_sigma is a number, got {sigma!r}")
+    if not sigma > 0:
+        raise ValueError(f"lift.fuse_align_sigma must be > 0 (metres), got {sigma!r}")
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= 8:
+        raise ValueError(f"lift.fuse_align_iters counts re-weightings, an integer in 0..8, got {iters!r}")
+    if cameras != "estimate":
+        if sigma != 0.05 or iters != 5:
+            raise ValueError("lift.fuse_align_sigma / lift.fuse_align_iters describe the estimate of a take's extrinsics: set lift.fuse_cameras=estimate")
+        return False, float(sigma), iters
+    if not lift_fuse_options(cfg)[0]:
+        raise ValueError("lift.fuse_cameras=estimate estimates the extrinsics the fusion uses: set lift.fuse=true")
+    return True, float(sigma), iters
+
+
 def _camera_index(cam):
     """fetch()'s 17th number, a camera dict's "index", or None"""
     if isinstance(cam, dict):
@@ -452,6 +477,60 @@ def _qrot(q, v):
     q, v = np.asarray(q, np.float64), np.asarray(v, np.float64)
     uv = np.cross(np.broadcast_to(q[1:], v.shape), v)
     return v + 2.0 * (q[0] * uv + np.cross(np.broadcast_to(q[1:], v.shape), uv))
+
+
+CAMERA_KEYS = ("quat", "trans", "rms", "trans_rms", "used", "ok", "err_deg", "err_m")       # of estimate_cameras' dict -> "<fused key>__cam_<k>" in lift.npz
+
+
+def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, refine, sigma, iters):
+    """lift.fuse_cameras=estimate on one group: every take's extrinsics from its views' merged poses (align_views), the first view's dataset camera
+    as the reference - so the world is the dataset's and its z is up.  The views' poses are taken root-relative in their cameras' frames (with
+    lift.frame=world they are rotated back, and so are ``hyps``, IN PLACE), every view's root trajectory is fitted on its own (place_poses with the
+    view's intrinsics and ``refine`` steps), and the rotation comes from the poses, the translation from the trajectories.  Returns
+    ``(est, nested, valid, place_valid)``: est = {CAMERA_KEYS: host arrays (G, V, ..)}, err_deg / err_m the angle and the distance between the
+    estimated and the dataset's extrinsics; nested: place_views' cameras with the dataset's intrinsics and the estimated extrinsics; valid without
+    the views whose rotation could not be estimated, place_valid also without those whose translation could not."""
+    from manipose_amd import align_views, camera_table, place_poses, to_world
+    V, ftot, J, dev, G = int(hyps.shape[0]), int(hyps.shape[1]), int(hyps.shape[3]), hyps.device, len(takes)
+    intr, quat, trans = (a.astype(np.float64) for a in camera_table(cams))
+    unit = quat / np.linalg.norm(quat, axis=1, keepdims=True)
+    back = (unit * np.array([1.0, -1.0, -1.0, -1.0])).astype(np.float32)             # world to camera: the conjugate
+    merged = torch.zeros(V, ftot, J, 3, dtype=torch.float32, device=dev)
+    table = np.zeros((V, G, 9), np.float32)
+    table[..., 0:2] = 1.0
+    for t, views in enumerate(takes):
+        for v, i in enumerate(views):
+            p = res.poses[i].clone()
+            if world:
+                p = to_world(p, back[i])
+                hyps[v, off[t]:off[t + 1]] = to_world(res.hyps[i].clone(), back[i])
+            merged[v, off[t]:off[t + 1]] = p - p[:, :1]
+            table[v, t] = intr[i]
+    starts = np.concatenate([v * ftot + off[:-1] for v in range(V)] + [[V * ftot]]).astype(np.int64)
+    traj, _, traj_ok = place_poses(merged.reshape(V * ftot, J, 3), kp.reshape(V * ftot, J, 2), table.reshape(V * G, 9), starts, refine=refine)
+    got = align_views(merged, valid, off, traj.reshape(V, ftot, 3), traj_ok.reshape(V, ftot) & valid, sigma, iters,
+                      reference=[cams[views[0]] for views in takes])
+    est = {k: getattr(got, k).cpu().numpy() for k in CAMERA_KEYS[:6]}
+    est["err_deg"], est["err_m"] = np.zeros((G, V), np.float32), np.zeros((G, V), np.float32)
+    nested, valid, place_valid = [], valid.clone(), valid.clone()
+    for t, views in enumerate(takes):
+        row = [None] * V
+        for v, i in enumerate(views):
+            q = est["quat"][t, v].astype(np.float64)
+            rel = unit[i][0] * q[1:] - q[0] * unit[i][1:] - np.cross(unit[i][1:], q[1:])           # the vector part of conj(q_dataset) q
+            est["err_deg"][t, v] = np.degrees(2.0 * np.arctan2(np.linalg.norm(rel), abs(float(q @ unit[i]))))
+            est["err_m"][t, v] = np.linalg.norm(est["trans"][t, v].astype(np.float64) - trans[i])
+            row[v] = np.concatenate([intr[i], est["quat"][t, v], est["trans"][t, v]])
+            if not est["ok"][t, v] & 1:
+                valid[v, off[t]:off[t + 1]] = 0
+                print(f"lift.fuse_cameras [{name}]: take {t}, view {views[v]}: its rotation could not be estimated ({int(est['used'][t, v])} frames used): "
+                      f"the view is left out of the take", flush=True)
+            if not (est["ok"][t, v] & 2 or v == 0) or not est["ok"][t, v] & 1:
+                place_valid[v, off[t]:off[t + 1]] = 0
+                if est["ok"][t, v] & 1:
+                    print(f"lift.fuse_cameras [{name}]: take {t}, view {views[v]}: its position could not be estimated: the view has no say in the root", flush=True)
+        nested.append(row)
+    return est, nested, valid, place_valid
 
 
 def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
@@ -490,13 +569,18 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
             valid[v, off[t]:off[t + 1]] = 1
             quat[t, v] = camera_table([cams[i]])[1][0]
     nested = [[cams[i] for i in views] + [None] * (V - len(views)) for views in takes]
+    estimate, align_sigma, align_iters = lift_fuse_align_options(cfg)
+    est, q_arg, place_valid = None, None if world else quat, valid
+    if estimate:                               # lift.fuse_cameras=estimate: the extrinsics come from the poses, not from the dataset
+        est, nested, valid, place_valid = estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, refine, align_sigma, align_iters)
+        q_arg = est["quat"]                    # (the hypotheses are back in their cameras' frames)
     if along:                                  # lift.fuse_path: the same choice, made jointly over the whole take
-        pose, choice, cost, spread, ok, path_cost = fuse_views_path(hyps, None if world else quat, valid, off, sigma, weight, path_sigma, path_switch)
+        pose, choice, cost, spread, ok, path_cost = fuse_views_path(hyps, q_arg, valid, off, sigma, weight, path_sigma, path_switch)
     else:
-        pose, choice, cost, spread, ok = fuse_views(hyps, None if world else quat, valid, off, sigma, weight)
+        pose, choice, cost, spread, ok = fuse_views(hyps, q_arg, valid, off, sigma, weight)
     if res.bones is not None:                  # lift.rigid: one table per take, the mean of its views'
         project_rigid(pose, torch.stack([torch.stack([res.bones[i] for i in views]).mean(dim=0) for views in takes]), seq_offset=off)
-    root, reproj, placed, steps = place_views(pose, kp, nested, valid, off, refine=refine, return_steps=True)
+    root, reproj, placed, steps = place_views(pose, kp, nested, place_valid, off, refine=refine, return_steps=True)
     unit = np.tile(np.array([1, 0, 0, 0], np.float32), (len(takes), 1))
     scene = to_world(pose.clone(), unit, traj=root, seq_offset=off, floor=True if floor else False)
     scene, d_floor = scene if floor else (scene, None)
@@ -519,6 +603,9 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
         out[key + "__ok"] = (ok[sl] & placed[sl]).cpu().numpy()
         out[key + "__reproj"], out[key + "__steps"] = reproj[:len(views), sl].cpu().numpy(), steps[sl].cpu().numpy()
         out[key + "__views"] = np.array(views, dtype=np.int64)
+        if est is not None:
+            for k in CAMERA_KEYS:
+                out[f"{key}__cam_{k}"] = est[k][t, :len(views)]
         if along:
             out[key + "__path_cost"] = path_cost[t].cpu().numpy()
         if floor:
@@ -565,7 +652,9 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     new take wherever the camera index, fetch()'s 17th number, does not increase - and every take ``t`` also gets ``<name>.fused<t>`` (N, 17, 3), the
     views' consensus pose at ONE world root, with ``__root`` (N, 3), ``__choice`` (N, V) uint8, ``__spread``, ``__cost``, ``__ok``, ``__steps`` (N,),
     ``__reproj`` (V, N), ``__views`` (the sequences' indices within the group), with lift.floor ``__floor`` and with lift.fuse_path (lift.fuse_path_sigma,
-    lift.fuse_path_switch) ``__path_cost``, a scalar (fuse_group); with ``targets`` the dict
+    lift.fuse_path_switch) ``__path_cost``, a scalar (fuse_group); with lift.fuse_cameras=estimate (lift.fuse_align_sigma, lift.fuse_align_iters) the
+    takes' extrinsics are estimated from the views' poses (estimate_cameras) and ``__cam_quat`` (V, 4), ``__cam_trans`` (V, 3), ``__cam_rms``,
+    ``__cam_trans_rms``, ``__cam_used``, ``__cam_ok``, ``__cam_err_deg``, ``__cam_err_m`` (V,) are added; with ``targets`` the dict
     ``fused_scores`` receives {fused key: score dict} of the fused pose and root against the first view's ground truth in the world."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
@@ -660,6 +749,7 @@ def run(argv, extra_defaults=None):
     lift_rotations_options(cfg)                # ... and a lift.rotations without run.lift
     lift_fuse_options(cfg)                     # ... and a lift.fuse without run.lift, without calibration or without hypotheses
     lift_fuse_path_options(cfg)                # ... and a lift.fuse_path without lift.fuse
+    lift_fuse_align_options(cfg)               # ... and a lift.fuse_cameras=estimate without lift.fuse
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")

@@ -756,6 +756,45 @@ int mp_lift_fuse_path(const float* hyps, int V, int64_t Ftot, int K, int J, int 
                       const float* quat, float sigma, float score_weight, float path_sigma, float switch_cost, float* pose, uint8_t* choice, float* cost,
                       float* spread, uint8_t* ok, double* path_cost, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* Aligning the views of a take WITHOUT extrinsics: mp_lift_fuse, mp_lift_fuse_place and mp_lift_fuse_path stand on every camera's calibrated
+ * orientation and position; this estimates them from the lifted poses themselves, up to the choice of a reference view.  Two views of one motion
+ * give, per frame, the same root-relative body in two camera frames: they differ by ONE rotation for the whole take, and their placed roots
+ * (mp_lift_place[_refine]) by that rotation and ONE translation.  The rotation is Horn's closed form over all frames of the take, re-weighted
+ * (single views do produce depth-mirrored bodies: mp_lift_fuse exists because of them).  The conventions are mp_lift_fuse's: takes, take_offset
+ * (entries clamped to 0 .. Ftot), valid (V, Ftot) bytes or null, 1 <= V <= MP_LIFT_FUSE_MAXV; fp64 between the float32 loads and the float32
+ * stores, without contraction into fused multiply-adds; no atomics, fixed orders: identical bits on every call; a take's result does not depend
+ * on the other takes of the call; the call does not synchronise.  Not measured on real data.
+ * poses (V, Ftot, J, C) read only, C = 3 or 4 (channel 3 is not read), 2 <= J <= 32: one pose per view and frame in that view's camera frame;
+ * traj (V, Ftot, 3) floats and traj_ok (V, Ftot) bytes, or both null: the views' camera-space roots; sigma > 0 in the poses' unit (+inf: every
+ * weight is exactly 1); 0 <= iters <= MP_LIFT_ALIGN_MAXITERS.  Per take g with frames [f0, f1):
+ * 1. b[v][f][j] = x[v][f][j] - x[v][f][0].
+ * 2. The reference view r is the lowest view with at least one valid frame in the take.  Its row: quat = (1, 0, 0, 0), trans = 0, rms = 0,
+ *    trans_rms = 0, used = its valid frames, ok = 1.  A take without such a view writes, for every view, quat = (1, 0, 0, 0), zeros and ok = 0.
+ * 3. Frame f is USED for view v if it is valid in v and in r and all 3 J coordinates of both poses are finite.
+ * 4. M = sum_f w_f S_f over the used frames,  S_f = sum_j b[v][f][j] b[r][f][j]^T (row: view v's channel, column: the reference's), joints in
+ *    order;  w_f = 1 in the first pass.  Horn's symmetric 4x4 N(M) as mp_lift_score's alignment forms it; its dominant eigenvector by cyclic Jacobi
+ *    sweeps until off(N) <= 2^-52 |N|_F (30 at most), normalised;  q is canonical: w >= 0, and if w == 0 the first non-zero component is positive.
+ * 5. iters times, with R = R(q):  e_f = (sum_j |b[r][f][j] - R b[v][f][j]|^2) / J,  w_f = 1 / (1 + e_f / sigma^2)^2, then step 4 again.
+ * 6. Degenerate: no used frame; sum w not > 0; one of the ten sums not finite; the dominant eigenvalue not > 0 (all at any solve);
+ *    (lambda_1 - lambda_2) <= 1e-9 |lambda_1| at the last solve.  Then ok = 0, quat = (1, 0, 0, 0), trans = 0, rms = 0, trans_rms = 0.
+ * 7. rms[g][v] = sqrt(sum_f w_f e_f / sum_f w_f), e_f at the final q, w_f the weights of the last solve (1 for iters = 0);  used[g][v] = the
+ *    number of used frames (also in a degenerate row).
+ * 8. With traj: over the used frames with traj_ok set in v and in r,  d_f = traj[r][f] - R traj[v][f],  T = sum w_f d_f / sum w_f,
+ *    trans_rms = sqrt(sum w_f |d_f - T|^2 / sum w_f) in a pass of its own after T, the weights those of step 7.  No such frame, sum w not > 0 or
+ *    a sum that is not finite: T = 0, trans_rms = 0 and ok keeps bit 0 only.  ok is a byte: bit 0 the rotation, bit 1 the translation.
+ * 9. x_ref = R_v x_v + T_v, mp_lift_fuse's camera-to-world with the reference view's frame as the world: quat and trans can be passed on as they are.
+ * One workgroup of 256 lanes per (take, view): a lane sums the frames f0 + lane, f0 + lane + 256, ... in order, the lanes' sums are added by a
+ * butterfly within a wave and the four waves' in wave order, every lane solves the 4x4 problem; the passes (iters + 2, with traj iters + 4)
+ * follow one another inside the workgroup.
+ * quat (G, V, 4), rms (G, V) floats, used (G, V) int32, ok (G, V) bytes; trans (G, V, 3) and trans_rms (G, V) floats, needed with traj, else they
+ * may be null (given without traj they are written as zeros).
+ * MP_ERR_ARG before anything is launched: poses, take_offset, quat, rms, used or ok null; V, J or C out of range; Ftot or G <= 0, G > Ftot,
+ * Ftot or G V > 2^31 - 1; sigma not > 0; iters out of range; exactly one of traj and traj_ok null; trans or trans_rms null while traj is given. */
+#define MP_LIFT_ALIGN_MAXITERS 8
+int mp_lift_align_views(const float* poses, int V, int64_t Ftot, int J, int C, const uint8_t* valid, const int64_t* take_offset, int G,
+                        const float* traj, const uint8_t* traj_ok, float sigma, int iters, float* quat, float* trans, float* rms, float* trans_rms,
+                        int32_t* used, uint8_t* ok, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -914,6 +914,124 @@ def place_views(pose, keypoints_2d, cameras, valid=None, take_offset=None, weigh
     return res if return_steps else res[:3]
 
 
+ALIGN_MAXITERS = 8           # MP_LIFT_ALIGN_MAXITERS of include/manipose_hip.h: re-weightings mp_lift_align_views takes at most
+ALIGN_SIGMA, ALIGN_ITERS = 0.05, 5           # defaults of align_views: the scale of a frame's residual in metres, the re-weightings (not tuned)
+# What align_views returns: quat (G, V, 4), trans (G, V, 3) or None, rms (G, V), trans_rms (G, V) or None float32, used (G, V) int32, ok (G, V) uint8
+ViewAlignment = namedtuple("ViewAlignment", "quat trans rms trans_rms used ok")
+
+
+def _align_options(sigma, iters):
+    if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not float(sigma) > 0:
+        raise ValueError(f"sigma must be a number > 0 (inf: every frame weighs 1), got {sigma!r}")
+    if not isinstance(iters, (int, np.integer)) or isinstance(iters, (bool, np.bool_)) or not 0 <= int(iters) <= ALIGN_MAXITERS:
+        raise ValueError(f"iters counts re-weightings, an integer in 0..{ALIGN_MAXITERS} (0: plain Horn), got {iters!r}")
+
+
+def _quat_matrix(q):
+    """the rotation matrix of q / |q| (w, x, y, z) in float64"""
+    w, x, y, z = np.asarray(q, np.float64) / np.linalg.norm(np.asarray(q, np.float64))
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _align_compose(quat, trans, ok, ref_quat, ref_trans):
+    """mp_lift_align_views' rows (G, V, ..) in the reference views' frames -> in the worlds of the reference views' known extrinsics, on the host
+    in float64: q = q_ref * q_v (q_ref normalised), T = R_ref T_v + T_ref.  A row whose ok lacks bit 0 is left as it is; the translation is composed
+    where ok has bit 1 and for the reference view itself, the lowest view of a take with bit 0 (its T_v = 0 is known); elsewhere it stays 0.
+    Returns float32 (quat, trans or None); q stays canonical (w >= 0, else the first non-zero component positive)."""
+    q64, ok = np.asarray(quat, np.float64).copy(), np.asarray(ok)
+    t64 = np.asarray(trans, np.float64).copy() if trans is not None else None
+    for g in range(q64.shape[0]):
+        a = np.asarray(ref_quat[g], np.float64)
+        a = a / np.linalg.norm(a)
+        R = _quat_matrix(a)
+        rot = np.nonzero(ok[g] & 1)[0]
+        for v in rot:
+            b = q64[g, v]
+            q = np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                          a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
+            nz = q[np.nonzero(q)[0][:1]]
+            q64[g, v] = -q if nz.size and nz[0] < 0 else q
+            if t64 is not None and (ok[g, v] & 2 or v == rot[0]):
+                t64[g, v] = R @ t64[g, v] + np.asarray(ref_trans[g], np.float64)
+    return q64.astype(np.float32), t64.astype(np.float32) if t64 is not None else None
+
+
+def _align(lib, poses, valid, d_off, G, traj, traj_ok, sigma, iters):
+    """``mp_lift_align_views`` on poses (V, Ftot, J, C): a ViewAlignment of new tensors"""
+    V, ftot, J, ch = (int(v) for v in poses.shape)
+    dev = poses.device
+    quat = torch.zeros(G, V, 4, dtype=torch.float32, device=dev)
+    quat[..., 0] = 1.0
+    trans = torch.zeros(G, V, 3, dtype=torch.float32, device=dev) if traj is not None else None
+    rms = torch.zeros(G, V, dtype=torch.float32, device=dev)
+    trans_rms = torch.zeros(G, V, dtype=torch.float32, device=dev) if traj is not None else None
+    used = torch.zeros(G, V, dtype=torch.int32, device=dev)
+    ok = torch.zeros(G, V, dtype=torch.uint8, device=dev)
+    if ftot > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_align_views(_lib.ptr(poses), V, ftot, J, ch, _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(traj), _lib.ptr(traj_ok),
+                                               float(sigma), int(iters), _lib.ptr(quat), _lib.ptr(trans), _lib.ptr(rms), _lib.ptr(trans_rms),
+                                               _lib.ptr(used), _lib.ptr(ok), _lib.stream_ptr()), "mp_lift_align_views")
+    return ViewAlignment(quat, trans, rms, trans_rms, used, ok)
+
+
+def align_views(poses, valid=None, take_offset=None, traj=None, traj_ok=None, sigma=ALIGN_SIGMA, iters=ALIGN_ITERS, reference=None):
+    """``mp_lift_align_views`` on device tensors: the extrinsics of a take's views estimated from their lifted poses, for takes whose cameras
+    were never calibrated against each other.  ``poses`` (V, Ftot, J, 3 | 4) float32, one pose per view and frame in that view's camera frame
+    (channel 3 is not read); ``valid`` (V, Ftot) uint8 device tensor or None; ``take_offset`` (G + 1) as for ``fuse_views``; ``traj`` (V, Ftot, 3)
+    float32 and ``traj_ok`` (V, Ftot) uint8, both or neither: the views' camera-space roots as ``place_poses`` returns them.  Per take the lowest
+    view with a valid frame is the reference; every other view's rotation onto it is Horn's closed form over the root-relative poses of all
+    frames valid in both, re-weighted ``iters`` (0..8) times with w = 1 / (1 + e / sigma^2)^2, e a frame's mean squared residual - a depth-mirrored
+    body loses its say; ``sigma`` > 0 in the poses' unit (inf: plain Horn) - and, with ``traj``, its translation the weighted mean of
+    traj_ref - R traj_v (include/manipose_hip.h has the rule).  The defaults are not tuned.  x_ref = R_v x_v + T_v: ``quat`` and ``trans`` are
+    ``fuse_views``' and ``place_views``' extrinsics with the reference view's frame as the world.  ``reference``: per take one camera in
+    ``camera_table``'s forms (a list of G; one camera alone for one take), the known extrinsics of the reference view: the result is composed on
+    the host in float64 into that world, q = q_ref * q_v, T = R_ref T_v + T_ref (this waits for the kernel).  Returns a ``ViewAlignment``:
+    ``(quat (G, V, 4), trans (G, V, 3) or None, rms (G, V): the weighted RMS residual of the poses, trans_rms (G, V) or None: that of the
+    roots - a monocular depth scale error shows here -, used (G, V) int32: the frames used, ok (G, V) uint8: bit 0 the rotation, bit 1 the
+    translation)``, new device tensors; a degenerate row is the identity with ok = 0.  Inputs are not modified; identical bits on every call.
+    Not measured on real data."""
+    _align_options(sigma, iters)
+    if (traj is None) != (traj_ok is None):
+        raise ValueError("traj and traj_ok come together: the views' roots and where they were fitted")
+    if torch.is_tensor(poses):
+        if poses.dim() != 4 or poses.shape[3] not in (3, 4) or poses.dtype != torch.float32 or not poses.is_contiguous():
+            raise ValueError(f"poses must be contiguous float32 (V, Ftot, J, 3 | 4), got {tuple(poses.shape)} {poses.dtype}")
+        V, ftot, J = (int(v) for v in poses.shape[:3])
+        if not 1 <= V <= FUSE_MAXV:
+            raise ValueError(f"poses have {V} views: 1..{FUSE_MAXV} expected")
+        if not 2 <= J <= 32:
+            raise ValueError(f"poses have {J} joints: 2..32 expected")
+        _score_valid(valid, (V, ftot), "valid")
+        if traj is not None:
+            if not torch.is_tensor(traj) or tuple(traj.shape) != (V, ftot, 3) or traj.dtype != torch.float32:
+                raise ValueError(f"traj must be a float32 tensor ({V}, {ftot}, 3), got "
+                                 f"{(tuple(traj.shape), traj.dtype) if torch.is_tensor(traj) else type(traj).__name__}")
+            if traj_ok is None or not torch.is_tensor(traj_ok):
+                raise ValueError(f"traj_ok must be a uint8 tensor of shape ({V}, {ftot})")
+            _score_valid(traj_ok, (V, ftot), "traj_ok")
+        G = 1 if take_offset is None else max(int(take_offset.numel() if torch.is_tensor(take_offset) else np.asarray(take_offset).size) - 1, 1)
+        if reference is not None:
+            single = isinstance(reference, dict) or torch.is_tensor(reference) or (hasattr(reference, "ndim") and getattr(reference, "ndim", 0) == 1)
+            _, ref_quat, ref_trans = camera_table([reference] if single else reference)
+            if ref_quat.shape[0] != G:
+                raise ValueError(f"reference lists {ref_quat.shape[0]} cameras, take_offset {G} takes")
+            if not ((ref_quat.astype(np.float64) ** 2).sum(-1) >= 1e-12).all():
+                raise ValueError("reference holds a zero quaternion")
+    if not torch.is_tensor(poses) or not poses.is_cuda or (traj is not None and not (traj.is_cuda and traj_ok.is_cuda)):
+        raise RuntimeError("manipose_amd: align_views takes device tensors; there is no CPU fallback")
+    valid = _fuse_valid(valid, V, ftot, "align_views")
+    d_off, G = _seq_table(take_offset, ftot, poses.device)
+    res = _align(_lib.load(), poses, valid, d_off, G, traj.contiguous() if traj is not None else None,
+                 traj_ok.contiguous() if traj_ok is not None else None, sigma, iters)
+    if reference is None:
+        return res
+    q, t = _align_compose(res.quat.cpu().numpy(), res.trans.cpu().numpy() if res.trans is not None else None, res.ok.cpu().numpy(), ref_quat, ref_trans)
+    return res._replace(quat=torch.from_numpy(q).to(poses.device), trans=torch.from_numpy(t).to(poses.device) if t is not None else None)
+
+
 def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirror, agg="weighted_ave", blend="mean", scale=1.0,
                   return_hyps=False, out=None, hyps=None, device_tables=None):
     """``mp_lift_merge`` on device tensors: poses (F*W, K, T, J, 3), scores (F*W, K, T, 1) or None (K == 1); win_seq / win_start (W)
@@ -1473,5 +1591,5 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
 
 
 __all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "reproject_poses", "pose_rotations", "to_world", "smooth_poses", "smooth_traj",
-           "select_path", "score_poses", "score_traj", "fuse_views", "fuse_views_path", "place_views", "lift_sequences",
+           "select_path", "score_poses", "score_traj", "fuse_views", "fuse_views_path", "place_views", "align_views", "lift_sequences",
            "lift_action"]

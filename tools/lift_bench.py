@@ -10,6 +10,10 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --rotations [frames=3000] [K=5] [reps=50]
     python tools/lift_bench.py --fuse [frames=3000] [K=5] [reps=200]
     python tools/lift_bench.py --fuse-path [frames=3000] [K=5] [reps=20]
+    python tools/lift_bench.py --align [frames=3000] [reps=20]
+--align times mp_lift_align_views (a take's extrinsics from its views' poses: one workgroup per (take, view), iters + 2 passes over the poses, with
+a trajectory iters + 4) through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints, in 30 % of the frames of views 1..3
+the hypothesis moved along the depth axis - as ONE take and cut into 16, and prints how far the estimate is from S11's calibration.
 --fuse-path times mp_lift_fuse_path (the views' hypotheses chosen jointly over the whole take: tables, scan and emit kernels) through its private
 launcher on --fuse's scene - 4 views x `frames` frames x K hypotheses - as ONE take (the scan is one workgroup walking the frames in order: the serial
 case) and cut into 16, next to mp_lift_fuse on the same scene.
@@ -292,6 +296,47 @@ def fuse_path_bench(argv):
     print(f"mp_lift_fuse on the same scene, for scale: {us:,.1f} us", flush=True)
 
 
+def align_bench(argv):
+    from manipose_amd import align_views
+    from manipose_amd.data.ingest import h36m_cameras
+    from manipose_amd.lifting import _align
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib, V, (quat, trans, _), _, hyps, _ = fuse_scene(frames, 2)
+    g = torch.Generator(device="cuda").manual_seed(2)
+    swap = torch.rand(V, frames, device="cuda", generator=g) < 0.3           # 30 % of a view's frames take the hypothesis moved along the depth axis
+    swap[0] = False
+    poses = torch.where(swap[:, :, None, None], hyps[:, :, 1], hyps[:, :, 0]).contiguous()
+    qn = quat[0] / quat[0].norm(dim=1, keepdim=True)
+    w, x, y, z = qn.unbind(1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                     2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).view(V, 3, 3)
+    root = torch.cat([2 * torch.rand(frames, 2, device="cuda", generator=g) - 1, 0.8 + 0.2 * torch.rand(frames, 1, device="cuda", generator=g)], dim=1)
+    traj = torch.einsum("vfc,vcd->vfd", root[None] - trans[0][:, None], R).contiguous()      # R^T (root - T): every view's camera-space root
+    traj_ok = torch.ones(V, frames, dtype=torch.uint8, device="cuda")
+    print(f"--align: {V} views x {frames} frames x 17 joints, {poses.numel() * 4 / 1e6:.2f} MB of poses, 30 % of the frames of views 1..3 moved along the depth axis "
+          f"(sigma 0.08 m); {reps} calls each after 5 of warm-up (the output allocations are inside the time)", flush=True)
+    cams = h36m_cameras()["S11"]
+    for iters in (0, 5):
+        got = align_views(poses, None, None, traj, traj_ok, 0.05, iters, reference=cams[0])
+        a, b = qn.double().cpu().numpy(), got.quat[0].double().cpu().numpy()     # the angle of conj(a) b by the arc tangent: accurate at small angles
+        vec = a[:, :1] * b[:, 1:] - b[:, :1] * a[:, 1:] - np.cross(a[:, 1:], b[:, 1:])
+        deg = np.degrees(2.0 * np.arctan2(np.linalg.norm(vec, axis=1), np.abs((a * b).sum(axis=1))))
+        print(f"iters={iters}: off S11's calibration by {', '.join(f'{x:.3f}' for x in deg[1:])} degrees and "
+              f"{', '.join(f'{d * 1e3:.1f}' for d in (got.trans[0] - trans[0]).norm(dim=1).tolist()[1:])} mm; rms {', '.join(f'{r * 1e3:.1f}' for r in got.rms[0].tolist()[1:])} mm",
+              flush=True)
+    for G in (1, 16):
+        off = torch.tensor([frames * i // G for i in range(G + 1)], dtype=torch.int64, device="cuda")
+        for iters, with_traj in ((0, False), (5, False), (5, True), (8, True)):
+            t, k = (traj, traj_ok) if with_traj else (None, None)
+            us = timed_us(lambda: _align(lib, poses, None, off, G, t, k, 0.05, iters), reps)
+            passes = iters + (4 if with_traj else 2)
+            print(f"mp_lift_align_views, {G} take(s), iters={iters}, {'with' if with_traj else 'no'} traj: {us:,.1f} us  {passes} passes, {us / passes:,.1f} us a pass", flush=True)
+
+
+if "--align" in sys.argv:
+    align_bench([a for a in sys.argv[1:] if a != "--align"])
+    sys.exit(0)
 if "--fuse-path" in sys.argv:
     fuse_path_bench([a for a in sys.argv[1:] if a != "--fuse-path"])
     sys.exit(0)
