@@ -274,7 +274,9 @@ def sk_device(model):
 LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj", "__hyps_reproj", "__hyps_ok", "__floor", "__cam", "__traj_fit", "__filled",
                  "__hyps_traj_fit", "__hyps_filled", "__path", "__path_cost", "__steps", "__hyps_steps", "__reproj_smooth", "__hyps_reproj_smooth",
                  "__quat", "__quat_ok", "__hyps_quat", "__hyps_quat_ok", "__root", "__choice", "__spread", "__cost", "__views", "__cam_quat", "__cam_trans",
-                 "__cam_rms", "__cam_trans_rms", "__cam_used", "__cam_ok", "__cam_err_deg", "__cam_err_m")
+                 "__cam_rms", "__cam_trans_rms", "__cam_used", "__cam_ok", "__cam_err_deg", "__cam_err_m", "__cam_quat_align", "__cam_trans_align",
+                 "__cam_err_deg_align", "__cam_err_m_align", "__cam_bundle_reproj", "__cam_bundle_cost", "__cam_bundle_steps", "__cam_bundle_ok",
+                 "__cam_bundle_used")
 
 
 def lift_place_options(cfg):
@@ -451,6 +453,25 @@ def lift_fuse_align_options(cfg):
     return True, float(sigma), iters
 
 
+def lift_fuse_bundle_options(cfg):
+    """(steps, sigma) of lift.fuse_bundle / lift.fuse_bundle_sigma; ValueError for a value or a combination that cannot run - before any model is
+    built."""
+    steps, sigma = cfg.lift.get("fuse_bundle", 0), cfg.lift.get("fuse_bundle_sigma", 0.05)
+    if isinstance(steps, bool) or not isinstance(steps, int) or not 0 <= steps <= 8:
+        raise ValueError(f"lift.fuse_bundle counts Gauss-Newton steps, an integer in 0..8 (0: off), got {steps!r}")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
+        raise ValueError(f"lift.fuse_bundle_sigma is a number, got {sigma!r}")
+    if not sigma > 0:
+        raise ValueError(f"lift.fuse_bundle_sigma must be > 0 (normalised screen units), got {sigma!r}")
+    if steps == 0:
+        if sigma != 0.05:
+            raise ValueError("lift.fuse_bundle_sigma describes the bundle adjustment of a take's estimated cameras: set lift.fuse_bundle=N, N steps")
+        return 0, float(sigma)
+    if not lift_fuse_align_options(cfg)[0]:
+        raise ValueError("lift.fuse_bundle refines the extrinsics that lift.fuse_cameras=estimate estimates: set lift.fuse_cameras=estimate")
+    return steps, float(sigma)
+
+
 def _camera_index(cam):
     """fetch()'s 17th number, a camera dict's "index", or None"""
     if isinstance(cam, dict):
@@ -480,6 +501,32 @@ def _qrot(q, v):
 
 
 CAMERA_KEYS = ("quat", "trans", "rms", "trans_rms", "used", "ok", "err_deg", "err_m")       # of estimate_cameras' dict -> "<fused key>__cam_<k>" in lift.npz
+# what lift.fuse_bundle adds to it: the closed form's cameras and their errors, and the bundle's own record
+BUNDLE_KEYS = ("quat_align", "trans_align", "err_deg_align", "err_m_align", "bundle_reproj", "bundle_cost", "bundle_steps", "bundle_ok", "bundle_used")
+
+
+def bundle_cameras(est, cams, takes, bun):
+    """lift.fuse_bundle on estimate_cameras' dict, IN PLACE: quat and trans become the bundle's (bundle_views' ViewBundle ``bun``), err_deg and
+    err_m are recomputed for them against the dataset's extrinsics, the closed form's values move to ``*_align`` and the bundle's reproj (G, V, 2),
+    cost (G, 2), steps, ok (G), used (G, V) are added as ``bundle_*``."""
+    from manipose_amd import camera_table
+    _, quat, trans = (a.astype(np.float64) for a in camera_table(cams))
+    unit = quat / np.linalg.norm(quat, axis=1, keepdims=True)
+    for k in ("quat", "trans", "err_deg", "err_m"):
+        est[k + "_align"] = est[k].copy()
+    est["quat"], est["trans"] = bun.quat.cpu().numpy(), bun.trans.cpu().numpy()
+    for t, views in enumerate(takes):
+        for v, i in enumerate(views):
+            est["err_deg"][t, v], est["err_m"][t, v] = _camera_error(est["quat"][t, v], est["trans"][t, v], unit[i], trans[i])
+    for k in ("reproj", "cost", "steps", "ok", "used"):
+        est["bundle_" + k] = getattr(bun, k).cpu().numpy()
+
+
+def _camera_error(q, t, unit, trans):
+    """(degrees, metres) between an estimated camera (q float32 unit, t) and the dataset's (unit quaternion, translation), in float64"""
+    q = q.astype(np.float64)
+    rel = unit[0] * q[1:] - q[0] * unit[1:] - np.cross(unit[1:], q[1:])                               # the vector part of conj(q_dataset) q
+    return np.degrees(2.0 * np.arctan2(np.linalg.norm(rel), abs(float(q @ unit)))), np.linalg.norm(t.astype(np.float64) - trans)
 
 
 def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, refine, sigma, iters):
@@ -516,10 +563,7 @@ def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, 
     for t, views in enumerate(takes):
         row = [None] * V
         for v, i in enumerate(views):
-            q = est["quat"][t, v].astype(np.float64)
-            rel = unit[i][0] * q[1:] - q[0] * unit[i][1:] - np.cross(unit[i][1:], q[1:])           # the vector part of conj(q_dataset) q
-            est["err_deg"][t, v] = np.degrees(2.0 * np.arctan2(np.linalg.norm(rel), abs(float(q @ unit[i]))))
-            est["err_m"][t, v] = np.linalg.norm(est["trans"][t, v].astype(np.float64) - trans[i])
+            est["err_deg"][t, v], est["err_m"][t, v] = _camera_error(est["quat"][t, v], est["trans"][t, v], unit[i], trans[i])
             row[v] = np.concatenate([intr[i], est["quat"][t, v], est["trans"][t, v]])
             if not est["ok"][t, v] & 1:
                 valid[v, off[t]:off[t + 1]] = 0
@@ -539,7 +583,7 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
     placed with ONE world root per frame (place_views); with lift.floor the take stands on z = 0.  ``res``: the group's _Lifted with hypotheses, taken
     after the smoothing and rigid stages.  Writes ``<name>.fused<t>`` and its ``__root``, ``__choice``, ``__spread``, ``__cost``, ``__ok`` (consensus
     and root fit both ok), ``__reproj`` (V, N), ``__steps``, ``__views`` (and ``__floor``) into ``out``; with ``targets`` the take's score into ``scores``."""
-    from manipose_amd import camera_table, fuse_views, fuse_views_path, place_views, project_rigid, score_poses, score_traj, to_world
+    from manipose_amd import bundle_views, camera_table, fuse_views, fuse_views_path, place_views, project_rigid, score_poses, score_traj, to_world
     from manipose_amd.lifting import SCORE_FIELDS
     _, sigma, weight, refine = lift_fuse_options(cfg)
     along, path_sigma, path_switch = lift_fuse_path_options(cfg)
@@ -581,6 +625,13 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
     if res.bones is not None:                  # lift.rigid: one table per take, the mean of its views'
         project_rigid(pose, torch.stack([torch.stack([res.bones[i] for i in views]).mean(dim=0) for views in takes]), seq_offset=off)
     root, reproj, placed, steps = place_views(pose, kp, nested, place_valid, off, refine=refine, return_steps=True)
+    bundle_steps, bundle_sigma = lift_fuse_bundle_options(cfg)
+    if bundle_steps:                           # lift.fuse_bundle: the estimated cameras and the roots refined jointly on the keypoints, the first view held
+        held = np.zeros((len(takes), V), np.uint8)
+        held[:, 0] = 1
+        bun = bundle_views(pose, root, kp, nested, place_valid, off, placed, held, sigma=bundle_sigma, iters=bundle_steps)
+        bundle_cameras(est, cams, takes, bun)
+        root, reproj, placed, steps = place_views(pose, kp, bun.cameras, place_valid, off, refine=refine, return_steps=True)
     unit = np.tile(np.array([1, 0, 0, 0], np.float32), (len(takes), 1))
     scene = to_world(pose.clone(), unit, traj=root, seq_offset=off, floor=True if floor else False)
     scene, d_floor = scene if floor else (scene, None)
@@ -606,6 +657,8 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None):
         if est is not None:
             for k in CAMERA_KEYS:
                 out[f"{key}__cam_{k}"] = est[k][t, :len(views)]
+            for k in BUNDLE_KEYS if bundle_steps else ():
+                out[f"{key}__cam_{k}"] = est[k][t, :len(views)] if est[k].ndim > 1 and k != "bundle_cost" else est[k][t]
         if along:
             out[key + "__path_cost"] = path_cost[t].cpu().numpy()
         if floor:
@@ -654,7 +707,11 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     ``__reproj`` (V, N), ``__views`` (the sequences' indices within the group), with lift.floor ``__floor`` and with lift.fuse_path (lift.fuse_path_sigma,
     lift.fuse_path_switch) ``__path_cost``, a scalar (fuse_group); with lift.fuse_cameras=estimate (lift.fuse_align_sigma, lift.fuse_align_iters) the
     takes' extrinsics are estimated from the views' poses (estimate_cameras) and ``__cam_quat`` (V, 4), ``__cam_trans`` (V, 3), ``__cam_rms``,
-    ``__cam_trans_rms``, ``__cam_used``, ``__cam_ok``, ``__cam_err_deg``, ``__cam_err_m`` (V,) are added; with ``targets`` the dict
+    ``__cam_trans_rms``, ``__cam_used``, ``__cam_ok``, ``__cam_err_deg``, ``__cam_err_m`` (V,) are added, and with lift.fuse_bundle=N
+    (lift.fuse_bundle_sigma) they are bundle-adjusted on the keypoints (bundle_views, the first view held; the roots are fitted once more under
+    the refined cameras): ``__cam_quat``, ``__cam_trans``, ``__cam_err_deg``, ``__cam_err_m`` are the refined cameras', the closed form's move
+    to ``__cam_quat_align``, ``__cam_trans_align``, ``__cam_err_deg_align``, ``__cam_err_m_align``, and ``__cam_bundle_reproj`` (V, 2),
+    ``__cam_bundle_cost`` (2,) float64, ``__cam_bundle_steps``, ``__cam_bundle_ok`` (scalars) and ``__cam_bundle_used`` (V,) are added; with ``targets`` the dict
     ``fused_scores`` receives {fused key: score dict} of the fused pose and root against the first view's ground truth in the world."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
@@ -750,6 +807,7 @@ def run(argv, extra_defaults=None):
     lift_fuse_options(cfg)                     # ... and a lift.fuse without run.lift, without calibration or without hypotheses
     lift_fuse_path_options(cfg)                # ... and a lift.fuse_path without lift.fuse
     lift_fuse_align_options(cfg)               # ... and a lift.fuse_cameras=estimate without lift.fuse
+    lift_fuse_bundle_options(cfg)              # ... and a lift.fuse_bundle without lift.fuse_cameras=estimate
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")

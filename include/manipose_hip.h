@@ -795,6 +795,65 @@ int mp_lift_align_views(const float* poses, int V, int64_t Ftot, int J, int C, c
                         const float* traj, const uint8_t* traj_ok, float sigma, int iters, float* quat, float* trans, float* rms, float* trans_rms,
                         int32_t* used, uint8_t* ok, void* stream);
 
+/* Bundle-adjusting a take's cameras: mp_lift_align_views gives the extrinsics in closed form from the lifted poses and the per-view roots, and the
+ * 2-D keypoints - the only measured quantity - decide nothing about them.  This is the joint Gauss-Newton refinement of all free cameras and all
+ * per-frame world roots of a take on the robust reprojection error, the roots eliminated by a Schur complement.  The reference has no counterpart.
+ * The conventions are mp_lift_fuse_place's: takes, take_offset (G + 1, entries clamped to 0 .. Ftot), valid (V, Ftot) bytes or null,
+ * 1 <= V <= MP_LIFT_FUSE_MAXV, 2 <= J <= 32, quat (G, V, 4), trans (G, V, 3), intr (G, V, 9), R the matrix of q / |q| normalised in fp64, a view whose
+ * |q|^2 is not finite or < 1e-12 counts as invalid, x_world = R x_cam + T, weights (J) or null, distort as for mp_lift_place_refine; fp64 between
+ * the float32 loads and the float32 stores, without contraction into fused multiply-adds; no atomics, fixed orders: identical bits on every call;
+ * a take's result does not depend on the other takes of the call; the call does not synchronise.  Not measured on real data.
+ * Read only: pose (Ftot, J, 3) the fused root-relative world pose; root (Ftot, 3) and root_ok (Ftot) bytes or null; kp (V, Ftot, J, 2); the camera
+ * tables; fixed (G, V) bytes or null; sigma > 0 in normalised screen units (+inf: every robust factor is exactly 1); 0 <= iters <=
+ * MP_LIFT_BUNDLE_MAXITERS.  Per take g with frames [f0, f1):
+ * 1. Observations.  (v, f) is USED if view v is valid at f (its valid byte and its quaternion), root_ok is null or non-zero at f, the root and
+ *    all 3 J coordinates of the pose are finite, and both coordinates of every keypoint of view v whose joint has a non-zero weight are finite.
+ *    A frame with no used observation is outside the problem: its root is copied through bit for bit.  used[g][v] = the used frames of view v.
+ * 2. Gauge.  A view is FIXED if fixed[g][v] != 0; with fixed null the fixed view is the lowest view with a used frame (mp_lift_align_views'
+ *    reference).  The FREE views are the views that are not fixed and have a used frame, in view order (their slots k = 0, 1, ..); a view that is
+ *    not fixed and has no used frame is outside the problem and copied through.  A take with no fixed view that has a used frame, or with no free
+ *    view, evaluates only: steps = 0, ok as step 5 finds it, reproj and cost written (start = end), cameras and roots copied through.  A fixed
+ *    view's quat and trans are copied through bit for bit in every case.
+ * 3. Residuals.  State in fp64: per view the unit quaternion q and T, per used frame the root r; at the start q = quat / |quat|, T = trans,
+ *    r = root.  P = R(q)^T (pose_j + r - T).  The projection, the clamp, its derivative and the 2x3 Jacobian J_pi with respect to P are exactly
+ *    step 2 of mp_lift_place_refine.  With res = (du, dv) and e = du^2 + dv^2:  t = 1 + e / sigma^2,  rho = e / t,  omega = 1 / t^2
+ *    (mp_lift_align_views' weight).  F = sum w_j rho over the used observations: views in order, within a view the joints in order - per frame, then
+ *    the frames in increasing order.  Per view E_v = sum w_j sqrt(e), W_v = sum w_j likewise; E_v / W_v is the view's weighted mean distance, as
+ *    mp_lift_fuse_place's reproj.  A joint of weight 0 is skipped.  deep: every weighted joint of every used observation has Z > 0.
+ * 4. Parameters.  A frame's root moves by dr, with Jacobian J_r = J_pi R^T.  A free camera moves by a left perturbation of the camera-space point,
+ *    P' = exp([w]x) P + tau, with Jacobian J_c = J_pi [-[P]x | I] (2x6, the rotation first).  Applied to the world-to-camera pair
+ *    (R^T, -R^T T) <- (exp([w]x) R^T, exp([w]x) (-R^T T) + tau) with the exact rotation of w, which in (q, T) reads
+ *    q <- q * conj(q_w),  q_w = (cos(th / 2), sin(th / 2) w / th) with th = |w|, and for th^2 <= 1e-16 the small-angle branch q_w = (1, w / 2);
+ *    the product is normalised and made canonical by mp_lift_align_views' sign rule (w >= 0, and if w == 0 the first non-zero component is
+ *    positive; a zero comes out as +0);  then T <- T - R(q) tau with the new q.
+ * 5. One step, normal equations with the weights w_j omega.  Per used frame, views in order, joints in order:  U_f = sum J_r^T J_r (3x3),
+ *    b_f = sum J_r^T res, and per free view used at f  W_fv = sum J_r^T J_c (3x6), A_fv = sum J_c^T J_c (6x6), a_fv = sum J_c^T res.  U_f^-1 by
+ *    cofactors with mp_lift_place_refine's test, det finite and > 1e-12 U00 U11 U22.  The reduced system over the free views' slots:
+ *    S = sum_f (blockdiag(A_f) - W_f^T (U_f^-1 W_f)),  s = sum_f (a_f - W_f^T (U_f^-1 b_f)), each frame's term formed first, then the frames added
+ *    in increasing order.  S = L L^T by Cholesky (row by row) in fp64; a pivot that is not finite and > 1e-12 times its diagonal entry of S means
+ *    "no step".  dc = -S^-1 s;  dr_f = -(U_f^-1 b_f + sum_k (U_f^-1 W_fk) dc_k), slots in order.  The candidate is the state moved by (dc, dr).
+ *    The step is taken iff every U_f and the factorisation pass, dc and the candidate cameras are finite, deep holds at the candidate and
+ *    F' <= (1 + 1e-6) F (a non-finite candidate root gives a non-finite F', which is not taken).  On the first step not taken the take's iteration
+ *    ends and its state stays.  If the first evaluation is not deep or F is not finite: ok = 0, everything copied through, steps = 0, reproj and
+ *    cost as evaluated (start = end); otherwise ok = 1.  At most iters steps.
+ * 6. Outputs.  quat_out (G, V, 4), trans_out (G, V, 3) floats: while steps = 0 the inputs bit for bit, else a free view's (q, T) rounded to
+ *    float32 (q unit and canonical), every other view copied through;  root_out (Ftot, 3): a used frame's r rounded to float32 (bit for bit the
+ *    input while steps = 0), every other frame of the call copied through;  reproj (G, V, 2) floats: E_v / W_v at the start and at the end, 0 for a
+ *    view with no used frame;  cost (G, 2) doubles: F at the start and at the end;  steps (G), ok (G) bytes;  used (G, V) int32.
+ * Schedule: one lane per frame evaluates, forms the frame's blocks view by view and writes its term of S and s (at most 171 + 18 doubles) to the
+ * scratch; one workgroup per take sums the terms, lane e entry e, frames in increasing order, then decides, factorises and forms the candidate
+ * cameras; the next pass of the frame kernel applies dc and its own dr at its head.  iters + 1 passes, launched in a fixed sequence.
+ * scratch: at least mp_lift_bundle_views_scratch_bytes(V, Ftot) bytes = 3056 Ftot (per frame: 200 doubles of its row, 118 of blocks kept between
+ * the passes, 64 of a take's state), 8-byte aligned; 0 for arguments out of range.
+ * MP_ERR_ARG before anything is launched: an input or output pointer null (root_ok, valid, fixed, weights may be null); V or J out of range; Ftot or
+ * G <= 0, G > Ftot, Ftot > 2^31 - 1; distort not 0 or 1; sigma not > 0; iters out of range; scratch null, too small or misaligned. */
+#define MP_LIFT_BUNDLE_MAXITERS 8
+int64_t mp_lift_bundle_views_scratch_bytes(int V, int64_t Ftot);
+int mp_lift_bundle_views(const float* pose, const float* root, const uint8_t* root_ok, const float* kp, int V, int64_t Ftot, int J, const uint8_t* valid,
+                         const int64_t* take_offset, int G, const float* quat, const float* trans, const float* intr, const uint8_t* fixed,
+                         const float* weights, int distort, float sigma, int iters, float* quat_out, float* trans_out, float* root_out, float* reproj,
+                         double* cost, uint8_t* steps, uint8_t* ok, int32_t* used, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

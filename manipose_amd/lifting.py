@@ -1032,6 +1032,109 @@ def align_views(poses, valid=None, take_offset=None, traj=None, traj_ok=None, si
     return res._replace(quat=torch.from_numpy(q).to(poses.device), trans=torch.from_numpy(t).to(poses.device) if t is not None else None)
 
 
+BUNDLE_MAXITERS = 8          # MP_LIFT_BUNDLE_MAXITERS of include/manipose_hip.h: Gauss-Newton steps mp_lift_bundle_views takes at most
+BUNDLE_SIGMA, BUNDLE_ITERS = 0.05, 3         # defaults of bundle_views: the robust scale in normalised screen units, the steps (not tuned)
+# What bundle_views returns: cameras: place_views' nested list [take][view] with the refined extrinsics; quat (G, V, 4), trans (G, V, 3), root (Ftot, 3),
+# reproj (G, V, 2) float32, cost (G, 2) float64, steps, ok (G) uint8, used (G, V) int32
+ViewBundle = namedtuple("ViewBundle", "cameras quat trans root reproj cost steps ok used")
+
+
+def _bundle_options(sigma, iters):
+    if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not float(sigma) > 0:
+        raise ValueError(f"sigma must be a number > 0 in normalised screen units (inf: no robust weight), got {sigma!r}")
+    if not isinstance(iters, (int, np.integer)) or isinstance(iters, (bool, np.bool_)) or not 0 <= int(iters) <= BUNDLE_MAXITERS:
+        raise ValueError(f"iters counts Gauss-Newton steps, an integer in 0..{BUNDLE_MAXITERS} (0: the evaluation alone), got {iters!r}")
+
+
+def _bundle(lib, pose, root, root_ok, kp, valid, d_off, G, d_quat, d_trans, d_intr, d_fixed, d_w, distort, sigma, iters):
+    """``mp_lift_bundle_views``: (quat, trans, root, reproj, cost, steps, ok, used), new tensors"""
+    V, ftot, J = int(kp.shape[0]), int(kp.shape[1]), int(kp.shape[2])
+    dev = pose.device
+    quat, trans = d_quat.clone(), d_trans.clone()
+    out_root = root.clone()
+    reproj = torch.zeros(G, V, 2, dtype=torch.float32, device=dev)
+    cost = torch.zeros(G, 2, dtype=torch.float64, device=dev)
+    steps, ok = torch.zeros(G, dtype=torch.uint8, device=dev), torch.zeros(G, dtype=torch.uint8, device=dev)
+    used = torch.zeros(G, V, dtype=torch.int32, device=dev)
+    if ftot > 0:
+        n = int(lib.mp_lift_bundle_views_scratch_bytes(V, ftot))
+        scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mp_lift_bundle_views(_lib.ptr(pose), _lib.ptr(root), _lib.ptr(root_ok), _lib.ptr(kp), V, ftot, J, _lib.ptr(valid), _lib.ptr(d_off),
+                                                G, _lib.ptr(d_quat), _lib.ptr(d_trans), _lib.ptr(d_intr), _lib.ptr(d_fixed), _lib.ptr(d_w), int(bool(distort)),
+                                                float(sigma), int(iters), _lib.ptr(quat), _lib.ptr(trans), _lib.ptr(out_root), _lib.ptr(reproj),
+                                                _lib.ptr(cost), _lib.ptr(steps), _lib.ptr(ok), _lib.ptr(used), _lib.ptr(scratch), n, _lib.stream_ptr()),
+                       "mp_lift_bundle_views")
+    return quat, trans, out_root, reproj, cost, steps, ok, used
+
+
+def bundle_views(pose, root, keypoints_2d, cameras, valid=None, take_offset=None, root_ok=None, fixed=None, weights=None, distort=True,
+                 sigma=BUNDLE_SIGMA, iters=BUNDLE_ITERS):
+    """``mp_lift_bundle_views`` on device tensors: a take's cameras and world roots refined JOINTLY on the reprojection error - the bundle adjustment
+    behind ``align_views``' closed form, in which the 2-D keypoints have no say.  ``pose`` (Ftot, J, 3) float32 as ``fuse_views`` returns it,
+    ``root`` (Ftot, 3) float32 and ``root_ok`` (Ftot) uint8 or None as ``place_views`` returns them, ``keypoints_2d`` (V, Ftot, J, 2), ``cameras``,
+    ``valid``, ``take_offset``, ``weights`` and ``distort`` as for ``place_views``; ``fixed`` (G, V) or, for one take, (V,): non-zero where a view's
+    extrinsics are held (host table; None: the lowest view of every take that observes a frame).  Up to ``iters`` (0..8) undamped Gauss-Newton steps
+    over all free cameras (6 parameters each: a left perturbation of the camera-space point, P' = exp([w]x) P + tau) and all roots, the roots
+    eliminated by a Schur complement, on sum w_j rho(|res|^2) with rho(e) = e / (1 + e / sigma^2); ``sigma`` > 0 in normalised screen units (inf:
+    plain least squares); a step is taken while the cost does not rise (``place_poses``' rule; include/manipose_hip.h has the rule in full).  The
+    defaults are not tuned.  Returns a ``ViewBundle``: ``(cameras: the nested list with the refined extrinsics, to be passed on to place_views
+    (this waits for the kernel), quat (G, V, 4), trans (G, V, 3), root (Ftot, 3), reproj (G, V, 2): every view's weighted mean reprojection error
+    at the start and at the end, cost (G, 2) float64, steps (G) uint8, ok (G) uint8: 0 where the start could not be evaluated (a joint behind a
+    camera), used (G, V) int32: the frames a view observes)``, new device tensors.  A fixed view, and every view of a take that took no step, is
+    copied through bit for bit.  Inputs are not modified; identical bits on every call.  Not measured on real data."""
+    _bundle_options(sigma, iters)
+    tensors = torch.is_tensor(pose) and torch.is_tensor(root) and torch.is_tensor(keypoints_2d)
+    if tensors:
+        if pose.dim() != 3 or pose.shape[2] != 3 or pose.dtype != torch.float32 or not pose.is_contiguous() or not 2 <= int(pose.shape[1]) <= 32:
+            raise ValueError(f"pose must be contiguous float32 (Ftot, J, 3) with 2..32 joints, got {tuple(pose.shape)} {pose.dtype}")
+        ftot, J = int(pose.shape[0]), int(pose.shape[1])
+        if tuple(root.shape) != (ftot, 3) or root.dtype != torch.float32:
+            raise ValueError(f"root must be float32 ({ftot}, 3), got {tuple(root.shape)} {root.dtype}")
+        kp = keypoints_2d
+        if kp.dim() != 4 or not 1 <= int(kp.shape[0]) <= FUSE_MAXV or tuple(kp.shape[1:]) != (ftot, J, 2) or kp.dtype != torch.float32:
+            raise ValueError(f"keypoints_2d must be float32 (V <= {FUSE_MAXV}, {ftot}, {J}, 2), got {tuple(kp.shape)} {kp.dtype}")
+        V = int(kp.shape[0])
+        if valid is not None:
+            _score_valid(valid, (V, ftot), "valid")
+        if root_ok is not None:
+            if not torch.is_tensor(root_ok):
+                raise ValueError(f"root_ok must be a uint8 tensor of shape ({ftot},)")
+            _score_valid(root_ok, (ftot,), "root_ok")
+        intr, quat, trans, present = _take_cameras(cameras, V)
+        G = intr.shape[0]
+        h_fixed = None
+        if fixed is not None:
+            h_fixed = np.asarray(fixed.detach().cpu().numpy() if torch.is_tensor(fixed) else fixed)
+            if h_fixed.shape == (V,) and G == 1:
+                h_fixed = h_fixed.reshape(1, V)
+            if h_fixed.shape != (G, V) or h_fixed.dtype.kind not in "biu":
+                raise ValueError(f"fixed must be a table ({G}, {V}) of flags, got {h_fixed.shape} {h_fixed.dtype}")
+            h_fixed = np.ascontiguousarray(h_fixed != 0, dtype=np.uint8)
+        h_w = _host_f32(weights, (J,), "weights", nonneg=True) if weights is not None else None
+    if not tensors or not (pose.is_cuda and root.is_cuda and keypoints_2d.is_cuda) or (root_ok is not None and not root_ok.is_cuda):
+        raise RuntimeError("manipose_amd: bundle_views takes device tensors; there is no CPU fallback")
+    dev = pose.device
+    valid = _fuse_valid(valid, V, ftot, "bundle_views")
+    d_off, G_off = _seq_table(take_offset, ftot, dev)
+    if G_off != G:
+        raise ValueError(f"cameras lists {G} takes, take_offset {G_off}")
+    if not present.all():                                  # a missing view is invalid in every frame of its take
+        off = d_off.cpu().numpy().clip(0, ftot)
+        mask = np.ones((V, ftot), np.uint8)
+        for g, v in zip(*np.nonzero(~present)):
+            mask[v, off[g]:max(off[g], off[g + 1])] = 0
+        mask = torch.from_numpy(mask).to(dev)
+        valid = mask if valid is None else valid & mask
+    res = _bundle(_lib.load(), pose, root.contiguous(), root_ok.contiguous() if root_ok is not None else None, keypoints_2d.contiguous(), valid, d_off, G,
+                  torch.from_numpy(quat).to(dev), torch.from_numpy(trans).to(dev), torch.from_numpy(intr).to(dev),
+                  torch.from_numpy(h_fixed).to(dev) if h_fixed is not None else None, torch.from_numpy(h_w).to(dev) if h_w is not None else None,
+                  distort, sigma, iters)
+    q, t = res[0].cpu().numpy(), res[1].cpu().numpy()
+    nested = [[np.concatenate([intr[g, v], q[g, v], t[g, v]]) if present[g, v] else None for v in range(V)] for g in range(G)]
+    return ViewBundle(nested, *res)
+
+
 def merge_windows(poses, scores, win_seq, win_start, seq_offset, *, T, tta, mirror, agg="weighted_ave", blend="mean", scale=1.0,
                   return_hyps=False, out=None, hyps=None, device_tables=None):
     """``mp_lift_merge`` on device tensors: poses (F*W, K, T, J, 3), scores (F*W, K, T, 1) or None (K == 1); win_seq / win_start (W)
@@ -1591,5 +1694,5 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
 
 
 __all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "reproject_poses", "pose_rotations", "to_world", "smooth_poses", "smooth_traj",
-           "select_path", "score_poses", "score_traj", "fuse_views", "fuse_views_path", "place_views", "align_views", "lift_sequences",
+           "select_path", "score_poses", "score_traj", "fuse_views", "fuse_views_path", "place_views", "align_views", "bundle_views", "lift_sequences",
            "lift_action"]

@@ -11,6 +11,11 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --fuse [frames=3000] [K=5] [reps=200]
     python tools/lift_bench.py --fuse-path [frames=3000] [K=5] [reps=20]
     python tools/lift_bench.py --align [frames=3000] [reps=20]
+    python tools/lift_bench.py --bundle [frames=3000] [reps=20]
+--bundle times mp_lift_bundle_views (the bundle adjustment of a take's cameras and roots on the 2-D keypoints: per pass one kernel with a lane per
+frame and one with a workgroup per take, iters + 1 passes) through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints,
+pinhole keypoints with 0.01 of noise - with the cameras of views 1..3 started 0.3 degrees and 0.15 m off S11's calibration and the roots fitted
+under them by mp_lift_fuse_place, as ONE take and cut into 16, and prints how far the cameras are from the calibration before and after.
 --align times mp_lift_align_views (a take's extrinsics from its views' poses: one workgroup per (take, view), iters + 2 passes over the poses, with
 a trajectory iters + 4) through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints, in 30 % of the frames of views 1..3
 the hypothesis moved along the depth axis - as ONE take and cut into 16, and prints how far the estimate is from S11's calibration.
@@ -334,6 +339,52 @@ def align_bench(argv):
             print(f"mp_lift_align_views, {G} take(s), iters={iters}, {'with' if with_traj else 'no'} traj: {us:,.1f} us  {passes} passes, {us / passes:,.1f} us a pass", flush=True)
 
 
+def bundle_bench(argv):
+    from manipose_amd.lifting import _bundle, _fuse_place
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib, V, (quat, trans, intr), pose, _, kp = fuse_scene(frames, 2)
+    g = np.random.default_rng(3)
+    qn = (quat[0] / quat[0].norm(dim=1, keepdim=True)).double().cpu().numpy()
+    q0, t0 = qn.copy(), trans[0].double().cpu().numpy()
+    for v in range(1, V):                                                 # views 1..3 start 0.3 degrees and 0.15 m off
+        axis, d = g.standard_normal(3), g.standard_normal(3)
+        h = 0.5 * np.radians(0.3)
+        b = np.concatenate([[np.cos(h)], np.sin(h) * axis / np.linalg.norm(axis)])
+        a = qn[v]
+        q0[v] = [a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                 a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]]
+        t0[v] += 0.15 * d / np.linalg.norm(d)
+
+    def off_by(q, t):
+        a, b = qn, q.double().cpu().numpy()
+        vec = a[:, :1] * b[:, 1:] - b[:, :1] * a[:, 1:] - np.cross(a[:, 1:], b[:, 1:])
+        deg = np.degrees(2.0 * np.arctan2(np.linalg.norm(vec, axis=1), np.abs((a * b).sum(axis=1))))
+        return (f"{', '.join(f'{x:.4f}' for x in deg[1:])} degrees and "
+                f"{', '.join(f'{x * 1e3:.2f}' for x in (t - trans[0]).norm(dim=1).tolist()[1:])} mm")
+
+    print(f"--bundle: {V} views x {frames} frames x 17 joints, pinhole keypoints with 0.01 of noise, sigma = inf; {reps} calls each after 5 of warm-up "
+          f"(the allocations of outputs and scratch are inside the time)", flush=True)
+    fixed = torch.tensor([[1, 0, 0, 0]], dtype=torch.uint8, device="cuda")
+    for G in (1, 16):
+        off = torch.tensor([frames * i // G for i in range(G + 1)], dtype=torch.int64, device="cuda")
+        q = torch.from_numpy(q0.astype(np.float32)).cuda().expand(G, V, 4).contiguous()
+        t = torch.from_numpy(t0.astype(np.float32)).cuda().expand(G, V, 3).contiguous()
+        k = intr.expand(G, V, 9).contiguous()
+        root, _, ok, _ = _fuse_place(lib, pose, kp, None, off, G, q, t, k, None, False, 3)
+        call = lambda iters: _bundle(lib, pose, root, ok, kp, None, off, G, q, t, k, fixed.expand(G, V).contiguous(), None, False, float("inf"), iters)
+        if G == 1:
+            print(f"start: off S11's calibration by {off_by(q[0], t[0])}", flush=True)
+        for iters in (0, 1, 3, 8):
+            res = call(iters)
+            us = timed_us(lambda: call(iters), reps)
+            print(f"mp_lift_bundle_views, {G} take(s), iters={iters}: {us:,.1f} us  {iters + 1} passes, {us / (iters + 1):,.1f} us a pass; take 0: {int(res[5][0])} steps, "
+                  f"cost {res[4][0, 0].item():.4f} -> {res[4][0, 1].item():.4f}, off by {off_by(res[0][0], res[1][0])}", flush=True)
+
+
+if "--bundle" in sys.argv:
+    bundle_bench([a for a in sys.argv[1:] if a != "--bundle"])
+    sys.exit(0)
 if "--align" in sys.argv:
     align_bench([a for a in sys.argv[1:] if a != "--align"])
     sys.exit(0)
