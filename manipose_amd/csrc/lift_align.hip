@@ -6,23 +6,22 @@
 // ONE WORKGROUP OF 256 LANES OWNS ONE (take, view).  A lane walks the frames f0 + lane, f0 + lane + 256, ... in order and keeps its eleven sums
 // (9 of M, sum w, the count) in registers: the arrays below are indexed by unrolled constants only, nothing lands in scratch.  The lanes' sums
 // are added by an xor butterfly within a wave - an addition is commutative, so all 64 lanes hold the same bits - and the four waves' sums through
-// LDS in wave order, (w0 + w1) + (w2 + w3); EVERY lane then solves the 4x4 eigenproblem (cyclic Jacobi in registers: lift_score.hip's
-// score_eig4_max restated, that kernel is pinned by its test and was left alone) on identical inputs, so the branches on its result are uniform
+// LDS in wave order, (w0 + w1) + (w2 + w3); EVERY lane then solves the 4x4 eigenproblem (cyclic Jacobi in registers: lift_geom.h's lift_eig4,
+// shared with lift_score.hip) on identical inputs, so the branches on its result are uniform
 // and the next pass has its rotation without a broadcast.  The passes follow one another inside the workgroup: no grid-wide synchronisation.
 // A pass reads both views' poses again (iters + 2 passes, with a trajectory iters + 4): a frame's J C floats are contiguous, consecutive lanes
 // are J C floats apart, every cache line fetched is used whole.  It runs once per take and sits on one CU; no rate is claimed for it.
 // Everything between the float32 loads and the float32 stores is fp64, without contraction; no atomics, fixed orders: identical bits on every call.
 #include "lift_common.h"
-#include "../../include/manipose_hip.h"
 
 #pragma clang fp contract(off)
+#include "lift_geom.h"                    // after the pragma: the shared code takes this file's mode
 
 namespace mp {
 
 constexpr int ALIGN_MAXV = MP_LIFT_FUSE_MAXV;
 constexpr int ALIGN_THREADS = 256, ALIGN_WAVES = ALIGN_THREADS / 64;
 constexpr int ALIGN_SUMS = 11;                   // of a pass: 9 of M, sum w, the used frames (fewer in the later passes)
-constexpr int ALIGN_SWEEPS = 30;                 // Jacobi sweeps at most, as lift_score.hip
 constexpr double ALIGN_GAP = 1e-9;               // (lambda_1 - lambda_2) <= ALIGN_GAP |lambda_1|: the rotation is not determined
 
 struct AlignArgs {
@@ -42,17 +41,6 @@ struct AlignArgs {
   int V, J, C, G, iters;
 };
 
-struct AlignRot { double r00, r01, r02, r10, r11, r12, r20, r21, r22; };
-
-__device__ __forceinline__ AlignRot align_rotation(const double (&q)[4]) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  AlignRot R;
-  R.r00 = 1.0 - 2.0 * (y * y + z * z); R.r01 = 2.0 * (x * y - w * z);       R.r02 = 2.0 * (x * z + w * y);
-  R.r10 = 2.0 * (x * y + w * z);       R.r11 = 1.0 - 2.0 * (x * x + z * z); R.r12 = 2.0 * (y * z - w * x);
-  R.r20 = 2.0 * (x * z - w * y);       R.r21 = 2.0 * (y * z + w * x);       R.r22 = 1.0 - 2.0 * (x * x + y * y);
-  return R;
-}
-
 // the lanes' sums added: a butterfly within the wave, then the waves in order; every lane returns with the workgroup's sums
 __device__ __forceinline__ void align_reduce(double (&x)[ALIGN_SUMS], double* lds) {
 #pragma unroll
@@ -69,63 +57,6 @@ __device__ __forceinline__ void align_reduce(double (&x)[ALIGN_SUMS], double* ld
 #pragma unroll
   for (int k = 0; k < ALIGN_SUMS; ++k)
     x[k] = (lds[k] + lds[ALIGN_SUMS + k]) + (lds[2 * ALIGN_SUMS + k] + lds[3 * ALIGN_SUMS + k]);
-}
-
-// eigenvalues lam1 >= lam2 >= .. of a symmetric 4x4 matrix and the eigenvector of lam1: cyclic Jacobi sweeps until off(A) <= 2^-52 |A|_F
-// (score_eig4_max's rule and order of operations)
-__device__ __forceinline__ void align_eig4(double (&a)[4][4], double (&q)[4], double& lam1, double& lam2) {
-  double v[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-#pragma unroll 1
-  for (int sweep = 0; sweep < ALIGN_SWEEPS; ++sweep) {
-    double off2 = 0.0, diag2 = 0.0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      diag2 += a[p][p] * a[p][p];
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) off2 += 2.0 * (a[p][r] * a[p][r]);
-    }
-    if (off2 <= 0x1p-104 * (off2 + diag2)) break;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) {
-        // (no branch: a pair that needs no rotation, or whose theta overflows, gets t = 0, c = 1, s = 0, which leaves every entry's bits alone)
-        const double apq = a[p][r];
-        const double theta = (a[r][r] - a[p][p]) / (2.0 * apq);
-        const double t = apq != 0.0 ? copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0)) : 0.0;
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {            // A <- A J (columns p, r)
-          const double akp = a[k][p], akr = a[k][r];
-          a[k][p] = c * akp - s * akr;
-          a[k][r] = s * akp + c * akr;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {            // A <- J^T A (rows p, r)
-          const double apk = a[p][k], ark = a[r][k];
-          a[p][k] = c * apk - s * ark;
-          a[r][k] = s * apk + c * ark;
-        }
-        a[p][r] = a[r][p] = t != 0.0 ? 0.0 : a[p][r];   // (what the rotation was built for)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {            // V <- V J
-          const double vkp = v[k][p], vkr = v[k][r];
-          v[k][p] = c * vkp - s * vkr;
-          v[k][r] = s * vkp + c * vkr;
-        }
-      }
-  }
-  int best = 0;
-  lam1 = a[0][0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k)
-    if (a[k][k] > lam1) { lam1 = a[k][k]; best = k; }
-  lam2 = -__builtin_inf();
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (k != best && a[k][k] > lam2) lam2 = a[k][k];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] = best == 0 ? v[k][0] : best == 1 ? v[k][1] : best == 2 ? v[k][2] : v[k][3];
 }
 
 // step 4 on the workgroup's sums s (9 of M, sum w): the canonical unit quaternion; false: degenerate (the gap is judged by the caller)
@@ -146,7 +77,7 @@ __device__ __forceinline__ bool align_solve(const double (&s)[ALIGN_SUMS], doubl
   n[2][2] = -s[0] + s[4] - s[8];
   n[2][3] = n[3][2] = s[5] + s[7];
   n[3][3] = -s[0] - s[4] + s[8];
-  align_eig4(n, q, lam1, lam2);
+  lift_eig4(n, q, lam1, lam2);
   if (!(lam1 > 0.0)) return false;
   const double qn = 1.0 / sqrt((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]));
 #pragma unroll
@@ -160,7 +91,7 @@ __device__ __forceinline__ bool align_solve(const double (&s)[ALIGN_SUMS], doubl
 }
 
 // |b_ref - R b_v|^2, channel order
-__device__ __forceinline__ double align_res2(const AlignRot& R, double vx, double vy, double vz, double rx, double ry, double rz) {
+__device__ __forceinline__ double align_res2(const Rot3& R, double vx, double vy, double vz, double rx, double ry, double rz) {
   const double ex = rx - ((R.r00 * vx + R.r01 * vy) + R.r02 * vz);
   const double ey = ry - ((R.r10 * vx + R.r11 * vy) + R.r12 * vz);
   const double ez = rz - ((R.r20 * vx + R.r21 * vy) + R.r22 * vz);
@@ -173,7 +104,7 @@ __device__ __forceinline__ double align_res2(const AlignRot& R, double vx, doubl
 // MODE 2: acc[0..2] += w d_f, acc[3] += w, d_f under Rf           (step 8: T)
 // MODE 3: acc[0] += w |d_f - T|^2, acc[1] += w                    (step 8: trans_rms)
 template <int MODE>
-__device__ __forceinline__ void align_pass(const AlignArgs& A, int v, int r, long f0, long f1, bool weighted, const AlignRot& Rw, const AlignRot& Rf,
+__device__ __forceinline__ void align_pass(const AlignArgs& A, int v, int r, long f0, long f1, bool weighted, const Rot3& Rw, const Rot3& Rf,
                                            double Tx, double Ty, double Tz, double (&acc)[ALIGN_SUMS]) {
   const int J = A.J, C = A.C;
 #pragma unroll
@@ -277,7 +208,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void lift_align_kernel(AlignArgs A) 
   if (v == r) { align_store(A, row, unit, 0.0, 0.0, 0.0, 0.0, 0.0, rcount, 1); return; }
 
   // 4., 5. the rotation
-  AlignRot Rw = align_rotation(unit), Rf = Rw;
+  Rot3 Rw = lift_rot3(1.0, 0.0, 0.0, 0.0), Rf = Rw;
   double q[4], lam1 = 0.0, lam2 = 0.0;
   align_pass<0>(A, v, r, fr.f0, fr.f1, false, Rw, Rf, 0.0, 0.0, 0.0, acc);
   align_reduce(acc, lds);
@@ -285,7 +216,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void lift_align_kernel(AlignArgs A) 
   bool good = used > 0 && align_solve(acc, q, lam1, lam2);
 #pragma unroll 1
   for (int it = 0; good && it < A.iters; ++it) {
-    Rw = align_rotation(q);
+    Rw = lift_rot3(q[0], q[1], q[2], q[3]);
     align_pass<0>(A, v, r, fr.f0, fr.f1, true, Rw, Rf, 0.0, 0.0, 0.0, acc);
     align_reduce(acc, lds);
     good = align_solve(acc, q, lam1, lam2);
@@ -295,7 +226,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void lift_align_kernel(AlignArgs A) 
 
   // 7. the residual at the final q under the weights of the last solve
   const bool weighted = A.iters > 0;
-  Rf = align_rotation(q);
+  Rf = lift_rot3(q[0], q[1], q[2], q[3]);
   align_pass<1>(A, v, r, fr.f0, fr.f1, weighted, Rw, Rf, 0.0, 0.0, 0.0, acc);
   align_reduce(acc, lds);
   const double rms = sqrt(acc[0] / acc[1]);
@@ -328,10 +259,9 @@ int mp_lift_align_views(const float* poses, int V, int64_t Ftot, int J, int C, c
                         int32_t* used, uint8_t* ok, void* stream) {
   static_assert(sizeof(long) == sizeof(int64_t), "LP64");
   MP_CHECK(poses && take_offset && quat && rms && used && ok, MP_ERR_ARG, "mp_lift_align_views: null pointer");
-  MP_CHECK(V >= 1 && V <= ALIGN_MAXV, MP_ERR_ARG, "mp_lift_align_views: V=%d outside 1..%d", V, ALIGN_MAXV);
-  MP_CHECK(J >= 2 && J <= LIFT_MAXJ, MP_ERR_ARG, "mp_lift_align_views: J=%d outside 2..%d", J, LIFT_MAXJ);
+  if (int rc = lift_take_shape("mp_lift_align_views", V, (long)Ftot, J, G)) return rc;
   MP_CHECK(C == 3 || C == 4, MP_ERR_ARG, "mp_lift_align_views: C=%d (3: poses, 4: hypotheses with their score)", C);
-  MP_CHECK(Ftot > 0 && G > 0 && (long)G <= Ftot && Ftot <= 0x7fffffffL, MP_ERR_ARG, "mp_lift_align_views: Ftot=%ld G=%d out of range", (long)Ftot, G);
+  MP_CHECK(Ftot <= 0x7fffffffL, MP_ERR_ARG, "mp_lift_align_views: Ftot=%ld G=%d out of range", (long)Ftot, G);
   MP_CHECK((long)G * V <= 0x7fffffffL, MP_ERR_ARG, "mp_lift_align_views: G=%d takes of %d views: too many for one launch", G, V);
   MP_CHECK(sigma > 0.f, MP_ERR_ARG, "mp_lift_align_views: sigma=%g must be > 0 (inf: every weight is 1)", (double)sigma);
   MP_CHECK(iters >= 0 && iters <= MP_LIFT_ALIGN_MAXITERS, MP_ERR_ARG, "mp_lift_align_views: iters=%d outside 0..%d", iters, MP_LIFT_ALIGN_MAXITERS);

@@ -20,9 +20,9 @@
 // (item * Ftot + f: consecutive lanes touch consecutive doubles), the rows frame-major (what the take kernel reads whole).
 // Everything between the float32 loads and the float32 stores is fp64, without contraction; no atomics, fixed orders: identical bits on every call.
 #include "lift_common.h"
-#include "../../include/manipose_hip.h"
 
 #pragma clang fp contract(off)
+#include "lift_geom.h"                    // after the pragma: the shared code takes this file's mode
 
 namespace mp {
 
@@ -73,24 +73,6 @@ struct BundleArgs {
   int V, J, G, distort, iters;
 };
 
-struct BundleRot { double r00, r01, r02, r10, r11, r12, r20, r21, r22; };
-
-__device__ __forceinline__ BundleRot bundle_rotation(double w, double x, double y, double z) {
-  BundleRot R;
-  R.r00 = 1.0 - 2.0 * (y * y + z * z); R.r01 = 2.0 * (x * y - w * z);       R.r02 = 2.0 * (x * z + w * y);
-  R.r10 = 2.0 * (x * y + w * z);       R.r11 = 1.0 - 2.0 * (x * x + z * z); R.r12 = 2.0 * (y * z - w * x);
-  R.r20 = 2.0 * (x * z - w * y);       R.r21 = 2.0 * (y * z + w * x);       R.r22 = 1.0 - 2.0 * (x * x + y * y);
-  return R;
-}
-
-__device__ __forceinline__ bool bundle_quat_ok(const float* q) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  const double n2 = w * w + x * x + y * y + z * z;
-  return __builtin_isfinite(n2) && n2 >= 1e-12;
-}
-
-__device__ __forceinline__ double bundle_clamp1(double x) { return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x); }
-
 __device__ __forceinline__ bool bundle_finite3(const float* x) { return __builtin_isfinite(((double)x[0] + (double)x[1]) + (double)x[2]); }
 
 // 1. of the rule: the views that observe frame f, the frame's root into the scratch and into root_out, its row zeroed
@@ -114,7 +96,7 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_mask_kernel(BundleArgs 
 #pragma unroll 1
     for (int v = 0; v < V; ++v) {
       if (A.valid != nullptr && A.valid[(long)v * A.Ftot + f] == 0) continue;
-      if (!bundle_quat_ok(A.quat + ((long)g * V + v) * 4)) continue;
+      if (!lift_quat_ok(A.quat + ((long)g * V + v) * 4)) continue;
       const float* U = A.kp + ((long)v * A.Ftot + f) * J * 2;
       bool fin = true;
 #pragma unroll 1
@@ -181,19 +163,23 @@ __global__ __launch_bounds__(BUNDLE_TAKE_THREADS) void bundle_init_kernel(Bundle
   for (int v = 0; v < BUNDLE_MAXV; ++v) {
     double* cam = ts + TS_CAM + 7 * v;
     cam[0] = 1.0; cam[1] = 0.0; cam[2] = 0.0; cam[3] = 0.0; cam[4] = 0.0; cam[5] = 0.0; cam[6] = 0.0;
-    if (v < V && bundle_quat_ok(A.quat + ((long)g * V + v) * 4)) {
+    double n2;
+    if (v < V && lift_quat_ok(A.quat + ((long)g * V + v) * 4, n2)) {
       const float* q = A.quat + ((long)g * V + v) * 4;
       const float* T = A.trans + ((long)g * V + v) * 3;
-      const double w0 = q[0], x0 = q[1], y0 = q[2], z0 = q[3];
-      const double nn = sqrt(w0 * w0 + x0 * x0 + y0 * y0 + z0 * z0);
-      cam[0] = w0 / nn; cam[1] = x0 / nn; cam[2] = y0 / nn; cam[3] = z0 / nn;
+      const double nn = sqrt(n2);
+      cam[0] = (double)q[0] / nn; cam[1] = (double)q[1] / nn; cam[2] = (double)q[2] / nn; cam[3] = (double)q[3] / nn;
       cam[4] = T[0]; cam[5] = T[1]; cam[6] = T[2];
     }
   }
   for (int i = 0; i < BUNDLE_N; ++i) ts[TS_DC + i] = 0.0;
 }
 
-// pass p of a frame: 4. and 5. its candidate root, 3. the evaluation of every view at the candidate, 5. its row of the reduced system
+// pass p of a frame: 4. and 5. its candidate root, 3. the evaluation of every view at the candidate, 5. its row of the reduced system.
+// The joint loop keeps its OWN statement of the camera model, the root's normal equations and their cofactor inverse (lift_geom.h's
+// lift_project, LiftNormal3 and lift_adj3 word for word): through the shared functions this kernel, at 250 VGPRs, kept its bits, registers and
+// fp64 opcode counts but was scheduled differently and ran 1 to 3 % slower in every pass with a Jacobian.  A change to the camera model or to
+// the 1e-12 rule in lift_geom.h is made here as well; tests/test_gpu_lift_bundle.py holds this copy to the float64 statement.
 __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_frame_kernel(BundleArgs A, int p) {
   const long f = (long)blockIdx.x * BUNDLE_THREADS + threadIdx.x;
   if (f >= A.Ftot) return;
@@ -232,7 +218,7 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_frame_kernel(BundleArgs
   for (int v = 0; v < V; ++v) {
     if (!((mask >> v) & 1)) continue;                                   // (its E, W and blocks stay the zeros of bundle_mask_kernel)
     const double* cq = ts + TS_CAM + 7 * v;
-    const BundleRot R = bundle_rotation(cq[0], cq[1], cq[2], cq[3]);
+    const Rot3 R = lift_rot3(cq[0], cq[1], cq[2], cq[3]);
     const float* cam = A.intr + ((long)g * V + v) * 9;
     const float* Uk = A.kp + ((long)v * Ftot + f) * J * 2;
     const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3], k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[7], p2 = cam[8];
@@ -255,7 +241,7 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_frame_kernel(BundleArgs
       const double X = R.r00 * wx + R.r10 * wy + R.r20 * wz, Y = R.r01 * wx + R.r11 * wy + R.r21 * wz, Z = R.r02 * wx + R.r12 * wy + R.r22 * wz;
       if (!(Z > 0.0)) notdeep = 1.0;
       const double qx = X / Z, qy = Y / Z;
-      const double xx = bundle_clamp1(qx), yy = bundle_clamp1(qy);
+      const double xx = lift_clamp1(qx), yy = lift_clamp1(qy);
       double px = xx, py = yy;
       double a = 1.0, b = 0.0, c = 0.0, d = 1.0;                        // d(px, py) / d(x, y)
       if (A.distort) {
@@ -487,7 +473,7 @@ __global__ __launch_bounds__(BUNDLE_TAKE_THREADS) void bundle_take_kernel(Bundle
     if (q0 < 0.0 || (q0 == 0.0 && (q1 < 0.0 || (q1 == 0.0 && (q2 < 0.0 || (q2 == 0.0 && q3 < 0.0)))))) {
       q0 = 0.0 - q0; q1 = 0.0 - q1; q2 = 0.0 - q2; q3 = 0.0 - q3;      // canonical, mp_lift_align_views' rule (0 - x: a zero comes out as +0)
     }
-    const BundleRot R = bundle_rotation(q0, q1, q2, q3);
+    const Rot3 R = lift_rot3(q0, q1, q2, q3);
     const double tx = x[6 * k + 3], ty = x[6 * k + 4], tz = x[6 * k + 5];
     double* c = cand[k];
     c[0] = q0; c[1] = q1; c[2] = q2; c[3] = q3;
@@ -533,9 +519,8 @@ int mp_lift_bundle_views(const float* pose, const float* root, const uint8_t* ro
   static_assert(sizeof(long) == sizeof(int64_t), "LP64");
   MP_CHECK(pose && root && kp && take_offset && quat && trans && intr, MP_ERR_ARG, "mp_lift_bundle_views: null input");
   MP_CHECK(quat_out && trans_out && root_out && reproj && cost && steps && ok && used, MP_ERR_ARG, "mp_lift_bundle_views: null output");
-  MP_CHECK(V >= 1 && V <= BUNDLE_MAXV, MP_ERR_ARG, "mp_lift_bundle_views: V=%d outside 1..%d", V, BUNDLE_MAXV);
-  MP_CHECK(J >= 2 && J <= LIFT_MAXJ, MP_ERR_ARG, "mp_lift_bundle_views: J=%d outside 2..%d", J, LIFT_MAXJ);
-  MP_CHECK(Ftot > 0 && G > 0 && (long)G <= Ftot && Ftot <= 0x7fffffffL, MP_ERR_ARG, "mp_lift_bundle_views: Ftot=%ld G=%d out of range", (long)Ftot, G);
+  if (int rc = lift_take_shape("mp_lift_bundle_views", V, (long)Ftot, J, G)) return rc;
+  MP_CHECK(Ftot <= 0x7fffffffL, MP_ERR_ARG, "mp_lift_bundle_views: Ftot=%ld G=%d out of range", (long)Ftot, G);
   MP_CHECK(distort == 0 || distort == 1, MP_ERR_ARG, "mp_lift_bundle_views: distort=%d (0: project_to_2d_linear, 1: project_to_2d)", distort);
   MP_CHECK(sigma > 0.f, MP_ERR_ARG, "mp_lift_bundle_views: sigma=%g must be > 0 (inf: every robust factor is 1)", (double)sigma);
   MP_CHECK(iters >= 0 && iters <= MP_LIFT_BUNDLE_MAXITERS, MP_ERR_ARG, "mp_lift_bundle_views: iters=%d outside 0..%d", iters, MP_LIFT_BUNDLE_MAXITERS);

@@ -12,11 +12,10 @@
 // every lane with the frame's choice.  The workgroup barriers are reached by every wave, whether its frame exists or not.
 // mp_lift_fuse_place: ONE LANE OWNS ONE FRAME, as in lift_place_refine_kernel; a view's rotation matrix is re-made from its quaternion at the head
 // of every pass (a few dozen operations against J joints of five divisions and a square root), so nothing sits in a register array indexed at
-// run time.  The per-joint projection and Jacobian are lift_place.hip's refine_eval restated for a rotated camera (that kernel is pinned bit for
-// bit by tests/golden/lift_place_bits.npz and was left alone).
+// run time.  The rotation, the view test, the per-joint projection with its Jacobian, the Gauss-Newton sums and the 3x3 solve are lift_geom.h's,
+// shared with lift_place.hip: here the Jacobian is taken through R^T.
 // Everything between the float32 loads and the float32 stores is fp64; no atomics, fixed orders: identical bits on every call.
-#include "lift_common.h"
-#include "../../include/manipose_hip.h"
+#include "lift_geom.h"
 
 namespace mp {
 
@@ -25,22 +24,6 @@ constexpr int FUSE_WAVES = 4;                  // frames of a workgroup at most 
 constexpr int FUSE_PLACE_THREADS = 64;         // lanes of a workgroup of the place kernel: one wave, as lift_place_refine_kernel
 constexpr double FUSE_BIG = 1e30;              // a pair cost that is not finite
 constexpr long FUSE_LDS_LIMIT = 64 * 1024;
-
-struct FuseRot { double r00, r01, r02, r10, r11, r12, r20, r21, r22; };
-
-// the matrix of q / |q|, normalised in fp64; false (and the identity) where |q|^2 is not finite or < 1e-12; q null: the identity
-__device__ __forceinline__ bool fuse_rotation(const float* q, FuseRot& R) {
-  R = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-  if (q == nullptr) return true;
-  const double w0 = q[0], x0 = q[1], y0 = q[2], z0 = q[3];
-  const double n2 = w0 * w0 + x0 * x0 + y0 * y0 + z0 * z0;
-  if (!(__builtin_isfinite(n2) && n2 >= 1e-12)) return false;
-  const double n = sqrt(n2), w = w0 / n, x = x0 / n, y = y0 / n, z = z0 / n;
-  R.r00 = 1.0 - 2.0 * (y * y + z * z); R.r01 = 2.0 * (x * y - w * z);       R.r02 = 2.0 * (x * z + w * y);
-  R.r10 = 2.0 * (x * y + w * z);       R.r11 = 1.0 - 2.0 * (x * x + z * z); R.r12 = 2.0 * (y * z - w * x);
-  R.r20 = 2.0 * (x * z - w * y);       R.r21 = 2.0 * (y * z + w * x);       R.r22 = 1.0 - 2.0 * (x * x + y * y);
-  return true;
-}
 
 struct FuseArgs {
   const float* hyps;             // (V, Ftot, K, J, C)
@@ -56,22 +39,6 @@ struct FuseArgs {
   double pair_factor, score_weight;   // 1 / (2 sigma^2), score_weight
   int V, K, J, C, G, waves, frame_doubles;
 };
-
-// bit v: view v of frame f counts (its valid byte and its take's quaternion)
-__device__ __forceinline__ int fuse_view_mask(const unsigned char* valid, const float* quat, int V, long Ftot, long f, int g) {
-  int mask = 0;
-  for (int v = 0; v < V; ++v) {
-    bool good = valid == nullptr || valid[(long)v * Ftot + f] != 0;
-    if (good && quat != nullptr) {
-      const float* q = quat + ((long)g * V + v) * 4;
-      const double w = q[0], x = q[1], y = q[2], z = q[3];
-      const double n2 = w * w + x * x + y * y + z * z;
-      good = __builtin_isfinite(n2) && n2 >= 1e-12;
-    }
-    if (good) mask |= 1 << v;
-  }
-  return mask;
-}
 
 // pair (a, b), a < b, in lexicographic order: its row in the pair table
 __device__ __forceinline__ int fuse_pair_index(int a, int b) { return a * (2 * FUSE_MAXV - a - 1) / 2 + (b - a - 1); }
@@ -89,10 +56,10 @@ __global__ __launch_bounds__(FUSE_WAVES * 64) void lift_fuse_kernel(FuseArgs A) 
   int g = 0, mask = 0;
   if (live) {
     g = lift_seq_of(A.take_offset, A.G, f);
-    mask = fuse_view_mask(A.valid, A.quat, V, A.Ftot, f, g);
+    mask = lift_view_mask(A.valid, A.quat, V, A.Ftot, f, g);
     if (lane < V && ((mask >> lane) & 1)) {
-      FuseRot R;
-      fuse_rotation(A.quat != nullptr ? A.quat + ((long)g * V + lane) * 4 : nullptr, R);
+      Rot3 R;
+      lift_rot3(A.quat != nullptr ? A.quat + ((long)g * V + lane) * 4 : nullptr, R);
       double* r = Rm + lane * 9;
       r[0] = R.r00; r[1] = R.r01; r[2] = R.r02; r[3] = R.r10; r[4] = R.r11; r[5] = R.r12; r[6] = R.r20; r[7] = R.r21; r[8] = R.r22;
     }
@@ -235,21 +202,13 @@ struct FusePlaceArgs {
   int V, J, G, distort, iters;
 };
 
-__device__ __forceinline__ double fuse_clamp1(double x) { return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x); }
-
-// what one pass over the weighted joints of the valid views at a root gives (mp_lift_place_refine's step 2, the Jacobian taken through R^T)
-struct FuseEval {
-  double F, E, W, H00, H01, H02, H11, H12, H22, g0, g1, g2;
-  bool deep;
-};
-
-// view `cam` (its row of the take's tables) added to e: P = R^T (pose_j + r - T), then lift_place.hip's projection and Jacobian
+// view `cam` (its row of the take's tables) added to e: P = R^T (pose_j + r - T), the projection's Jacobian taken through R^T
 template <bool JAC>
-__device__ __forceinline__ void fuse_eval_view(FuseEval& e, const float* P, const float* U, const float* weights, int J, int distort, const float* q,
+__device__ __forceinline__ void fuse_eval_view(LiftGN& e, const float* P, const float* U, const float* weights, int J, int distort, const float* q,
                                                const float* T, const float* cam, double rx, double ry, double rz) {
-  FuseRot R;
-  fuse_rotation(q, R);
-  const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3], k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[7], p2 = cam[8];
+  Rot3 R;
+  lift_rot3(q, R);
+  const LiftCam K = lift_cam(cam);
   const double ox = rx - (double)T[0], oy = ry - (double)T[1], oz = rz - (double)T[2];
   for (int j = 0; j < J; ++j) {                                         // sums in joint order
     const double w = weights != nullptr ? (double)weights[j] : 1.0;
@@ -257,57 +216,19 @@ __device__ __forceinline__ void fuse_eval_view(FuseEval& e, const float* P, cons
     const double wx = (double)P[j * 3] + ox, wy = (double)P[j * 3 + 1] + oy, wz = (double)P[j * 3 + 2] + oz;
     const double X = R.r00 * wx + R.r10 * wy + R.r20 * wz, Y = R.r01 * wx + R.r11 * wy + R.r21 * wz, Z = R.r02 * wx + R.r12 * wy + R.r22 * wz;
     if (!(Z > 0.0)) e.deep = false;
-    const double qx = X / Z, qy = Y / Z;
-    const double xx = fuse_clamp1(qx), yy = fuse_clamp1(qy);
-    double px = xx, py = yy;
-    double a = 1.0, b = 0.0, c = 0.0, d = 1.0;                          // d(px, py) / d(x, y)
-    if (distort) {
-      const double r2 = xx * xx + yy * yy;
-      const double m = 1.0 + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2)) + (p1 * xx + p2 * yy);
-      px = xx * m + p1 * r2;
-      py = yy * m + p2 * r2;
-      if (JAC) {
-        const double dm = k1 + 2.0 * k2 * r2 + 3.0 * k3 * (r2 * r2);
-        const double mx = 2.0 * xx * dm + p1, my = 2.0 * yy * dm + p2;
-        a = m + xx * mx + 2.0 * p1 * xx;
-        b = xx * my + 2.0 * p1 * yy;
-        c = yy * mx + 2.0 * p2 * xx;
-        d = m + yy * my + 2.0 * p2 * yy;
-      }
-    }
-    const double du = fx * px + cx - (double)U[2 * j], dv = fy * py + cy - (double)U[2 * j + 1];
-    const double rr = du * du + dv * dv;
-    e.W += w;
-    e.E += w * sqrt(rr);
-    e.F += w * rr;
-    if (JAC) {
-      const double sx = (qx >= -1.0 && qx <= 1.0) ? 1.0 : 0.0, sy = (qy >= -1.0 && qy <= 1.0) ? 1.0 : 0.0;   // the derivative of the clamp
-      const double iz = 1.0 / Z;
-      const double xz = sx * iz, yz = sy * iz, xq = sx * (-qx / Z), yq = sy * (-qy / Z);
-      const double c00 = fx * (a * xz), c01 = fx * (b * yz), c02 = fx * (a * xq + b * yq);                  // J_j with respect to the camera-space point
-      const double c10 = fy * (c * xz), c11 = fy * (d * yz), c12 = fy * (c * xq + d * yq);
-      const double j00 = c00 * R.r00 + c01 * R.r01 + c02 * R.r02, j01 = c00 * R.r10 + c01 * R.r11 + c02 * R.r12,
-                   j02 = c00 * R.r20 + c01 * R.r21 + c02 * R.r22;                                            // J_j R^T: with respect to r
-      const double j10 = c10 * R.r00 + c11 * R.r01 + c12 * R.r02, j11 = c10 * R.r10 + c11 * R.r11 + c12 * R.r12,
-                   j12 = c10 * R.r20 + c11 * R.r21 + c12 * R.r22;
-      e.H00 += w * (j00 * j00 + j10 * j10);
-      e.H01 += w * (j00 * j01 + j10 * j11);
-      e.H02 += w * (j00 * j02 + j10 * j12);
-      e.H11 += w * (j01 * j01 + j11 * j11);
-      e.H12 += w * (j01 * j02 + j11 * j12);
-      e.H22 += w * (j02 * j02 + j12 * j12);
-      e.g0 += w * (j00 * du + j10 * dv);
-      e.g1 += w * (j01 * du + j11 * dv);
-      e.g2 += w * (j02 * du + j12 * dv);
-    }
+    const LiftProj pr = lift_project<JAC>(X, Y, Z, U + 2 * j, K, distort);
+    const double j00 = pr.c00 * R.r00 + pr.c01 * R.r01 + pr.c02 * R.r02, j01 = pr.c00 * R.r10 + pr.c01 * R.r11 + pr.c02 * R.r12,
+                 j02 = pr.c00 * R.r20 + pr.c01 * R.r21 + pr.c02 * R.r22;                                  // J_j R^T: with respect to r
+    const double j10 = pr.c10 * R.r00 + pr.c11 * R.r01 + pr.c12 * R.r02, j11 = pr.c10 * R.r10 + pr.c11 * R.r11 + pr.c12 * R.r12,
+                 j12 = pr.c10 * R.r20 + pr.c11 * R.r21 + pr.c12 * R.r22;
+    lift_gn_add<JAC>(e, w, pr, j00, j01, j02, j10, j11, j12);
   }
 }
 
 // the sums over the valid views in order, then the joints in order
 template <bool JAC>
-__device__ __forceinline__ FuseEval fuse_eval(const FusePlaceArgs& A, long f, int g, int mask, double rx, double ry, double rz) {
-  FuseEval e = {};
-  e.deep = true;
+__device__ __forceinline__ LiftGN fuse_eval(const FusePlaceArgs& A, long f, int g, int mask, double rx, double ry, double rz) {
+  LiftGN e = lift_gn_start();
   for (int v = 0; v < A.V; ++v) {
     if (!((mask >> v) & 1)) continue;
     const long gv = (long)g * A.V + v;
@@ -322,15 +243,16 @@ __global__ __launch_bounds__(FUSE_PLACE_THREADS) void lift_fuse_place_kernel(Fus
   const long f = (long)blockIdx.x * FUSE_PLACE_THREADS + threadIdx.x;
   if (f >= A.Ftot) return;
   const int g = lift_seq_of(A.take_offset, A.G, f);
-  const int mask = fuse_view_mask(A.valid, A.quat, V, A.Ftot, f, g);
+  const int mask = lift_view_mask(A.valid, A.quat, V, A.Ftot, f, g);
   const float* P = A.pose + f * J * 3;
   // 1. the linear pinhole fit over all valid views
-  double H00 = 0.0, H01 = 0.0, H02 = 0.0, H11 = 0.0, H12 = 0.0, H22 = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0, W = 0.0;
+  LiftNormal3 lin = {};
+  double W = 0.0;
   for (int v = 0; v < V; ++v) {
     if (!((mask >> v) & 1)) continue;
     const long gv = (long)g * V + v;
-    FuseRot R;
-    fuse_rotation(A.quat != nullptr ? A.quat + gv * 4 : nullptr, R);
+    Rot3 R;
+    lift_rot3(A.quat != nullptr ? A.quat + gv * 4 : nullptr, R);
     const float* cam = A.intr + gv * 9;
     const float* T = A.trans + gv * 3;
     const float* U = A.kp + ((long)v * A.Ftot + f) * J * 2;
@@ -345,44 +267,33 @@ __global__ __launch_bounds__(FUSE_PLACE_THREADS) void lift_fuse_place_kernel(Fus
       const double c0 = Tx - (double)P[j * 3], c1 = Ty - (double)P[j * 3 + 1], c2 = Tz - (double)P[j * 3 + 2];
       const double sx = mx0 * c0 + mx1 * c1 + mx2 * c2, sy = my0 * c0 + my1 * c1 + my2 * c2;
       W += w;
-      H00 += w * (mx0 * mx0 + my0 * my0); H01 += w * (mx0 * mx1 + my0 * my1); H02 += w * (mx0 * mx2 + my0 * my2);
-      H11 += w * (mx1 * mx1 + my1 * my1); H12 += w * (mx1 * mx2 + my1 * my2); H22 += w * (mx2 * mx2 + my2 * my2);
-      h0 += w * (mx0 * sx + my0 * sy); h1 += w * (mx1 * sx + my1 * sy); h2 += w * (mx2 * sx + my2 * sy);
+      lift_normal3_add(lin, w, sx, sy, mx0, mx1, mx2, my0, my1, my2);
     }
   }
   double rx = 0.0, ry = 0.0, rz = 0.0;
   bool have = false;
   {
-    const double c00 = H11 * H22 - H12 * H12, c01 = H02 * H12 - H01 * H22, c02 = H01 * H12 - H02 * H11;
-    const double det = H00 * c00 + H01 * c01 + H02 * c02, scale = H00 * H11 * H22;
-    const bool finite = __builtin_isfinite(W) && __builtin_isfinite(H00) && __builtin_isfinite(H01) && __builtin_isfinite(H02) && __builtin_isfinite(H11) &&
-                        __builtin_isfinite(H12) && __builtin_isfinite(H22) && __builtin_isfinite(h0) && __builtin_isfinite(h1) && __builtin_isfinite(h2) &&
-                        __builtin_isfinite(det) && __builtin_isfinite(scale);
-    if (mask != 0 && W > 0.0 && finite && det > 1e-12 * scale) {
-      const double c11 = H00 * H22 - H02 * H02, c12 = H01 * H02 - H00 * H12, c22 = H00 * H11 - H01 * H01;
-      rx = (c00 * h0 + c01 * h1 + c02 * h2) / det;
-      ry = (c01 * h0 + c11 * h1 + c12 * h2) / det;
-      rz = (c02 * h0 + c12 * h1 + c22 * h2) / det;
+    LiftAdj3 adj;
+    const bool solvable = lift_adj3(lin, adj);
+    const bool finite = __builtin_isfinite(W) && __builtin_isfinite(lin.H00) && __builtin_isfinite(lin.H01) && __builtin_isfinite(lin.H02) &&
+                        __builtin_isfinite(lin.H11) && __builtin_isfinite(lin.H12) && __builtin_isfinite(lin.H22) && __builtin_isfinite(lin.g0) &&
+                        __builtin_isfinite(lin.g1) && __builtin_isfinite(lin.g2);
+    if (mask != 0 && W > 0.0 && finite && solvable) {
+      lift_adj3_solve(adj, lin.g0, lin.g1, lin.g2, rx, ry, rz);
       have = __builtin_isfinite(rx) && __builtin_isfinite(ry) && __builtin_isfinite(rz);
       if (!have) { rx = 0.0; ry = 0.0; rz = 0.0; }
     }
   }
   unsigned char ok = 0, taken = 0;
   if (have) {                                                           // 2., 3. of mp_lift_place_refine
-    FuseEval e = A.iters > 0 ? fuse_eval<true>(A, f, g, mask, rx, ry, rz) : fuse_eval<false>(A, f, g, mask, rx, ry, rz);
+    LiftGN e = A.iters > 0 ? fuse_eval<true>(A, f, g, mask, rx, ry, rz) : fuse_eval<false>(A, f, g, mask, rx, ry, rz);
     if (e.deep && __builtin_isfinite(e.F)) {
       ok = 1;
       for (int k = 0; k < A.iters; ++k) {
-        const double c00 = e.H11 * e.H22 - e.H12 * e.H12, c01 = e.H02 * e.H12 - e.H01 * e.H22, c02 = e.H01 * e.H12 - e.H02 * e.H11;
-        const double det = e.H00 * c00 + e.H01 * c01 + e.H02 * c02, scale = e.H00 * e.H11 * e.H22;
-        if (!(__builtin_isfinite(det) && __builtin_isfinite(scale) && det > 1e-12 * scale)) break;
-        const double c11 = e.H00 * e.H22 - e.H02 * e.H02, c12 = e.H01 * e.H02 - e.H00 * e.H12, c22 = e.H00 * e.H11 - e.H01 * e.H01;
-        const double nx = rx - (c00 * e.g0 + c01 * e.g1 + c02 * e.g2) / det;
-        const double ny = ry - (c01 * e.g0 + c11 * e.g1 + c12 * e.g2) / det;
-        const double nz = rz - (c02 * e.g0 + c12 * e.g1 + c22 * e.g2) / det;
-        if (!(__builtin_isfinite(nx) && __builtin_isfinite(ny) && __builtin_isfinite(nz))) break;
-        const FuseEval n = fuse_eval<true>(A, f, g, mask, nx, ny, nz);
-        if (!(n.deep && n.F <= (1.0 + 1e-6) * e.F)) break;              // (a NaN cost is not taken either)
+        double nx, ny, nz;
+        if (!lift_gn_step(e, rx, ry, rz, nx, ny, nz)) break;
+        const LiftGN n = fuse_eval<true>(A, f, g, mask, nx, ny, nz);
+        if (!lift_gn_accept(n, e)) break;
         rx = nx; ry = ny; rz = nz; e = n; ++taken;
       }
     }
@@ -392,8 +303,7 @@ __global__ __launch_bounds__(FUSE_PLACE_THREADS) void lift_fuse_place_kernel(Fus
     double err = 0.0;
     if (have && ((mask >> v) & 1)) {
       const long gv = (long)g * V + v;
-      FuseEval e = {};
-      e.deep = true;
+      LiftGN e = lift_gn_start();
       fuse_eval_view<false>(e, P, A.kp + ((long)v * A.Ftot + f) * J * 2, A.weights, J, A.distort, A.quat != nullptr ? A.quat + gv * 4 : nullptr,
                             A.trans + gv * 3, A.intr + gv * 9, rx, ry, rz);
       err = e.E / e.W;
@@ -402,14 +312,6 @@ __global__ __launch_bounds__(FUSE_PLACE_THREADS) void lift_fuse_place_kernel(Fus
   }
   A.ok[f] = ok;
   if (A.steps != nullptr) A.steps[f] = taken;
-}
-
-// the checks both entry points share: the views, the frames and the takes
-static int fuse_shape(const char* who, int V, long Ftot, int J, int G) {
-  MP_CHECK(V >= 1 && V <= FUSE_MAXV, MP_ERR_ARG, "%s: V=%d outside 1..%d", who, V, FUSE_MAXV);
-  MP_CHECK(J >= 2 && J <= LIFT_MAXJ, MP_ERR_ARG, "%s: J=%d outside 2..%d", who, J, LIFT_MAXJ);
-  MP_CHECK(Ftot > 0 && G > 0 && (long)G <= Ftot, MP_ERR_ARG, "%s: Ftot=%ld G=%d out of range", who, Ftot, G);
-  return MP_OK;
 }
 
 }  // namespace mp
@@ -421,7 +323,7 @@ int mp_lift_fuse(const float* hyps, int V, int64_t Ftot, int K, int J, int C, co
                  float sigma, float score_weight, float* pose, uint8_t* choice, float* cost, float* spread, uint8_t* ok, void* stream) {
   static_assert(sizeof(long) == sizeof(int64_t), "LP64");
   MP_CHECK(hyps && take_offset && pose && choice && cost && spread && ok, MP_ERR_ARG, "mp_lift_fuse: null pointer");
-  if (int rc = fuse_shape("mp_lift_fuse", V, (long)Ftot, J, G)) return rc;
+  if (int rc = lift_take_shape("mp_lift_fuse", V, (long)Ftot, J, G)) return rc;
   MP_CHECK(K >= 1 && K <= FUSE_MAXK, MP_ERR_ARG, "mp_lift_fuse: K=%d outside 1..%d", K, FUSE_MAXK);
   MP_CHECK(C == 3 || C == 4, MP_ERR_ARG, "mp_lift_fuse: C=%d (3: poses, 4: hypotheses with their score)", C);
   MP_CHECK(sigma > 0.f, MP_ERR_ARG, "mp_lift_fuse: sigma=%g must be > 0 (inf: the pair factor is 0)", (double)sigma);
@@ -447,7 +349,7 @@ int mp_lift_fuse_place(const float* pose, const float* kp, int V, int64_t Ftot, 
                        const float* quat, const float* trans, const float* intr, const float* weights, int distort, int iters, float* root,
                        float* reproj, uint8_t* ok, uint8_t* steps, void* stream) {
   MP_CHECK(pose && kp && take_offset && trans && intr && root && reproj && ok, MP_ERR_ARG, "mp_lift_fuse_place: null pointer");
-  if (int rc = fuse_shape("mp_lift_fuse_place", V, (long)Ftot, J, G)) return rc;
+  if (int rc = lift_take_shape("mp_lift_fuse_place", V, (long)Ftot, J, G)) return rc;
   MP_CHECK(distort == 0 || distort == 1, MP_ERR_ARG, "mp_lift_fuse_place: distort=%d (0: project_to_2d_linear, 1: project_to_2d)", distort);
   MP_CHECK(iters >= 0 && iters <= MP_LIFT_REFINE_MAXITERS, MP_ERR_ARG, "mp_lift_fuse_place: iters=%d outside 0..%d", iters, MP_LIFT_REFINE_MAXITERS);
   const long blocks = ((long)Ftot + FUSE_PLACE_THREADS - 1) / FUSE_PLACE_THREADS;

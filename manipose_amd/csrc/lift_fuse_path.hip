@@ -19,15 +19,16 @@
 //           the chunk (the digits kept apart: no division), all lanes store the path.
 //   emit:   ONE LANE OWNS ONE FRAME: the frame cost of the chosen state from the row, in the scan's order (the same bits); the views' rotations
 //           re-made in registers (the view loop is unrolled: nothing is indexed at run time), mean and spread in joint order, views in order.
-// lift_fuse.hip's rotation, masks and emit step are restated here, not moved: that file keeps its bytes and mp_lift_fuse its bits.
+// The rotation and the view test are lift_geom.h's, shared with lift_fuse.hip (compiled here without contraction: the header is included after
+// the pragma); mp_lift_fuse's emit step is restated for one lane per frame.
 // Everything between the float32 loads and the stores is fp64 without contraction; a take's frames are its CLAMPED range and every digit read
 // back is clamped to K - 1, so whatever the device table holds nothing outside the arrays is touched.  No atomics: identical bits on every call.
 #include <algorithm>
 
 #include "lift_common.h"
-#include "../../include/manipose_hip.h"
 
 #pragma clang fp contract(off)
+#include "lift_geom.h"                    // after the pragma: the shared code takes this file's mode
 
 namespace mp {
 
@@ -39,22 +40,6 @@ constexpr long FP_TILE_LDS = 60 * 1024;                                // the ta
 constexpr long FP_SCAN_MIN_LDS = 32 * 1024;                            // the scan's main region at least: what a backtrack chunk gets
 static_assert(FP_MAXV == 4 && FP_MAXK <= 8, "3 bits a view, 4 views: 12 bits of a 16-bit back-pointer word");
 static_assert(FP_CHUNK >= 1 && FP_CHUNK <= 1024, "the path of a chunk lives in LDS");
-
-struct FpRot { double r00, r01, r02, r10, r11, r12, r20, r21, r22; };
-
-// lift_fuse.hip's fuse_rotation: the matrix of q / |q|, normalised in fp64; false where |q|^2 is not finite or < 1e-12; q null: the identity
-__device__ __forceinline__ bool fp_rotation(const float* q, FpRot& R) {
-  R = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-  if (q == nullptr) return true;
-  const double w0 = q[0], x0 = q[1], y0 = q[2], z0 = q[3];
-  const double n2 = w0 * w0 + x0 * x0 + y0 * y0 + z0 * z0;
-  if (!(__builtin_isfinite(n2) && n2 >= 1e-12)) return false;
-  const double n = sqrt(n2), w = w0 / n, x = x0 / n, y = y0 / n, z = z0 / n;
-  R.r00 = 1.0 - 2.0 * (y * y + z * z); R.r01 = 2.0 * (x * y - w * z);       R.r02 = 2.0 * (x * z + w * y);
-  R.r10 = 2.0 * (x * y + w * z);       R.r11 = 1.0 - 2.0 * (x * x + z * z); R.r12 = 2.0 * (y * z - w * x);
-  R.r20 = 2.0 * (x * z - w * y);       R.r21 = 2.0 * (y * z + w * x);       R.r22 = 1.0 - 2.0 * (x * x + y * y);
-  return true;
-}
 
 struct FusePathArgs {
   const float* hyps;             // (V, Ftot, K, J, C)
@@ -78,18 +63,6 @@ struct FusePathArgs {
   int lds_main, chunk;           // scan: bytes of its main LDS region, frames of a backtrack chunk
 };
 
-// is view v of frame f, take g, valid: its valid byte and its take's quaternion (lift_fuse.hip's fuse_view_mask, one view)
-__device__ __forceinline__ bool fp_view_ok(const unsigned char* valid, const float* quat, int V, long Ftot, long f, int g, int v) {
-  bool good = valid == nullptr || valid[(long)v * Ftot + f] != 0;
-  if (good && quat != nullptr) {
-    const float* q = quat + ((long)g * V + v) * 4;
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double n2 = w * w + x * x + y * y + z * z;
-    good = __builtin_isfinite(n2) && n2 >= 1e-12;
-  }
-  return good;
-}
-
 __global__ __launch_bounds__(POSE_THREADS) void lift_fuse_path_tables_kernel(FusePathArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fpt_lds[];
   const int V = A.V, K = A.K, J = A.J, C = A.C, TF = A.TF, KK = K * K, R = A.R, VKJ = V * K * J;
@@ -103,9 +76,9 @@ __global__ __launch_bounds__(POSE_THREADS) void lift_fuse_path_tables_kernel(Fus
     int good = 0;
     if (v < V && gf >= 0 && gf < A.Ftot) {
       const int g = lift_seq_of(A.take_offset, A.G, gf);
-      if (fp_view_ok(A.valid, A.quat, V, A.Ftot, gf, g, v)) {
-        FpRot Q;
-        fp_rotation(A.quat != nullptr ? A.quat + ((long)g * V + v) * 4 : nullptr, Q);
+      if (lift_view_ok(A.valid, A.quat, V, A.Ftot, gf, g, v)) {
+        Rot3 Q;
+        lift_rot3(A.quat != nullptr ? A.quat + ((long)g * V + v) * 4 : nullptr, Q);
         double* r = fr + (long)h * A.frame_doubles + v * 9;
         r[0] = Q.r00; r[1] = Q.r01; r[2] = Q.r02; r[3] = Q.r10; r[4] = Q.r11; r[5] = Q.r12; r[6] = Q.r20; r[7] = Q.r21; r[8] = Q.r22;
         good = 1;
@@ -388,7 +361,7 @@ __global__ __launch_bounds__(64) void lift_fuse_path_emit_kernel(FusePathArgs A)
     if (v < V) {
       dg |= (c % K) << (3 * v);
       c /= K;
-      if (fp_view_ok(A.valid, A.quat, V, A.Ftot, f, g, v)) { mask |= 1 << v; ++n; }
+      if (lift_view_ok(A.valid, A.quat, V, A.Ftot, f, g, v)) { mask |= 1 << v; ++n; }
     }
   if (n == 0) {
     for (int it = 0; it < J * 3; ++it) A.pose[f * J * 3 + it] = 0.f;
@@ -397,13 +370,13 @@ __global__ __launch_bounds__(64) void lift_fuse_path_emit_kernel(FusePathArgs A)
     return;
   }
   const double E = fp_frame_cost(A.rows + f * A.R, dg, V, K, A.NP, A.pair_factor, A.score_weight);
-  FpRot Q[FP_MAXV];
+  Rot3 Q[FP_MAXV];
   const float* x[FP_MAXV];
 #pragma unroll
   for (int v = 0; v < FP_MAXV; ++v) {
     x[v] = nullptr;
     if (v < V && ((mask >> v) & 1)) {
-      fp_rotation(A.quat != nullptr ? A.quat + ((long)g * V + v) * 4 : nullptr, Q[v]);
+      lift_rot3(A.quat != nullptr ? A.quat + ((long)g * V + v) * 4 : nullptr, Q[v]);
       x[v] = A.hyps + (((long)v * A.Ftot + f) * K + ((dg >> (3 * v)) & 7)) * J * C;
     }
   }
@@ -472,9 +445,7 @@ int mp_lift_fuse_path(const float* hyps, int V, int64_t Ftot, int K, int J, int 
                       float* spread, uint8_t* ok, double* path_cost, void* scratch, int64_t scratch_bytes, void* stream) {
   static_assert(sizeof(long) == sizeof(int64_t), "LP64");
   MP_CHECK(hyps && take_offset && pose && choice && cost && spread && ok && path_cost && scratch, MP_ERR_ARG, "mp_lift_fuse_path: null pointer");
-  MP_CHECK(V >= 1 && V <= FP_MAXV, MP_ERR_ARG, "mp_lift_fuse_path: V=%d outside 1..%d", V, FP_MAXV);
-  MP_CHECK(J >= 2 && J <= LIFT_MAXJ, MP_ERR_ARG, "mp_lift_fuse_path: J=%d outside 2..%d", J, LIFT_MAXJ);
-  MP_CHECK(Ftot > 0 && G > 0 && (long)G <= Ftot, MP_ERR_ARG, "mp_lift_fuse_path: Ftot=%ld G=%d out of range", (long)Ftot, G);
+  if (int rc = lift_take_shape("mp_lift_fuse_path", V, (long)Ftot, J, G)) return rc;
   MP_CHECK(K >= 1 && K <= FP_MAXK, MP_ERR_ARG, "mp_lift_fuse_path: K=%d outside 1..%d", K, FP_MAXK);
   MP_CHECK(C == 3 || C == 4, MP_ERR_ARG, "mp_lift_fuse_path: C=%d (3: poses, 4: hypotheses with their score)", C);
   MP_CHECK(sigma > 0.f, MP_ERR_ARG, "mp_lift_fuse_path: sigma=%g must be > 0 (inf: the pair factor is 0)", (double)sigma);

@@ -23,21 +23,18 @@
 // 15.4 / 47.9 / 99.4 us.  Staging does not pay: the time goes to the fp64 arithmetic of a pass (five divisions and a square root per joint), not to
 // the loads.  (mp_lift_place once had a kernel of its own, the linear fit and one error pass in workgroups of 256 lanes: into outputs allocated
 // once it took 14.9 us on the same poses, this kernel at iters = 0 takes 11.7 us - 59 workgroups against 235 on 256 CUs.  One kernel is also one
-// place to change the camera model and the degenerate-fit rule.  DESIGN.md, "Refining the placement", has both measurements.)
+// place to change the camera model and the degenerate-fit rule.  DESIGN.md, "Refining the placement", has both measurements.)  The camera model, the
+// Gauss-Newton sums, the 3x3 solve and the accept rule are lift_geom.h's, shared with lift_fuse.hip and lift_bundle.hip.
 //
 // Floor (mode 1): the minimum is taken from the STORED float32 values by a second kernel - MP_LIFT_WORLD_SHARES workgroups per sequence, each
 // over one contiguous share of the sequence's poses, DPP inside a wave, LDS across the 4 waves, one partial per workgroup - and the third
 // kernel merges a sequence's partials in share order, subtracts, and writes floor[s].  No atomics: the same bits on every call.
-#include "lift_common.h"
-#include "../../include/manipose_hip.h"
+#include "lift_geom.h"
 
 namespace mp {
 
 constexpr int FLOOR_SHARES = MP_LIFT_WORLD_SHARES;
 constexpr int REFINE_THREADS = 64;   // lanes of a workgroup of the fit kernel: one wave (235 workgroups for 15,000 poses; 256 lanes measured slower)
-
-// torch.clamp(x, -1, 1): a NaN stays a NaN
-__device__ __forceinline__ double refine_clamp1(double x) { return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x); }
 
 struct RefineArgs {
   const float* poses;            // (Ntot, inner, J, C)
@@ -55,67 +52,20 @@ struct RefineArgs {
   int inner, J, C, S, distort, iters;
 };
 
-struct RefineCam { double fx, fy, cx, cy, k1, k2, k3, p1, p2; };
-
-// what one pass over the weighted joints at a translation gives: F = sum w |r|^2, E = sum w |r|, W = sum w, H = sum w J^T J (upper triangle),
-// g = sum w J^T r, deep = every weighted Z > 0
-struct RefineEval {
-  double F, E, W, H00, H01, H02, H11, H12, H22, g0, g1, g2;
-  bool deep;
-};
-
-// P: the lane's pose (J rows of C floats), U: its frame's keypoints (J rows of 2 floats).  JAC = false leaves H and g at zero
+// one pass over the weighted joints of a pose at the translation t: the camera's frame is the pose's, so the Jacobian with respect to t is the
+// projection's own.  P: the lane's pose (J rows of C floats), U: its frame's keypoints (J rows of 2 floats).  JAC = false leaves H and g at zero
 // (iters = 0: the reprojection error alone)
 template <bool JAC>
-__device__ __forceinline__ RefineEval refine_eval(const float* P, const float* U, const float* weights, int J, int C, int distort, const RefineCam& cam,
-                                                  double tx, double ty, double tz) {
-  RefineEval e = {};
-  e.deep = true;
-  const double fx = cam.fx, fy = cam.fy, cx = cam.cx, cy = cam.cy, k1 = cam.k1, k2 = cam.k2, k3 = cam.k3, p1 = cam.p1, p2 = cam.p2;
+__device__ __forceinline__ LiftGN refine_eval(const float* P, const float* U, const float* weights, int J, int C, int distort, const LiftCam& cam,
+                                              double tx, double ty, double tz) {
+  LiftGN e = lift_gn_start();
   for (int j = 0; j < J; ++j) {                                        // sums in joint order
     const double w = weights != nullptr ? (double)weights[j] : 1.0;
     if (w == 0.0) continue;                                            // a joint of weight 0 is not looked at
     const double X = (double)P[j * C] + tx, Y = (double)P[j * C + 1] + ty, Z = (double)P[j * C + 2] + tz;
     if (!(Z > 0.0)) e.deep = false;
-    const double qx = X / Z, qy = Y / Z;
-    const double xx = refine_clamp1(qx), yy = refine_clamp1(qy);
-    double px = xx, py = yy;
-    double a = 1.0, b = 0.0, c = 0.0, d = 1.0;                         // d(px, py) / d(x, y)
-    if (distort) {
-      const double r2 = xx * xx + yy * yy;
-      const double m = 1.0 + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2)) + (p1 * xx + p2 * yy);
-      px = xx * m + p1 * r2;
-      py = yy * m + p2 * r2;
-      if (JAC) {
-        const double dm = k1 + 2.0 * k2 * r2 + 3.0 * k3 * (r2 * r2);
-        const double mx = 2.0 * xx * dm + p1, my = 2.0 * yy * dm + p2;
-        a = m + xx * mx + 2.0 * p1 * xx;
-        b = xx * my + 2.0 * p1 * yy;
-        c = yy * mx + 2.0 * p2 * xx;
-        d = m + yy * my + 2.0 * p2 * yy;
-      }
-    }
-    const double du = fx * px + cx - (double)U[2 * j], dv = fy * py + cy - (double)U[2 * j + 1];
-    const double rr = du * du + dv * dv;
-    e.W += w;
-    e.E += w * sqrt(rr);
-    e.F += w * rr;
-    if (JAC) {
-      const double sx = (qx >= -1.0 && qx <= 1.0) ? 1.0 : 0.0, sy = (qy >= -1.0 && qy <= 1.0) ? 1.0 : 0.0;   // the derivative of the clamp
-      const double iz = 1.0 / Z;
-      const double xz = sx * iz, yz = sy * iz, xq = sx * (-qx / Z), yq = sy * (-qy / Z);   // dx/dt = (xz, 0, xq), dy/dt = (0, yz, yq)
-      const double j00 = fx * (a * xz), j01 = fx * (b * yz), j02 = fx * (a * xq + b * yq);
-      const double j10 = fy * (c * xz), j11 = fy * (d * yz), j12 = fy * (c * xq + d * yq);
-      e.H00 += w * (j00 * j00 + j10 * j10);
-      e.H01 += w * (j00 * j01 + j10 * j11);
-      e.H02 += w * (j00 * j02 + j10 * j12);
-      e.H11 += w * (j01 * j01 + j11 * j11);
-      e.H12 += w * (j01 * j02 + j11 * j12);
-      e.H22 += w * (j02 * j02 + j12 * j12);
-      e.g0 += w * (j00 * du + j10 * dv);
-      e.g1 += w * (j01 * du + j11 * dv);
-      e.g2 += w * (j02 * du + j12 * dv);
-    }
+    const LiftProj pr = lift_project<JAC>(X, Y, Z, U + 2 * j, cam, distort);
+    lift_gn_add<JAC>(e, w, pr, pr.c00, pr.c01, pr.c02, pr.c10, pr.c11, pr.c12);
   }
   return e;
 }
@@ -127,7 +77,7 @@ __global__ __launch_bounds__(REFINE_THREADS) void lift_place_refine_kernel(Refin
   const long g = i / A.inner;                                          // frame
   const int s = lift_seq_of(A.seq_offset, A.S, g);
   const float* cam = A.intr + (long)s * 9;
-  const RefineCam K = {cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7], cam[8]};
+  const LiftCam K = lift_cam(cam);
   const float* P = A.poses + i * J * C;
   const float* U = A.kp + g * J * 2;
   double tx = 0.0, ty = 0.0, tz = 0.0;
@@ -169,21 +119,15 @@ __global__ __launch_bounds__(REFINE_THREADS) void lift_place_refine_kernel(Refin
   unsigned char ok = 0, taken = 0;
   double err = 0.0;
   if (have) {
-    RefineEval e = A.iters > 0 ? refine_eval<true>(P, U, A.weights, J, C, A.distort, K, tx, ty, tz)
-                               : refine_eval<false>(P, U, A.weights, J, C, A.distort, K, tx, ty, tz);
+    LiftGN e = A.iters > 0 ? refine_eval<true>(P, U, A.weights, J, C, A.distort, K, tx, ty, tz)
+                           : refine_eval<false>(P, U, A.weights, J, C, A.distort, K, tx, ty, tz);
     if (e.deep && __builtin_isfinite(e.F)) {
       ok = 1;
       for (int k = 0; k < A.iters; ++k) {
-        const double c00 = e.H11 * e.H22 - e.H12 * e.H12, c01 = e.H02 * e.H12 - e.H01 * e.H22, c02 = e.H01 * e.H12 - e.H02 * e.H11;
-        const double det = e.H00 * c00 + e.H01 * c01 + e.H02 * c02, scale = e.H00 * e.H11 * e.H22;
-        if (!(__builtin_isfinite(det) && __builtin_isfinite(scale) && det > 1e-12 * scale)) break;
-        const double c11 = e.H00 * e.H22 - e.H02 * e.H02, c12 = e.H01 * e.H02 - e.H00 * e.H12, c22 = e.H00 * e.H11 - e.H01 * e.H01;
-        const double nx = tx - (c00 * e.g0 + c01 * e.g1 + c02 * e.g2) / det;       // t + d, d = -adj(H) g / det
-        const double ny = ty - (c01 * e.g0 + c11 * e.g1 + c12 * e.g2) / det;
-        const double nz = tz - (c02 * e.g0 + c12 * e.g1 + c22 * e.g2) / det;
-        if (!(__builtin_isfinite(nx) && __builtin_isfinite(ny) && __builtin_isfinite(nz))) break;
-        const RefineEval n = refine_eval<true>(P, U, A.weights, J, C, A.distort, K, nx, ny, nz);
-        if (!(n.deep && n.F <= (1.0 + 1e-6) * e.F)) break;             // (a NaN cost is not taken either)
+        double nx, ny, nz;                                             // t + d, d = -adj(H) g / det
+        if (!lift_gn_step(e, tx, ty, tz, nx, ny, nz)) break;
+        const LiftGN n = refine_eval<true>(P, U, A.weights, J, C, A.distort, K, nx, ny, nz);
+        if (!lift_gn_accept(n, e)) break;
         tx = nx; ty = ny; tz = nz; e = n; ++taken;
       }
     }

@@ -16,16 +16,15 @@
 // range (lift_seq_frames): whatever the device table holds, no frame outside 0 .. Ntot - 1 is touched.  No atomics, fixed order: identical bits on
 // every call, and a sequence's row does not depend on the other sequences of the call.
 #include "lift_common.h"
-#include "../../include/manipose_hip.h"
 
 #pragma clang fp contract(off)
+#include "lift_geom.h"                    // after the pragma: the shared code takes this file's mode
 
 namespace mp {
 
 constexpr int SCORE_MAXM = LIFT_MAXJ;
 constexpr int SCORE_MAXTF = 64;                  // frames of a tile at most (M <= 4); 256 / M otherwise: 15 at M = 17, 8 at M = 32
 constexpr int SCORE_SUMS = 7;                    // per (frame, joint) lane: e, e^2, velocity, acceleration, L, L^2, |LG - L|
-constexpr int SCORE_SWEEPS = 30;                 // Jacobi sweeps at most (quadratic convergence: 6 to 8 in practice)
 
 struct ScoreArgs {
   const float* pred;             // (Ntot, inner, M, C)
@@ -54,58 +53,6 @@ __device__ __forceinline__ void score_point(const float* x, int C, int j, double
 }
 
 __device__ __forceinline__ double score_norm3(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
-
-// dominant eigenpair of a symmetric 4x4 matrix: cyclic Jacobi sweeps until off(A) <= 2^-52 |A|_F
-__device__ __forceinline__ void score_eig4_max(double (&a)[4][4], double (&q)[4], double& lam) {
-  double v[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-#pragma unroll 1
-  for (int sweep = 0; sweep < SCORE_SWEEPS; ++sweep) {
-    double off2 = 0.0, diag2 = 0.0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      diag2 += a[p][p] * a[p][p];
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) off2 += 2.0 * (a[p][r] * a[p][r]);
-    }
-    if (off2 <= 0x1p-104 * (off2 + diag2)) break;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) {
-        // (no branch: a pair that needs no rotation, or whose theta overflows, gets t = 0, c = 1, s = 0, which leaves every entry's bits alone)
-        const double apq = a[p][r];
-        const double theta = (a[r][r] - a[p][p]) / (2.0 * apq);
-        const double t = apq != 0.0 ? copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0)) : 0.0;
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {            // A <- A J (columns p, r)
-          const double akp = a[k][p], akr = a[k][r];
-          a[k][p] = c * akp - s * akr;
-          a[k][r] = s * akp + c * akr;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {            // A <- J^T A (rows p, r)
-          const double apk = a[p][k], ark = a[r][k];
-          a[p][k] = c * apk - s * ark;
-          a[r][k] = s * apk + c * ark;
-        }
-        a[p][r] = a[r][p] = t != 0.0 ? 0.0 : a[p][r];   // (what the rotation was built for)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {            // V <- V J
-          const double vkp = v[k][p], vkr = v[k][r];
-          v[k][p] = c * vkp - s * vkr;
-          v[k][r] = s * vkp + c * vkr;
-        }
-      }
-  }
-  int best = 0;
-  lam = a[0][0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k)
-    if (a[k][k] > lam) { lam = a[k][k]; best = k; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] = best == 0 ? v[k][0] : best == 1 ? v[k][1] : best == 2 ? v[k][2] : v[k][3];
-}
 
 // sum_j |a R (y_j - my) + mx - x_j| of the similarity transform that takes the pose y (xp) onto x (xg) best; false: a centred pose is a point
 __device__ __forceinline__ bool score_align(const float* xp, const float* xg, int M, int C, double ps, double gs, bool rr, double& err) {
@@ -147,8 +94,8 @@ __device__ __forceinline__ bool score_align(const float* xp, const float* xg, in
   n[2][2] = -h[0][0] + h[1][1] - h[2][2];
   n[2][3] = n[3][2] = h[1][2] + h[2][1];
   n[3][3] = -h[0][0] - h[1][1] + h[2][2];
-  double q[4], lam;
-  score_eig4_max(n, q, lam);
+  double q[4], lam, lam2;                        // (the second eigenvalue is not used here)
+  lift_eig4(n, q, lam, lam2);
   const double qn = 1.0 / sqrt((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]));
   const double w = q[0] * qn, qx = q[1] * qn, qy = q[2] * qn, qz = q[3] * qn;
   double R[3][3];                               // x0 ~ a R y0
