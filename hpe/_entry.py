@@ -28,6 +28,7 @@ if ROOT not in sys.path:
 
 from manipose_amd.hydra_lite import Cfg, parse_value  # noqa: E402,F401
 from manipose_amd import hydra_lite  # noqa: E402
+from manipose_amd.lift_args import is_int_in, is_number  # noqa: E402  (host checks alone: no library, no device)
 
 
 def load_config(argv, extra_defaults=None):
@@ -279,6 +280,18 @@ LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj
                  "__cam_bundle_used")
 
 
+def _scale_and_cost(scale, cost=None, unit="metres"):
+    """What the lift.* options check of a scale and, where one goes with it, a cost, each a (key, value): they are numbers, the scale is > 0, the
+    cost finite and >= 0.  (That they stay at their defaults while the feature they describe is off is said where the feature is read.)"""
+    for key, v in (scale, cost) if cost else (scale,):
+        if not is_number(v):
+            raise ValueError(f"lift.{key} is a number, got {v!r}")
+    if not scale[1] > 0:
+        raise ValueError(f"lift.{scale[0]} must be > 0 ({unit}), got {scale[1]!r}")
+    if cost and not 0 <= cost[1] < float("inf"):
+        raise ValueError(f"lift.{cost[0]} must be finite and >= 0, got {cost[1]!r}")
+
+
 def lift_place_options(cfg):
     """(place, world, floor) of lift.place / lift.frame / lift.floor; ValueError for a combination that cannot run - before any model is built."""
     place, frame, floor = bool(cfg.lift.get("place", False)), str(cfg.lift.get("frame", "camera")), bool(cfg.lift.get("floor", False))
@@ -295,7 +308,7 @@ def lift_refine_options(cfg):
     """lift.place_refine as an int: the Gauss-Newton steps after lift.place's linear fit (0: none); ValueError for a value or a combination that
     cannot run - before any model is built."""
     n = cfg.lift.get("place_refine", 0)
-    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 16:
+    if not is_int_in(n, 0, 16):
         raise ValueError(f"lift.place_refine counts Gauss-Newton steps, an integer in 0..16 (0: off), got {n!r}")
     if n and not bool(cfg.lift.get("place", False)):
         raise ValueError("lift.place_refine refines the trajectory that lift.place fits: set lift.place=true")
@@ -308,11 +321,11 @@ def lift_smooth_options(cfg):
     radii = []
     for key in ("smooth_poses", "smooth_traj"):
         r = cfg.lift.get(key, 0)
-        if isinstance(r, bool) or not isinstance(r, int) or not 0 <= r <= 64:
+        if not is_int_in(r, 0, 64):
             raise ValueError(f"lift.{key} is a radius in frames, an integer in 0..64 (0: off), got {r!r}")
         radii.append(r)
     degree, taper = cfg.lift.get("smooth_degree", 2), str(cfg.lift.get("smooth_taper", "uniform"))
-    if isinstance(degree, bool) or not isinstance(degree, int) or not 0 <= degree <= 2:
+    if not is_int_in(degree, 0, 2):
         raise ValueError(f"lift.smooth_degree must be 0, 1 or 2, got {degree!r}")
     if taper not in ("uniform", "biweight"):
         raise ValueError(f"lift.smooth_taper must be uniform or biweight, got {taper!r}")
@@ -330,13 +343,7 @@ def lift_path_options(cfg):
     sigma, switch = cfg.lift.get("path_sigma", 0.02), cfg.lift.get("path_switch", 0.0)
     if agg not in ("weighted_ave", "best_score", "path"):
         raise ValueError(f"lift.agg must be weighted_ave, best_score or path, got {agg!r}")
-    for key, v in (("path_sigma", sigma), ("path_switch", switch)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise ValueError(f"lift.{key} is a number, got {v!r}")
-    if not sigma > 0:
-        raise ValueError(f"lift.path_sigma must be > 0 (metres), got {sigma!r}")
-    if not 0 <= switch < float("inf"):
-        raise ValueError(f"lift.path_switch must be finite and >= 0, got {switch!r}")
+    _scale_and_cost(("path_sigma", sigma), ("path_switch", switch))
     if agg != "path":
         if sigma != 0.02 or switch != 0.0:
             raise ValueError("lift.path_sigma / lift.path_switch describe the hypothesis path: set lift.agg=path")
@@ -379,14 +386,8 @@ def lift_fuse_options(cfg):
     sigma, weight, refine = cfg.lift.get("fuse_sigma", 0.02), cfg.lift.get("fuse_score_weight", 1.0), cfg.lift.get("fuse_refine", 3)
     if not isinstance(fuse, bool):
         raise ValueError(f"lift.fuse must be true or false, got {fuse!r}")
-    for key, v in (("fuse_sigma", sigma), ("fuse_score_weight", weight)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise ValueError(f"lift.{key} is a number, got {v!r}")
-    if not sigma > 0:
-        raise ValueError(f"lift.fuse_sigma must be > 0 (metres), got {sigma!r}")
-    if not 0 <= weight < float("inf"):
-        raise ValueError(f"lift.fuse_score_weight must be finite and >= 0, got {weight!r}")
-    if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
+    _scale_and_cost(("fuse_sigma", sigma), ("fuse_score_weight", weight))
+    if not is_int_in(refine, 0, 16):
         raise ValueError(f"lift.fuse_refine counts Gauss-Newton steps, an integer in 0..16, got {refine!r}")
     if not fuse:
         if sigma != 0.02 or weight != 1.0 or refine != 3:
@@ -415,13 +416,7 @@ def lift_fuse_path_options(cfg):
     sigma, switch = cfg.lift.get("fuse_path_sigma", 0.02), cfg.lift.get("fuse_path_switch", 0.0)
     if not isinstance(path, bool):
         raise ValueError(f"lift.fuse_path must be true or false, got {path!r}")
-    for key, v in (("fuse_path_sigma", sigma), ("fuse_path_switch", switch)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise ValueError(f"lift.{key} is a number, got {v!r}")
-    if not sigma > 0:
-        raise ValueError(f"lift.fuse_path_sigma must be > 0 (metres), got {sigma!r}")
-    if not 0 <= switch < float("inf"):
-        raise ValueError(f"lift.fuse_path_switch must be finite and >= 0, got {switch!r}")
+    _scale_and_cost(("fuse_path_sigma", sigma), ("fuse_path_switch", switch))
     if not path:
         if sigma != 0.02 or switch != 0.0:
             raise ValueError("lift.fuse_path_sigma / lift.fuse_path_switch describe the path through a take's fused views: set lift.fuse_path=true")
@@ -438,11 +433,8 @@ def lift_fuse_align_options(cfg):
     sigma, iters = cfg.lift.get("fuse_align_sigma", 0.05), cfg.lift.get("fuse_align_iters", 5)
     if cameras not in ("dataset", "estimate"):
         raise ValueError(f"lift.fuse_cameras must be dataset or estimate, got {cameras!r}")
-    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
-        raise ValueError(f"lift.fuse_align_sigma is a number, got {sigma!r}")
-    if not sigma > 0:
-        raise ValueError(f"lift.fuse_align_sigma must be > 0 (metres), got {sigma!r}")
-    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= 8:
+    _scale_and_cost(("fuse_align_sigma", sigma))
+    if not is_int_in(iters, 0, 8):
         raise ValueError(f"lift.fuse_align_iters counts re-weightings, an integer in 0..8, got {iters!r}")
     if cameras != "estimate":
         if sigma != 0.05 or iters != 5:
@@ -457,12 +449,9 @@ def lift_fuse_bundle_options(cfg):
     """(steps, sigma) of lift.fuse_bundle / lift.fuse_bundle_sigma; ValueError for a value or a combination that cannot run - before any model is
     built."""
     steps, sigma = cfg.lift.get("fuse_bundle", 0), cfg.lift.get("fuse_bundle_sigma", 0.05)
-    if isinstance(steps, bool) or not isinstance(steps, int) or not 0 <= steps <= 8:
+    if not is_int_in(steps, 0, 8):
         raise ValueError(f"lift.fuse_bundle counts Gauss-Newton steps, an integer in 0..8 (0: off), got {steps!r}")
-    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
-        raise ValueError(f"lift.fuse_bundle_sigma is a number, got {sigma!r}")
-    if not sigma > 0:
-        raise ValueError(f"lift.fuse_bundle_sigma must be > 0 (normalised screen units), got {sigma!r}")
+    _scale_and_cost(("fuse_bundle_sigma", sigma), unit="normalised screen units")
     if steps == 0:
         if sigma != 0.05:
             raise ValueError("lift.fuse_bundle_sigma describes the bundle adjustment of a take's estimated cameras: set lift.fuse_bundle=N, N steps")

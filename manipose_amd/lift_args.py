@@ -1,0 +1,123 @@
+"""The argument checks of the lifting bindings (lift_ops.py, lift_views.py, lifting.py, hpe/_entry.py), and nothing else: host code that looks
+at types, shapes and dtypes.  Nothing here loads the library, allocates or reads a device tensor's contents.  Predicates (``is_*``) return a bool,
+and their callers word the error; everything else raises - a ValueError, but for ``need_device``, the RuntimeError that refuses CPU tensors ("no
+CPU fallback") and that an entry point raises after its ValueErrors.  A new entry point composes these and does not write its own."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+
+def is_number(v):
+    """an int or a float, numpy's included; a bool is not a number"""
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def is_int_in(v, lowest, highest):
+    """an integer (not a bool) in lowest..highest"""
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and lowest <= int(v) <= highest
+
+
+def sigma_pair(sigma, other, names):
+    """the rule of a (scale, cost) pair, under the callers' names: both numbers, sigma > 0 as the kernel takes it (a float32; +inf is allowed),
+    the other finite and >= 0"""
+    for v in (sigma, other):
+        if not is_number(v):
+            raise ValueError(f"{names[0]} and {names[1]} are numbers, got {v!r}")
+    if not float(np.float32(sigma)) > 0:
+        raise ValueError(f"{names[0]} must be > 0 (inf: the step costs nothing), got {sigma!r}")
+    if not 0 <= float(other) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"{names[1]} must be finite and >= 0, got {other!r}")
+
+
+def _got(t):
+    return (tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__
+
+
+def mask(m, shape, name, bare=False):
+    """m is None or a uint8 tensor of ``shape``; ``bare``: what is no tensor at all is refused without saying what it is"""
+    if m is None:
+        return
+    if bare and not torch.is_tensor(m):
+        raise ValueError(f"{name} must be a uint8 tensor of shape {tuple(shape)}")
+    if not torch.is_tensor(m) or tuple(m.shape) != tuple(shape) or m.dtype != torch.uint8:
+        raise ValueError(f"{name} must be a uint8 tensor of shape {tuple(shape)}, got {_got(m)}")
+
+
+def f32(t, shape, name, contiguous=False, plain=False):
+    """t is a float32 tensor of ``shape``, ``contiguous`` where the kernel reads it as it is.  ``plain``: t is known to be a tensor, and the
+    message is the short one"""
+    shape = tuple(shape)
+    if torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == torch.float32 and (t.is_contiguous() or not contiguous):
+        return
+    if plain:
+        raise ValueError(f"{name} must be float32 {shape}, got {tuple(t.shape)} {t.dtype}")
+    raise ValueError(f"{name} must be a {'contiguous ' if contiguous else ''}float32 tensor {shape}, got {_got(t)}")
+
+
+def _count(name, n, noun, lowest, highest):
+    if not lowest <= n <= highest:
+        raise ValueError(f"{name} have {n} {noun}: {lowest}..{highest} expected")
+
+
+def poses4(poses):
+    """poses (Ntot, J, 3) or (Ntot, inner, J, 3 | 4), contiguous float32, 2..32 joints -> its 4-D view"""
+    p4 = poses.unsqueeze(1) if poses.dim() == 3 else poses
+    if p4.dim() != 4 or p4.shape[3] not in (3, 4) or (poses.dim() == 3 and poses.shape[2] != 3) or poses.dtype != torch.float32 \
+            or not poses.is_contiguous():
+        raise ValueError(f"poses must be contiguous float32 (Ntot, J, 3) or (Ntot, inner, J, 3 | 4), got {tuple(poses.shape)} {poses.dtype}")
+    _count("poses", int(p4.shape[2]), "joints", 2, 32)
+    return p4
+
+
+def traj3(traj):
+    if traj.dim() not in (2, 3) or traj.shape[-1] != 3 or traj.dtype != torch.float32 or not traj.is_contiguous():
+        raise ValueError(f"traj must be contiguous float32 (Ntot, 3) or (Ntot, inner, 3), got {tuple(traj.shape)} {traj.dtype}")
+
+
+def hyps4(hyps, maxk):
+    if hyps.dim() != 4 or hyps.shape[3] != 4 or hyps.dtype != torch.float32 or not hyps.is_contiguous():
+        raise ValueError(f"hyps must be contiguous float32 (Ntot, K, J, 4), got {tuple(hyps.shape)} {hyps.dtype}")
+    _count("hyps", int(hyps.shape[1]), "hypotheses", 1, maxk)
+    _count("hyps", int(hyps.shape[2]), "joints", 2, 32)
+
+
+def hyps5(hyps, maxv, maxk):
+    if hyps.dim() != 5 or hyps.shape[4] not in (3, 4) or hyps.dtype != torch.float32 or not hyps.is_contiguous():
+        raise ValueError(f"hyps must be contiguous float32 (V, Ftot, K, J, 3 | 4), got {tuple(hyps.shape)} {hyps.dtype}")
+    _count("hyps", int(hyps.shape[0]), "views", 1, maxv)
+    _count("hyps", int(hyps.shape[2]), "hypotheses", 1, maxk)
+    _count("hyps", int(hyps.shape[3]), "joints", 2, 32)
+
+
+def view_poses4(poses, maxv):
+    if poses.dim() != 4 or poses.shape[3] not in (3, 4) or poses.dtype != torch.float32 or not poses.is_contiguous():
+        raise ValueError(f"poses must be contiguous float32 (V, Ftot, J, 3 | 4), got {tuple(poses.shape)} {poses.dtype}")
+    _count("poses", int(poses.shape[0]), "views", 1, maxv)
+    _count("poses", int(poses.shape[2]), "joints", 2, 32)
+
+
+def take_pose_keypoints(pose, keypoints_2d, maxv, root=None):
+    """pose (Ftot, J, 3) contiguous float32 with 2..32 joints, root (Ftot, 3) float32 if there is one, and keypoints_2d (V <= maxv, Ftot, J, 2)
+    float32, all tensors -> (V, Ftot, J)"""
+    if pose.dim() != 3 or pose.shape[2] != 3 or pose.dtype != torch.float32 or not pose.is_contiguous() or not 2 <= int(pose.shape[1]) <= 32:
+        raise ValueError(f"pose must be contiguous float32 (Ftot, J, 3) with 2..32 joints, got {tuple(pose.shape)} {pose.dtype}")
+    ftot, J, kp = int(pose.shape[0]), int(pose.shape[1]), keypoints_2d
+    if root is not None:
+        f32(root, (ftot, 3), "root", plain=True)
+    if kp.dim() != 4 or not 1 <= int(kp.shape[0]) <= maxv or tuple(kp.shape[1:]) != (ftot, J, 2) or kp.dtype != torch.float32:
+        raise ValueError(f"keypoints_2d must be float32 (V <= {maxv}, {ftot}, {J}, 2), got {tuple(kp.shape)} {kp.dtype}")
+    return int(kp.shape[0]), ftot, J
+
+
+def take_count(take_offset):
+    """the G of a (G + 1) table of first frames, host or device, read from its size alone (None: one take)"""
+    if take_offset is None:
+        return 1
+    return max(int(take_offset.numel() if torch.is_tensor(take_offset) else np.asarray(take_offset).size) - 1, 1)
+
+
+def need_device(who, *tensors, optional=()):
+    """the refusal of CPU inputs, after every ValueError: ``tensors`` are device tensors, and so is what is not None of ``optional``"""
+    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors) or not all(t.is_cuda for t in optional if t is not None):
+        raise RuntimeError(f"manipose_amd: {who} takes device tensors; there is no CPU fallback")

@@ -1,0 +1,559 @@
+"""The per-sequence operators of lifting: what one kernel of the library does to the frames of sequences laid end to end, as a public function
+on device tensors (``project_rigid``, ``pose_rotations``, ``smooth_poses`` ...) and as the private launcher behind it (``_rigid``, ``_rotations``,
+``_smooth`` ...), which ``lift_sequences``' stages (lifting.py) call on their own buffers.  A public function checks its arguments with lift_args'
+vocabulary - the ValueErrors first, then ``need_device``'s refusal of CPU tensors (``_poses4``, for project_rigid, place_poses and to_world, refuses
+before it looks at the shape, as those three always have) - uploads its tables and calls its launcher; a launcher allocates its outputs, and where
+there is a frame goes through ``_launch``, the one way into the library.
+
+Rigid lifting (``rigid=True``, off by default): the merged poses of a sequence do not share their bone lengths (averaged hypotheses, blended
+windows, one length prediction per window), so after the merge every sequence gets ONE table of J - 1 bone lengths - the model's own
+(``"model"``), the mean lengths of the merged poses (``"measured"``, ``mp_bone_length_means``) or the caller's - and ``mp_lift_rigid``
+re-assembles every emitted pose and hypothesis along its own bone directions with them (include/manipose_hip.h has the definition).
+
+Placing (``place`` / ``frame="world"`` / ``floor``, all off by default): the merged poses are root-relative and in the camera's frame.  With
+the sequences' cameras (``camera_table``) ``mp_lift_place`` fits, per pose and per hypothesis, the root translation whose pinhole projection meets
+the 2-D keypoints the pose was lifted from, and reports the reprojection error under the full H36M camera model; ``mp_lift_world`` rotates
+everything into the world frame (the reference's ``camera_to_world``, hpe/viz.py:93-98) and, with ``floor``, puts the sequence on z = 0.
+
+Refining the placement (``place_refine``, Gauss-Newton steps, 0 = off, the default): the fit above uses the pinhole part of the camera only, because
+that fit is linear in the translation, while the H36M cameras distort (k1 ~ -0.2, k2 ~ 0.25): on noise-free keypoints made with the full model the
+linear fit misses the true root by up to 0.17 m, almost all of it depth.  ``mp_lift_place_refine`` starts from the linear fit and takes up to
+``place_refine`` undamped Gauss-Newton steps on the squared reprojection error of the FULL projection (include/manipose_hip.h has the rule); three
+steps recover the translation of that construction to the float32 rounding of its keypoints.  The same entry point with zero steps and a given
+trajectory is ``reproject_poses``.  What this does to accuracy on real H36M data has not been measured (no dataset here).
+
+Joint rotations (``rotations``, off by default): every stage here emits joint POSITIONS, while the model decodes (6-D rotation per joint, segment
+lengths) by forward kinematics.  ``mp_lift_rotations`` is the inverse on the poses as they are emitted: per pose the root orientation from the
+frame the hip and the spine span, per joint the shortest-arc (twist-free) rotation that turns the bone's T-pose direction into its measured one
+(include/manipose_hip.h has the rule), as unit quaternions (w, x, y, z) that are sign-continuous along every sequence, and as the 6-D form the
+decoder takes.  ``pose_rotations`` is the public form.  No accuracy of these rotations on real data has been measured (no dataset here).
+
+Smoothing in time (``smooth_poses`` / ``smooth_traj``, radii, 0 = off, the default): every stage above treats every frame on its own.
+``mp_lift_smooth`` fits, per frame and coordinate, a polynomial of degree ``smooth_degree`` to the frames within the radius that belong to the same
+sequence and are valid (Savitzky-Golay with validity weights; include/manipose_hip.h has the rule) and stores its value at the frame.  The merged
+poses and the hypotheses are smoothed BEFORE the rigid stage (bone lengths stay constant, and placing fits the trajectory to the poses that are
+emitted); the fitted root trajectories AFTER ``mp_lift_place`` and before ``mp_lift_world``, with the fit's ``ok`` as validity, so a frame whose fit
+was degenerate is filled from its neighbours.  Whether this lowers MPJPE / MPJVE on real data has not been measured (no dataset here).
+
+One hypothesis path (``agg="path"``): ``weighted_ave`` averages K poses that share their bone lengths but differ in rotation (the result lies off
+the manifold the model stays on), and ``best_score`` keeps a real hypothesis in every frame but chooses each frame on its own, so the sequence jumps
+from head to head whenever two scores cross.  ``mp_lift_path`` emits exactly one of the model's own hypotheses per frame, chosen jointly over the
+whole sequence: the most probable path of a hidden Markov model whose states are the hypotheses (unary cost -log score, transition cost the mean
+squared joint step over 2 sigma^2 plus a cost per switch), found with the Viterbi algorithm (include/manipose_hip.h has the rule).  It runs right
+after the merge, on the hypotheses of the un-mirrored pass, and every later stage starts from the selected poses.  Whether it lowers MPJPE / MPJVE
+on real data has not been measured (no dataset here), and the default sigma is not tuned.
+
+Scoring (``targets`` / ``return_score``, off by default): ``mp_lift_score`` holds what the stages emit against the dataset's 3-D sequences, per
+sequence and on the device - MPJPE, P-MPJPE, velocity and acceleration errors, per-joint errors, bone-length statistics, and the trajectory's error
+with ``place`` (include/manipose_hip.h has the rule; ``score_poses`` / ``score_traj`` are the stand-alone forms).  It is the instrument for the
+sentences above that say "has not been measured"; no number is claimed here.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import lift_args
+
+TAPER = {"uniform": 0, "biweight": 1}
+SMOOTH_MAXR = 64             # MP_LIFT_SMOOTH_MAXR of include/manipose_hip.h
+PATH_MAXK = 8                # hypotheses mp_lift_path takes
+PATH_SIGMA, PATH_SWITCH = 0.02, 0.0      # defaults of agg="path": the step's standard deviation in metres (not tuned), the cost of a switch
+
+
+def _launch(dev, name, *call):
+    """The one way into the library: entry point ``name`` on ``call`` and, last, the current stream of ``dev``; its status is checked under its name.
+    (Every launcher keeps its leading ``lib`` argument, though only those that size a scratch buffer read it: the tests' and the bench's call
+    lines stay as they are.)"""
+    with torch.cuda.device(dev):
+        _lib.check(getattr(_lib.load(), name)(*call, _lib.stream_ptr()), name)
+
+
+def _skeleton_of(model=None, skeleton=None):
+    """``skeleton`` if given, else the model's own, else the 17-joint H36M tree (MixSTE carries none)"""
+    from .data import h36m_skeleton
+    if skeleton is not None:
+        return skeleton
+    return model.decoder.skeleton if model is not None and hasattr(model, "decoder") else h36m_skeleton()
+
+
+def _parents_c(sk, J):
+    par = [int(p) for p in sk.parents]
+    if par[0] != -1 or any(not 0 <= p < j for j, p in enumerate(par) if j):
+        raise ValueError("rigid lifting: joint 0 must be the root and parents must precede their children")
+    if len(par) != J:
+        raise ValueError(f"{J} joints, but the skeleton has {len(par)}")
+    return (C.c_int32 * J)(*par)
+
+
+def _host_f32(a, shape, what, row=None, nonneg=False):
+    """A per-sequence table (tensor or array) as float32 numpy of ``shape``, after its dtype, shape and finiteness were checked on the host; a
+    copy: the caller's table is never aliased.  A table of shape ``row`` is one row for every sequence; ``nonneg`` also refuses negative entries."""
+    h = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    got = h.shape
+    if row is not None and h.shape == row:
+        h = np.broadcast_to(h, shape)
+    if h.dtype.kind not in "fiu" or h.shape != shape:
+        raise ValueError(f"{what} must be {shape}{'' if row is None else f' or {row}'} numbers, got shape {tuple(got)} {h.dtype}")
+    h = np.array(h, dtype=np.float32, order="C")
+    if not np.isfinite(h).all() or (nonneg and (h < 0).any()):
+        raise ValueError(f"{what} must be finite{' and non-negative' if nonneg else ''}")
+    return h
+
+
+def _device_f32(a, dev, shape, what, row=None, nonneg=False):
+    return torch.from_numpy(_host_f32(a, shape, what, row, nonneg)).to(dev)
+
+
+def _device_i64(a, dev):
+    if torch.is_tensor(a):
+        return a.to(dev, torch.int64).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+
+
+def _seq_table(seq_offset, ntot, dev):
+    d_off = _device_i64(seq_offset if seq_offset is not None else [0, ntot], dev)
+    if d_off.dim() != 1 or d_off.numel() < 2:
+        raise ValueError("seq_offset must hold S + 1 >= 2 frame numbers")
+    return d_off, int(d_off.numel()) - 1
+
+
+def _poses4(poses, who):
+    """the 4-D view of device poses; for the functions that refuse a CPU tensor before they look at its shape"""
+    lift_args.need_device(who, poses)
+    return lift_args.poses4(poses)
+
+
+def _rigid(lib, poses4, d_off, S, d_lengths, parents):
+    ntot, inner, J, ch = (int(v) for v in poses4.shape)
+    _launch(poses4.device, "mp_lift_rigid", _lib.ptr(poses4), ntot, inner, J, ch, _lib.ptr(d_off), S, _lib.ptr(d_lengths), parents)
+
+
+def bone_length_means(poses, seq_offset=None, real_frames=None, skeleton=None):
+    """``mp_bone_length_means``: (S, J - 1) mean bone lengths per sequence of the device tensor poses (Ntot, J, 3); ``seq_offset`` (S + 1) HOST
+    table or device int64 tensor (default: one sequence); ``real_frames`` (S) or None: only the first that many frames of a sequence count."""
+    if poses.dim() != 3 or poses.shape[2] != 3 or poses.dtype != torch.float32:
+        raise ValueError(f"poses must be float32 (Ntot, J, 3), got {tuple(poses.shape)} {poses.dtype}")
+    dev, J = poses.device, int(poses.shape[1])
+    parents = _parents_c(_skeleton_of(skeleton=skeleton), J)
+    d_off, S = _seq_table(seq_offset, int(poses.shape[0]), dev)
+    d_real = _device_i64(real_frames, dev) if real_frames is not None else None
+    if d_real is not None and int(d_real.numel()) != S:
+        raise ValueError(f"real_frames must have {S} entries")
+    out = torch.empty(S, J - 1, dtype=torch.float32, device=dev)
+    _launch(dev, "mp_bone_length_means", _lib.ptr(poses), int(poses.shape[0]), J, _lib.ptr(d_off), _lib.ptr(d_real), S, parents, _lib.ptr(out))
+    return out
+
+
+def project_rigid(poses, lengths, seq_offset=None, skeleton=None):
+    """``mp_lift_rigid`` on a device tensor, IN PLACE (and returned): poses (Ntot, J, 3), or (Ntot, inner, J, C) with C = 3 or 4 (channel 3, a
+    hypothesis' score, is left alone).  Every pose keeps its root and its bone directions and gets the bone lengths of its sequence:
+    ``lengths`` (S, J - 1) or (J - 1,), tensor or array, in the unit of the poses; ``seq_offset`` (S + 1): first frame of every sequence, HOST
+    table or device int64 tensor (default: all frames are one sequence).  A bone of length zero takes its parent bone's direction, (0, 0, 1)
+    under the root.  ``skeleton``: default the 17-joint H36M tree."""
+    p4 = _poses4(poses, "project_rigid")
+    ntot, J = int(p4.shape[0]), int(p4.shape[2])
+    parents = _parents_c(_skeleton_of(skeleton=skeleton), J)
+    d_off, S = _seq_table(seq_offset, ntot, poses.device)
+    table = _device_f32(lengths, poses.device, (S, J - 1), "lengths", row=(J - 1,), nonneg=True)
+    if ntot > 0:
+        _rigid(_lib.load(), p4, d_off, S, table, parents)
+    return poses
+
+
+ROT_CONTINUOUS = 1           # MP_LIFT_ROT_CONTINUOUS of include/manipose_hip.h
+
+
+def _rest_c(sk, J):
+    """The (J, 3) T-pose directions of a skeleton's ``t_pose_operators`` (joint -> direction of the bone parent -> joint; the root has none) as a C
+    float table, row 0 zero; ValueError for a missing, non-finite or zero direction (the entry point normalises them)"""
+    ops = getattr(sk, "t_pose_operators", None)
+    if ops is None:
+        raise ValueError("joint rotations need the skeleton's t_pose_operators: the T-pose direction of every bone")
+    rest = np.zeros((J, 3), dtype=np.float32)
+    for j in range(1, J):
+        try:
+            v = ops[j]
+        except (KeyError, IndexError):
+            raise ValueError(f"t_pose_operators has no direction for joint {j}") from None
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        if v.shape != (3,) or v.dtype.kind not in "fiu":
+            raise ValueError(f"t_pose_operators[{j}] must be 3 numbers, got shape {tuple(v.shape)} {v.dtype}")
+        with np.errstate(over="ignore"):
+            v = v.astype(np.float32)
+        if not np.isfinite(v).all() or not (v != 0).any():
+            raise ValueError(f"t_pose_operators[{j}] = {v.tolist()}: a T-pose direction must be finite and not zero")
+        rest[j] = v
+    return (C.c_float * (3 * J))(*rest.ravel().tolist())
+
+
+def _rotations(lib, p4, d_off, S, parents, rest, continuous=True, want_rot6d=False):
+    """``mp_lift_rotations`` on p4 (Ntot, inner, J, C): (quat (Ntot, inner, J, 4), ok (Ntot, inner) uint8, rot6d (Ntot, inner, J, 6) or None), new
+    tensors; p4 is read only"""
+    ntot, inner, J, ch = (int(v) for v in p4.shape)
+    dev = p4.device
+    quat = torch.empty(ntot, inner, J, 4, dtype=torch.float32, device=dev)
+    ok = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
+    rot6d = torch.empty(ntot, inner, J, 6, dtype=torch.float32, device=dev) if want_rot6d else None
+    if ntot > 0:
+        _launch(dev, "mp_lift_rotations", _lib.ptr(p4), ntot, inner, J, ch, _lib.ptr(d_off), S, parents, rest, ROT_CONTINUOUS if continuous else 0,
+                _lib.ptr(quat), _lib.ptr(rot6d), _lib.ptr(ok))
+    return quat, ok, rot6d
+
+
+def pose_rotations(poses, seq_offset=None, skeleton=None, continuous=True, return_rot6d=False):
+    """``mp_lift_rotations`` on a device tensor, OUT of place: the joint rotations that, with each pose's own bone lengths and root position, ARE the
+    pose under the decoder's forward kinematics (Rw[0] = R[0], Rw[j] = Rw[parent] R[j], p[j] = p[parent] + Rw[j] (len_j rest_j)).  ``poses``
+    (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32 (channel 3, a hypothesis' score, is not read); ``skeleton``: anything with ``parents`` and
+    ``t_pose_operators`` (default, for J = 17 only: the H36M tree); ``seq_offset`` (S + 1): first frame of every sequence, HOST table or device
+    int64 tensor (default: one sequence), used by ``continuous`` alone.  Returns ``(quat, ok)`` and with ``return_rot6d`` also ``rot6d``: quat
+    (Ntot[, inner], J, 4) float32 unit quaternions (w, x, y, z), quat[:, 0] the root's orientation (the frame of the bones to its first child and to
+    its first child in another direction - H36M: right hip and spine - against the T-pose's), quat[:, j] the shortest-arc rotation of bone j in
+    its parent's frame: the twist about a bone is zero by construction, a convention and not a measurement.  ok (Ntot[, inner]) uint8: 0 where a
+    bone has no direction (length 0, a non-finite coordinate: identity; any non-finite coordinate makes the whole pose identities), lies exactly
+    opposite its T-pose direction (a half turn about a fixed axis) or the root's two bones are collinear.  rot6d (Ntot[, inner], J, 6): columns 0
+    then 1 of each quaternion's matrix, what ``torch.ops.manipose.fk_decode`` / ``mp_fk_decode_fwd`` take.  A quaternion's sign is the one that
+    makes its first non-zero component positive; with ``continuous`` it is then flipped along every (sequence, inner index, joint) track wherever
+    that keeps consecutive frames in one hemisphere (dot >= 0), so the track can be filtered or interpolated; rot6d does not depend on the sign.
+    fp64 inside, identical bits on every call (include/manipose_hip.h has the rule)."""
+    if torch.is_tensor(poses):
+        lift_args.poses4(poses)
+        J = int(poses.shape[-2])
+        if skeleton is None and J != 17:
+            raise ValueError(f"poses have {J} joints: the default skeleton is the 17-joint H36M tree; pass a skeleton with parents and t_pose_operators")
+        sk = _skeleton_of(skeleton=skeleton)
+        parents, rest = _parents_c(sk, J), _rest_c(sk, J)
+    p4 = _poses4(poses, "pose_rotations")
+    d_off, S = _seq_table(seq_offset, int(p4.shape[0]), poses.device)
+    quat, ok, rot6d = _rotations(_lib.load(), p4, d_off, S, parents, rest, bool(continuous), bool(return_rot6d))
+    res = (quat, ok, rot6d) if return_rot6d else (quat, ok)
+    return tuple(r[:, 0] for r in res) if poses.dim() == 3 else res
+
+
+def _smooth_options(radius, degree, taper):
+    if not lift_args.is_int_in(radius, 1, SMOOTH_MAXR):
+        raise ValueError(f"radius must be an integer in 1..{SMOOTH_MAXR}, got {radius!r}")
+    if not lift_args.is_int_in(degree, 0, 2):
+        raise ValueError(f"degree must be 0, 1 or 2, got {degree!r}")
+    if taper not in TAPER:
+        raise ValueError(f"taper must be one of {sorted(TAPER)}, got {taper!r}")
+
+
+def _smooth(lib, x4, valid, d_off, S, radius, degree, taper, want_filled=False):
+    """``mp_lift_smooth`` on x4 (Ntot, inner, M, C) with valid (Ntot, inner) uint8 or None: (a new tensor, filled (Ntot, inner) uint8 or None)"""
+    ntot, inner, M, ch = (int(v) for v in x4.shape)
+    out = torch.empty_like(x4)
+    filled = torch.empty(ntot, inner, dtype=torch.uint8, device=x4.device) if want_filled else None
+    if ntot > 0:
+        _launch(x4.device, "mp_lift_smooth", _lib.ptr(x4), _lib.ptr(out), ntot, inner, M, ch, _lib.ptr(valid), _lib.ptr(d_off), S, int(radius), int(degree),
+                TAPER[taper], _lib.ptr(filled))
+    return out, filled
+
+
+def smooth_poses(poses, seq_offset=None, radius=4, degree=2, taper="uniform"):
+    """``mp_lift_smooth`` on a device tensor, OUT of place: poses (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32 (channel 3, a hypothesis' score,
+    is copied) -> a new tensor of the same shape in which every coordinate of frame g is p(0) of the polynomial p of degree ``degree`` (0..2)
+    fitted by least squares to the frames g - radius .. g + radius of the same sequence (radius 1..64; at the ends of a sequence the window is
+    shorter, never padded, and the degree falls to the number of frames - 1), in the variable (frame - g) / radius.  ``taper``: "uniform"
+    (all taps weigh 1: the classical Savitzky-Golay filter) or "biweight" ((1 - (tau / (radius + 1))^2)^2).  ``seq_offset`` (S + 1): first frame
+    of every sequence, HOST table or device int64 tensor (default: one sequence).  Every frame counts as valid; fp64 inside, identical bits on
+    every call."""
+    _smooth_options(radius, degree, taper)
+    if torch.is_tensor(poses):
+        lift_args.poses4(poses)                          # (the ValueErrors come before the refusal of a CPU tensor)
+    p4 = _poses4(poses, "smooth_poses")
+    d_off, S = _seq_table(seq_offset, int(p4.shape[0]), poses.device)
+    return _smooth(_lib.load(), p4, None, d_off, S, radius, degree, taper)[0].view(poses.shape)
+
+
+def smooth_traj(traj, ok=None, seq_offset=None, radius=4, degree=2, taper="uniform"):
+    """``mp_lift_smooth`` on root trajectories, OUT of place: traj (Ntot, 3) or (Ntot, inner, 3) float32 device tensor as ``place_poses`` returns it,
+    ``ok`` uint8 of shape (Ntot[, inner]) or None (every frame is valid): a frame with ok = 0 does not enter any fit, and gets the value the fit
+    through its valid neighbours has at it - constant where valid frames lie on one side only.  Returns ``(smoothed, filled)``: filled uint8
+    (Ntot[, inner]) is 0 where no frame within the radius in the same sequence is valid; such a frame keeps its input bits.  The other arguments
+    as for ``smooth_poses``."""
+    _smooth_options(radius, degree, taper)
+    if torch.is_tensor(traj):
+        lift_args.traj3(traj)
+        lift_args.mask(ok, traj.shape[:-1], "ok")
+    lift_args.need_device("smooth_traj", traj, optional=(ok,))
+    ntot = int(traj.shape[0])
+    d_off, S = _seq_table(seq_offset, ntot, traj.device)
+    out, filled = _smooth(_lib.load(), traj.view(ntot, -1, 1, 3), None if ok is None else ok.contiguous().view(ntot, -1), d_off, S, radius, degree,
+                          taper, want_filled=True)
+    return out.view(traj.shape), filled.view(traj.shape[:-1])
+
+
+def _path(lib, hyps, d_off, S, sigma, switch_cost):
+    """``mp_lift_path`` on hyps (Ntot, K, J, 4): (poses (Ntot, J, 3), path (Ntot,) uint8, cost (S,) float64), new tensors"""
+    ntot, K, J, _ = (int(v) for v in hyps.shape)
+    dev = hyps.device
+    out = torch.empty(ntot, J, 3, dtype=torch.float32, device=dev)
+    path = torch.empty(ntot, dtype=torch.uint8, device=dev)
+    cost = torch.zeros(S, dtype=torch.float64, device=dev)
+    if ntot > 0:
+        n = int(lib.mp_lift_path_scratch_floats(ntot, K))
+        scratch = torch.empty(n, dtype=torch.float32, device=dev)
+        _launch(dev, "mp_lift_path", _lib.ptr(hyps), ntot, K, J, _lib.ptr(d_off), S, float(sigma), float(switch_cost), _lib.ptr(path), _lib.ptr(out),
+                _lib.ptr(cost), _lib.ptr(scratch), n)
+    return out, path, cost
+
+
+def select_path(hyps, seq_offset=None, sigma=PATH_SIGMA, switch_cost=PATH_SWITCH):
+    """``mp_lift_path`` on a device tensor: hyps (Ntot, K, J, 4) float32 as ``lift_sequences(return_hyps=True)`` returns them (xyz, and the
+    hypothesis' score in channel 3), K in 1..8 -> ``(poses (Ntot, J, 3), path (Ntot,) uint8, cost (S,) float64)``, new device tensors: per frame
+    exactly one hypothesis, poses[g] = hyps[g, path[g], :, :3] bit for bit, the path being the cheapest one through the sequence under the unary cost
+    -log(score) (a score that is not > 1e-12 counts as 1e-12) and, from hypothesis a of a frame to hypothesis b of the next, the transition cost
+    mean_j |x_b[j] - x_a[j]|^2 / (2 sigma^2) + (switch_cost if a != b): the maximum a posteriori path of that hidden Markov model, by the Viterbi
+    algorithm in fp64, ties to the lowest index.  ``sigma`` > 0 in the unit of the hypotheses (inf: steps cost nothing, and with switch_cost = 0 the
+    path is the best score of every frame); ``switch_cost`` >= 0.  ``seq_offset`` (S + 1): first frame of every sequence, HOST table or device int64
+    tensor (default: one sequence); a path never crosses a sequence boundary, and a frame that no sequence of the table holds is left unwritten.  ``cost``: the cost of each sequence's path.  hyps is not modified;
+    identical bits on every call."""
+    lift_args.sigma_pair(sigma, switch_cost, ("sigma", "switch_cost"))
+    if torch.is_tensor(hyps):
+        lift_args.hyps4(hyps, PATH_MAXK)                 # (the ValueErrors come before the refusal of a CPU tensor)
+    lift_args.need_device("select_path", hyps)
+    d_off, S = _seq_table(seq_offset, int(hyps.shape[0]), hyps.device)
+    return _path(_lib.load(), hyps, d_off, S, sigma, switch_cost)
+
+
+SCORE_SHARES = 32            # MP_LIFT_SCORE_SHARES of include/manipose_hip.h: partial rows per (sequence, inner) in mp_lift_score's scratch
+SCORE_ROOT_RELATIVE, SCORE_PROCRUSTES = 1, 2     # mp_lift_score's flags
+# What score_poses returns: device float64 tensors of shape (S,), or (S, inner) for 4-D poses; per_joint (.., M); bone_* (.., M - 1) or None without a
+# skeleton; rows: mp_lift_score's raw sums (.., 9 + M + 3 (M - 1)); frame_err (Ntot[, inner]) float32 with return_frames, else None
+PoseScore = namedtuple("PoseScore", "frames mpjpe rmse mpjve accel p_mpjpe per_joint bone_mean bone_std bone_err rows frame_err")
+# What score_traj returns: (S,) or (S, inner) device float64 tensors
+TrajScore = namedtuple("TrajScore", "frames ate rmse velocity accel")
+
+
+def _score(lib, p4, gt, valid, d_off, S, parents, pred_scale, gt_scale, flags, want_frames=False):
+    """``mp_lift_score`` on p4 (Ntot, inner, M, C) against gt (Ntot, M, 3), valid (Ntot, inner) uint8 or None: (rows (S, inner, R) float64, frame_err
+    (Ntot, inner) float32 or None), new tensors.  A frame that no sequence holds keeps frame_err = -1."""
+    ntot, inner, M, ch = (int(v) for v in p4.shape)
+    dev = p4.device
+    rows = torch.zeros(S, inner, 6 + 4 * M, dtype=torch.float64, device=dev)
+    frame_err = torch.full((ntot, inner), -1.0, dtype=torch.float32, device=dev) if want_frames else None
+    if ntot > 0:
+        n = int(lib.mp_lift_score_scratch_doubles(S, inner, M))
+        scratch = torch.empty(n, dtype=torch.float64, device=dev)
+        _launch(dev, "mp_lift_score", _lib.ptr(p4), ntot, inner, M, ch, _lib.ptr(gt), _lib.ptr(valid), _lib.ptr(d_off), S, parents, float(pred_scale),
+                float(gt_scale), int(flags), _lib.ptr(rows), _lib.ptr(frame_err), _lib.ptr(scratch), n)
+    return rows, frame_err
+
+
+def _ratio(num, den):
+    """num / den in float64, NaN where the count den is 0"""
+    return torch.where(den > 0, num / den.clamp(min=1.0), torch.full_like(num, float("nan")))
+
+
+def _pose_record(rows, M, procrustes, bones, frame_err=None):
+    """mp_lift_score's rows (.., R) as a PoseScore"""
+    n, nm = rows[..., 0], rows[..., 0] * M
+    bone_mean = bone_std = bone_err = None
+    if bones:
+        b = rows[..., 9 + M:].reshape(*rows.shape[:-1], M - 1, 3)
+        cnt = n.unsqueeze(-1).expand(b.shape[:-1])
+        bone_mean, bone_err = _ratio(b[..., 0], cnt), _ratio(b[..., 2], cnt)
+        bone_std = torch.sqrt((_ratio(b[..., 1], cnt) - bone_mean * bone_mean).clamp(min=0.0))      # (NaN stays NaN under clamp)
+    p = _ratio(rows[..., 7], (n - rows[..., 8]) * M) if procrustes else torch.full_like(n, float("nan"))
+    return PoseScore(n, _ratio(rows[..., 1], nm), torch.sqrt(_ratio(rows[..., 2], nm)), _ratio(rows[..., 4], rows[..., 3] * M),
+                     _ratio(rows[..., 6], rows[..., 5] * M), p, _ratio(rows[..., 9:9 + M], n.unsqueeze(-1).expand(*n.shape, M)), bone_mean, bone_std,
+                     bone_err, rows, frame_err)
+
+
+def score_poses(poses, target, seq_offset=None, valid=None, skeleton=None, root_relative=False, procrustes=True, pose_scale=1.0, target_scale=1.0,
+                return_frames=False):
+    """``mp_lift_score`` on device tensors: lifted poses against ground truth, per sequence.  ``poses`` (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32
+    (channel 3, a hypothesis' score, is not read); ``target`` (Ntot, J, 3) float32, shared by the ``inner`` poses of a frame; ``seq_offset`` (S + 1):
+    first frame of every sequence, HOST table or device int64 tensor (default: one sequence); ``valid`` uint8 (Ntot[, inner]) or None (every frame is
+    valid).  With P = pose_scale * poses and G = target_scale * target in fp64 (``root_relative``: joint 0 of the same pose subtracted from both), a
+    frame is COUNTED if it is valid and all its coordinates of P and G are finite, and e[g][j] = |P[g][j] - G[g][j]|.  Returns a ``PoseScore`` of
+    device float64 tensors of shape (S,) - (S, inner) for 4-D poses: ``frames`` counted; ``mpjpe`` the mean of e; ``rmse`` the root of the mean of
+    e^2; ``mpjve`` the mean over the pairs of consecutive counted frames of |(P[g] - P[g-1]) - (G[g] - G[g-1])|; ``accel`` the same of the second
+    differences over triples; ``p_mpjpe`` (``procrustes``, needs J >= 3; NaN without it) the mean of e after the similarity alignment of every P[g]
+    onto G[g], the reference's p_mpjpe, over the counted frames whose centred poses are not single points; ``per_joint`` (.., J); ``bone_mean``,
+    ``bone_std`` (population standard deviation over the frames) and ``bone_err`` (mean |target's length - pose's length|), each (.., J - 1), of
+    the bones of ``skeleton`` (default: the 17-joint H36M tree for 17 joints, else None: no bone statistics); ``rows``: the kernel's raw sums
+    (include/manipose_hip.h has the slots); ``frame_err`` (Ntot[, inner]) float32 with ``return_frames``: the mean of e over the joints, -1 for a
+    frame that is not counted or that no sequence holds.  A ratio whose count is 0 is NaN.  No term crosses a sequence boundary; fp64 inside,
+    identical bits on every call."""
+    if not all(lift_args.is_number(v) and np.isfinite(float(v)) and float(v) > 0 for v in (pose_scale, target_scale)):
+        raise ValueError(f"pose_scale and target_scale must be finite numbers > 0, got {pose_scale!r}, {target_scale!r}")
+    parents = None
+    if torch.is_tensor(poses):
+        p4 = lift_args.poses4(poses)                     # (the ValueErrors come before the refusal of a CPU tensor)
+        ntot, inner, J = int(p4.shape[0]), int(p4.shape[1]), int(p4.shape[2])
+        lift_args.f32(target, (ntot, J, 3), "target", contiguous=True)
+        lift_args.mask(valid, poses.shape[:-2], "valid")
+        if procrustes and J < 3:
+            raise ValueError(f"procrustes=True aligns poses of at least 3 joints, got {J}")
+        if skeleton is not None or J == 17:
+            parents = _parents_c(_skeleton_of(skeleton=skeleton), J)
+    lift_args.need_device("score_poses", poses, target, optional=(valid,))
+    d_off, S = _seq_table(seq_offset, ntot, poses.device)
+    flags = (SCORE_ROOT_RELATIVE if root_relative else 0) | (SCORE_PROCRUSTES if procrustes else 0)
+    rows, fe = _score(_lib.load(), p4, target, None if valid is None else valid.contiguous().view(ntot, inner), d_off, S, parents, pose_scale,
+                      target_scale, flags, return_frames)
+    if poses.dim() == 3:
+        rows, fe = rows[:, 0], (fe[:, 0] if fe is not None else None)
+    return _pose_record(rows, J, bool(procrustes), parents is not None, fe)
+
+
+def score_traj(traj, target, ok=None, seq_offset=None):
+    """``mp_lift_score`` on root trajectories (its M = 1 form: no alignment, no bones): ``traj`` (Ntot, 3) or (Ntot, inner, 3) float32 device tensor
+    as ``place_poses`` returns it, ``target`` (Ntot, 3) float32 in the same unit, ``ok`` uint8 (Ntot[, inner]) or None: a frame with ok = 0 or a
+    non-finite coordinate is not counted.  Returns a ``TrajScore`` of device float64 tensors (S,) or (S, inner): ``frames`` counted, ``ate`` the mean
+    distance, ``rmse`` the root of the mean squared distance, ``velocity`` / ``accel`` the mean norms of the first / second differences of the error
+    over consecutive counted frames of one sequence.  A ratio whose count is 0 is NaN.  ``seq_offset`` as for ``score_poses``."""
+    if torch.is_tensor(traj):
+        lift_args.traj3(traj)
+        lift_args.f32(target, (int(traj.shape[0]), 3), "target", contiguous=True)
+        lift_args.mask(ok, traj.shape[:-1], "ok")
+    lift_args.need_device("score_traj", traj, target, optional=(ok,))
+    ntot = int(traj.shape[0])
+    d_off, S = _seq_table(seq_offset, ntot, traj.device)
+    rows = _score(_lib.load(), traj.view(ntot, -1, 1, 3), target.view(ntot, 1, 3), None if ok is None else ok.contiguous().view(ntot, -1), d_off, S, None,
+                  1.0, 1.0, 0)[0]
+    return _traj_record(rows[:, 0] if traj.dim() == 2 else rows)
+
+
+def _traj_record(rows):
+    n = rows[..., 0]
+    return TrajScore(n, _ratio(rows[..., 1], n), torch.sqrt(_ratio(rows[..., 2], n)), _ratio(rows[..., 4], rows[..., 3]), _ratio(rows[..., 6], rows[..., 5]))
+
+
+REFINE_MAXITERS = 16         # MP_LIFT_REFINE_MAXITERS of include/manipose_hip.h: Gauss-Newton steps mp_lift_place_refine takes at most
+FLOOR_SHARES = 16            # MP_LIFT_WORLD_SHARES of include/manipose_hip.h: partial minima per sequence in mp_lift_world's scratch
+
+
+def camera_table(cameras):
+    """Per-sequence cameras as the float32 numpy tables the kernels read: ``intr`` (S, 9) = (fx, fy, cx, cy, k1, k2, k3, p1, p2) in normalised
+    screen units, ``quat`` (S, 4) = (w, x, y, z), ``trans`` (S, 3) in metres.  ``cameras``: one entry per sequence, either a dict as
+    ``h36m_cameras()`` gives (``intrinsic``, ``orientation``, optionally ``translation``: zeros when absent) or a 1-D array of at least 16
+    numbers in ``fetch()``'s order (intrinsic 9, orientation 4, translation 3[, camera index]).  ValueError for a wrong shape or a non-finite entry."""
+    if isinstance(cameras, dict) or (hasattr(cameras, "ndim") and getattr(cameras, "ndim", 0) == 1):
+        raise ValueError("cameras must be a list with one camera per sequence (a dict or a 1-D array of >= 16 numbers each)")
+    cams = list(cameras)
+    if not cams:
+        raise ValueError("cameras is empty: one camera per sequence expected")
+    rows = np.zeros((len(cams), 16), dtype=np.float32)
+    for s, cam in enumerate(cams):
+        if isinstance(cam, dict):
+            if "intrinsic" not in cam or "orientation" not in cam:
+                raise ValueError(f"camera {s}: a camera dict needs 'intrinsic' (9) and 'orientation' (4)")
+            parts = [np.asarray(cam["intrinsic"]), np.asarray(cam["orientation"]), np.asarray(cam.get("translation", np.zeros(3)))]
+            for name, a, n in zip(("intrinsic", "orientation", "translation"), parts, (9, 4, 3)):
+                if a.shape != (n,) or a.dtype.kind not in "fiu":
+                    raise ValueError(f"camera {s}: '{name}' must be {n} numbers, got shape {a.shape} {a.dtype}")
+            row = np.concatenate([a.astype(np.float64) for a in parts])
+        else:
+            a = cam.detach().cpu().numpy() if torch.is_tensor(cam) else np.asarray(cam)
+            if a.ndim != 1 or a.shape[0] < 16 or a.dtype.kind not in "fiu":
+                raise ValueError(f"camera {s}: expected a dict or a 1-D array of at least 16 numbers (intrinsic 9, orientation 4, translation 3), "
+                                 f"got shape {a.shape} {a.dtype}")
+            row = a[:16].astype(np.float64)
+        if not np.isfinite(row).all():
+            raise ValueError(f"camera {s}: non-finite entry")
+        rows[s] = row
+    return rows[:, :9].copy(), rows[:, 9:13].copy(), rows[:, 13:16].copy()
+
+
+def _place_refine(lib, p4, kp, d_off, S, d_intr, d_w, distort, iters, start=None, start_ok=None):
+    """``mp_lift_place_refine`` on p4 (Ntot, inner, J, C), the one launcher of the fit: (traj, reproj, ok, steps), new tensors; start (Ntot, inner, 3)
+    or None: the linear fit (with iters = 0: what ``mp_lift_place`` computes, by the same kernel), start_ok (Ntot, inner) uint8 or None"""
+    ntot, inner, J, ch = (int(v) for v in p4.shape)
+    dev = p4.device
+    traj = torch.empty(ntot, inner, 3, dtype=torch.float32, device=dev)
+    reproj = torch.empty(ntot, inner, dtype=torch.float32, device=dev)
+    ok = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
+    steps = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
+    if ntot > 0:
+        _launch(dev, "mp_lift_place_refine", _lib.ptr(p4), ntot, inner, J, ch, _lib.ptr(kp), _lib.ptr(d_off), S, _lib.ptr(d_intr), _lib.ptr(d_w),
+                int(bool(distort)), _lib.ptr(start), _lib.ptr(start_ok), int(iters), _lib.ptr(traj), _lib.ptr(reproj), _lib.ptr(ok), _lib.ptr(steps))
+    return traj, reproj, ok, steps
+
+
+def _world(lib, p4, traj, d_off, S, d_quat, d_trans, floor_mode=0, d_floor=None):
+    ntot, inner, J, ch = (int(v) for v in p4.shape)
+    if ntot == 0:
+        return
+    scratch = torch.empty(S * FLOOR_SHARES, dtype=torch.float32, device=p4.device) if floor_mode == 1 else None
+    _launch(p4.device, "mp_lift_world", _lib.ptr(p4), ntot, inner, J, ch, _lib.ptr(traj), _lib.ptr(d_off), S, _lib.ptr(d_quat), _lib.ptr(d_trans),
+            int(floor_mode), _lib.ptr(d_floor), _lib.ptr(scratch), S * FLOOR_SHARES if floor_mode == 1 else 0)
+
+
+def _place_inputs(poses, keypoints_2d, intrinsics, seq_offset, weights, who):
+    """the checks and uploads place_poses and reproject_poses share: (p4, keypoints, d_off, S, d_intr, d_w)"""
+    p4 = _poses4(poses, who)
+    dev, ntot, J = poses.device, int(p4.shape[0]), int(p4.shape[2])
+    lift_args.need_device(who, keypoints_2d)
+    lift_args.f32(keypoints_2d, (ntot, J, 2), "keypoints_2d", plain=True)
+    d_off, S = _seq_table(seq_offset, ntot, dev)
+    d_intr = _device_f32(intrinsics, dev, (S, 9), "intrinsics", row=(9,) if S == 1 else None)
+    d_w = _device_f32(weights, dev, (J,), "weights", nonneg=True) if weights is not None else None
+    return p4, keypoints_2d.contiguous(), d_off, S, d_intr, d_w
+
+
+def place_poses(poses, keypoints_2d, intrinsics, seq_offset=None, weights=None, distort=True, refine=0, return_steps=False):
+    """``mp_lift_place`` on device tensors: per pose the root translation that fits the frame's 2-D keypoints, and the reprojection error.
+    ``poses`` (Ntot, J, 3) or (Ntot, inner, J, 3 | 4) float32 (channel 3, a hypothesis' score, is not read); ``keypoints_2d`` (Ntot, J, 2) in
+    normalised screen coordinates, shared by the ``inner`` poses of a frame; ``intrinsics`` (S, 9) or (9,), tensor or array, as
+    ``camera_table`` / ``h36m_cameras()[s][i]["intrinsic"]``; ``seq_offset`` (S + 1): first frame of every sequence, HOST table or device int64
+    tensor (default: one sequence); ``weights`` (J) non-negative or None (all ones; a joint of weight 0 is skipped).  The fit uses the pinhole
+    part of the camera; the error the full model (``distort=True``, the reference's project_to_2d) or project_to_2d_linear, in normalised screen
+    units (times res_w / 2: pixels).  Returns ``traj`` (Ntot[, inner], 3) in the poses' unit, ``reproj`` (Ntot[, inner]), ``ok`` uint8: 0 where the
+    fit is degenerate (no weight, a non-finite input, all keypoints on one spot: traj and reproj are 0) or puts a joint behind the camera.
+    ``refine`` (0..16, default 0: the linear fit alone, ``mp_lift_place``): ``mp_lift_place_refine`` starts from that fit and takes up to that many
+    undamped Gauss-Newton steps on the weighted squared reprojection error of the projection ``distort`` names - the fit then uses the model the
+    error is measured with; a step is taken only while the normal matrix is regular, the translation stays finite and in front of the camera, and
+    the cost does not rise (include/manipose_hip.h has the rule); ``reproj`` is the error at the refined translation.  ``return_steps`` appends
+    ``steps`` uint8 (Ntot[, inner]): the steps taken (0 everywhere without ``refine``)."""
+    if not lift_args.is_int_in(refine, 0, REFINE_MAXITERS):
+        raise ValueError(f"refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: the linear fit alone), got {refine!r}")
+    p4, kp, d_off, S, d_intr, d_w = _place_inputs(poses, keypoints_2d, intrinsics, seq_offset, weights, "place_poses")
+    res = _place_refine(_lib.load(), p4, kp, d_off, S, d_intr, d_w, distort, refine)[:4 if return_steps else 3]
+    return tuple(r[:, 0] for r in res) if poses.dim() == 3 else tuple(res)
+
+
+def reproject_poses(poses, traj, keypoints_2d, intrinsics, ok=None, seq_offset=None, weights=None, distort=True):
+    """``mp_lift_place_refine`` with zero steps on a GIVEN trajectory: the reprojection error of poses placed at ``traj`` - a smoothed trajectory,
+    a ground-truth one, another method's.  ``traj`` (Ntot[, inner], 3) float32 device tensor shaped like ``place_poses`` returns it, ``ok`` uint8
+    (Ntot[, inner]) or None (every frame is given); the other arguments as for ``place_poses``.  Returns ``(reproj, ok)``: reproj (Ntot[, inner])
+    float32 in normalised screen units, the weighted mean distance between the keypoints and the projection of pose + traj; ok uint8, 0 with
+    reproj = 0 where ``ok`` was 0 or traj is not finite, 0 with reproj as computed where a joint lies behind the camera or the error is not
+    finite, else 1."""
+    if torch.is_tensor(poses) and torch.is_tensor(traj):
+        lift_args.poses4(poses)
+        lift_args.f32(traj, tuple(poses.shape[:-2]) + (3,), "traj", plain=True)
+        lift_args.mask(ok, traj.shape[:-1], "ok")
+    lift_args.need_device("reproject_poses", traj, optional=(ok,))
+    p4, kp, d_off, S, d_intr, d_w = _place_inputs(poses, keypoints_2d, intrinsics, seq_offset, weights, "reproject_poses")
+    _, reproj, good, _ = _place_refine(_lib.load(), p4, kp, d_off, S, d_intr, d_w, distort, 0, traj.contiguous(), None if ok is None else ok.contiguous())
+    return (reproj[:, 0], good[:, 0]) if poses.dim() == 3 else (reproj, good)
+
+
+def to_world(poses, orientation, translation=None, traj=None, seq_offset=None, floor=False):
+    """``mp_lift_world`` on a device tensor, IN PLACE (and returned): every joint p <- qrot(q_s, p + traj) + t_s.  ``poses`` (Ntot, J, 3) or
+    (Ntot, inner, J, 3 | 4) (channel 3 is left alone); ``orientation`` (S, 4) or (4,) quaternions (w, x, y, z) as the dataset stores them (not
+    normalised here, like the reference's qrot); ``translation`` (S, 3) / (3,) or None; ``traj`` (Ntot[, inner], 3) device tensor as
+    ``place_poses`` returns it, or None - with both None this is the reference's camera_to_world(., R, t = 0); ``seq_offset`` as for
+    ``place_poses``.  ``floor=True``: every sequence's lowest joint is put on z = 0 and ``(poses, offsets)`` is returned, offsets (S,) = the
+    minimum z subtracted; ``floor`` = a tensor or array (S,): those offsets are subtracted instead (one scene for several arrays)."""
+    p4 = _poses4(poses, "to_world")
+    dev, ntot = poses.device, int(p4.shape[0])
+    d_off, S = _seq_table(seq_offset, ntot, dev)
+    d_quat = _device_f32(orientation, dev, (S, 4), "orientation", row=(4,) if S == 1 else None)
+    d_trans = _device_f32(translation, dev, (S, 3), "translation", row=(3,) if S == 1 else None) if translation is not None else None
+    if traj is not None:
+        lift_args.need_device("to_world", traj)
+        lift_args.f32(traj, tuple(poses.shape[:-2]) + (3,), "traj", plain=True)
+        traj = traj.contiguous()
+    mode = 1 if floor is True else 0 if floor is False or floor is None else 2          # mp_lift_world's floor_mode: measure, none, given
+    d_floor = None if mode == 0 else torch.empty(S, dtype=torch.float32, device=dev) if mode == 1 else \
+        _device_f32(floor, dev, (S,), "floor", row=() if S == 1 else None)
+    _world(_lib.load(), p4, traj, d_off, S, d_quat, d_trans, mode, d_floor)
+    return (poses, d_floor) if mode == 1 else poses

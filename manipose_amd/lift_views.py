@@ -1,0 +1,368 @@
+"""The take-level operators of lifting: the camera views of a take - V sequences of the same frames, one per camera - fused into one motion in one
+world.  They are NOT stages of ``lift_sequences``' chain (lifting.py): they work on what it returns for the views, and hpe/_entry.py (``lift.fuse``)
+cuts a group's sequences into takes and calls them.  ``fuse_views``: one hypothesis per view, chosen jointly, and their mean;
+``fuse_views_path``: that choice made jointly over the whole take, a Viterbi path over the combinations, so that a hypothesis all views agree on -
+a mirrored body - cannot make the fused motion flicker; ``place_views``: one world root per frame from all views; ``align_views``: the views'
+extrinsics estimated from their lifted poses, for takes that were never calibrated; ``bundle_views``: those cameras and the roots refined jointly
+on the reprojection error.  Built like lift_ops.py: a public function composes lift_args' checks (``_fuse_front`` and ``_take_front`` are the
+fronts two of them share), then uploads and calls its private launcher, which allocates the outputs and goes through ``_launch``.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib, lift_args
+from .lift_ops import PATH_SIGMA, PATH_SWITCH, REFINE_MAXITERS, _host_f32, _launch, _seq_table, camera_table
+
+FUSE_MAXV, FUSE_MAXK = 4, 8  # MP_LIFT_FUSE_MAXV, MP_LIFT_FUSE_MAXK of include/manipose_hip.h: views of a take, hypotheses of a view
+FUSE_SIGMA, FUSE_SCORE_WEIGHT = 0.02, 1.0    # defaults of fuse_views: the views' disagreement in metres (not tuned), the weight of -log(score)
+
+
+def _fuse_quat(orientation, G, V):
+    """(G, V, 4) float32 host quaternions, (V, 4) standing for one take; a zero quaternion is refused here (the kernel would ignore the view)"""
+    h = _host_f32(orientation, (G, V, 4), "orientation", row=(V, 4) if G == 1 else None)
+    if not ((h.astype(np.float64) ** 2).sum(-1) >= 1e-12).all():
+        raise ValueError("orientation holds a zero quaternion: mark a missing view in valid and give it any unit quaternion")
+    return h
+
+
+def _fuse_outputs(hyps):
+    """what mp_lift_fuse and mp_lift_fuse_path both write: (pose (Ftot, J, 3), choice (Ftot, V), cost, spread, ok (Ftot)), uninitialised"""
+    V, ftot, _, J, _ = (int(v) for v in hyps.shape)
+    dev = hyps.device
+    return (torch.empty(ftot, J, 3, dtype=torch.float32, device=dev), torch.empty(ftot, V, dtype=torch.uint8, device=dev),
+            torch.empty(ftot, dtype=torch.float32, device=dev), torch.empty(ftot, dtype=torch.float32, device=dev),
+            torch.empty(ftot, dtype=torch.uint8, device=dev))
+
+
+def _fuse(lib, hyps, valid, d_off, G, d_quat, sigma, score_weight):
+    """``mp_lift_fuse`` on hyps (V, Ftot, K, J, C): (pose, choice, cost, spread, ok), new tensors"""
+    V, ftot, K, J, ch = (int(v) for v in hyps.shape)
+    pose, choice, cost, spread, ok = _fuse_outputs(hyps)
+    if ftot > 0:
+        _launch(hyps.device, "mp_lift_fuse", _lib.ptr(hyps), V, ftot, K, J, ch, _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(d_quat), float(sigma),
+                float(score_weight), _lib.ptr(pose), _lib.ptr(choice), _lib.ptr(cost), _lib.ptr(spread), _lib.ptr(ok))
+    return pose, choice, cost, spread, ok
+
+
+def _fuse_place(lib, pose, kp, valid, d_off, G, d_quat, d_trans, d_intr, d_w, distort, iters):
+    """``mp_lift_fuse_place`` on pose (Ftot, J, 3), kp (V, Ftot, J, 2): (root, reproj, ok, steps), new tensors"""
+    V, ftot, J = int(kp.shape[0]), int(kp.shape[1]), int(kp.shape[2])
+    dev = pose.device
+    root = torch.empty(ftot, 3, dtype=torch.float32, device=dev)
+    reproj = torch.empty(V, ftot, dtype=torch.float32, device=dev)
+    ok = torch.empty(ftot, dtype=torch.uint8, device=dev)
+    steps = torch.empty(ftot, dtype=torch.uint8, device=dev)
+    if ftot > 0:
+        _launch(dev, "mp_lift_fuse_place", _lib.ptr(pose), _lib.ptr(kp), V, ftot, J, _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(d_quat),
+                _lib.ptr(d_trans), _lib.ptr(d_intr), _lib.ptr(d_w), int(bool(distort)), int(iters), _lib.ptr(root), _lib.ptr(reproj), _lib.ptr(ok),
+                _lib.ptr(steps))
+    return root, reproj, ok, steps
+
+
+def _fuse_front(who, hyps, orientation, valid, take_offset):
+    """what fuse_views and fuse_views_path do between their options and their launch: the checks of hyps, valid and orientation, the refusal of CPU
+    tensors, the uploads: (valid, d_off, G, d_quat)"""
+    if torch.is_tensor(hyps):
+        lift_args.hyps5(hyps, FUSE_MAXV, FUSE_MAXK)       # (the ValueErrors come before the refusal of a CPU tensor)
+        V, ftot = int(hyps.shape[0]), int(hyps.shape[1])
+        lift_args.mask(valid, (V, ftot), "valid")
+        h_quat = _fuse_quat(orientation, lift_args.take_count(take_offset), V) if orientation is not None else None
+    lift_args.need_device(who, hyps, optional=(valid,))
+    valid = valid.contiguous() if valid is not None else None
+    d_off, G = _seq_table(take_offset, ftot, hyps.device)
+    return valid, d_off, G, torch.from_numpy(h_quat).to(hyps.device) if h_quat is not None else None
+
+
+def fuse_views(hyps, orientation=None, valid=None, take_offset=None, sigma=FUSE_SIGMA, score_weight=FUSE_SCORE_WEIGHT):
+    """``mp_lift_fuse`` on device tensors: the camera views of a take fused into one pose per frame.  ``hyps`` (V, Ftot, K, J, 3 | 4) float32, the
+    K hypotheses of each of V <= 4 views of the same frames, each in its camera's frame (channel 3 of joint 0: the hypothesis' score; without it
+    every hypothesis is equally likely); ``orientation`` (G, V, 4) or, for one take, (V, 4) camera quaternions (w, x, y, z), tensor or array,
+    normalised in the kernel, or None: the views are in the world's orientation already; ``valid`` (V, Ftot) uint8 device tensor or None: 0 where a
+    view is missing (a take with fewer than V views: all of its frames); ``take_offset`` (G + 1): first frame of every take, HOST table or device
+    int64 tensor (default: one take).  Per frame the ONE combination of a hypothesis per valid view is chosen that minimises
+    sum_{a < b} mean_j |w_a - w_b|^2 / (2 sigma^2) + score_weight sum_v -log(score_v), w the root-relative hypothesis rotated into the world - the
+    first minimum in lexicographic order - and the chosen hypotheses are averaged (include/manipose_hip.h has the rule).  ``sigma`` > 0 in the
+    poses' unit (inf: the views do not see each other and every view takes its best score), ``score_weight`` >= 0.  Returns ``(pose (Ftot, J, 3)
+    root-relative in the world's orientation, choice (Ftot, V) uint8 (255: invalid view), cost (Ftot), spread (Ftot) the chosen hypotheses' RMS
+    distance from their mean, ok (Ftot) uint8)``, new device tensors.  hyps is not modified; identical bits on every call."""
+    lift_args.sigma_pair(sigma, score_weight, ("sigma", "score_weight"))
+    valid, d_off, G, d_quat = _fuse_front("fuse_views", hyps, orientation, valid, take_offset)
+    return _fuse(_lib.load(), hyps, valid, d_off, G, d_quat, sigma, score_weight)
+
+
+def _fuse_path(lib, hyps, valid, d_off, G, d_quat, sigma, score_weight, path_sigma, switch_cost):
+    """``mp_lift_fuse_path`` on hyps (V, Ftot, K, J, C): (pose, choice, cost, spread, ok, path_cost (G,) float64), new tensors"""
+    V, ftot, K, J, ch = (int(v) for v in hyps.shape)
+    dev = hyps.device
+    pose, choice, cost, spread, ok = _fuse_outputs(hyps)
+    path_cost = torch.zeros(G, dtype=torch.float64, device=dev)
+    if ftot > 0:
+        n = int(lib.mp_lift_fuse_path_scratch_bytes(V, ftot, K))
+        scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
+        _launch(dev, "mp_lift_fuse_path", _lib.ptr(hyps), V, ftot, K, J, ch, _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(d_quat), float(sigma),
+                float(score_weight), float(path_sigma), float(switch_cost), _lib.ptr(pose), _lib.ptr(choice), _lib.ptr(cost), _lib.ptr(spread),
+                _lib.ptr(ok), _lib.ptr(path_cost), _lib.ptr(scratch), n)
+    return pose, choice, cost, spread, ok, path_cost
+
+
+def fuse_views_path(hyps, orientation=None, valid=None, take_offset=None, sigma=FUSE_SIGMA, score_weight=FUSE_SCORE_WEIGHT, path_sigma=PATH_SIGMA,
+                    switch_cost=PATH_SWITCH):
+    """``mp_lift_fuse_path`` on device tensors: the camera views of a take fused along time.  The arguments are ``fuse_views``'; the choice is not
+    made frame by frame but jointly over the whole take: the cheapest PATH through the combinations (one hypothesis per view: K^V states, at most
+    4096) under ``fuse_views``' cost per frame and, per view, ``select_path``'s cost per step - mean_j |w_b[j] - w_a[j]|^2 / (2 path_sigma^2) +
+    (switch_cost if a != b) from hypothesis a of a frame to hypothesis b of the next, w the rotated root-relative hypothesis; by the Viterbi
+    algorithm in fp64, staged per view, ties to the first combination (include/manipose_hip.h has the rule).  ``fuse_views`` takes a hypothesis
+    that all views agree on - a left/right-mirrored body - in every frame where its score is higher, and the fused motion flickers; the path does
+    not jump.  A view missing at a frame (``valid``) has no say there and its chain is cut.  ``path_sigma`` > 0 in the poses' unit (inf: steps cost
+    nothing, and with switch_cost = 0 the choice is ``fuse_views``'), ``switch_cost`` >= 0.  Returns ``(pose, choice, cost, spread, ok, path_cost
+    (G,) float64: the cost of every take's path)``, the first five as ``fuse_views`` returns them, new device tensors.  A frame that no take of
+    ``take_offset`` holds is left unwritten.  hyps is not modified; identical bits on every call.  Not measured on real data."""
+    lift_args.sigma_pair(sigma, score_weight, ("sigma", "score_weight"))
+    lift_args.sigma_pair(path_sigma, switch_cost, ("path_sigma", "switch_cost"))
+    valid, d_off, G, d_quat = _fuse_front("fuse_views_path", hyps, orientation, valid, take_offset)
+    return _fuse_path(_lib.load(), hyps, valid, d_off, G, d_quat, sigma, score_weight, path_sigma, switch_cost)
+
+
+def _take_cameras(cameras, V):
+    """cameras[take][view] (camera_table's forms, None: a missing view) -> host (intr (G, V, 9), quat (G, V, 4), trans (G, V, 3), present (G, V) bool);
+    a missing view gets the identity camera, which is never read"""
+    if isinstance(cameras, dict) or not hasattr(cameras, "__len__") or len(cameras) == 0:
+        raise ValueError("cameras must be a nested list [take][view] of cameras (None: a missing view)")
+    G = len(cameras)
+    intr, quat, trans = np.zeros((G, V, 9), np.float32), np.zeros((G, V, 4), np.float32), np.zeros((G, V, 3), np.float32)
+    present = np.zeros((G, V), bool)
+    intr[..., 0:2], quat[..., 0] = 1.0, 1.0
+    for g, take in enumerate(cameras):
+        if isinstance(take, dict) or not hasattr(take, "__len__") or len(take) != V:
+            raise ValueError(f"cameras[{g}] must list {V} views (None: a missing view)")
+        for v, cam in enumerate(take):
+            if cam is None:
+                continue
+            try:
+                i, q, t = camera_table([cam])
+            except ValueError as e:
+                raise ValueError(f"take {g}, view {v}: {e}") from None
+            if not float((q.astype(np.float64) ** 2).sum()) >= 1e-12:
+                raise ValueError(f"take {g}, view {v}: zero quaternion")
+            intr[g, v], quat[g, v], trans[g, v], present[g, v] = i[0], q[0], t[0], True
+    return intr, quat, trans, present
+
+
+def _take_front(who, pose, keypoints_2d, cameras, valid, take_offset, weights, roots=None):
+    """What place_views and bundle_views do before their uploads: the checks of the take's pose, keypoints, masks, cameras and weights - with ``roots`` =
+    (root, root_ok, fixed) also of bundle_views' three, each where bundle_views has always checked it -, the refusal of CPU tensors, the offsets'
+    upload, and the mask that makes a missing view (None in ``cameras``) invalid in every frame of its take: (valid, d_off, G, (intr, quat, trans,
+    present) host tables, h_w, h_fixed)"""
+    root, root_ok, fixed = roots if roots is not None else (None, None, None)
+    given = (pose, keypoints_2d) if roots is None else (pose, root, keypoints_2d)
+    if all(torch.is_tensor(t) for t in given):
+        V, ftot, J = lift_args.take_pose_keypoints(pose, keypoints_2d, FUSE_MAXV, root)
+        lift_args.mask(valid, (V, ftot), "valid")
+        lift_args.mask(root_ok, (ftot,), "root_ok", bare=True)
+        cams = _take_cameras(cameras, V)
+        G, present = cams[0].shape[0], cams[3]
+        h_fixed = None
+        if fixed is not None:
+            h_fixed = np.asarray(fixed.detach().cpu().numpy() if torch.is_tensor(fixed) else fixed)
+            if h_fixed.shape == (V,) and G == 1:
+                h_fixed = h_fixed.reshape(1, V)
+            if h_fixed.shape != (G, V) or h_fixed.dtype.kind not in "biu":
+                raise ValueError(f"fixed must be a table ({G}, {V}) of flags, got {h_fixed.shape} {h_fixed.dtype}")
+            h_fixed = np.ascontiguousarray(h_fixed != 0, dtype=np.uint8)
+        h_w = _host_f32(weights, (J,), "weights", nonneg=True) if weights is not None else None
+    lift_args.need_device(who, *given, optional=(valid, root_ok))
+    dev = pose.device
+    valid = valid.contiguous() if valid is not None else None
+    d_off, G_off = _seq_table(take_offset, ftot, dev)
+    if G_off != G:
+        raise ValueError(f"cameras lists {G} takes, take_offset {G_off}")
+    if not present.all():                                  # a missing view is invalid in every frame of its take
+        off = d_off.cpu().numpy().clip(0, ftot)
+        mask = np.ones((V, ftot), np.uint8)
+        for g, v in zip(*np.nonzero(~present)):
+            mask[v, off[g]:max(off[g], off[g + 1])] = 0
+        mask = torch.from_numpy(mask).to(dev)
+        valid = mask if valid is None else valid & mask
+    return valid, d_off, G, cams, h_w, h_fixed
+
+
+def place_views(pose, keypoints_2d, cameras, valid=None, take_offset=None, weights=None, distort=True, refine=3, return_steps=False):
+    """``mp_lift_fuse_place`` on device tensors: ONE world root per frame from all views of its take.  ``pose`` (Ftot, J, 3) float32, root-relative
+    in the world's orientation, as ``fuse_views`` returns it; ``keypoints_2d`` (V, Ftot, J, 2) float32, every view's keypoints in normalised screen
+    coordinates; ``cameras``: nested list [take][view] of cameras in ``camera_table``'s forms (a dict of ``h36m_cameras()`` with its
+    ``translation``, or ``fetch()``'s 16 numbers), None for a view the take does not have; ``valid`` (V, Ftot) uint8 device tensor or None;
+    ``take_offset`` (G + 1) as for ``fuse_views``; ``weights`` (J) or None.  The root starts at the linear fit of all views' pinhole projections
+    (condition number about 6 with H36M's four cameras, against 6e2 for one view) and takes up to ``refine`` (0..16) Gauss-Newton steps under the
+    camera model ``distort`` names, with ``place_poses``' acceptance rule.  Returns ``(root (Ftot, 3), reproj (V, Ftot): every view's own mean
+    reprojection error at the root, 0 for an invalid view, ok (Ftot) uint8[, steps (Ftot) uint8])``."""
+    if not lift_args.is_int_in(refine, 0, REFINE_MAXITERS):
+        raise ValueError(f"refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: the linear fit alone), got {refine!r}")
+    valid, d_off, G, (intr, quat, trans, _), h_w, _ = _take_front("place_views", pose, keypoints_2d, cameras, valid, take_offset, weights)
+    dev = pose.device
+    res = _fuse_place(_lib.load(), pose, keypoints_2d.contiguous(), valid, d_off, G, torch.from_numpy(quat).to(dev), torch.from_numpy(trans).to(dev),
+                      torch.from_numpy(intr).to(dev), torch.from_numpy(h_w).to(dev) if h_w is not None else None, distort, refine)
+    return res if return_steps else res[:3]
+
+
+ALIGN_MAXITERS = 8           # MP_LIFT_ALIGN_MAXITERS of include/manipose_hip.h: re-weightings mp_lift_align_views takes at most
+ALIGN_SIGMA, ALIGN_ITERS = 0.05, 5           # defaults of align_views: the scale of a frame's residual in metres, the re-weightings (not tuned)
+# What align_views returns: quat (G, V, 4), trans (G, V, 3) or None, rms (G, V), trans_rms (G, V) or None float32, used (G, V) int32, ok (G, V) uint8
+ViewAlignment = namedtuple("ViewAlignment", "quat trans rms trans_rms used ok")
+
+
+def _quat_matrix(q):
+    """the rotation matrix of q / |q| (w, x, y, z) in float64"""
+    w, x, y, z = np.asarray(q, np.float64) / np.linalg.norm(np.asarray(q, np.float64))
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _align_compose(quat, trans, ok, ref_quat, ref_trans):
+    """mp_lift_align_views' rows (G, V, ..) in the reference views' frames -> in the worlds of the reference views' known extrinsics, on the host
+    in float64: q = q_ref * q_v (q_ref normalised), T = R_ref T_v + T_ref.  A row whose ok lacks bit 0 is left as it is; the translation is composed
+    where ok has bit 1 and for the reference view itself, the lowest view of a take with bit 0 (its T_v = 0 is known); elsewhere it stays 0.
+    Returns float32 (quat, trans or None); q stays canonical (w >= 0, else the first non-zero component positive)."""
+    q64, ok = np.asarray(quat, np.float64).copy(), np.asarray(ok)
+    t64 = np.asarray(trans, np.float64).copy() if trans is not None else None
+    for g in range(q64.shape[0]):
+        a = np.asarray(ref_quat[g], np.float64)
+        a = a / np.linalg.norm(a)
+        R = _quat_matrix(a)
+        rot = np.nonzero(ok[g] & 1)[0]
+        for v in rot:
+            b = q64[g, v]
+            q = np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                          a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
+            nz = q[np.nonzero(q)[0][:1]]
+            q64[g, v] = -q if nz.size and nz[0] < 0 else q
+            if t64 is not None and (ok[g, v] & 2 or v == rot[0]):
+                t64[g, v] = R @ t64[g, v] + np.asarray(ref_trans[g], np.float64)
+    return q64.astype(np.float32), t64.astype(np.float32) if t64 is not None else None
+
+
+def _align(lib, poses, valid, d_off, G, traj, traj_ok, sigma, iters):
+    """``mp_lift_align_views`` on poses (V, Ftot, J, C): a ViewAlignment of new tensors"""
+    V, ftot, J, ch = (int(v) for v in poses.shape)
+    dev = poses.device
+    quat = torch.zeros(G, V, 4, dtype=torch.float32, device=dev)
+    quat[..., 0] = 1.0
+    trans = torch.zeros(G, V, 3, dtype=torch.float32, device=dev) if traj is not None else None
+    rms = torch.zeros(G, V, dtype=torch.float32, device=dev)
+    trans_rms = torch.zeros(G, V, dtype=torch.float32, device=dev) if traj is not None else None
+    used = torch.zeros(G, V, dtype=torch.int32, device=dev)
+    ok = torch.zeros(G, V, dtype=torch.uint8, device=dev)
+    if ftot > 0:
+        _launch(dev, "mp_lift_align_views", _lib.ptr(poses), V, ftot, J, ch, _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(traj), _lib.ptr(traj_ok),
+                float(sigma), int(iters), _lib.ptr(quat), _lib.ptr(trans), _lib.ptr(rms), _lib.ptr(trans_rms), _lib.ptr(used), _lib.ptr(ok))
+    return ViewAlignment(quat, trans, rms, trans_rms, used, ok)
+
+
+def align_views(poses, valid=None, take_offset=None, traj=None, traj_ok=None, sigma=ALIGN_SIGMA, iters=ALIGN_ITERS, reference=None):
+    """``mp_lift_align_views`` on device tensors: the extrinsics of a take's views estimated from their lifted poses, for takes whose cameras
+    were never calibrated against each other.  ``poses`` (V, Ftot, J, 3 | 4) float32, one pose per view and frame in that view's camera frame
+    (channel 3 is not read); ``valid`` (V, Ftot) uint8 device tensor or None; ``take_offset`` (G + 1) as for ``fuse_views``; ``traj`` (V, Ftot, 3)
+    float32 and ``traj_ok`` (V, Ftot) uint8, both or neither: the views' camera-space roots as ``place_poses`` returns them.  Per take the lowest
+    view with a valid frame is the reference; every other view's rotation onto it is Horn's closed form over the root-relative poses of all
+    frames valid in both, re-weighted ``iters`` (0..8) times with w = 1 / (1 + e / sigma^2)^2, e a frame's mean squared residual - a depth-mirrored
+    body loses its say; ``sigma`` > 0 in the poses' unit (inf: plain Horn) - and, with ``traj``, its translation the weighted mean of
+    traj_ref - R traj_v (include/manipose_hip.h has the rule).  The defaults are not tuned.  x_ref = R_v x_v + T_v: ``quat`` and ``trans`` are
+    ``fuse_views``' and ``place_views``' extrinsics with the reference view's frame as the world.  ``reference``: per take one camera in
+    ``camera_table``'s forms (a list of G; one camera alone for one take), the known extrinsics of the reference view: the result is composed on
+    the host in float64 into that world, q = q_ref * q_v, T = R_ref T_v + T_ref (this waits for the kernel).  Returns a ``ViewAlignment``:
+    ``(quat (G, V, 4), trans (G, V, 3) or None, rms (G, V): the weighted RMS residual of the poses, trans_rms (G, V) or None: that of the
+    roots - a monocular depth scale error shows here -, used (G, V) int32: the frames used, ok (G, V) uint8: bit 0 the rotation, bit 1 the
+    translation)``, new device tensors; a degenerate row is the identity with ok = 0.  Inputs are not modified; identical bits on every call.
+    Not measured on real data."""
+    if not lift_args.is_number(sigma) or not float(sigma) > 0:
+        raise ValueError(f"sigma must be a number > 0 (inf: every frame weighs 1), got {sigma!r}")
+    if not lift_args.is_int_in(iters, 0, ALIGN_MAXITERS):
+        raise ValueError(f"iters counts re-weightings, an integer in 0..{ALIGN_MAXITERS} (0: plain Horn), got {iters!r}")
+    if (traj is None) != (traj_ok is None):
+        raise ValueError("traj and traj_ok come together: the views' roots and where they were fitted")
+    if torch.is_tensor(poses):
+        lift_args.view_poses4(poses, FUSE_MAXV)
+        V, ftot = int(poses.shape[0]), int(poses.shape[1])
+        lift_args.mask(valid, (V, ftot), "valid")
+        if traj is not None:
+            lift_args.f32(traj, (V, ftot, 3), "traj")       # (made contiguous below: any strides)
+            lift_args.mask(traj_ok, (V, ftot), "traj_ok", bare=True)
+        G = lift_args.take_count(take_offset)
+        if reference is not None:
+            single = isinstance(reference, dict) or torch.is_tensor(reference) or (hasattr(reference, "ndim") and getattr(reference, "ndim", 0) == 1)
+            _, ref_quat, ref_trans = camera_table([reference] if single else reference)
+            if ref_quat.shape[0] != G:
+                raise ValueError(f"reference lists {ref_quat.shape[0]} cameras, take_offset {G} takes")
+            if not ((ref_quat.astype(np.float64) ** 2).sum(-1) >= 1e-12).all():
+                raise ValueError("reference holds a zero quaternion")
+    lift_args.need_device("align_views", poses, optional=(valid, traj, traj_ok))
+    valid = valid.contiguous() if valid is not None else None
+    d_off, G = _seq_table(take_offset, ftot, poses.device)
+    res = _align(_lib.load(), poses, valid, d_off, G, traj.contiguous() if traj is not None else None,
+                 traj_ok.contiguous() if traj_ok is not None else None, sigma, iters)
+    if reference is None:
+        return res
+    q, t = _align_compose(res.quat.cpu().numpy(), res.trans.cpu().numpy() if res.trans is not None else None, res.ok.cpu().numpy(), ref_quat, ref_trans)
+    return res._replace(quat=torch.from_numpy(q).to(poses.device), trans=torch.from_numpy(t).to(poses.device) if t is not None else None)
+
+
+BUNDLE_MAXITERS = 8          # MP_LIFT_BUNDLE_MAXITERS of include/manipose_hip.h: Gauss-Newton steps mp_lift_bundle_views takes at most
+BUNDLE_SIGMA, BUNDLE_ITERS = 0.05, 3         # defaults of bundle_views: the robust scale in normalised screen units, the steps (not tuned)
+# What bundle_views returns: cameras: place_views' nested list [take][view] with the refined extrinsics; quat (G, V, 4), trans (G, V, 3), root (Ftot, 3),
+# reproj (G, V, 2) float32, cost (G, 2) float64, steps, ok (G) uint8, used (G, V) int32
+ViewBundle = namedtuple("ViewBundle", "cameras quat trans root reproj cost steps ok used")
+
+
+def _bundle(lib, pose, root, root_ok, kp, valid, d_off, G, d_quat, d_trans, d_intr, d_fixed, d_w, distort, sigma, iters):
+    """``mp_lift_bundle_views``: (quat, trans, root, reproj, cost, steps, ok, used), new tensors"""
+    V, ftot, J = int(kp.shape[0]), int(kp.shape[1]), int(kp.shape[2])
+    dev = pose.device
+    quat, trans = d_quat.clone(), d_trans.clone()
+    out_root = root.clone()
+    reproj = torch.zeros(G, V, 2, dtype=torch.float32, device=dev)
+    cost = torch.zeros(G, 2, dtype=torch.float64, device=dev)
+    steps, ok = torch.zeros(G, dtype=torch.uint8, device=dev), torch.zeros(G, dtype=torch.uint8, device=dev)
+    used = torch.zeros(G, V, dtype=torch.int32, device=dev)
+    if ftot > 0:
+        n = int(lib.mp_lift_bundle_views_scratch_bytes(V, ftot))
+        scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
+        _launch(dev, "mp_lift_bundle_views", _lib.ptr(pose), _lib.ptr(root), _lib.ptr(root_ok), _lib.ptr(kp), V, ftot, J, _lib.ptr(valid), _lib.ptr(d_off),
+                G, _lib.ptr(d_quat), _lib.ptr(d_trans), _lib.ptr(d_intr), _lib.ptr(d_fixed), _lib.ptr(d_w), int(bool(distort)), float(sigma), int(iters),
+                _lib.ptr(quat), _lib.ptr(trans), _lib.ptr(out_root), _lib.ptr(reproj), _lib.ptr(cost), _lib.ptr(steps), _lib.ptr(ok), _lib.ptr(used),
+                _lib.ptr(scratch), n)
+    return quat, trans, out_root, reproj, cost, steps, ok, used
+
+
+def bundle_views(pose, root, keypoints_2d, cameras, valid=None, take_offset=None, root_ok=None, fixed=None, weights=None, distort=True,
+                 sigma=BUNDLE_SIGMA, iters=BUNDLE_ITERS):
+    """``mp_lift_bundle_views`` on device tensors: a take's cameras and world roots refined JOINTLY on the reprojection error - the bundle adjustment
+    behind ``align_views``' closed form, in which the 2-D keypoints have no say.  ``pose`` (Ftot, J, 3) float32 as ``fuse_views`` returns it,
+    ``root`` (Ftot, 3) float32 and ``root_ok`` (Ftot) uint8 or None as ``place_views`` returns them, ``keypoints_2d`` (V, Ftot, J, 2), ``cameras``,
+    ``valid``, ``take_offset``, ``weights`` and ``distort`` as for ``place_views``; ``fixed`` (G, V) or, for one take, (V,): non-zero where a view's
+    extrinsics are held (host table; None: the lowest view of every take that observes a frame).  Up to ``iters`` (0..8) undamped Gauss-Newton steps
+    over all free cameras (6 parameters each: a left perturbation of the camera-space point, P' = exp([w]x) P + tau) and all roots, the roots
+    eliminated by a Schur complement, on sum w_j rho(|res|^2) with rho(e) = e / (1 + e / sigma^2); ``sigma`` > 0 in normalised screen units (inf:
+    plain least squares); a step is taken while the cost does not rise (``place_poses``' rule; include/manipose_hip.h has the rule in full).  The
+    defaults are not tuned.  Returns a ``ViewBundle``: ``(cameras: the nested list with the refined extrinsics, to be passed on to place_views
+    (this waits for the kernel), quat (G, V, 4), trans (G, V, 3), root (Ftot, 3), reproj (G, V, 2): every view's weighted mean reprojection error
+    at the start and at the end, cost (G, 2) float64, steps (G) uint8, ok (G) uint8: 0 where the start could not be evaluated (a joint behind a
+    camera), used (G, V) int32: the frames a view observes)``, new device tensors.  A fixed view, and every view of a take that took no step, is
+    copied through bit for bit.  Inputs are not modified; identical bits on every call.  Not measured on real data."""
+    if not lift_args.is_number(sigma) or not float(sigma) > 0:
+        raise ValueError(f"sigma must be a number > 0 in normalised screen units (inf: no robust weight), got {sigma!r}")
+    if not lift_args.is_int_in(iters, 0, BUNDLE_MAXITERS):
+        raise ValueError(f"iters counts Gauss-Newton steps, an integer in 0..{BUNDLE_MAXITERS} (0: the evaluation alone), got {iters!r}")
+    valid, d_off, G, (intr, quat, trans, present), h_w, h_fixed = _take_front("bundle_views", pose, keypoints_2d, cameras, valid, take_offset, weights,
+                                                                             roots=(root, root_ok, fixed))
+    dev, V = pose.device, int(keypoints_2d.shape[0])
+    res = _bundle(_lib.load(), pose, root.contiguous(), root_ok.contiguous() if root_ok is not None else None, keypoints_2d.contiguous(), valid, d_off, G,
+                  torch.from_numpy(quat).to(dev), torch.from_numpy(trans).to(dev), torch.from_numpy(intr).to(dev),
+                  torch.from_numpy(h_fixed).to(dev) if h_fixed is not None else None, torch.from_numpy(h_w).to(dev) if h_w is not None else None,
+                  distort, sigma, iters)
+    q, t = res[0].cpu().numpy(), res[1].cpu().numpy()
+    nested = [[np.concatenate([intr[g, v], q[g, v], t[g, v]]) if present[g, v] else None for v in range(V)] for g in range(G)]
+    return ViewBundle(nested, *res)

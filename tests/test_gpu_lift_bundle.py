@@ -198,6 +198,8 @@ def test_entry_point_rejects_bad_arguments_before_any_launch(lib):
         bundle_views(pose.cpu(), root, kp, cams)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         bundle_views(pose, root, kp, cams, root_ok=torch.ones(6, dtype=torch.uint8))
+    with pytest.raises(RuntimeError, match="bundle_views takes device tensors"):
+        bundle_views(pose, root, kp, cams, valid=torch.ones(kp.shape[0], 6, dtype=torch.uint8))
     with pytest.raises(ValueError, match="lists 1 takes, take_offset 2"):
         bundle_views(pose, root, kp, cams, take_offset=[0, 3, 6])
 

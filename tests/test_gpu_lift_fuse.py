@@ -93,7 +93,7 @@ def test_fuse_constructed_cases():
 
 
 def test_fuse_ignores_a_view_with_a_zero_quaternion(lib):
-    from manipose_amd.lifting import _fuse as launch
+    from manipose_amd.lift_views import _fuse as launch
     hyps, quat, off = ref.fuse_scene(4, 5, 4, lens=[3, 5], seed=32)
     dead = quat.copy()
     dead[1, 2] = 0                                                        # view 2 of take 1 (fuse_views refuses this table: the entry point itself)
@@ -132,10 +132,37 @@ def test_fuse_place_degenerate_frames():
     assert got[2][ref.ONE_SPOT] == 0 and not got[0][ref.ONE_SPOT].any() and not got[1][:, ref.ONE_SPOT].any() and got[3][ref.ONE_SPOT] == 0
 
 
+def test_two_small_takes_a_missing_view_and_a_device_offset_table():
+    """The smallest shape at which what fuse_views / fuse_views_path and place_views / bundle_views share in front of their launchers can go wrong:
+    V = 2, K = 2, J = 3, takes of 1 and 2 frames, view 1 missing in the second take - for place_views said by None in the cameras ALONE
+    (valid=None: the mask is made from the cameras), for fuse_views by valid - and the (G + 1) offsets a DEVICE table, so the number of takes is
+    read from its size.  Against the float64 statement within the store bound; the decisions' margins are those of the host test."""
+    from manipose_amd import place_views
+    valid = np.ones((2, 3), np.uint8)
+    valid[1, 1:] = 0
+    hyps, quat, off = ref.fuse_scene(2, 2, 4, J=3, lens=[1, 2], seed=42)
+    want = ref.fuse_all(hyps, quat, valid, off)
+    assert (want["gap"] / (1.0 + np.abs(want["cost"]))).min() >= 1e-6
+    got = _fuse(hyps, quat, valid, _dev(np.asarray(off, np.int64)))
+    assert np.array_equal(got["choice"], want["choice"]) and np.array_equal(got["ok"], want["ok"]) and (got["choice"][1:, 1] == 255).all()
+    for k in ("pose", "cost", "spread"):
+        _check(f"two small takes: {k}", got[k], want[k])
+    pose, kp, _, cams, off = ref.place_scene(2, J=3, lens=[1, 2], seed=42)
+    trace = []
+    want = ref.place_all(pose, kp, *cams, valid, off, iters=3, trace=trace)
+    assert ref.margin(trace) >= 1e-3
+    nested = _nested(cams)
+    nested[1][1] = None
+    got = [r.cpu().numpy() for r in place_views(_dev(pose), _dev(kp), nested, None, _dev(np.asarray(off, np.int64)), None, True, 3, return_steps=True)]
+    _check("two small takes: root", got[0], want[0])
+    _check("two small takes: reproj", got[1], want[1])
+    assert np.array_equal(got[2], want[2]) and np.array_equal(got[3], want[3]) and got[2].all() and not got[1][1, 1:].any() and (got[1][0] > 0).all()
+
+
 def test_one_view_at_the_identity_is_place_poses():
     """V = 1 with no quaternion table and no translation is mp_lift_place_refine's problem: the two kernels agree to the bound"""
     from manipose_amd import place_poses
-    from manipose_amd.lifting import _fuse_place
+    from manipose_amd.lift_views import _fuse_place
     from manipose_amd import _lib
     import lift_refine_ref as refine
     poses, kp, _, off = refine.recovery_scene()
@@ -238,6 +265,8 @@ def test_entry_points_reject_bad_arguments_before_any_launch(lib):
         fuse_views(hyps, valid=torch.ones(V, F, dtype=torch.uint8))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         place_views(pose, kp.cpu(), _nested(ref.s11_tables()))
+    with pytest.raises(RuntimeError, match="place_views takes device tensors"):
+        place_views(pose, kp, _nested(ref.s11_tables()), valid=torch.ones(kp.shape[0], kp.shape[1], dtype=torch.uint8))
     with pytest.raises(ValueError, match="takes"):
         place_views(pose, kp, _nested(ref.s11_tables()), take_offset=[0, 2, F])
     with pytest.raises(RuntimeError, match="out of range"):

@@ -160,7 +160,7 @@ def test_invariants():
         assert all(_same(alone[k], x[sl].cpu().numpy()) for k, x in zip(KEYS[:5], a))
         assert _same(alone["path_cost"], a[5][t:t + 1].cpu().numpy())
     # a frame that no take holds is not written; an empty take costs 0
-    from manipose_amd.lifting import _fuse_path
+    from manipose_amd.lift_views import _fuse_path
     from manipose_amd import _lib
     part = _dev(np.array([0, 6, 6, 30], np.int64))
     res = _fuse_path(_lib.load(), d_hyps, None, part, 3, _dev(np.ascontiguousarray(quat)), 0.02, 1.0, 0.2, 0.4)

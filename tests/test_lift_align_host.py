@@ -92,7 +92,7 @@ def test_every_degenerate_rule():
 
 
 def test_composition_with_a_reference_camera():
-    from manipose_amd.lifting import _align_compose
+    from manipose_amd.lift_views import _align_compose
     sc = ref.scene(4, 9, [20, 20], seed=9)
     valid = np.ones((4, 40), np.uint8)
     valid[0, 20:] = 0                                                     # take 1: view 1 is the reference

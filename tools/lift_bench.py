@@ -260,7 +260,8 @@ def fuse_scene(frames, K):
 def fuse_bench(argv):
     from manipose_amd import _lib
     from manipose_amd.data.ingest import h36m_cameras
-    from manipose_amd.lifting import _fuse, _fuse_place, _path
+    from manipose_amd.lift_ops import _path
+    from manipose_amd.lift_views import _fuse, _fuse_place
     frames = int(argv[0]) if len(argv) > 0 else 3000
     K = int(argv[1]) if len(argv) > 1 else 5
     reps = int(argv[2]) if len(argv) > 2 else 200
@@ -281,7 +282,7 @@ def fuse_bench(argv):
 
 
 def fuse_path_bench(argv):
-    from manipose_amd.lifting import _fuse, _fuse_path
+    from manipose_amd.lift_views import _fuse, _fuse_path
     frames = int(argv[0]) if len(argv) > 0 else 3000
     K = int(argv[1]) if len(argv) > 1 else 5
     reps = int(argv[2]) if len(argv) > 2 else 20
@@ -304,7 +305,7 @@ def fuse_path_bench(argv):
 def align_bench(argv):
     from manipose_amd import align_views
     from manipose_amd.data.ingest import h36m_cameras
-    from manipose_amd.lifting import _align
+    from manipose_amd.lift_views import _align
     frames = int(argv[0]) if len(argv) > 0 else 3000
     reps = int(argv[1]) if len(argv) > 1 else 20
     lib, V, (quat, trans, _), _, hyps, _ = fuse_scene(frames, 2)
@@ -340,7 +341,7 @@ def align_bench(argv):
 
 
 def bundle_bench(argv):
-    from manipose_amd.lifting import _bundle, _fuse_place
+    from manipose_amd.lift_views import _bundle, _fuse_place
     frames = int(argv[0]) if len(argv) > 0 else 3000
     reps = int(argv[1]) if len(argv) > 1 else 20
     lib, V, (quat, trans, intr), pose, _, kp = fuse_scene(frames, 2)
