@@ -175,52 +175,27 @@ __global__ __launch_bounds__(WPB * 64) void attn_spatial_bwd_kernel(const TS* __
   }
 }
 
-// head_dim ** -0.5 (mix_ste.py:243-244) unless the model engine has set another scale for the launches it is about to issue on this
-// thread (muP: 1 / head_dim, mix_ste.py:243; or an explicit qk_scale): attn_scale_override(s > 0), reset with 0
-static thread_local float g_scale_override = 0.f;
-void attn_scale_override(float s) { g_scale_override = s; }
-float attn_qk_scale(int D) { return g_scale_override > 0.f ? g_scale_override : 1.0f / sqrtf((float)D); }
-static float qk_scale(int D) { return attn_qk_scale(D); }
-
 template <typename TS>
-static int spatial_fwd_t(const TS* qkv, TS* out, int B, int T, int J, int C, int H, hipStream_t st) {
-  const int D = C / H, F = B * T;
+static int spatial_fwd_t(const AttnArgs& a, hipStream_t st) {
+  const int D = a.C / a.H, F = a.B * a.T;
   constexpr int WPB = 4;
-  const size_t lds = (size_t)WPB * spatial_lds_floats_host(false, J, D) * sizeof(float);
+  const size_t lds = (size_t)WPB * spatial_lds_floats_host(false, a.J, D) * sizeof(float);
   MP_CHECK(lds <= 160 * 1024, MP_ERR_ARG, "attn_spatial_fwd: LDS %zu too large", lds);
-  hipLaunchKernelGGL((attn_spatial_fwd_kernel<WPB, TS>), dim3(cdiv((long)F * H, WPB)), dim3(WPB * 64), lds, st, qkv, out, F, J, C, H,
-                     D, qk_scale(D));
+  hipLaunchKernelGGL((attn_spatial_fwd_kernel<WPB, TS>), dim3(cdiv((long)F * a.H, WPB)), dim3(WPB * 64), lds, st, (const TS*)a.qkv, (TS*)a.out, F, a.J,
+                     a.C, a.H, D, attn_qk_scale(a.scale, D));
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
 template <typename TS>
-static int spatial_bwd_t(const TS* qkv, const TS* dout, TS* dqkv, int B, int T, int J, int C, int H, hipStream_t st) {
-  const int D = C / H, F = B * T;
+static int spatial_bwd_t(const AttnArgs& a, hipStream_t st) {
+  const int D = a.C / a.H, F = a.B * a.T;
   constexpr int WPB = 2;
-  const size_t lds = (size_t)WPB * spatial_lds_floats_host(true, J, D) * sizeof(float);
+  const size_t lds = (size_t)WPB * spatial_lds_floats_host(true, a.J, D) * sizeof(float);
   MP_CHECK(lds <= 160 * 1024, MP_ERR_ARG, "attn_spatial_bwd: LDS %zu too large", lds);
-  hipLaunchKernelGGL((attn_spatial_bwd_kernel<WPB, TS>), dim3(cdiv((long)F * H, WPB)), dim3(WPB * 64), lds, st, qkv, dout, dqkv, F, J,
-                     C, H, D, qk_scale(D));
+  hipLaunchKernelGGL((attn_spatial_bwd_kernel<WPB, TS>), dim3(cdiv((long)F * a.H, WPB)), dim3(WPB * 64), lds, st, (const TS*)a.qkv, (const TS*)a.dout,
+                     (TS*)a.dqkv, F, a.J, a.C, a.H, D, attn_qk_scale(a.scale, D));
   MP_LAUNCH_CHECK();
   return MP_OK;
-}
-
-bool attn_smfma_supported(int N, int D, int H);
-int attn_smfma_fwd(const bf16* qkv, bf16* out, int B, int T, int J, int C, int H, hipStream_t st);
-int attn_smfma_bwd(const bf16* qkv, const bf16* dout, bf16* dqkv, int B, int T, int J, int C, int H, hipStream_t st);
-
-int attn_spatial_fwd(const void* qkv, void* out, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st) {
-  MP_CHECK(C % H == 0 && (C / H) % 4 == 0 && J <= 32, MP_ERR_ARG, "attn_spatial_fwd: C=%d H=%d J=%d unsupported", C, H, J);
-  if (is_bf16 && attn_smfma_supported(J, C / H, H)) return attn_smfma_fwd((const bf16*)qkv, (bf16*)out, B, T, J, C, H, st);
-  return is_bf16 ? spatial_fwd_t<bf16>((const bf16*)qkv, (bf16*)out, B, T, J, C, H, st)
-                 : spatial_fwd_t<float>((const float*)qkv, (float*)out, B, T, J, C, H, st);
-}
-int attn_spatial_bwd(const void* qkv, const void* dout, void* dqkv, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st) {
-  MP_CHECK(C % H == 0 && (C / H) % 4 == 0 && J <= 32, MP_ERR_ARG, "attn_spatial_bwd: C=%d H=%d J=%d unsupported", C, H, J);
-  if (is_bf16 && attn_smfma_supported(J, C / H, H))
-    return attn_smfma_bwd((const bf16*)qkv, (const bf16*)dout, (bf16*)dqkv, B, T, J, C, H, st);
-  return is_bf16 ? spatial_bwd_t<bf16>((const bf16*)qkv, (const bf16*)dout, (bf16*)dqkv, B, T, J, C, H, st)
-                 : spatial_bwd_t<float>((const float*)qkv, (const float*)dout, (float*)dqkv, B, T, J, C, H, st);
 }
 
 // =============================================================================================
@@ -449,49 +424,70 @@ __global__ __launch_bounds__(256) void attn_temporal_bwd_dkv_kernel(const TS* __
   }
 
 template <typename TS>
-static int temporal_fwd_t(const TS* qkv, TS* out, float* lse, int B, int T, int J, int C, int H, hipStream_t st) {
-  const int D = C / H;
-  dim3 grid(B * J * H, cdiv(T, 256));
-  MP_DISPATCH_D(D, hipLaunchKernelGGL((attn_temporal_fwd_kernel<DD, TS>), grid, dim3(256), 0, st, qkv, out, lse, T, J, C, H, qk_scale(D)));
+static int temporal_fwd_t(const AttnArgs& a, hipStream_t st) {
+  const int D = a.C / a.H, T = a.T, J = a.J, C = a.C, H = a.H;
+  const TS* qkv = (const TS*)a.qkv;
+  TS* out = (TS*)a.out;
+  float* lse = a.lse;
+  const float scale = attn_qk_scale(a.scale, D);
+  dim3 grid(a.B * J * H, cdiv(T, 256));
+  MP_DISPATCH_D(D, hipLaunchKernelGGL((attn_temporal_fwd_kernel<DD, TS>), grid, dim3(256), 0, st, qkv, out, lse, T, J, C, H, scale));
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
 template <typename TS>
-static int temporal_bwd_t(const TS* qkv, const TS* out, const TS* dout, const float* lse, float* delta, TS* dqkv, int B, int T, int J,
-                          int C, int H, hipStream_t st) {
-  const int D = C / H;
-  dim3 grid(B * J * H, cdiv(T, 256));
+static int temporal_bwd_t(const AttnArgs& a, hipStream_t st) {
+  const int D = a.C / a.H, T = a.T, J = a.J, C = a.C, H = a.H;
+  const TS *qkv = (const TS*)a.qkv, *out = (const TS*)a.out, *dout = (const TS*)a.dout;
+  TS* dqkv = (TS*)a.dqkv;
+  const float* lse = a.lse;
+  float* delta = a.delta;
+  const float scale = attn_qk_scale(a.scale, D);
+  dim3 grid(a.B * J * H, cdiv(T, 256));
   // k is pre-multiplied by `scale` in the dK/dV kernel and q in the dQ kernel, so that a = scale * q.k in both
   MP_DISPATCH_D(D, hipLaunchKernelGGL((attn_temporal_bwd_dq_kernel<DD, TS>), grid, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv,
-                                      T, J, C, H, qk_scale(D)));
+                                      T, J, C, H, scale));
   MP_LAUNCH_CHECK();
   MP_DISPATCH_D(D, hipLaunchKernelGGL((attn_temporal_bwd_dkv_kernel<DD, TS>), grid, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, T, J,
-                                      C, H, qk_scale(D)));
+                                      C, H, scale));
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
 
-bool attn_tmfma_supported(int T, int D);
-int attn_tmfma_fwd(const bf16* qkv, bf16* out, float* lse, int B, int T, int J, int C, int H, hipStream_t st);
-int attn_tmfma_bwd(const bf16* qkv, const bf16* out, const bf16* dout, const float* lse, bf16* dqkv, int B, int T, int J, int C, int H,
-                   hipStream_t st, int out_f16);
-
-int attn_temporal_fwd(const void* qkv, void* out, float* lse, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st) {
-  MP_CHECK(C % H == 0, MP_ERR_ARG, "attn_temporal_fwd: C %% H");
-  if (is_bf16 && attn_tmfma_supported(T, C / H)) return attn_tmfma_fwd((const bf16*)qkv, (bf16*)out, lse, B, T, J, C, H, st);
-  return is_bf16 ? temporal_fwd_t<bf16>((const bf16*)qkv, (bf16*)out, lse, B, T, J, C, H, st)
-                 : temporal_fwd_t<float>((const float*)qkv, (float*)out, lse, B, T, J, C, H, st);
+// =============================================================================================
+// the two dispatchers: everything about a launch is in the argument block (kernels.h); bf16 shapes the MFMA kernels cover go to
+// attention_mfma.hip, the rest to the row kernels above
+// =============================================================================================
+int attn_fwd(const AttnArgs& a, int temporal, hipStream_t st) {
+  if (a.form == ATTN_BF16X3) return temporal ? attn_temporal_fwd_x3(a, st) : attn_spatial_fwd_x3(a, st);
+  const bool b16 = a.form == ATTN_BF16;
+  if (temporal) {
+    MP_CHECK(a.C % a.H == 0, MP_ERR_ARG, "attn_temporal_fwd: C %% H");
+    if (b16 && attn_tmfma_supported(a.T, a.C / a.H)) return attn_tmfma_fwd(a, st);
+    return b16 ? temporal_fwd_t<bf16>(a, st) : temporal_fwd_t<float>(a, st);
+  }
+  MP_CHECK(a.C % a.H == 0 && (a.C / a.H) % 4 == 0 && a.J <= 32, MP_ERR_ARG, "attn_spatial_fwd: C=%d H=%d J=%d unsupported", a.C, a.H, a.J);
+  if (b16 && attn_smfma_supported(a.J, a.C / a.H, a.H)) return attn_smfma_fwd(a, st);
+  return b16 ? spatial_fwd_t<bf16>(a, st) : spatial_fwd_t<float>(a, st);
 }
-int attn_temporal_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int is_bf16,
-                      int B, int T, int J, int C, int H, hipStream_t st, int out_f16) {
-  MP_CHECK(C % H == 0, MP_ERR_ARG, "attn_temporal_bwd: C %% H");
-  if (is_bf16 && attn_tmfma_supported(T, C / H))
-    return attn_tmfma_bwd((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, B, T, J, C, H, st, out_f16);
-  // the row kernels below read O in the storage type of qkv: an fp16 O plane would be taken for bf16 bits
-  MP_CHECK(!out_f16, MP_ERR_ARG, "attn_temporal_bwd: O as an fp16 plane needs the MFMA backward (T=%d, head dim %d, is_bf16 %d)", T, C / H, is_bf16);
-  return is_bf16 ? temporal_bwd_t<bf16>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, B, T, J, C, H, st)
-                 : temporal_bwd_t<float>((const float*)qkv, (const float*)out, (const float*)dout, lse, delta, (float*)dqkv, B, T, J, C,
-                                         H, st);
+int attn_bwd(const AttnArgs& a, int temporal, hipStream_t st) {
+  MP_CHECK(a.form == ATTN_F32 || a.form == ATTN_BF16, MP_ERR_ARG, "attn_bwd: storage form %d has no backward", a.form);
+  const bool b16 = a.form == ATTN_BF16;
+  const char* who = temporal ? "attn_temporal_bwd" : "attn_spatial_bwd";
+  if (temporal) {
+    MP_CHECK(a.C % a.H == 0, MP_ERR_ARG, "attn_temporal_bwd: C %% H");
+    if (b16 && attn_tmfma_supported(a.T, a.C / a.H)) return attn_tmfma_bwd(a, st);
+  } else {
+    MP_CHECK(a.C % a.H == 0 && (a.C / a.H) % 4 == 0 && a.J <= 32, MP_ERR_ARG, "attn_spatial_bwd: C=%d H=%d J=%d unsupported", a.C, a.H, a.J);
+    if (b16 && attn_smfma_supported(a.J, a.C / a.H, a.H)) return attn_smfma_bwd(a, st);
+  }
+  // the row kernels below read O and write dQ / dK / dV in the storage type of qkv: an fp16 O plane would be taken for bf16 bits, and a caller
+  // that asked for scaled fp16 gradients would be handed bf16
+  MP_CHECK(!a.out_f16 || !temporal, MP_ERR_ARG, "attn_temporal_bwd: O as an fp16 plane needs the MFMA backward (T=%d, head dim %d, is_bf16 %d)", a.T, a.C / a.H, (int)b16);
+  MP_CHECK(a.grad_f16 == nullptr, MP_ERR_ARG, "%s: scaled fp16 gradients need the MFMA backward (T=%d J=%d, head dim %d, H=%d, is_bf16 %d)", who, a.T, a.J,
+           a.C / a.H, a.H, (int)b16);
+  if (temporal) return b16 ? temporal_bwd_t<bf16>(a, st) : temporal_bwd_t<float>(a, st);
+  return b16 ? spatial_bwd_t<bf16>(a, st) : spatial_bwd_t<float>(a, st);
 }
 
 }  // namespace mp

@@ -193,9 +193,7 @@ __device__ __forceinline__ void store4g(bf16* p, const f32x4& v, float s, float 
     *reinterpret_cast<uint2*>(p) = sat_f16x4(v[0] * s, v[1] * s, v[2] * s, v[3] * s, cnt);      // saturating: common.h
   } else store4(p, v, s);
 }
-// set by the engine for the backward launches issued next on this thread: device address of the scale (null = bf16 outputs); see store4g
-static thread_local const float* g_grad_f16 = nullptr;
-void attn_grad_f16_override(const float* gout) { g_grad_f16 = gout; }
+// (the launchers choose F16G by AttnArgs::grad_f16, kernels.h: the device address of the scale, null = bf16 outputs)
 
 // =============================================================================================
 // forward: O = softmax(scale Q K^T) V ; lse = log sum exp of the scaled scores
@@ -753,13 +751,14 @@ __global__ __launch_bounds__(512) void attn_smfma_bwd_kernel(const bf16* __restr
   (void)pA;
 }
 
-float attn_qk_scale(int D);      // attention.hip: head_dim ** -0.5 or the engine's override (muP)
 bool attn_smfma_supported(int N, int D, int H) { return N >= 16 && N <= 32 && (D == 64 || D == 16) && H >= 1 && H <= 8; }
 
-int attn_smfma_fwd(const bf16* qkv, bf16* out, int B, int T, int J, int C, int H, hipStream_t st) {
-  const int D = C / H;
+int attn_smfma_fwd(const AttnArgs& a, hipStream_t st) {
+  const int J = a.J, C = a.C, H = a.H, D = C / H;
   MP_CHECK(attn_smfma_supported(J, D, H) && C % 8 == 0, MP_ERR_ARG, "attn_smfma_fwd: J=%d D=%d H=%d unsupported", J, D, H);
-  const float scale = attn_qk_scale(D);
+  const bf16* qkv = (const bf16*)a.qkv;
+  bf16* out = (bf16*)a.out;
+  const float scale = attn_qk_scale(a.scale, D);
   const size_t lds = (size_t)J * (6 * C + 16);
   if (D == 64) {
     static bool attr_set = false;
@@ -767,19 +766,24 @@ int attn_smfma_fwd(const bf16* qkv, bf16* out, int B, int T, int J, int C, int H
       MP_HIP(hipFuncSetAttribute((const void*)attn_smfma_fwd_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr_set = true;
     }
-    hipLaunchKernelGGL(attn_smfma_fwd_kernel<64>, dim3(B * T), dim3(H * 64), lds, st, qkv, out, J, C, H, scale);
+    hipLaunchKernelGGL(attn_smfma_fwd_kernel<64>, dim3(a.B * a.T), dim3(H * 64), lds, st, qkv, out, J, C, H, scale);
   } else {
-    hipLaunchKernelGGL(attn_smfma_fwd_kernel<16>, dim3(B * T), dim3(H * 64), lds, st, qkv, out, J, C, H, scale);
+    hipLaunchKernelGGL(attn_smfma_fwd_kernel<16>, dim3(a.B * a.T), dim3(H * 64), lds, st, qkv, out, J, C, H, scale);
   }
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
 
-int attn_smfma_bwd(const bf16* qkv, const bf16* dout, bf16* dqkv, int B, int T, int J, int C, int H, hipStream_t st) {
-  const int D = C / H;
+template <int D, bool F16G>
+static void launch_smfma_bwd(const AttnArgs& a, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL((attn_smfma_bwd_kernel<D, F16G>), dim3(a.B * a.T), dim3(a.H * 64), lds, st, (const bf16*)a.qkv, (const bf16*)a.dout, (bf16*)a.dqkv, a.J,
+                     a.C, a.H, attn_qk_scale(a.scale, D), a.grad_f16);
+}
+int attn_smfma_bwd(const AttnArgs& a, hipStream_t st) {
+  const int J = a.J, C = a.C, H = a.H, D = C / H;
   MP_CHECK(attn_smfma_supported(J, D, H) && C % 8 == 0, MP_ERR_ARG, "attn_smfma_bwd: J=%d D=%d H=%d unsupported", J, D, H);
-  const float scale = attn_qk_scale(D);
   const size_t lds = (size_t)J * (6 * C + 16) + (size_t)J * (2 * C + 16);
+  const bool f16g = a.grad_f16 != nullptr;
   if (D == 64) {
     static bool attr_set = false;
     if (!attr_set) {
@@ -787,11 +791,9 @@ int attn_smfma_bwd(const bf16* qkv, const bf16* dout, bf16* dqkv, int B, int T, 
       MP_HIP(hipFuncSetAttribute((const void*)attn_smfma_bwd_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr_set = true;
     }
-    if (g_grad_f16 != nullptr) hipLaunchKernelGGL((attn_smfma_bwd_kernel<64, true>), dim3(B * T), dim3(H * 64), lds, st, qkv, dout, dqkv, J, C, H, scale, g_grad_f16);
-    else hipLaunchKernelGGL((attn_smfma_bwd_kernel<64, false>), dim3(B * T), dim3(H * 64), lds, st, qkv, dout, dqkv, J, C, H, scale, g_grad_f16);
+    f16g ? launch_smfma_bwd<64, true>(a, lds, st) : launch_smfma_bwd<64, false>(a, lds, st);
   } else {
-    if (g_grad_f16 != nullptr) hipLaunchKernelGGL((attn_smfma_bwd_kernel<16, true>), dim3(B * T), dim3(H * 64), lds, st, qkv, dout, dqkv, J, C, H, scale, g_grad_f16);
-    else hipLaunchKernelGGL((attn_smfma_bwd_kernel<16, false>), dim3(B * T), dim3(H * 64), lds, st, qkv, dout, dqkv, J, C, H, scale, g_grad_f16);
+    f16g ? launch_smfma_bwd<16, true>(a, lds, st) : launch_smfma_bwd<16, false>(a, lds, st);
   }
   MP_LAUNCH_CHECK();
   return MP_OK;
@@ -1338,7 +1340,6 @@ static int num_cus() {
   }
   return n;
 }
-bool attn_tmfma_supported(int T, int D);
 bool attn_x3_needs_scratch(int temporal, int T, int J, int C, int H) {
   const int D = C / H;
   if (temporal) return !(attn_tmfma_supported(T, D) && C % 8 == 0);
@@ -1346,21 +1347,32 @@ bool attn_x3_needs_scratch(int temporal, int T, int J, int C, int H) {
   return !(attn_smfma_supported(J, D, H) && C % 8 == 0 && 2L * J * (6 * C + 16) <= 160 * 1024 && (long)J * (6 * C / 16) <= 7L * H * 64);
 }
 
-int attn_spatial_fwd_x3(const bf16* qkv_hi, const bf16* qkv_lo, bf16* out_hi, bf16* out_lo, float* scratch, int B, int T, int J, int C, int H,
-                        hipStream_t st, int out_f16f8) {
+// shapes the MFMA kernels do not cover: the planes are joined to fp32 in the scratch, the fp32 row kernel runs there - with THIS launch's softmax
+// scale - and its result is split into the output planes
+static int fwd_x3_by_fp32(const AttnArgs& a, int temporal, hipStream_t st) {
+  const long M = (long)a.B * a.T * a.J;
+  int rc = join_planes((const bf16*)a.qkv, (const bf16*)a.qkv_lo, a.scratch, 3 * M * a.C, st);
+  if (rc) return rc;
+  AttnArgs f = {};
+  f.qkv = a.scratch; f.out = a.scratch + 3 * M * a.C; f.lse = a.lse; f.B = a.B; f.T = a.T; f.J = a.J; f.C = a.C; f.H = a.H; f.form = ATTN_F32;
+  f.scale = a.scale;
+  rc = attn_fwd(f, temporal, st);
+  if (rc) return rc;
+  return split_planes(a.scratch + 3 * M * a.C, (bf16*)a.out, (bf16*)a.out_lo, M * a.C, st);
+}
+
+int attn_spatial_fwd_x3(const AttnArgs& a, hipStream_t st) {
+  const int B = a.B, T = a.T, J = a.J, C = a.C, H = a.H, out_f16f8 = a.out_f16f8;
+  const bf16 *qkv_hi = (const bf16*)a.qkv, *qkv_lo = (const bf16*)a.qkv_lo;
+  bf16 *out_hi = (bf16*)a.out, *out_lo = (bf16*)a.out_lo;
   MP_CHECK(C % H == 0 && C % 4 == 0, MP_ERR_ARG, "attn_spatial_fwd_x3: C=%d H=%d", C, H);
   const int D = C / H;
-  const long M = (long)B * T * J;
   MP_CHECK(!out_f16f8 || (D == 64 && !attn_x3_needs_scratch(0, T, J, C, H)), MP_ERR_ARG, "attn_spatial_fwd_x3: f16f8 output needs head dim 64 and the MFMA kernel (J=%d C=%d H=%d)", J, C, H);
   if (attn_x3_needs_scratch(0, T, J, C, H)) {
-    MP_CHECK(scratch != nullptr, MP_ERR_ARG, "attn_spatial_fwd_x3: J=%d D=%d H=%d needs the fp32 scratch", J, D, H);
-    int rc = join_planes(qkv_hi, qkv_lo, scratch, 3 * M * C, st);
-    if (rc) return rc;
-    rc = attn_spatial_fwd(scratch, scratch + 3 * M * C, 0, B, T, J, C, H, st);
-    if (rc) return rc;
-    return split_planes(scratch + 3 * M * C, out_hi, out_lo, M * C, st);
+    MP_CHECK(a.scratch != nullptr, MP_ERR_ARG, "attn_spatial_fwd_x3: J=%d D=%d H=%d needs the fp32 scratch", J, D, H);
+    return fwd_x3_by_fp32(a, 0, st);
   }
-  const float scale = attn_qk_scale(D);
+  const float scale = attn_qk_scale(a.scale, D);
   const size_t lds = 2 * (size_t)J * (6 * C + 16);
   MP_CHECK(lds <= 160 * 1024, MP_ERR_ARG, "attn_spatial_fwd_x3: frame block of %zu bytes exceeds the LDS", lds);
   MP_CHECK((long)J * (6 * C / 16) <= 7L * H * 64, MP_ERR_ARG, "attn_spatial_fwd_x3: frame block too large for the register prefetch (J=%d C=%d H=%d)", J, C, H);
@@ -1401,8 +1413,12 @@ int attn_spatial_fwd_x3(const bf16* qkv_hi, const bf16* qkv_lo, bf16* out_hi, bf
 #define ATTN_X3P_FULL_GUARD
 #endif
 template <int D, bool F8O = false>
-static int launch_tmfma_fwd_x3(const bf16* qkv_hi, const bf16* qkv_lo, bf16* out_hi, bf16* out_lo, float* lse, int units, int T, int J, int C,
-                               int H, float scale, hipStream_t st) {
+static int launch_tmfma_fwd_x3(const AttnArgs& a, hipStream_t st) {
+  const int T = a.T, J = a.J, C = a.C, H = a.H, units = a.B * J * H;
+  const bf16 *qkv_hi = (const bf16*)a.qkv, *qkv_lo = (const bf16*)a.qkv_lo;
+  bf16 *out_hi = (bf16*)a.out, *out_lo = (bf16*)a.out_lo;
+  float* lse = a.lse;
+  const float scale = attn_qk_scale(a.scale, D);
   const int ntile = (T + 15) >> 4;
   const int rows = (T + 31) & ~31;
   // waves: two query strips each, and enough threads that an image is at most 4 chunks per thread (register prefetch)
@@ -1429,23 +1445,21 @@ static int launch_tmfma_fwd_x3(const bf16* qkv_hi, const bf16* qkv_lo, bf16* out
   return MP_OK;
 }
 
-int attn_temporal_fwd_x3(const bf16* qkv_hi, const bf16* qkv_lo, bf16* out_hi, bf16* out_lo, float* lse, float* scratch, int B, int T, int J,
-                         int C, int H, hipStream_t st, int out_f16f8) {
+int attn_temporal_fwd_x3(const AttnArgs& a, hipStream_t st) {
+  const int B = a.B, T = a.T, J = a.J, C = a.C, H = a.H, out_f16f8 = a.out_f16f8;
   MP_CHECK(C % H == 0 && C % 4 == 0, MP_ERR_ARG, "attn_temporal_fwd_x3: C=%d H=%d", C, H);
   const int D = C / H;
-  const long M = (long)B * T * J;
   MP_CHECK(!out_f16f8 || (D == 64 && !attn_x3_needs_scratch(1, T, J, C, H)), MP_ERR_ARG, "attn_temporal_fwd_x3: f16f8 output needs head dim 64 and the MFMA kernel (T=%d C=%d H=%d)", T, C, H);
   if (attn_x3_needs_scratch(1, T, J, C, H)) {
-    MP_CHECK(scratch != nullptr, MP_ERR_ARG, "attn_temporal_fwd_x3: T=%d D=%d needs the fp32 scratch", T, D);
-    int rc = join_planes(qkv_hi, qkv_lo, scratch, 3 * M * C, st);
-    if (rc) return rc;
-    rc = attn_temporal_fwd(scratch, scratch + 3 * M * C, lse, 0, B, T, J, C, H, st);
-    if (rc) return rc;
-    return split_planes(scratch + 3 * M * C, out_hi, out_lo, M * C, st);
+    MP_CHECK(a.scratch != nullptr, MP_ERR_ARG, "attn_temporal_fwd_x3: T=%d D=%d needs the fp32 scratch", T, D);
+    return fwd_x3_by_fp32(a, 1, st);
   }
-  const float scale = attn_qk_scale(D);
-  const int units = B * J * H;
   if (D == 64 && T > 128 && (g_attn_two_phase & 1) && (C * 2) % 128 == 0 && (3L * C * 2) % 16 == 0) {
+    const bf16 *qkv_hi = (const bf16*)a.qkv, *qkv_lo = (const bf16*)a.qkv_lo;
+    bf16 *out_hi = (bf16*)a.out, *out_lo = (bf16*)a.out_lo;
+    float* lse = a.lse;
+    const float scale = attn_qk_scale(a.scale, D);
+    const int units = B * J * H;
     const int rows = (T + 31) & ~31;
     const size_t lds = 4 * (size_t)rows * 128 + 8 * 16 * 144;
     static bool attr_set = false;
@@ -1468,18 +1482,18 @@ int attn_temporal_fwd_x3(const bf16* qkv_hi, const bf16* qkv_lo, bf16* out_hi, b
     MP_LAUNCH_CHECK();
     return MP_OK;
   }
-  if (D == 64 && out_f16f8) return launch_tmfma_fwd_x3<64, true>(qkv_hi, qkv_lo, out_hi, out_lo, lse, units, T, J, C, H, scale, st);
-  if (D == 64) return launch_tmfma_fwd_x3<64>(qkv_hi, qkv_lo, out_hi, out_lo, lse, units, T, J, C, H, scale, st);
-  return launch_tmfma_fwd_x3<16>(qkv_hi, qkv_lo, out_hi, out_lo, lse, units, T, J, C, H, scale, st);
+  if (D == 64 && out_f16f8) return launch_tmfma_fwd_x3<64, true>(a, st);
+  if (D == 64) return launch_tmfma_fwd_x3<64>(a, st);
+  return launch_tmfma_fwd_x3<16>(a, st);
 }
 
 bool attn_tmfma_supported(int T, int D) { return T <= TP && (D == 64 || D == 16); }
 
 template <int D, int NTC>
-static int launch_tmfma_fwd(const bf16* qkv, bf16* out, float* lse, int units, int T, int J, int C, int H, float scale, hipStream_t st) {
+static int launch_tmfma_fwd(const AttnArgs& a, hipStream_t st) {
   // waves per workgroup: two 16-query strips per wave up to 128 frames (more, smaller workgroups per CU overlap their load / compute /
   // store phases: T=81 602 -> 442 us, T=128 443 -> 428 us, T=27 411 -> 387 us at the bench's token count), 8 waves beyond
-  const int ntile = (T + 15) >> 4;
+  const int T = a.T, ntile = (T + 15) >> 4;
   const int waves = NTC ? 8 : (ntile <= 8 ? (ntile + 1) / 2 : 8);
   const int rows = NTC ? TP : (T + 31) & ~31;
   const size_t lds = 2 * (size_t)rows * ACfg<D>::ROWB;
@@ -1489,60 +1503,53 @@ static int launch_tmfma_fwd(const bf16* qkv, bf16* out, float* lse, int units, i
                                (int)(2 * TP * ACfg<D>::ROWB)));
     attr_set = true;
   }
-  hipLaunchKernelGGL((attn_tmfma_fwd_kernel<D, NTC>), dim3(units), dim3(64 * waves), lds, st, qkv, out, lse, T, J, C, H, scale);
+  hipLaunchKernelGGL((attn_tmfma_fwd_kernel<D, NTC>), dim3(a.B * a.J * a.H), dim3(64 * waves), lds, st, (const bf16*)a.qkv, (bf16*)a.out, a.lse, T, a.J, a.C,
+                     a.H, attn_qk_scale(a.scale, D));
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
-int attn_tmfma_fwd(const bf16* qkv, bf16* out, float* lse, int B, int T, int J, int C, int H, hipStream_t st) {
-  const int D = C / H;
-  MP_CHECK(attn_tmfma_supported(T, D) && C % 8 == 0, MP_ERR_ARG, "attn_tmfma_fwd: T=%d D=%d unsupported", T, D);
-  const float scale = attn_qk_scale(D);
-  const int units = B * J * H;
+int attn_tmfma_fwd(const AttnArgs& a, hipStream_t st) {
+  const int D = a.C / a.H;
+  MP_CHECK(attn_tmfma_supported(a.T, D) && a.C % 8 == 0, MP_ERR_ARG, "attn_tmfma_fwd: T=%d D=%d unsupported", a.T, D);
   // (run-time tile count only: with a compile-time count the scheduler hoists across the whole score strip and spills)
-  if (D == 64) return launch_tmfma_fwd<64, 0>(qkv, out, lse, units, T, J, C, H, scale, st);
-  return launch_tmfma_fwd<16, 0>(qkv, out, lse, units, T, J, C, H, scale, st);
+  if (D == 64) return launch_tmfma_fwd<64, 0>(a, st);
+  return launch_tmfma_fwd<16, 0>(a, st);
 }
 
-template <int D, int NTC>
-static int launch_tmfma_bwd(const bf16* qkv, const bf16* out, const bf16* dout, const float* lse, bf16* dqkv, int units, int T, int J, int C,
-                            int H, float scale, int dbg, hipStream_t st, int out_f16) {
+template <int D, int NTC, bool F16G>
+static int launch_tmfma_bwd_g(const AttnArgs& a, hipStream_t st) {
   // waves per workgroup: one per 16-frame strip, except 4 for 5-7 strips (T=81: 971 -> 906 us; 8 strips and more measured best at one each)
-  const int ntile = (T + 15) >> 4;
+  const int T = a.T, ntile = (T + 15) >> 4;
   const int waves = NTC ? 16 : ((ntile >= 5 && ntile <= 7) ? 4 : min(16, ntile));
   const int rows = NTC ? TP : (T + 31) & ~31;
   const size_t lds = 4 * (size_t)rows * ACfg<D>::ROWB + 2 * rows * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    MP_HIP(hipFuncSetAttribute((const void*)attn_tmfma_bwd_kernel<D, NTC, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(4 * TP * ACfg<D>::ROWB + 2 * TP * sizeof(float))));
-    MP_HIP(hipFuncSetAttribute((const void*)attn_tmfma_bwd_kernel<D, NTC, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    MP_HIP(hipFuncSetAttribute((const void*)attn_tmfma_bwd_kernel<D, NTC, F16G>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)(4 * TP * ACfg<D>::ROWB + 2 * TP * sizeof(float))));
     attr_set = true;
   }
-  if (g_grad_f16 != nullptr)
-    hipLaunchKernelGGL((attn_tmfma_bwd_kernel<D, NTC, true>), dim3(units), dim3(64 * waves), lds, st, qkv, out, dout, lse, dqkv, T, J, C, H, scale, dbg, g_grad_f16, out_f16);
-  else
-    hipLaunchKernelGGL((attn_tmfma_bwd_kernel<D, NTC, false>), dim3(units), dim3(64 * waves), lds, st, qkv, out, dout, lse, dqkv, T, J, C, H, scale, dbg, g_grad_f16, out_f16);
-  MP_LAUNCH_CHECK();
-  return MP_OK;
-}
-int attn_tmfma_bwd(const bf16* qkv, const bf16* out, const bf16* dout, const float* lse, bf16* dqkv, int B, int T, int J, int C, int H,
-                   hipStream_t st, int out_f16) {
-  const int D = C / H;
-  MP_CHECK(attn_tmfma_supported(T, D) && C % 8 == 0, MP_ERR_ARG, "attn_tmfma_bwd: T=%d D=%d unsupported", T, D);
-  const float scale = attn_qk_scale(D);
-  const int units = B * J * H;
   // timing ablations (1 staging only, 2 no dK/dV pass: results wrong by design) exist in the diagnostics build only
 #ifdef MP_GEMM_DIAG
   static const int dbg = [] { const char* e = getenv("MANIPOSE_ATTN_DEBUG"); return e ? atoi(e) : 0; }();
 #else
   constexpr int dbg = 0;
 #endif
-  const bool full = T > 240;
-  if (D == 64) return full ? launch_tmfma_bwd<64, 16>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st, out_f16)
-                           : launch_tmfma_bwd<64, 0>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st, out_f16);
-  return full ? launch_tmfma_bwd<16, 16>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st, out_f16)
-              : launch_tmfma_bwd<16, 0>(qkv, out, dout, lse, dqkv, units, T, J, C, H, scale, dbg, st, out_f16);
+  hipLaunchKernelGGL((attn_tmfma_bwd_kernel<D, NTC, F16G>), dim3(a.B * a.J * a.H), dim3(64 * waves), lds, st, (const bf16*)a.qkv, (const bf16*)a.out,
+                     (const bf16*)a.dout, a.lse, (bf16*)a.dqkv, T, a.J, a.C, a.H, attn_qk_scale(a.scale, D), dbg, a.grad_f16, a.out_f16);
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+template <int D, int NTC>
+static int launch_tmfma_bwd(const AttnArgs& a, hipStream_t st) {
+  return a.grad_f16 != nullptr ? launch_tmfma_bwd_g<D, NTC, true>(a, st) : launch_tmfma_bwd_g<D, NTC, false>(a, st);
+}
+int attn_tmfma_bwd(const AttnArgs& a, hipStream_t st) {
+  const int D = a.C / a.H;
+  MP_CHECK(attn_tmfma_supported(a.T, D) && a.C % 8 == 0, MP_ERR_ARG, "attn_tmfma_bwd: T=%d D=%d unsupported", a.T, D);
+  const bool full = a.T > 240;
+  if (D == 64) return full ? launch_tmfma_bwd<64, 16>(a, st) : launch_tmfma_bwd<64, 0>(a, st);
+  return full ? launch_tmfma_bwd<16, 16>(a, st) : launch_tmfma_bwd<16, 0>(a, st);
 }
 
 }  // namespace mp

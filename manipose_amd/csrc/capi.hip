@@ -7,8 +7,6 @@
 namespace mp {
 const char* last_error();
 long wgrad_f32_slab_floats(int Mtok, int Nout, int Kin);
-bool attn_tmfma_supported(int T, int D);            // attention_mfma.hip
-bool attn_smfma_supported(int N, int D, int H);
 }
 using namespace mp;
 
@@ -17,6 +15,40 @@ static LossCfg to_cfg(const mp_loss_config* c) {
   l.beta = c->rmcl_score_reg; l.vel_w = c->vel_loss; l.smooth_w = c->smooth_reg; l.use_joint_weights = c->w_loss; l.squared = c->sq_loss;
   for (int j = 0; j < 17; ++j) l.joint_weights[j] = c->joint_weights[j];
   return l;
+}
+
+// The ten attention entry points: check, fill the argument block (kernels.h AttnArgs), call.  `who` names the entry point in the messages; a
+// plain entry point is its _ex / _scale_ex form at the defaults, which pass those forms' further checks.
+static int attention_fwd(const char* who, int form, const void* qkv, void* out, float* lse, int temporal, int B, int T, int J, int C, int H,
+                         float qk_scale, void* stream) {
+  MP_CHECK(qkv && out && (!temporal || lse), MP_ERR_ARG, "%s: null pointer", who);
+  MP_CHECK(qk_scale >= 0.f && qk_scale <= 3.0e38f, MP_ERR_ARG, "%s: qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)", who);
+  AttnArgs a = {};
+  a.qkv = qkv; a.out = out; a.lse = lse; a.B = B; a.T = T; a.J = J; a.C = C; a.H = H; a.form = form; a.scale = qk_scale;
+  return attn_fwd(a, temporal, (hipStream_t)stream);
+}
+static int attention_bwd(const char* who, int form, const void* qkv, const void* out, const void* d_out, const float* lse, float* delta, void* d_qkv,
+                         int temporal, int B, int T, int J, int C, int H, int out_f16, float qk_scale, const float* grad_scale, void* stream) {
+  MP_CHECK(qkv && d_out && d_qkv && (!temporal || (out && lse && delta)), MP_ERR_ARG, "%s: null pointer", who);
+  MP_CHECK(!out_f16 || temporal, MP_ERR_ARG, "%s: only the temporal backward reads O", who);
+  MP_CHECK(qk_scale >= 0.f && qk_scale <= 3.0e38f, MP_ERR_ARG, "%s: qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)", who);
+  if (grad_scale != nullptr) {      // the row kernels know no fp16 store (attn_bwd refuses too; this message names the shape as the caller gave it)
+    const bool mfma = H > 0 && C % H == 0 && C % 8 == 0 && (temporal ? attn_tmfma_supported(T, C / H) : attn_smfma_supported(J, C / H, H));
+    MP_CHECK(mfma, MP_ERR_ARG, "%s: scaled fp16 gradients need an MFMA backward (temporal %d, T=%d J=%d C=%d H=%d)", who, temporal, T, J, C, H);
+  }
+  AttnArgs a = {};
+  a.qkv = qkv; a.out = const_cast<void*>(out); a.dout = d_out; a.dqkv = d_qkv; a.lse = const_cast<float*>(lse); a.delta = delta;
+  a.B = B; a.T = T; a.J = J; a.C = C; a.H = H; a.form = form; a.scale = qk_scale; a.grad_f16 = grad_scale; a.out_f16 = out_f16;
+  return attn_bwd(a, temporal, (hipStream_t)stream);
+}
+static int attention_fwd_x3(const char* who, const char* bad, const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, float* scratch,
+                            int temporal, int B, int T, int J, int C, int H, int out_form, float qk_scale, void* stream) {
+  MP_CHECK(qkv_hi && qkv_lo && out_hi && out_lo && (!temporal || lse) && (out_form == 0 || out_form == 1), MP_ERR_ARG, "%s: %s", who, bad);
+  MP_CHECK(qk_scale >= 0.f && qk_scale <= 3.0e38f, MP_ERR_ARG, "%s: qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)", who);
+  AttnArgs a = {};
+  a.qkv = qkv_hi; a.qkv_lo = qkv_lo; a.out = out_hi; a.out_lo = out_lo; a.lse = lse; a.scratch = scratch;
+  a.B = B; a.T = T; a.J = J; a.C = C; a.H = H; a.form = ATTN_BF16X3; a.scale = qk_scale; a.out_f16f8 = out_form;
+  return attn_fwd(a, temporal, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -134,27 +166,19 @@ int mp_linear_bwd_bf16(const void* dy, int dy_f32, const void* x, const void* W,
 }
 
 int mp_attention_fwd(const float* qkv, float* out, float* lse, int temporal, int B, int T, int J, int C, int H, void* stream) {
-  MP_CHECK(qkv && out && (!temporal || lse), MP_ERR_ARG, "mp_attention_fwd: null pointer");
-  return temporal ? attn_temporal_fwd(qkv, out, lse, 0, B, T, J, C, H, (hipStream_t)stream)
-                  : attn_spatial_fwd(qkv, out, 0, B, T, J, C, H, (hipStream_t)stream);
+  return attention_fwd("mp_attention_fwd", ATTN_F32, qkv, out, lse, temporal, B, T, J, C, H, 0.f, stream);
 }
 int mp_attention_bwd(const float* qkv, const float* out, const float* d_out, const float* lse, float* delta, float* d_qkv,
                      int temporal, int B, int T, int J, int C, int H, void* stream) {
-  MP_CHECK(qkv && d_out && d_qkv && (!temporal || (out && lse && delta)), MP_ERR_ARG, "mp_attention_bwd: null pointer");
-  return temporal ? attn_temporal_bwd(qkv, out, d_out, lse, delta, d_qkv, 0, B, T, J, C, H, (hipStream_t)stream)
-                  : attn_spatial_bwd(qkv, d_out, d_qkv, 0, B, T, J, C, H, (hipStream_t)stream);
+  return attention_bwd("mp_attention_bwd", ATTN_F32, qkv, out, d_out, lse, delta, d_qkv, temporal, B, T, J, C, H, 0, 0.f, nullptr, stream);
 }
 
 int mp_attention_fwd_bf16(const void* qkv, void* out, float* lse, int temporal, int B, int T, int J, int C, int H, void* stream) {
-  MP_CHECK(qkv && out && (!temporal || lse), MP_ERR_ARG, "mp_attention_fwd_bf16: null pointer");
-  return temporal ? attn_temporal_fwd(qkv, out, lse, 1, B, T, J, C, H, (hipStream_t)stream)
-                  : attn_spatial_fwd(qkv, out, 1, B, T, J, C, H, (hipStream_t)stream);
+  return attention_fwd("mp_attention_fwd_bf16", ATTN_BF16, qkv, out, lse, temporal, B, T, J, C, H, 0.f, stream);
 }
 int mp_attention_bwd_bf16(const void* qkv, const void* out, const void* d_out, const float* lse, float* delta, void* d_qkv,
                           int temporal, int B, int T, int J, int C, int H, void* stream) {
-  MP_CHECK(qkv && d_out && d_qkv && (!temporal || (out && lse && delta)), MP_ERR_ARG, "mp_attention_bwd_bf16: null pointer");
-  return temporal ? attn_temporal_bwd(qkv, out, d_out, lse, delta, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream)
-                  : attn_spatial_bwd(qkv, d_out, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream);
+  return attention_bwd("mp_attention_bwd_bf16", ATTN_BF16, qkv, out, d_out, lse, delta, d_qkv, temporal, B, T, J, C, H, 0, 0.f, nullptr, stream);
 }
 
 /* split precision ("bf16x3"): planar hi/lo bf16 operands, three matrix-core products per k-tile */
@@ -198,11 +222,7 @@ int mp_linear_fwd_f16f8(const void* x16, const void* x8, const void* W16, const 
 }
 int mp_attention_fwd_bf16x3(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, float* scratch, int temporal,
                             int B, int T, int J, int C, int H, void* stream) {
-  MP_CHECK(qkv_hi && qkv_lo && out_hi && out_lo && (!temporal || lse), MP_ERR_ARG, "mp_attention_fwd_bf16x3: null pointer");
-  return temporal ? attn_temporal_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, lse, scratch, B, T, J, C, H,
-                                         (hipStream_t)stream)
-                  : attn_spatial_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, scratch, B, T, J, C, H,
-                                        (hipStream_t)stream);
+  return attention_fwd_x3("mp_attention_fwd_bf16x3", "null pointer", qkv_hi, qkv_lo, out_hi, out_lo, lse, scratch, temporal, B, T, J, C, H, 0, 0.f, stream);
 }
 
 /* unit-test entry points of the f16f8 forms the engine launches (include/manipose_hip.h): each fills the argument block engine.hip fills
@@ -238,69 +258,27 @@ int mp_layernorm_fwd_ex(const float* x, int M, int C, const float* g1, const flo
 }
 int mp_attention_fwd_bf16x3_ex(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, float* scratch, int temporal,
                                int B, int T, int J, int C, int H, int out_form, void* stream) {
-  MP_CHECK(qkv_hi && qkv_lo && out_hi && out_lo && (!temporal || lse) && (out_form == 0 || out_form == 1), MP_ERR_ARG,
-           "mp_attention_fwd_bf16x3_ex: bad argument");
-  return temporal ? attn_temporal_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, lse, scratch, B, T, J, C, H,
-                                         (hipStream_t)stream, out_form)
-                  : attn_spatial_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, scratch, B, T, J, C, H,
-                                        (hipStream_t)stream, out_form);
+  return attention_fwd_x3("mp_attention_fwd_bf16x3_ex", "bad argument", qkv_hi, qkv_lo, out_hi, out_lo, lse, scratch, temporal, B, T, J, C, H, out_form, 0.f,
+                          stream);
 }
 int mp_attention_bwd_bf16_ex(const void* qkv, const void* out, const void* d_out, const float* lse, float* delta, void* d_qkv, int temporal, int B,
                              int T, int J, int C, int H, int out_f16, void* stream) {
-  MP_CHECK(qkv && d_out && d_qkv && (!temporal || (out && lse && delta)), MP_ERR_ARG, "mp_attention_bwd_bf16_ex: null pointer");
-  MP_CHECK(!out_f16 || temporal, MP_ERR_ARG, "mp_attention_bwd_bf16_ex: only the temporal backward reads O");
-  return temporal ? attn_temporal_bwd(qkv, out, d_out, lse, delta, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream, out_f16)
-                  : attn_spatial_bwd(qkv, d_out, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream);
+  return attention_bwd("mp_attention_bwd_bf16_ex", ATTN_BF16, qkv, out, d_out, lse, delta, d_qkv, temporal, B, T, J, C, H, out_f16, 0.f, nullptr, stream);
 }
-/* the attention forms only the engine reaches: a softmax scale of its own (attn_scale_override) and the scaled-fp16 gradient stores of the
- * MFMA backward kernels (attn_grad_f16_override); both are thread-local settings of the launches issued next, reset on every exit path */
-namespace {
-struct AttnScaleScope {
-  explicit AttnScaleScope(float s) { attn_scale_override(s); }
-  ~AttnScaleScope() { attn_scale_override(0.f); }
-  AttnScaleScope(const AttnScaleScope&) = delete;
-  AttnScaleScope& operator=(const AttnScaleScope&) = delete;
-};
-struct AttnGradF16Scope {
-  explicit AttnGradF16Scope(const float* gsc) { attn_grad_f16_override(gsc); }
-  ~AttnGradF16Scope() { attn_grad_f16_override(nullptr); }
-  AttnGradF16Scope(const AttnGradF16Scope&) = delete;
-  AttnGradF16Scope& operator=(const AttnGradF16Scope&) = delete;
-};
-}  // namespace
+/* the attention forms only the engine reaches: a softmax scale of its own and the scaled-fp16 gradient stores of the MFMA backward kernels */
 int mp_attention_fwd_bf16_scale_ex(const void* qkv, void* out, float* lse, int temporal, int B, int T, int J, int C, int H, float qk_scale,
                                    void* stream) {
-  MP_CHECK(qkv && out && (!temporal || lse), MP_ERR_ARG, "mp_attention_fwd_bf16_scale_ex: null pointer");
-  MP_CHECK(qk_scale >= 0.f && qk_scale <= 3.0e38f, MP_ERR_ARG, "mp_attention_fwd_bf16_scale_ex: qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)");
-  AttnScaleScope scale(qk_scale);
-  return temporal ? attn_temporal_fwd(qkv, out, lse, 1, B, T, J, C, H, (hipStream_t)stream)
-                  : attn_spatial_fwd(qkv, out, 1, B, T, J, C, H, (hipStream_t)stream);
+  return attention_fwd("mp_attention_fwd_bf16_scale_ex", ATTN_BF16, qkv, out, lse, temporal, B, T, J, C, H, qk_scale, stream);
 }
 int mp_attention_bwd_bf16_scale_ex(const void* qkv, const void* out, const void* d_out, const float* lse, float* delta, void* d_qkv, int temporal,
                                    int B, int T, int J, int C, int H, int out_f16, float qk_scale, const float* grad_scale, void* stream) {
-  MP_CHECK(qkv && d_out && d_qkv && (!temporal || (out && lse && delta)), MP_ERR_ARG, "mp_attention_bwd_bf16_scale_ex: null pointer");
-  MP_CHECK(!out_f16 || temporal, MP_ERR_ARG, "mp_attention_bwd_bf16_scale_ex: only the temporal backward reads O");
-  MP_CHECK(qk_scale >= 0.f && qk_scale <= 3.0e38f, MP_ERR_ARG, "mp_attention_bwd_bf16_scale_ex: qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)");
-  if (grad_scale != nullptr) {      // the row kernels know no fp16 store: they would write bf16 where the caller expects scaled fp16
-    const bool mfma = H > 0 && C % H == 0 && C % 8 == 0 && (temporal ? attn_tmfma_supported(T, C / H) : attn_smfma_supported(J, C / H, H));
-    MP_CHECK(mfma, MP_ERR_ARG, "mp_attention_bwd_bf16_scale_ex: scaled fp16 gradients need an MFMA backward (temporal %d, T=%d J=%d C=%d H=%d)", temporal,
-             T, J, C, H);
-  }
-  AttnScaleScope scale(qk_scale);
-  AttnGradF16Scope f16_out(grad_scale);
-  return temporal ? attn_temporal_bwd(qkv, out, d_out, lse, delta, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream, out_f16)
-                  : attn_spatial_bwd(qkv, d_out, d_qkv, 1, B, T, J, C, H, (hipStream_t)stream);
+  return attention_bwd("mp_attention_bwd_bf16_scale_ex", ATTN_BF16, qkv, out, d_out, lse, delta, d_qkv, temporal, B, T, J, C, H, out_f16, qk_scale, grad_scale,
+                       stream);
 }
 int mp_attention_fwd_bf16x3_scale_ex(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, float* scratch, int temporal,
                                      int B, int T, int J, int C, int H, int out_form, float qk_scale, void* stream) {
-  MP_CHECK(qkv_hi && qkv_lo && out_hi && out_lo && (!temporal || lse) && (out_form == 0 || out_form == 1), MP_ERR_ARG,
-           "mp_attention_fwd_bf16x3_scale_ex: bad argument");
-  MP_CHECK(qk_scale >= 0.f && qk_scale <= 3.0e38f, MP_ERR_ARG, "mp_attention_fwd_bf16x3_scale_ex: qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)");
-  AttnScaleScope scale(qk_scale);
-  return temporal ? attn_temporal_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, lse, scratch, B, T, J, C, H,
-                                         (hipStream_t)stream, out_form)
-                  : attn_spatial_fwd_x3((const bf16*)qkv_hi, (const bf16*)qkv_lo, (bf16*)out_hi, (bf16*)out_lo, scratch, B, T, J, C, H,
-                                        (hipStream_t)stream, out_form);
+  return attention_fwd_x3("mp_attention_fwd_bf16x3_scale_ex", "bad argument", qkv_hi, qkv_lo, out_hi, out_lo, lse, scratch, temporal, B, T, J, C, H, out_form,
+                          qk_scale, stream);
 }
 int mp_linear_bwd_f16(const void* dy, const void* x, const void* W, void* dx, const void* z, const float* gout, uint32_t* gsat, float* dW, float* db,
                       int M, int N, int K, int f16, int x_f16, const float* oscale, float* slab, int64_t slab_floats, void* stream) {

@@ -14,8 +14,6 @@
 
 namespace mp {
 
-bool attn_tmfma_supported(int T, int D);            // attention_mfma.hip
-bool attn_smfma_supported(int N, int D, int H);
 // Gradient operands of a layer whose backward GEMMs run on fp16 operands (mp_model_config::f16_backward) are carried as fp16 of S x value,
 // S a power of two chosen per backward on the device (grad_scale, elementwise.hip: the largest element of the residual gradient at the top
 // of the backbone lands in [2^11, 2^12), which leaves fp16 a factor 2^4 of headroom above it and 2^25 of normal range below - measured, see
@@ -24,14 +22,6 @@ bool attn_smfma_supported(int N, int D, int H);
 
 const char* last_error();
 long wgrad_f32_slab_floats(int Mtok, int Nout, int Kin);
-
-// the attention backward launches issued inside the guard's scope write dQ / dK / dV as scaled fp16 (null: bf16); reset on every exit path
-struct AttnGradF16Scope {
-  explicit AttnGradF16Scope(const float* gsc) { attn_grad_f16_override(gsc); }
-  ~AttnGradF16Scope() { attn_grad_f16_override(nullptr); }
-  AttnGradF16Scope(const AttnGradF16Scope&) = delete;
-  AttnGradF16Scope& operator=(const AttnGradF16Scope&) = delete;
-};
 
 struct ParamDesc { std::string name; long offset, numel; };
 struct BlockP { int n1w, n1b, qkvw, qkvb, pw, pb, n2w, n2b, f1w, f1b, f2w, f2b; };
@@ -505,22 +495,18 @@ static bool lazy_block_input(const mp_model* m, const Module& md, int l) {
 
 static int backbone_fwd_impl(mp_model* m, Module& md, const float* fp, int B, hipStream_t st);
 static int backbone_bwd_impl(mp_model* m, Module& md, const float* fp, float* fg, int B, hipStream_t st);
-// the module's attention scale / residual scale apply to every launch of its backbone (attention launchers read the thread's override)
+// the module's residual scale applies to every GEMM launch of its backbone (m->cur_rs; the attention launches carry md.qk_scale themselves)
 static int backbone_fwd(mp_model* m, Module& md, const float* fp, int B, hipStream_t st) {
-  attn_scale_override(md.qk_scale);
   m->cur_rs = md.rs;
   const int rc = backbone_fwd_impl(m, md, fp, B, st);
   m->cur_kind = -1;
-  attn_scale_override(0.f);
   m->cur_rs = 1.0f;
   return rc;
 }
 static int backbone_bwd(mp_model* m, Module& md, const float* fp, float* fg, int B, hipStream_t st) {
-  attn_scale_override(md.qk_scale);
   m->cur_rs = md.rs;
   const int rc = backbone_bwd_impl(m, md, fp, fg, B, st);
   m->cur_kind = -1;
-  attn_scale_override(0.f);
   m->cur_rs = 1.0f;
   return rc;
 }
@@ -559,11 +545,13 @@ static int backbone_fwd_impl(mp_model* m, Module& md, const float* fp, int B, hi
       HZ(st, "attention_fwd", HR(w.qkv, eb * M * 3 * C), HR(x3 ? w.qkvl : nullptr, eb * M * 3 * C), HW(w.ao, eb * M * C), HW(x3 ? w.aol : nullptr, eb * M * C),
          HW(spatial ? nullptr : w.lse, 4.0 * B * N * H * T), HW(xattn, xattn ? 16.0 * M * C : 0.0));
     }
-    if (x3) {
-      if (spatial) RUN(PC_ATTN, 12.0 * B * T * N * N * C, attn_spatial_fwd_x3((const bf16*)w.qkv, (const bf16*)w.qkvl, (bf16*)w.ao, (bf16*)w.aol, xattn, B, T, N, C, H, st, md.f8a));
-      else RUN(PC_ATTN, 12.0 * B * N * (double)T * T * C, attn_temporal_fwd_x3((const bf16*)w.qkv, (const bf16*)w.qkvl, (bf16*)w.ao, (bf16*)w.aol, w.lse, xattn, B, T, N, C, H, st, md.f8a));
-    } else if (spatial) RUN(PC_ATTN, 4.0 * B * T * N * N * C, attn_spatial_fwd(w.qkv, w.ao, half, B, T, N, C, H, st));
-    else RUN(PC_ATTN, 4.0 * B * N * (double)T * T * C, attn_temporal_fwd(w.qkv, w.ao, w.lse, half, B, T, N, C, H, st));
+    {
+      AttnArgs a = {};
+      a.qkv = w.qkv; a.qkv_lo = w.qkvl; a.out = w.ao; a.out_lo = w.aol; a.lse = w.lse; a.scratch = xattn; a.B = B; a.T = T; a.J = N; a.C = C; a.H = H;
+      a.form = m->cfg.precision; a.scale = md.qk_scale; a.out_f16f8 = md.f8a;      // (precision 0 / 1 / 2 = ATTN_F32 / ATTN_BF16 / ATTN_BF16X3)
+      const double pairs = spatial ? (double)B * T * N * N : B * N * (double)T * T;      // x3: three matrix-core products per product
+      RUN(PC_ATTN, (x3 ? 12.0 : 4.0) * pairs * C, attn_fwd(a, !spatial, st));
+    }
     // block input: materialised (blocks 0 and 1: embedding / positional table involved), or - bf16 mode - recomputed in the
     // residual epilogue as the shared post-norm of the previous block's output (ln_fwd below does not store it then)
     const bool lazy_in = lazy_block_input(m, md, l);
@@ -726,13 +714,12 @@ static int backbone_bwd_impl(mp_model* m, Module& md, const float* fp, float* fg
       const double eb = half ? 2.0 : 4.0;
       HZ(st, "attention_bwd", HR(w.qkv, eb * M * 3 * C), HR(spatial ? nullptr : w.ao, eb * M * C), HR(m->tmpC, eb * M * C), HR(spatial ? nullptr : w.lse, 4.0 * B * N * H * T),
          HW(spatial ? nullptr : m->delta, 4.0 * B * N * H * T), HW(m->tmp3C, eb * M * 3 * C));
-      AttnGradF16Scope f16_out(md.f8g ? m->gsc : nullptr);      // f8g: dqkv leaves as scaled fp16 (its two consumers below run on fp16 operands)
-      if (spatial) RUN(PC_ATTN, 10.0 * B * T * N * N * C, attn_spatial_bwd(w.qkv, m->tmpC, m->tmp3C, half, B, T, N, C, H, st));
-      else {
-        ProfScope ps__(m, st, PC_ATTN, 10.0 * B * N * (double)T * T * C);
-        const int rc__ = attn_temporal_bwd(w.qkv, w.ao, m->tmpC, w.lse, m->delta, m->tmp3C, half, B, T, N, C, H, st, md.f8a ? 1 : 0);      // f8a: O exists as an fp16 plane
-        if (rc__) return rc__;
-      }
+      AttnArgs a = {};
+      a.qkv = w.qkv; a.out = w.ao; a.dout = m->tmpC; a.dqkv = m->tmp3C; a.lse = w.lse; a.delta = m->delta; a.B = B; a.T = T; a.J = N; a.C = C; a.H = H;
+      a.form = half ? ATTN_BF16 : ATTN_F32; a.scale = md.qk_scale;
+      a.grad_f16 = md.f8g ? m->gsc : nullptr;      // f8g: dqkv leaves as scaled fp16 (its two consumers below run on fp16 operands)
+      a.out_f16 = md.f8a ? 1 : 0;                  // f8a: O exists as an fp16 plane (read by the temporal backward only)
+      RUN(PC_ATTN, 10.0 * (spatial ? (double)B * T * N * N : B * N * (double)T * T) * C, attn_bwd(a, !spatial, st));
     }
     // (g) qkv
     E_READY(3);                                                    // dqkv (tmp3C) is ready

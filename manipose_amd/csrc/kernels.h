@@ -153,24 +153,41 @@ struct MaskDesc { int offset, count; float keep; };
 int droppath_masks(float* masks, const MaskDesc* descs, int ndesc, unsigned long long seed, unsigned long long step,
                    hipStream_t st);
 
-// ---------------------------------------------------------------- attention.hip
-void attn_grad_f16_override(const float* gout);   // attention_mfma.hip: the MFMA backward launches issued next on this thread write dQ / dK / dV as fp16(*gout x value) (device address; null = bf16)
-void attn_scale_override(float s);   // softmax scale of the attention launches issued next on this thread (0 = head_dim ** -0.5)
+// ---------------------------------------------------------------- attention.hip, attention_mfma.hip
+// One attention launch, stated in full: no launcher reads anything about it from elsewhere.
 // qkv: [M][3C] (q | k | v, head-major inside each), out: [M][C]; token layout m = (b*T + t)*J + j
-int attn_spatial_fwd(const void* qkv, void* out, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st);
-int attn_spatial_bwd(const void* qkv, const void* dout, void* dqkv, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st);
-int attn_temporal_fwd(const void* qkv, void* out, float* lse, int is_bf16, int B, int T, int J, int C, int H, hipStream_t st);
-// out_f16: O is the fp16 plane of an f16f8 activation (mp_model_config::f16f8 = 3), read as fp16 by the MFMA backward; refused elsewhere
-int attn_temporal_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int is_bf16,
-                      int B, int T, int J, int C, int H, hipStream_t st, int out_f16 = 0);
-// split-precision forward (planar hi/lo qkv and output, common.h).  scratch (4 M C floats) is only used for shapes the MFMA kernels
-// do not cover (the planes are joined to fp32, the fp32 kernels run, the result is split again); may be null otherwise.
+enum { ATTN_F32 = 0, ATTN_BF16 = 1, ATTN_BF16X3 = 2 };
+struct AttnArgs {
+  const void* qkv;         // ATTN_BF16X3: the hi plane
+  const void* qkv_lo;      // ATTN_BF16X3: the lo plane (planar hi/lo, common.h)
+  void* out;               // forward: written; temporal backward: O as the forward wrote it (read)
+  void* out_lo;            // ATTN_BF16X3: the lo plane of the output
+  const void* dout;        // backward
+  void* dqkv;              // backward
+  float* lse;              // temporal: [B J H][T], written by the forward, read by the backward
+  float* delta;            // temporal backward, row kernels: [B J H][T] scratch
+  float* scratch;          // ATTN_BF16X3: 4 M C floats, only used for shapes the MFMA kernels do not cover (attn_x3_needs_scratch: the planes are
+                           // joined to fp32, the fp32 kernels run, the result is split again); may be null otherwise
+  int B, T, J, C, H;
+  int form;                // ATTN_*: storage of qkv, out, dout and dqkv (ATTN_BF16X3: forward only)
+  float scale;             // softmax scale; 0 means head_dim ** -0.5 (muP: 1 / head_dim, mix_ste.py:243)
+  const float* grad_f16;   // backward: non-null writes dQ / dK / dV as fp16 of *grad_f16 x value instead of bf16 (device address); MFMA kernels only, refused elsewhere
+  int out_f16;             // temporal backward: O is the fp16 plane of an f16f8 activation (mp_model_config::f16f8 = 3); MFMA kernel only, refused elsewhere
+  int out_f16f8;           // ATTN_BF16X3: the output leaves as "f16f8" planes (out = fp16 plane, out_lo = 8-bit correction plane; head dim 64, MFMA kernels only)
+};
+inline float attn_qk_scale(float scale, int D) { return scale > 0.f ? scale : 1.0f / sqrtf((float)D); }
+int attn_fwd(const AttnArgs& a, int temporal, hipStream_t st);      // every form; ATTN_BF16X3 goes to the two _x3 launchers
+int attn_bwd(const AttnArgs& a, int temporal, hipStream_t st);      // ATTN_F32 and ATTN_BF16
+// attention_mfma.hip: which shapes the bf16 MFMA kernels cover, and their launchers (attn_fwd / attn_bwd dispatch to them)
+bool attn_tmfma_supported(int T, int D);
+bool attn_smfma_supported(int N, int D, int H);
 bool attn_x3_needs_scratch(int temporal, int T, int J, int C, int H);
-// out_f16f8: the output leaves as "f16f8" planes (out_hi = fp16 plane, out_lo = 8-bit correction plane; head dim 64, MFMA kernels only)
-int attn_spatial_fwd_x3(const bf16* qkv_hi, const bf16* qkv_lo, bf16* out_hi, bf16* out_lo, float* scratch, int B, int T, int J, int C, int H,
-                        hipStream_t st, int out_f16f8 = 0);
-int attn_temporal_fwd_x3(const bf16* qkv_hi, const bf16* qkv_lo, bf16* out_hi, bf16* out_lo, float* lse, float* scratch, int B, int T, int J,
-                         int C, int H, hipStream_t st, int out_f16f8 = 0);
+int attn_smfma_fwd(const AttnArgs& a, hipStream_t st);
+int attn_smfma_bwd(const AttnArgs& a, hipStream_t st);
+int attn_tmfma_fwd(const AttnArgs& a, hipStream_t st);
+int attn_tmfma_bwd(const AttnArgs& a, hipStream_t st);
+int attn_spatial_fwd_x3(const AttnArgs& a, hipStream_t st);
+int attn_temporal_fwd_x3(const AttnArgs& a, hipStream_t st);
 void attn_two_phase(int on);        // 0 = one-strip-at-a-time split-precision temporal forward for every shape (mp_set_option)
 int join_planes(const bf16* hi, const bf16* lo, float* out, long n, hipStream_t st);
 int split_planes(const float* in, bf16* hi, bf16* lo, long n, hipStream_t st);

@@ -7,7 +7,7 @@ row kernels and for every log-sum-exp.  Outputs are pre-filled with NaN (an elem
 views into larger allocations whose guard rows hold NaN (inputs) or a sentinel that must be untouched afterwards (outputs), and the backward
 is fed the kernel's own forward O and lse, as the engine feeds it.
 
-Which kernel a shape reaches (attention.hip attn_{temporal,spatial}_{fwd,bwd}, attention_mfma.hip attn_tmfma_supported / attn_smfma_supported /
+Which kernel a shape reaches (attention.hip attn_fwd / attn_bwd, attention_mfma.hip attn_tmfma_supported / attn_smfma_supported /
 attn_x3_needs_scratch) is restated in route() / x3_route() and asserted for every parametrisation that is about a kernel.
 
 Constants (C_* below): the worst error / scale ratio measured on the MI355X over this module -> asserted at about 2.5 x, two digits; split per
@@ -21,6 +21,12 @@ form only where the measurements differ by more than a factor of two:
   split-precision O .............. C_ATTN = 0.25 of test_gpu_f16f8_kernels.py unchanged (0.239 at the worst here)
 (the CPU rounding model of attn_ref.py had predicted O 1.5, dQ 0.49, dK 0.61, dV 1.9 for the MFMA kernels)
 """
+import hashlib
+import json
+import os
+import zlib
+
+import numpy as np
 import pytest
 import torch
 
@@ -466,3 +472,151 @@ def test_fp16_gradients_are_refused_where_a_row_kernel_would_write_bf16(lib):
                                                           2, T, J, C, H, 0, 0.0, gsc.ptr(), st()))
     with pytest.raises(RuntimeError, match="qk_scale"):
         _lib.check(lib.mp_attention_fwd_bf16_scale_ex(q.data_ptr(), o.data_ptr(), lse.data_ptr(), 0, 2, 5, 17, 256, 16, -1.0, st()))
+
+
+# ------------------------------------------------------------------------------------------------ softmax scale on the routes without an MFMA kernel
+def other_scale(which, D):
+    return 1.0 / D if which == "mup" else 0.173
+
+
+@pytest.mark.parametrize("temporal,T,J,C,H", [(0, 5, 32, 64, 1), (1, 257, 2, 32, 2)])
+@pytest.mark.parametrize("which", ["mup", "arbitrary"])
+def test_softmax_scale_through_the_split_precision_fallback(lib, which, temporal, T, J, C, H):
+    """mp_attention_fwd_bf16x3_scale_ex on shapes no MFMA kernel covers (spatial: head dim 64 beyond the register prefetch; temporal: T > 256):
+    join_planes, the fp32 row kernel, split_planes - the fp32 launch has to run with the caller's scale.  Same bounds as every split-precision
+    forward; then the default scale on the same shape: nothing outlives the call."""
+    qk = other_scale(which, C // H)
+    for i, family in enumerate(("randn", "peaked")):
+        x3_forward(lib, temporal, 1, T, J, C, H, family, seed=61 + i + T, qk_scale=qk, want_route="scratch")
+    x3_forward(lib, temporal, 1, T, J, C, H, "randn", seed=5, want_route="scratch")
+
+
+@pytest.mark.parametrize("temporal,T,J,C,H", [(1, 17, 2, 64, 2), (0, 5, 15, 128, 2)])
+@pytest.mark.parametrize("which", ["mup", "arbitrary"])
+def test_softmax_scale_through_the_bf16_row_kernels(lib, which, temporal, T, J, C, H):
+    """mp_attention_{fwd,bwd}_bf16_scale_ex where the bf16 row kernels run (temporal: head dim 32; spatial: 15 tokens), forward and backward,
+    against the reference with THAT scale within the row kernels' constants; then the default scale again"""
+    qk = other_scale(which, C // H)
+    for i, family in enumerate(("randn", "peaked")):
+        one_case(lib, family, "bf16", temporal, 2, T, J, C, H, seed=67 + i + T, qk_scale=qk, want_route="row")
+    one_case(lib, "randn", "bf16", temporal, 2, T, J, C, H, seed=5, want_route="row")
+
+
+# ------------------------------------------------------------------------------------------------ bits
+# Every public attention entry point once per route it reaches, on inputs from a seeded numpy generator; the SHA-256 of every output tensor's
+# bytes is compared with tests/golden/attn_bits.json (tools/gen_golden_attn_bits.py: the recording and the test run the same code).
+GOLD_BITS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attn_bits.json")
+#               temporal, B, T, J, C, H
+BITS_SHAPES = {
+    "s_row": (0, 2, 5, 15, 64, 2),       # spatial, 15 tokens, head dim 32: row kernels; split precision: scratch
+    "s_d16": (0, 2, 5, 17, 32, 2),       # spatial MFMA, head dim 16
+    "s_d64": (0, 2, 5, 17, 128, 2),      # spatial MFMA, head dim 64
+    "t_row": (1, 2, 17, 3, 64, 2),       # temporal, head dim 32: row kernels; split precision: scratch
+    "t_d16": (1, 2, 17, 3, 32, 2),       # temporal MFMA, head dim 16
+    "t_d64": (1, 2, 17, 3, 128, 2),      # temporal MFMA, head dim 64; split precision: the one-strip kernel
+    "t_d16_full": (1, 1, 241, 2, 32, 2),     # the full-window backward (T > 240)
+    "t_d64_full": (1, 1, 241, 2, 128, 2),    # ... and the two-phase split-precision forward (x3p)
+}
+BITS_ROUTES = {"s_row": ("row", "scratch"), "s_d16": ("mfma", "x3"), "s_d64": ("mfma", "x3"), "t_row": ("row", "scratch"), "t_d16": ("mfma", "x3"),
+               "t_d64": ("mfma", "x3"), "t_d16_full": ("mfma", "x3"), "t_d64_full": ("mfma", "x3p")}
+QK_BITS = 0.173
+
+
+def bits_table():
+    """(entry point, shape, options) rows: qk = softmax scale, form = out_form (1: f16f8 planes), o16 = out_f16, S = gradient-scale block"""
+    rows = []
+    for s, (route_, _) in BITS_ROUTES.items():
+        mfma, temporal, d64 = route_ == "mfma", BITS_SHAPES[s][0], BITS_SHAPES[s][4] // BITS_SHAPES[s][5] == 64
+        if not mfma:
+            rows += [("mp_attention_fwd", s, {}), ("mp_attention_bwd", s, {})]
+        rows += [("mp_attention_fwd_bf16", s, {}), ("mp_attention_bwd_bf16", s, {}), ("mp_attention_bwd_bf16_ex", s, {}),
+                 ("mp_attention_fwd_bf16_scale_ex", s, dict(qk=QK_BITS)), ("mp_attention_bwd_bf16_scale_ex", s, dict(qk=QK_BITS)),
+                 ("mp_attention_fwd_bf16x3", s, {}), ("mp_attention_fwd_bf16x3_ex", s, {}), ("mp_attention_fwd_bf16x3_scale_ex", s, dict(qk=QK_BITS))]
+        if mfma:
+            rows += [("mp_attention_bwd_bf16_scale_ex", s, dict(S=16.0)), ("mp_attention_bwd_bf16_scale_ex", s, dict(qk=QK_BITS, S=16.0))]
+        if mfma and temporal:
+            rows += [("mp_attention_bwd_bf16_ex", s, dict(o16=1)), ("mp_attention_bwd_bf16_scale_ex", s, dict(qk=QK_BITS, S=16.0, o16=1))]
+        if mfma and d64:
+            rows += [("mp_attention_fwd_bf16x3_ex", s, dict(form=1)), ("mp_attention_fwd_bf16x3_scale_ex", s, dict(qk=QK_BITS, form=1))]
+    return rows
+
+
+def bits_name(entry, shape, opt):
+    return "/".join([entry, shape] + [f"{k}={opt[k]:g}" for k in sorted(opt)])
+
+
+def bits_outputs(lib, entry, shape, opt):
+    """{tensor name: host tensor} of one row; outputs are pre-filled with 0 (the MFMA backward leaves delta alone)"""
+    _lib = lib_()
+    temporal, B, T, J, C, H = BITS_SHAPES[shape]
+    qk, form, o16, S = opt.get("qk", 0.0), opt.get("form", 0), opt.get("o16", 0), opt.get("S")
+    assert B <= 2 and J <= 17 and C <= 128
+    rng = np.random.default_rng(zlib.crc32(shape.encode()))
+    M, L = B * T * J, B * J * H * T
+    qkv = torch.from_numpy(rng.standard_normal((M, 3 * C), dtype=np.float32))
+    dout = torch.from_numpy(rng.standard_normal((M, C), dtype=np.float32))
+    f32 = entry in ("mp_attention_fwd", "mp_attention_bwd")
+    dt = torch.float32 if f32 else torch.bfloat16
+
+    def zeros(*shape_, dtype=dt):
+        return torch.zeros(*shape_, device="cuda", dtype=dtype)
+
+    lse = zeros(L, dtype=torch.float32)
+    lp = lse.data_ptr() if temporal else None
+    dims = (temporal, B, T, J, C, H)
+    if "x3" in entry:
+        assert x3_route(temporal, T, J, C, H) == BITS_ROUTES[shape][1]
+        hi = qkv.bfloat16()
+        lo = (qkv - hi.float()).bfloat16()
+        hi, lo, oh, ol = hi.cuda(), lo.cuda(), zeros(M, C), zeros(M, C)
+        scratch = zeros(4 * M * C, dtype=torch.float32) if BITS_ROUTES[shape][1] == "scratch" else None
+        tail = {"mp_attention_fwd_bf16x3": (), "mp_attention_fwd_bf16x3_ex": (form,), "mp_attention_fwd_bf16x3_scale_ex": (form, qk)}[entry]
+        _lib.check(getattr(lib, entry)(hi.data_ptr(), lo.data_ptr(), oh.data_ptr(), ol.data_ptr(), lp, scratch.data_ptr() if scratch is not None else None,
+                                       *dims, *tail, st()), entry)
+        outs = dict(out_hi=oh, out_lo=ol)
+    else:
+        assert route("f32" if f32 else "bf16", temporal, T, J, C, H) == ("row" if f32 else BITS_ROUTES[shape][0])
+        q, do, out = qkv.to(dt).cuda(), dout.to(dt).cuda(), zeros(M, C)
+        fwd = "mp_attention_fwd" if f32 else ("mp_attention_fwd_bf16_scale_ex" if entry.endswith("_scale_ex") else "mp_attention_fwd_bf16")
+        _lib.check(getattr(lib, fwd)(q.data_ptr(), out.data_ptr(), lp, *dims, *((qk,) if fwd.endswith("_scale_ex") else ()), st()), fwd)
+        outs = dict(out=out)
+        if "_bwd" in entry:
+            o_in = out.to(torch.float16) if o16 else out
+            delta = zeros(L, dtype=torch.float32)
+            dq = zeros(M, 3 * C, dtype=torch.float16 if S else dt)
+            gsc = torch.tensor([S, 1.0 / S, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0], device="cuda") if S else None
+            tail = {"mp_attention_bwd": (), "mp_attention_bwd_bf16": (), "mp_attention_bwd_bf16_ex": (o16,),
+                    "mp_attention_bwd_bf16_scale_ex": (o16, qk, gsc.data_ptr() if S else None)}[entry]
+            _lib.check(getattr(lib, entry)(q.data_ptr(), o_in.data_ptr(), do.data_ptr(), lp, delta.data_ptr() if temporal else None, dq.data_ptr(), *dims, *tail,
+                                           st()), entry)
+            outs = dict(dqkv=dq)
+            if temporal:
+                outs["delta"] = delta
+            if S:
+                outs["gsc"] = gsc
+    if temporal and "_bwd" not in entry:
+        outs["lse"] = lse
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in outs.items()}
+
+
+def bits_digests(lib):
+    """{row / tensor: {"shape": [...], "sha256": hex}} over bits_table()"""
+    out = {}
+    for entry, shape, opt in bits_table():
+        for k, t in bits_outputs(lib, entry, shape, opt).items():
+            raw = t.contiguous().view(torch.uint8).numpy().tobytes()
+            out[bits_name(entry, shape, opt) + "/" + k] = {"shape": list(t.shape), "sha256": hashlib.sha256(raw).hexdigest()}
+    return out
+
+
+def test_every_entry_point_repeats_the_recorded_bits(lib):
+    """the launchers changed, the kernels and what they are given did not: every output of every entry point on every route has the bytes it had
+    at the commit the fixture was recorded at (tools/gen_golden_attn_bits.py)"""
+    with open(GOLD_BITS) as f:
+        want = json.load(f)
+    got = bits_digests(lib)
+    assert len({e for e, _, _ in bits_table()}) == 10
+    assert sorted(got) == sorted(want), sorted(set(got) ^ set(want))
+    bad = [k for k in sorted(want) if got[k] != want[k]]
+    assert not bad, "entry point / shape / options / tensor with other bits than recorded: " + ", ".join(bad)

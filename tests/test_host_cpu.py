@@ -91,6 +91,47 @@ def test_no_cpu_fallback_and_argument_errors():
     assert lib.mp_model_create(C.byref(cfg), C.byref(h)) == 1 and b"arch" in lib.mp_last_error()
 
 
+def test_attention_entry_points_refuse_bad_arguments_before_any_launch():
+    """the ten attention shims: null pointers, a negative softmax scale, out_f16 on the spatial backward, out_form out of range and scaled
+    fp16 gradients on a row-kernel shape are MP_ERR_ARG with the entry point's name in the message - no launch, so no GPU is needed"""
+    import ctypes as C
+    from manipose_amd import _lib
+    lib = _lib.load()
+    buf = C.create_string_buffer(64)
+    p = C.addressof(buf)           # never dereferenced: every call below returns from its checks
+    dims = (2, 5, 17, 128, 2)      # B, T, J, C, H
+
+    def refused(name, args, message):
+        assert getattr(lib, name)(*args) == 1, name
+        assert lib.mp_last_error().decode() == message, (name, lib.mp_last_error())
+
+    for name in ("mp_attention_fwd", "mp_attention_fwd_bf16"):
+        refused(name, (p, None, None, 0, *dims, None), f"{name}: null pointer")
+        refused(name, (p, p, None, 1, *dims, None), f"{name}: null pointer")                    # temporal: lse
+    refused("mp_attention_fwd_bf16_scale_ex", (None, p, p, 1, *dims, 0.0, None), "mp_attention_fwd_bf16_scale_ex: null pointer")
+    for name, tail in (("mp_attention_bwd", ()), ("mp_attention_bwd_bf16", ()), ("mp_attention_bwd_bf16_ex", (0,)), ("mp_attention_bwd_bf16_scale_ex", (0, 0.0, None))):
+        refused(name, (p, None, p, None, None, None, 0, *dims, *tail, None), f"{name}: null pointer")
+        refused(name, (p, p, p, p, None, p, 1, *dims, *tail, None), f"{name}: null pointer")    # temporal: delta
+    refused("mp_attention_fwd_bf16x3", (p, None, p, p, None, None, 0, *dims, None), "mp_attention_fwd_bf16x3: null pointer")
+    refused("mp_attention_fwd_bf16x3_ex", (p, p, p, None, None, None, 0, *dims, 0, None), "mp_attention_fwd_bf16x3_ex: bad argument")
+    refused("mp_attention_fwd_bf16x3_scale_ex", (p, p, p, p, None, None, 1, *dims, 0, 0.0, None), "mp_attention_fwd_bf16x3_scale_ex: bad argument")
+    for out_form in (-1, 2):
+        refused("mp_attention_fwd_bf16x3_ex", (p, p, p, p, p, None, 0, *dims, out_form, None), "mp_attention_fwd_bf16x3_ex: bad argument")
+        refused("mp_attention_fwd_bf16x3_scale_ex", (p, p, p, p, p, None, 0, *dims, out_form, 0.0, None), "mp_attention_fwd_bf16x3_scale_ex: bad argument")
+    scale_msg = "qk_scale must be finite and >= 0 (0 = head_dim ** -0.5)"
+    for qk in (-1.0, float("nan"), float("inf")):
+        refused("mp_attention_fwd_bf16_scale_ex", (p, p, p, 1, *dims, qk, None), "mp_attention_fwd_bf16_scale_ex: " + scale_msg)
+        refused("mp_attention_bwd_bf16_scale_ex", (p, p, p, p, p, p, 1, *dims, 0, qk, None, None), "mp_attention_bwd_bf16_scale_ex: " + scale_msg)
+        refused("mp_attention_fwd_bf16x3_scale_ex", (p, p, p, p, p, None, 1, *dims, 0, qk, None), "mp_attention_fwd_bf16x3_scale_ex: " + scale_msg)
+    refused("mp_attention_bwd_bf16_ex", (p, p, p, p, p, p, 0, *dims, 1, None), "mp_attention_bwd_bf16_ex: only the temporal backward reads O")
+    refused("mp_attention_bwd_bf16_scale_ex", (p, p, p, p, p, p, 0, *dims, 1, -1.0, None, None), "mp_attention_bwd_bf16_scale_ex: only the temporal backward reads O")
+    # scaled fp16 gradients where a row kernel would run (temporal: head dim 32; spatial: 15 tokens): refused by the shim, before the launcher's own refusal
+    refused("mp_attention_bwd_bf16_scale_ex", (p, p, p, p, p, p, 1, 2, 17, 2, 64, 2, 0, 0.0, p, None),
+            "mp_attention_bwd_bf16_scale_ex: scaled fp16 gradients need an MFMA backward (temporal 1, T=17 J=2 C=64 H=2)")
+    refused("mp_attention_bwd_bf16_scale_ex", (p, p, p, p, p, p, 0, 2, 5, 15, 128, 2, 0, 0.0, p, None),
+            "mp_attention_bwd_bf16_scale_ex: scaled fp16 gradients need an MFMA backward (temporal 0, T=5 J=15 C=128 H=2)")
+
+
 def test_skeleton_tables():
     from manipose_amd.data import h36m_skeleton
     sk = h36m_skeleton()
