@@ -854,6 +854,48 @@ int mp_lift_bundle_views(const float* pose, const float* root, const uint8_t* ro
                          const float* weights, int distort, float sigma, int iters, float* quat_out, float* trans_out, float* root_out, float* reproj,
                          double* cost, uint8_t* steps, uint8_t* ok, int32_t* used, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* Triangulating a fused take's joints on the 2-D keypoints: after mp_lift_fuse, mp_lift_fuse_place and mp_lift_bundle_views the keypoints - the only
+ * measured quantity - decide the root (three numbers per frame) and the cameras; the body is still the mean of one lifted hypothesis per view,
+ * though every joint is seen by up to four cameras.  Here every joint of every frame becomes a world point of its own, triangulated from its
+ * observations; the fused pose plus root chooses the start where the linear system cannot, stands in where fewer than two cameras see the joint,
+ * and may pull (prior).  The reference has no counterpart.  The conventions are mp_lift_fuse_place's: takes, take_offset (G + 1, entries clamped
+ * to 0 .. Ftot), valid (V, Ftot) bytes or null, 1 <= V <= MP_LIFT_FUSE_MAXV, 2 <= J <= 32, quat (G, V, 4), trans (G, V, 3), intr (G, V, 9), R the matrix
+ * of q / |q| normalised in fp64, a view whose |q|^2 is not finite or < 1e-12 counts as invalid in its take, the camera-space point of the world point
+ * X is P = R^T (X - T_v), distort as for mp_lift_place_refine, 0 <= iters <= MP_LIFT_REFINE_MAXITERS; fp64 between the float32 loads and the
+ * float32 stores, without contraction into fused multiply-adds; no atomics, fixed orders: identical bits on every call; an item depends on no
+ * other item; the call does not synchronise.  Not measured on real data.
+ * Read only: pose (Ftot, J, 3) as mp_lift_fuse wrote it; root (Ftot, 3) and root_ok (Ftot) bytes or null; kp (V, Ftot, J, 2); kp_weight (V, Ftot, J)
+ * floats or null (every weight 1): a weight per observation, the detector's confidence or an occlusion mask; the camera tables; sigma > 0 in
+ * normalised screen units (+inf: every robust factor is exactly 1); prior >= 0 and finite.  Per item (frame f of take g, joint j):
+ * 1. Prior point.  X0 = pose[f][j] + root[f];  USABLE iff root_ok is null or non-zero at f and the three coordinates of X0 are finite.
+ * 2. Observations.  View v is an observation iff it counts at the frame (its valid byte and its take's quaternion), both coordinates of its
+ *    keypoint are finite and its weight w_v is finite and > 0 (a zero, negative or non-finite weight: not observed, no error; an invalid view's
+ *    keypoint and weight are never looked at).  n = the number of observations; every sum below runs over them in view order.
+ * 3. Linear start, under the pinhole part as step 1 of mp_lift_fuse_place: with a = (u - cx) / fx, b = (v - cy) / fy and rho_x, rho_y, rho_z the
+ *    rows of R^T,  m_x = rho_x - a rho_z,  m_y = rho_y - b rho_z,  H = sum w_v (m_x m_x^T + m_y m_y^T),  h = sum w_v (m_x (m_x . T_v) + m_y (m_y . T_v)),
+ *    X = adj(H) h / det by cofactors.  If n >= 2, det and H00 H11 H22 are finite, det > 1e-12 H00 H11 H22 and X is finite, X is the start and the
+ *    item is TRIANGULATED; otherwise the start is X0 if usable; otherwise the item FAILS: points = 0, err = 0, ok = 0, steps = 0 (views as step 2).
+ * 4. Evaluation at X.  Per observation the projection, the clamp, its derivative and the 2x3 Jacobian J_pi with respect to P are exactly step 2
+ *    of mp_lift_place_refine; with (du, dv) the residual and e = du^2 + dv^2:  t = 1 + e / sigma^2,  rho = e / t,  omega = 1 / t^2
+ *    (mp_lift_bundle_views' form).  F = sum w_v rho,  E = sum w_v sqrt(e),  W = sum w_v,  H = sum (w_v omega) (J_pi R^T)^T (J_pi R^T),
+ *    g = sum (w_v omega) (J_pi R^T)^T (du, dv),  deep = every observation's Z > 0;  then, iff prior > 0 and X0 is usable, F += prior |X - X0|^2,
+ *    H += prior I, g += prior (X - X0).  If the triangulated start is not deep and X0 is usable, the item starts once more from X0 and is no
+ *    longer triangulated.  A start that is not deep, or whose F is not finite, fails as in step 3.
+ * 5. Steps.  Up to iters undamped Gauss-Newton steps X' = X - adj(H) g / det under the tests of mp_lift_place_refine (det and H00 H11 H22 finite,
+ *    det > 1e-12 H00 H11 H22, X' finite); X' is taken iff it is deep and F' <= (1 + 1e-6) F.  The first step not taken ends the item and its state
+ *    stays.  With one observation and prior = 0, H has rank 2: the step is refused and the joint stays at X0 - the intended fallback; with no
+ *    observation and prior = 0 likewise (H = 0).  (With no observation and prior > 0 the steps are taken and move nothing: at X0, g = 0 and F = 0.)
+ * 6. points (Ftot, J, 3) floats: X;  err (Ftot, J) floats: E / W at the final X, the weighted mean reprojection distance (0 when n = 0);
+ *    views (Ftot, J) bytes: bit v set iff view v was an observation;  ok (Ftot, J) bytes: bit 0 a finite result, bit 1 triangulated;
+ *    steps (Ftot, J) bytes or null: the steps taken.  A frame outside every take's clamped range is not written.
+ * One lane owns one item, items in f J + j order.
+ * MP_ERR_ARG before anything is launched: an input or output pointer null (valid, root_ok, kp_weight, steps may be null); V or J out of range;
+ * Ftot or G <= 0, G > Ftot; distort not 0 or 1; iters out of range; sigma not > 0; prior negative or not finite; more items than one grid holds. */
+int mp_lift_triangulate(const float* pose, const float* root, const uint8_t* root_ok, const float* kp, const float* kp_weight, int V, int64_t Ftot,
+                        int J, const uint8_t* valid, const int64_t* take_offset, int G, const float* quat, const float* trans, const float* intr,
+                        int distort, float sigma, float prior, int iters, float* points, float* err, uint8_t* views, uint8_t* ok, uint8_t* steps,
+                        void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -110,6 +110,24 @@ def take_pose_keypoints(pose, keypoints_2d, maxv, root=None):
     return int(kp.shape[0]), ftot, J
 
 
+def keypoint_weights(kp_weight, shape):
+    """kp_weight is None or a float32 tensor (V, Ftot, J), a weight per observation (made contiguous by the caller: any strides)"""
+    if kp_weight is not None:
+        f32(kp_weight, shape, "kp_weight")
+
+
+def robust_scale(sigma):
+    """sigma is a number > 0 as the kernel takes it (a float32; +inf is allowed), in normalised screen units"""
+    if not is_number(sigma) or not float(np.float32(sigma)) > 0:
+        raise ValueError(f"sigma must be a number > 0 in normalised screen units (inf: no robust weight), got {sigma!r}")
+
+
+def prior_weight(prior):
+    """prior is a finite number >= 0 (a float32)"""
+    if not is_number(prior) or not 0 <= float(prior) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"prior must be a finite number >= 0 (0: no pull towards the fused pose), got {prior!r}")
+
+
 def take_count(take_offset):
     """the G of a (G + 1) table of first frames, host or device, read from its size alone (None: one take)"""
     if take_offset is None:

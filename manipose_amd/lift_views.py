@@ -4,7 +4,8 @@ cuts a group's sequences into takes and calls them.  ``fuse_views``: one hypothe
 ``fuse_views_path``: that choice made jointly over the whole take, a Viterbi path over the combinations, so that a hypothesis all views agree on -
 a mirrored body - cannot make the fused motion flicker; ``place_views``: one world root per frame from all views; ``align_views``: the views'
 extrinsics estimated from their lifted poses, for takes that were never calibrated; ``bundle_views``: those cameras and the roots refined jointly
-on the reprojection error.  Built like lift_ops.py: a public function composes lift_args' checks (``_fuse_front`` and ``_take_front`` are the
+on the reprojection error; ``triangulate_views``: every joint of the fused take triangulated on the keypoints of the cameras that see it.  Built
+like lift_ops.py: a public function composes lift_args' checks (``_fuse_front`` and ``_take_front`` are the
 fronts two of them share), then uploads and calls its private launcher, which allocates the outputs and goes through ``_launch``.
 """
 from __future__ import annotations
@@ -366,3 +367,55 @@ def bundle_views(pose, root, keypoints_2d, cameras, valid=None, take_offset=None
     q, t = res[0].cpu().numpy(), res[1].cpu().numpy()
     nested = [[np.concatenate([intr[g, v], q[g, v], t[g, v]]) if present[g, v] else None for v in range(V)] for g in range(G)]
     return ViewBundle(nested, *res)
+
+
+TRIANGULATE_SIGMA, TRIANGULATE_PRIOR, TRIANGULATE_STEPS = float("inf"), 0.0, 3          # defaults of triangulate_views (not tuned)
+# What triangulate_views returns: points (Ftot, J, 3), err (Ftot, J) float32, views, ok, steps (Ftot, J) uint8
+ViewTriangulation = namedtuple("ViewTriangulation", "points err views ok steps")
+
+
+def _triangulate(lib, pose, root, root_ok, kp, kp_weight, valid, d_off, G, d_quat, d_trans, d_intr, distort, sigma, prior, iters):
+    """``mp_lift_triangulate`` on pose (Ftot, J, 3), root (Ftot, 3), kp (V, Ftot, J, 2): a ViewTriangulation of new tensors (zeros where no take
+    holds a frame)"""
+    V, ftot, J = int(kp.shape[0]), int(kp.shape[1]), int(kp.shape[2])
+    dev = pose.device
+    points = torch.zeros(ftot, J, 3, dtype=torch.float32, device=dev)
+    err = torch.zeros(ftot, J, dtype=torch.float32, device=dev)
+    views, ok, steps = (torch.zeros(ftot, J, dtype=torch.uint8, device=dev) for _ in range(3))
+    if ftot > 0:
+        _launch(dev, "mp_lift_triangulate", _lib.ptr(pose), _lib.ptr(root), _lib.ptr(root_ok), _lib.ptr(kp), _lib.ptr(kp_weight), V, ftot, J,
+                _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(d_quat), _lib.ptr(d_trans), _lib.ptr(d_intr), int(bool(distort)), float(sigma),
+                float(prior), int(iters), _lib.ptr(points), _lib.ptr(err), _lib.ptr(views), _lib.ptr(ok), _lib.ptr(steps))
+    return ViewTriangulation(points, err, views, ok, steps)
+
+
+def triangulate_views(pose, root, keypoints_2d, cameras, valid=None, take_offset=None, root_ok=None, kp_weight=None, distort=True,
+                      sigma=TRIANGULATE_SIGMA, prior=TRIANGULATE_PRIOR, refine=TRIANGULATE_STEPS):
+    """``mp_lift_triangulate`` on device tensors: every joint of a fused take TRIANGULATED on the 2-D keypoints of the cameras that see it - after
+    ``fuse_views`` and ``place_views`` the keypoints decide one root per frame and the body is the mean of the views' lifted hypotheses.  ``pose``
+    (Ftot, J, 3) float32 as ``fuse_views`` returns it, ``root`` (Ftot, 3) float32 and ``root_ok`` (Ftot) uint8 or None as ``place_views`` returns
+    them, ``keypoints_2d`` (V, Ftot, J, 2), ``cameras``, ``valid``, ``take_offset`` and ``distort`` as for ``place_views``; ``kp_weight``
+    (V, Ftot, J) float32 device tensor or None (every weight 1): a weight per observation - the detector's confidence, an occlusion mask; a
+    weight that is 0, negative or not finite means "not observed".  Per joint the start is the linear pinhole triangulation over its
+    observations; with fewer than two, or a degenerate system, it is the prior point pose + root.  Then up to ``refine`` (0..16) undamped
+    Gauss-Newton steps on sum w rho(|res|^2) + prior |X - (pose + root)|^2 under the camera model ``distort`` names, rho(e) = e / (1 + e / sigma^2);
+    ``sigma`` > 0 in normalised screen units (inf: plain least squares), ``prior`` >= 0 (0: no pull; a joint one camera sees then stays at the
+    prior point); a step is taken while the cost does not rise (``place_poses``' rule; include/manipose_hip.h has the rule in full).  The
+    defaults are not tuned.  Returns a ``ViewTriangulation``: ``(points (Ftot, J, 3) world positions, err (Ftot, J): the weighted mean
+    reprojection distance of the joint's observations, views (Ftot, J) uint8: bit v set where view v observed the joint, ok (Ftot, J) uint8: bit 0
+    a finite result, bit 1 triangulated (not started from the prior point), steps (Ftot, J) uint8)``, new device tensors; an item without a result
+    is 0 with ok = 0.  Inputs are not modified; identical bits on every call.  Not measured on real data."""
+    lift_args.robust_scale(sigma)
+    lift_args.prior_weight(prior)
+    if not lift_args.is_int_in(refine, 0, REFINE_MAXITERS):
+        raise ValueError(f"refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: the start alone), got {refine!r}")
+    if all(torch.is_tensor(t) for t in (pose, root, keypoints_2d)):
+        lift_args.take_pose_keypoints(pose, keypoints_2d, FUSE_MAXV, root)
+        lift_args.keypoint_weights(kp_weight, tuple(keypoints_2d.shape[:3]))
+    valid, d_off, G, (intr, quat, trans, _), _, _ = _take_front("triangulate_views", pose, keypoints_2d, cameras, valid, take_offset, None,
+                                                                roots=(root, root_ok, None))
+    lift_args.need_device("triangulate_views", pose, optional=(kp_weight,))
+    dev = pose.device
+    return _triangulate(_lib.load(), pose, root.contiguous(), root_ok.contiguous() if root_ok is not None else None, keypoints_2d.contiguous(),
+                        kp_weight.contiguous() if kp_weight is not None else None, valid, d_off, G, torch.from_numpy(quat).to(dev),
+                        torch.from_numpy(trans).to(dev), torch.from_numpy(intr).to(dev), distort, sigma, prior, refine)

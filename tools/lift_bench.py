@@ -12,6 +12,11 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --fuse-path [frames=3000] [K=5] [reps=20]
     python tools/lift_bench.py --align [frames=3000] [reps=20]
     python tools/lift_bench.py --bundle [frames=3000] [reps=20]
+    python tools/lift_bench.py --triangulate [frames=3000] [reps=20]
+--triangulate times mp_lift_triangulate (every joint of a fused take triangulated on the 2-D keypoints: one kernel, one lane per (frame, joint))
+through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints, pinhole keypoints with 0.01 of noise, the lifted pose
+0.03 m N(0, 1) off, the roots fitted by mp_lift_fuse_place - at iters 0, 1 and 3, as ONE take and cut into 16, next to mp_lift_fuse_place's time
+for the same frames.
 --bundle times mp_lift_bundle_views (the bundle adjustment of a take's cameras and roots on the 2-D keypoints: per pass one kernel with a lane per
 frame and one with a workgroup per take, iters + 1 passes) through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints,
 pinhole keypoints with 0.01 of noise - with the cameras of views 1..3 started 0.3 degrees and 0.15 m off S11's calibration and the roots fitted
@@ -383,6 +388,42 @@ def bundle_bench(argv):
                   f"cost {res[4][0, 0].item():.4f} -> {res[4][0, 1].item():.4f}, off by {off_by(res[0][0], res[1][0])}", flush=True)
 
 
+def triangulate_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.lift_ops import _launch
+    from manipose_amd.lift_views import _fuse_place, _triangulate
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib, V, (quat, trans, intr), pose, _, kp = fuse_scene(frames, 2)
+    g = torch.Generator(device="cuda").manual_seed(4)
+    lifted = pose + 0.03 * torch.randn(frames, 17, 3, device="cuda", generator=g)      # the lifted body: 0.03 m N(0, 1) off per coordinate
+    lifted[:, 0] = 0
+    print(f"--triangulate: {V} views x {frames} frames x 17 joints = {frames * 17} items, pinhole keypoints with 0.01 of noise, the lifted pose 0.03 m N(0, 1) off, "
+          f"sigma = inf, prior = 0; {reps} calls each after 5 of warm-up (the output allocations are inside the time)", flush=True)
+    for G in (1, 16):
+        off = torch.tensor([frames * i // G for i in range(G + 1)], dtype=torch.int64, device="cuda")
+        q, t, k = quat.expand(G, V, 4).contiguous(), trans.expand(G, V, 3).contiguous(), intr.expand(G, V, 9).contiguous()
+        place = lambda: _fuse_place(lib, lifted, kp, None, off, G, q, t, k, None, False, 3)
+        root, _, ok, _ = place()
+        us = timed_us(place, reps)
+        print(f"mp_lift_fuse_place, {G} take(s), iters=3, on the same frames: {us:,.1f} us", flush=True)
+        for iters in (0, 1, 3):
+            call = lambda: _triangulate(lib, lifted, root, ok, kp, None, None, off, G, q, t, k, False, float("inf"), 0.0, iters)
+            res = call()
+            us = timed_us(call, reps)
+            moved = (res.points - (lifted + root[:, None])).norm(dim=2).mean().item()
+            direct = lambda: _launch(res.points.device, "mp_lift_triangulate", _lib.ptr(lifted), _lib.ptr(root), _lib.ptr(ok), _lib.ptr(kp), None, V, frames, 17, None,
+                                     _lib.ptr(off), G, _lib.ptr(q), _lib.ptr(t), _lib.ptr(k), 0, float("inf"), 0.0, iters, _lib.ptr(res.points), _lib.ptr(res.err),
+                                     _lib.ptr(res.views), _lib.ptr(res.ok), _lib.ptr(res.steps))
+            alone = timed_us(direct, reps)                                # the entry point into outputs allocated once: the kernel without the launcher's five fills
+            print(f"mp_lift_triangulate, {G} take(s), iters={iters}: {us:,.1f} us ({alone:,.1f} us into outputs allocated once)  {frames * 17 / us:,.2f} M items/s; {res.steps.float().mean().item():.2f} steps an item, "
+                  f"{(res.ok == 3).float().mean().item():.3f} triangulated, mean reprojection {res.err.mean().item():.5f}, {moved * 1e3:.1f} mm from the lifted pose plus root "
+                  f"and {(res.points - (pose + root[:, None])).norm(dim=2).mean().item() * 1e3:.1f} mm from the true pose plus the fitted root", flush=True)
+
+
+if "--triangulate" in sys.argv:
+    triangulate_bench([a for a in sys.argv[1:] if a != "--triangulate"])
+    sys.exit(0)
 if "--bundle" in sys.argv:
     bundle_bench([a for a in sys.argv[1:] if a != "--bundle"])
     sys.exit(0)
