@@ -184,7 +184,7 @@ def test_wta_loss_kernel_forms_by_scratch_size_and_ragged_frame_counts(lib):
     """mp_wta_loss through the C ABI on the fixture and on frame counts that do not fill the last wave / workgroup (a lane per joint, three frames per
     wave, shuffle sums over a frame's 17 lanes, winner broadcast by a shuffle): with the ABI's minimum scratch (256 frames per workgroup) and with
     >= 4 ceil(B T / 48) floats (48 frames per workgroup) - the same argmin, the same gradients bit for bit (they do not depend on the partial sums),
-    terms equal to the oracle's."""
+    terms equal to the oracle's.  The gradients themselves are checked per element against fp64, in each form, by tests/test_gpu_loss_kernels.py."""
     import ctypes as C
     from manipose_amd import _lib
     g = torch.Generator().manual_seed(9)
