@@ -277,7 +277,8 @@ LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj
                  "__quat", "__quat_ok", "__hyps_quat", "__hyps_quat_ok", "__root", "__choice", "__spread", "__cost", "__views", "__cam_quat", "__cam_trans",
                  "__cam_rms", "__cam_trans_rms", "__cam_used", "__cam_ok", "__cam_err_deg", "__cam_err_m", "__cam_quat_align", "__cam_trans_align",
                  "__cam_err_deg_align", "__cam_err_m_align", "__cam_bundle_reproj", "__cam_bundle_cost", "__cam_bundle_steps", "__cam_bundle_ok",
-                 "__cam_bundle_used", "__tri", "__tri_err", "__tri_views", "__tri_ok", "__tri_steps")
+                 "__cam_bundle_used", "__tri", "__tri_err", "__tri_views", "__tri_ok", "__tri_steps", "__skel", "__skel_bones", "__skel_err", "__skel_ok",
+                 "__skel_steps", "__skel_quat", "__skel_quat_ok")
 
 
 def _scale_and_cost(scale, cost=None, unit="metres"):
@@ -481,6 +482,26 @@ def lift_fuse_triangulate_options(cfg):
     return True, steps, float(sigma), float(prior)
 
 
+def lift_fuse_skeleton_options(cfg):
+    """(skeleton, steps, sigma, prior) of lift.fuse_skeleton / lift.fuse_skeleton_steps / lift.fuse_skeleton_sigma / lift.fuse_skeleton_prior;
+    ValueError for a value or a combination that cannot run - before any model is built."""
+    skel, steps = cfg.lift.get("fuse_skeleton", False), cfg.lift.get("fuse_skeleton_steps", 3)
+    sigma, prior = cfg.lift.get("fuse_skeleton_sigma", float("inf")), cfg.lift.get("fuse_skeleton_prior", 0.0001)
+    if not isinstance(skel, bool):
+        raise ValueError(f"lift.fuse_skeleton must be true or false, got {skel!r}")
+    if not is_int_in(steps, 0, 16):
+        raise ValueError(f"lift.fuse_skeleton_steps counts Gauss-Newton steps, an integer in 0..16 (0: the rigid start alone), got {steps!r}")
+    _scale_and_cost(("fuse_skeleton_sigma", sigma), ("fuse_skeleton_prior", prior), unit="normalised screen units; inf: no robust weight")
+    if not skel:
+        if steps != 3 or sigma != float("inf") or prior != 0.0001:
+            raise ValueError("lift.fuse_skeleton_steps / lift.fuse_skeleton_sigma / lift.fuse_skeleton_prior describe the skeleton fit of a fused "
+                             "take: set lift.fuse_skeleton=true")
+        return False, steps, float(sigma), float(prior)
+    if not lift_fuse_options(cfg)[0]:
+        raise ValueError("lift.fuse_skeleton fits one skeleton to the keypoints of a fused take: set lift.fuse=true")
+    return True, steps, float(sigma), float(prior)
+
+
 def _camera_index(cam):
     """fetch()'s 17th number, a camera dict's "index", or None"""
     if isinstance(cam, dict):
@@ -586,7 +607,7 @@ def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, 
     return est, nested, valid, place_valid
 
 
-def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_scores=None):
+def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_scores=None, skel_scores=None):
     """lift.fuse on one group: its sequences are cut into takes (split_takes), every take's views are fused (fuse_views: one hypothesis per view,
     chosen jointly; their mean, root-relative in the world's orientation), with lift.rigid re-assembled with the mean of the views' bone tables, and
     placed with ONE world root per frame (place_views); with lift.floor the take stands on z = 0.  ``res``: the group's _Lifted with hypotheses, taken
@@ -594,9 +615,15 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     and root fit both ok), ``__reproj`` (V, N), ``__steps``, ``__views`` (and ``__floor``) into ``out``; with ``targets`` the take's score into ``scores``.
     With lift.fuse_triangulate every joint is then triangulated on the keypoints (triangulate_views, under the cameras and with the root and ok of the last place_views call) and ``__tri`` (N, 17, 3), in the
     frame of ``<name>.fused<t>``, ``__tri_err``, ``__tri_views``, ``__tri_ok``, ``__tri_steps`` (N, 17) are added; with ``targets`` the triangulated
-    pose's score goes into ``tri_scores`` (the frames with a joint whose ok is 0 left out)."""
-    from manipose_amd import (bundle_views, camera_table, fuse_views, fuse_views_path, place_views, project_rigid, score_poses, score_traj, to_world,
-                              triangulate_views)
+    pose's score goes into ``tri_scores`` (the frames with a joint whose ok is 0 left out).
+    With lift.fuse_skeleton one skeleton is then fitted to the keypoints (fit_skeleton_views, under the same cameras): the start is the
+    triangulated point where it has a result and the fused pose plus root elsewhere, a frame is fitted where its root was placed or every joint
+    was triangulated, the bone table is the take's lift.rigid table or the start's median; ``__skel`` (N, 17, 3), in the frame of
+    ``<name>.fused<t>``, ``__skel_bones`` (16,), ``__skel_err`` (N, 2), ``__skel_ok``, ``__skel_steps`` (N,) and with lift.rotations ``__skel_quat``
+    (N, 17, 4), ``__skel_quat_ok`` (N,) are added; with ``targets`` the fitted pose's score goes into ``skel_scores`` (the frames without a
+    result left out)."""
+    from manipose_amd import (bundle_views, camera_table, fit_skeleton_views, fuse_views, fuse_views_path, place_views, pose_rotations, project_rigid,
+                              score_poses, score_traj, to_world, triangulate_views)
     from manipose_amd.lifting import SCORE_FIELDS
     _, sigma, weight, refine = lift_fuse_options(cfg)
     along, path_sigma, path_switch = lift_fuse_path_options(cfg)
@@ -635,8 +662,10 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
         pose, choice, cost, spread, ok, path_cost = fuse_views_path(hyps, q_arg, valid, off, sigma, weight, path_sigma, path_switch)
     else:
         pose, choice, cost, spread, ok = fuse_views(hyps, q_arg, valid, off, sigma, weight)
+    tables = None
     if res.bones is not None:                  # lift.rigid: one table per take, the mean of its views'
-        project_rigid(pose, torch.stack([torch.stack([res.bones[i] for i in views]).mean(dim=0) for views in takes]), seq_offset=off)
+        tables = torch.stack([torch.stack([res.bones[i] for i in views]).mean(dim=0) for views in takes])
+        project_rigid(pose, tables, seq_offset=off)
     root, reproj, placed, steps = place_views(pose, kp, nested, place_valid, off, refine=refine, return_steps=True)
     placed_cams = nested
     bundle_steps, bundle_sigma = lift_fuse_bundle_options(cfg)
@@ -651,6 +680,18 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     tri = None
     if tri_on:                                 # lift.fuse_triangulate: every joint on its own, under the cameras and the root of the last placement
         tri = triangulate_views(pose, root, kp, placed_cams, place_valid, off, placed, sigma=tri_sigma, prior=tri_prior, refine=tri_steps)
+    skel_on, skel_steps, skel_sigma, skel_prior = lift_fuse_skeleton_options(cfg)
+    skel = skel_rot = None
+    if skel_on:                                # lift.fuse_skeleton: one body of constant bones per frame, fitted to the keypoints under the same cameras
+        start, start_ok = pose + root[:, None], placed
+        if tri is not None:
+            start = torch.where((tri.ok != 0)[..., None], tri.points, start)
+            start_ok = placed | (tri.ok != 0).all(dim=1).to(torch.uint8)
+        skel = fit_skeleton_views(start.contiguous(), kp, placed_cams, tables, place_valid, off, start_ok.contiguous(), sigma=skel_sigma,
+                                  prior=skel_prior, refine=skel_steps)
+        rotations, rot_continuous = lift_rotations_options(cfg)
+        if rotations:
+            skel_rot = pose_rotations(skel.pose, seq_offset=off, continuous=rot_continuous)
     unit = np.tile(np.array([1, 0, 0, 0], np.float32), (len(takes), 1))
     scene = to_world(pose.clone(), unit, traj=root, seq_offset=off, floor=True if floor else False)
     scene, d_floor = scene if floor else (scene, None)
@@ -668,6 +709,9 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
         if tri is not None:                    # the triangulated pose, made root-relative, against the same ground truth
             tri_rec = score_poses(tri.points, d_pose, seq_offset=off, valid=(tri.ok != 0).all(dim=1).to(torch.uint8), root_relative=True)
             tri_ate = score_traj(tri.points[:, 0].contiguous(), d_root, ok=(tri.ok[:, 0] != 0).to(torch.uint8), seq_offset=off)
+        if skel is not None:                   # the fitted pose likewise
+            skel_rec = score_poses(skel.pose, d_pose, seq_offset=off, valid=(skel.ok & 1).contiguous(), root_relative=True)
+            skel_ate = score_traj(skel.pose[:, 0].contiguous(), d_root, ok=(skel.ok & 1).contiguous(), seq_offset=off)
     for t, views in enumerate(takes):
         key, sl = f"{name}.fused{t}", slice(int(off[t]), int(off[t + 1]))
         out[key] = scene[sl].cpu().numpy()
@@ -691,12 +735,23 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
                 points[..., 2] = torch.where(tri.ok[sl] != 0, points[..., 2] - d_floor[t], points[..., 2])
             out[key + "__tri"], out[key + "__tri_err"] = points.cpu().numpy(), tri.err[sl].cpu().numpy()
             out[key + "__tri_views"], out[key + "__tri_ok"], out[key + "__tri_steps"] = (v[sl].cpu().numpy() for v in (tri.views, tri.ok, tri.steps))
+        if skel is not None:
+            fitted = skel.pose[sl].clone()
+            if floor:                          # the frame of the fused pose: the same offset off z (a frame without a result stays 0)
+                fitted[..., 2] = torch.where((skel.ok[sl] & 1 != 0)[:, None], fitted[..., 2] - d_floor[t], fitted[..., 2])
+            out[key + "__skel"], out[key + "__skel_bones"], out[key + "__skel_err"] = fitted.cpu().numpy(), skel.lengths[t].cpu().numpy(), skel.err[sl].cpu().numpy()
+            out[key + "__skel_ok"], out[key + "__skel_steps"] = skel.ok[sl].cpu().numpy(), skel.steps[sl].cpu().numpy()
+            if skel_rot is not None:
+                out[key + "__skel_quat"], out[key + "__skel_quat_ok"] = skel_rot[0][sl].cpu().numpy(), skel_rot[1][sl].cpu().numpy()
         if targets is not None and scores is not None:
             scores[key] = {f: getattr(rec, f)[t].cpu().numpy() for f in SCORE_FIELDS}
             scores[key]["traj"] = {"ate": ate.ate[t].cpu().numpy(), "frames": ate.frames[t].cpu().numpy()}
         if targets is not None and tri is not None and tri_scores is not None:
             tri_scores[key] = {f: getattr(tri_rec, f)[t].cpu().numpy() for f in SCORE_FIELDS}
             tri_scores[key]["traj"] = {"ate": tri_ate.ate[t].cpu().numpy(), "frames": tri_ate.frames[t].cpu().numpy()}
+        if targets is not None and skel is not None and skel_scores is not None:
+            skel_scores[key] = {f: getattr(skel_rec, f)[t].cpu().numpy() for f in SCORE_FIELDS}
+            skel_scores[key]["traj"] = {"ate": skel_ate.ate[t].cpu().numpy(), "frames": skel_ate.frames[t].cpu().numpy()}
 
 
 ROTATION_KEYS = {"quat": "__quat", "ok": "__quat_ok", "hyps_quat": "__hyps_quat", "hyps_ok": "__hyps_quat_ok"}      # of a rotations dict -> in lift.npz
@@ -713,7 +768,7 @@ def synthetic_cameras(groups):
     return cams
 
 
-def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None, fused_scores=None, tri_scores=None):
+def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None, fused_scores=None, tri_scores=None, skel_scores=None):
     """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
     hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
     it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
@@ -746,7 +801,11 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     ``fused_scores`` receives {fused key: score dict} of the fused pose and root against the first view's ground truth in the world.  With
     lift.fuse_triangulate (lift.fuse_triangulate_steps, lift.fuse_triangulate_sigma, lift.fuse_triangulate_prior) every joint of a fused take is
     triangulated on the keypoints of the views that see it (triangulate_views) and ``__tri`` (N, 17, 3), ``__tri_err``, ``__tri_views``, ``__tri_ok``,
-    ``__tri_steps`` (N, 17) are added; with ``targets`` the dict ``tri_scores`` receives {fused key: score dict} of the triangulated pose."""
+    ``__tri_steps`` (N, 17) are added; with ``targets`` the dict ``tri_scores`` receives {fused key: score dict} of the triangulated pose.  With
+    lift.fuse_skeleton (lift.fuse_skeleton_steps, lift.fuse_skeleton_sigma, lift.fuse_skeleton_prior) one skeleton of constant bones is fitted to
+    the keypoints of every fused take (fit_skeleton_views) and ``__skel`` (N, 17, 3), ``__skel_bones`` (16,), ``__skel_err`` (N, 2), ``__skel_ok``,
+    ``__skel_steps`` (N,) and with lift.rotations ``__skel_quat`` (N, 17, 4), ``__skel_quat_ok`` (N,) are added; with ``targets`` the dict
+    ``skel_scores`` receives {fused key: score dict} of the fitted pose."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
     out = {}
@@ -794,7 +853,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
             if res.score is not None and scores is not None:
                 scores[key] = to_host(asked(res.score[i]))
         if fuse:
-            fuse_group(out, name, res, seqs, cameras[name], cfg, targets[name] if targets is not None else None, fused_scores, tri_scores)
+            fuse_group(out, name, res, seqs, cameras[name], cfg, targets[name] if targets is not None else None, fused_scores, tri_scores, skel_scores)
     np.savez(path, **out)
     return out
 
@@ -843,6 +902,7 @@ def run(argv, extra_defaults=None):
     lift_fuse_align_options(cfg)               # ... and a lift.fuse_cameras=estimate without lift.fuse
     lift_fuse_bundle_options(cfg)              # ... and a lift.fuse_bundle without lift.fuse_cameras=estimate
     lift_fuse_triangulate_options(cfg)         # ... and a lift.fuse_triangulate without lift.fuse
+    lift_fuse_skeleton_options(cfg)            # ... and a lift.fuse_skeleton without lift.fuse
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")
@@ -1013,10 +1073,10 @@ def run(argv, extra_defaults=None):
         cams = None
         if any(lift_place_options(cfg)[:2]) or lift_fuse_options(cfg)[0]:
             cams = seqs["test_cams"] if real else synthetic_cameras(groups)
-        targets, scores, fused_scores, tri_scores = None, {}, {}, {}
+        targets, scores, fused_scores, tri_scores, skel_scores = None, {}, {}, {}, {}
         if lift_score_options(cfg):            # the 3-D ground truth beside the 2-D sequences that are lifted
             targets = {name: sq[0] for name, sq in seqs["test"].items()} if real else synthetic_sequences_3d(cfg, cfg.run.seed)
-        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores, tri_scores)
+        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores, tri_scores, skel_scores)
         is_pose = lambda k: not k.endswith(LIFT_SUFFIXES) and ".fused" not in k
         print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if is_pose(k))} frames of {len(groups)} groups -> {path}", flush=True)
         if lift_fuse_options(cfg)[0]:
@@ -1034,5 +1094,8 @@ def run(argv, extra_defaults=None):
                       flush=True)
             if tri_scores:
                 print(f"lift score, triangulated takes -> {report.write_lift_score_report(out_dir, tri_scores, name='lift_score_tri', joints=False)[0]}",
+                      flush=True)
+            if skel_scores:
+                print(f"lift score, fitted skeletons -> {report.write_lift_score_report(out_dir, skel_scores, name='lift_score_skel', joints=False)[0]}",
                       flush=True)
     return best_val

@@ -896,6 +896,60 @@ int mp_lift_triangulate(const float* pose, const float* root, const uint8_t* roo
                         int distort, float sigma, float prior, int iters, float* points, float* err, uint8_t* views, uint8_t* ok, uint8_t* steps,
                         void* stream);
 
+/* Fitting ONE SKELETON to a fused take's keypoints.  mp_lift_triangulate leaves 17 points per frame, not a body: bone lengths change from frame
+ * to frame, a joint that fewer than two cameras see falls back to the lifted pose, nothing ties a joint to its neighbours.  mp_lift_rigid gives
+ * constant bones by keeping every bone's direction and re-assembling the pose bone by bone: the keypoints have no say, and an error in the hip's
+ * direction moves the whole leg.  Here a frame's pose IS the root and one unit direction per bone of a fixed bone table, and these
+ * U = 3 + 2 (J - 1) unknowns are fitted to the keypoints of all joints at once by undamped Gauss-Newton steps.  The reference has no counterpart.
+ * The conventions are mp_lift_triangulate's: takes, take_offset (G + 1, entries clamped to 0 .. Ftot), valid (V, Ftot) bytes or null, kp
+ * (V, Ftot, J, 2), kp_weight (V, Ftot, J) or null, 1 <= V <= MP_LIFT_FUSE_MAXV, quat (G, V, 4), trans (G, V, 3), intr (G, V, 9), R the matrix of
+ * q / |q| normalised in fp64, a view whose |q|^2 is not finite or < 1e-12 counts as invalid in its take, P = R^T (X - T_v), distort, sigma > 0 in
+ * normalised screen units (+inf: every robust factor is exactly 1), prior >= 0 and finite, 0 <= iters <= MP_LIFT_REFINE_MAXITERS; fp64 between the
+ * float32 loads and the float32 stores, without contraction into fused multiply-adds, a sum a + b + c is (a + b) + c; no atomics, fixed orders:
+ * identical bits on every call; a frame depends on no other frame; the call neither synchronises nor modifies its inputs.  Not measured on real data.
+ * Read only: start (Ftot, J, 3) world points, the pose to start from and to be pulled towards; start_ok (Ftot) bytes or null; lengths (G, J - 1)
+ * device floats, one bone table per take; parents (J) HOST int32 with mp_lift_rigid's conditions (parents[0] = -1, 0 <= parents[j] < j), bone
+ * b = j - 1 joins joint j to parents[j]; 2 <= J <= 32.  Per frame f of take g:
+ *  0. Not fitted.  If start_ok[f] is 0, a start coordinate is not finite, or a length of the take's row is not finite or not > 0:  pose = 0,
+ *     err = 0, ok = 0, steps = 0.
+ *  1. Start.  r = start[0].  For j = 1 .. J-1:  v = start[j] - start[parent],  n = sqrt(v . v);  d_b = v / n where n is finite and > 1e-12;
+ *     otherwise d_b is the direction of the parent's bone ((0, 0, 1) under the root; decided in joint order) and bit 1 of ok is cleared.
+ *  2. Observations.  Rule 2 of mp_lift_triangulate: view v counts by its valid byte and its take's quaternion; (v, j) is an observation where
+ *     both keypoint coordinates and the weight are finite and the weight is > 0.  An invalid view's data is never looked at.
+ *  3. Evaluation at (r, d).  p[0] = r,  p[j] = p[parent] + L_b d_b in joint order.  Per joint j over its observations in view order, rule 4 of
+ *     mp_lift_triangulate at X = p[j]: camera point, deep (Z > 0), projection with its Jacobian, e = du^2 + dv^2, t = 1 + e / sigma^2, W_j += w,
+ *     E_j += w sqrt(e), F_j += w (e / t), and S_j (3x3), g_j the normal equations of the 2x3 Jacobian J_pi R^T with weight w (1 / t^2); then, iff
+ *     prior > 0, the pull: F_j += prior |p_j - start_j|^2, the diagonal of S_j += prior, g_j += prior (p_j - start_j).  F, E and W of the frame
+ *     are the sums over the joints in joint order; deep asks every observation of every joint.
+ *  4. Subtree sums.  T_j = S_j, h_j = g_j;  for j = J-1 down to 1:  T_parent += T_j,  h_parent += h_j.
+ *  5. Tangent bases.  e = the unit axis of the coordinate where |d_b| is smallest, the lowest on a tie (step 4 of mp_lift_rotations);
+ *     e1 = u / |u| with u = e - (e . d_b) d_b,  e2 = d_b x e1,  B_b = L_b [e1 e2] (3x2).
+ *  6. The system of the U unknowns, the root's three and then (alpha_b, beta_b) per bone in bone order, p_j moving by B_b (alpha_b, beta_b) for
+ *     every bone b between the root and j:  H_rr = T_0, right side h_0;  M_b = T_{b+1} B_b,  H_{r,b} = M_b;  H_{a,b} = B_a^T M_b for every bone a
+ *     that is b or lies on the path from the root to b, 0 for every other pair;  the right side of bone b is B_b^T h_{b+1}.  This is
+ *     sum_j J_j^T S_j J_j with the dense 3 x U Jacobian J_j of p_j, which is never formed.
+ *  7. The solve.  H = C C^T, the lower factor:  entry (i, k) is H_ik minus the products C_im C_km for m = 0 .. k-1, one subtraction at a time in
+ *     that order, over C_kk; a pivot (the diagonal entry before its square root) that is not finite or not > 1e-12 H_kk means NO STEP.
+ *     Forward substitution  y_i = (b_i - sum_{k < i} C_ik y_k) / C_ii, i ascending, and back substitution
+ *     delta_i = (y_i - sum_{k > i} C_ki delta_k) / C_ii, i descending, both sums one subtraction at a time with k ascending.
+ *  8. The candidate.  r' = r - delta_r;  t_b = (d_b - delta_alpha e1) - delta_beta e2,  d'_b = t_b / |t_b| (|t_b| >= 1: nothing can vanish).  A
+ *     non-finite number in r' or d' ends the frame's steps.
+ *  9. Accept.  mp_lift_place_refine's rule: the candidate stands iff it is deep and F' <= (1 + 1e-6) F.  The steps end at the first refusal, at a
+ *     failed pivot, or after iters.  If the start itself is not deep, or its F is not finite, the frame has NO RESULT: pose = 0, err = 0, steps =
+ *     0, bit 0 of ok stays clear, bit 1 keeps what step 1 found.
+ * 10. pose (Ftot, J, 3) floats: p;  err (Ftot, 2) floats: E / W, the weighted mean reprojection distance of the frame, at the rigid start and at
+ *     the result (0 where nothing is observed);  ok (Ftot) bytes: bit 0 a finite result, bit 1 every bone of the start had a direction of its
+ *     own;  steps (Ftot) bytes or null.  A frame outside every take's clamped range is not written.
+ * With iters = 0 the result is the rigid start: mp_lift_rigid's rule applied to start in fp64.  With no observation and prior = 0, H = 0: no
+ * step.  One 64-lane workgroup owns one frame; lane j evaluates joint j; the system lives in LDS.
+ * MP_ERR_ARG before anything is launched: an input or output pointer null (start_ok, kp_weight, valid, steps may be null); V or J out of range;
+ * Ftot or G <= 0, G > Ftot, Ftot > 2^31 - 1; a parent table that breaks its conditions; distort not 0 or 1; iters out of range; sigma not > 0;
+ * prior negative or not finite. */
+int mp_lift_fit_skeleton(const float* start, const uint8_t* start_ok, const float* kp, const float* kp_weight, int V, int64_t Ftot, int J,
+                         const uint8_t* valid, const int64_t* take_offset, int G, const float* quat, const float* trans, const float* intr,
+                         const float* lengths, const int32_t* parents, int distort, float sigma, float prior, int iters, float* pose, float* err,
+                         uint8_t* ok, uint8_t* steps, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -38,4 +38,17 @@ static int lift_pose_shape(const char* who, long Ntot, int inner, int J, int C, 
   return MP_OK;
 }
 
+// host: a skeleton's parent table (J) copied into a kernel's arguments: parents precede children, exactly one root (joint 0)
+static int rigid_parents(const char* who, const int* parents, int J, signed char* dst) {
+  MP_CHECK(parents != nullptr, MP_ERR_ARG, "%s: null parent table", who);
+  MP_CHECK(J >= 2 && J <= LIFT_MAXJ, MP_ERR_ARG, "%s: J=%d outside 2..%d", who, J, LIFT_MAXJ);
+  MP_CHECK(parents[0] == -1, MP_ERR_ARG, "%s: parents[0] = %d: joint 0 must be the root (-1)", who, parents[0]);
+  for (int j = 1; j < J; ++j) {
+    MP_CHECK(parents[j] >= 0 && parents[j] < j, MP_ERR_ARG, "%s: parents[%d] = %d: parents precede their children", who, j, parents[j]);
+    dst[j] = (signed char)parents[j];
+  }
+  dst[0] = -1;
+  return MP_OK;
+}
+
 }  // namespace mp

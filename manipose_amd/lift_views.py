@@ -4,7 +4,8 @@ cuts a group's sequences into takes and calls them.  ``fuse_views``: one hypothe
 ``fuse_views_path``: that choice made jointly over the whole take, a Viterbi path over the combinations, so that a hypothesis all views agree on -
 a mirrored body - cannot make the fused motion flicker; ``place_views``: one world root per frame from all views; ``align_views``: the views'
 extrinsics estimated from their lifted poses, for takes that were never calibrated; ``bundle_views``: those cameras and the roots refined jointly
-on the reprojection error; ``triangulate_views``: every joint of the fused take triangulated on the keypoints of the cameras that see it.  Built
+on the reprojection error; ``triangulate_views``: every joint of the fused take triangulated on the keypoints of the cameras that see it;
+``fit_skeleton_views``: one skeleton of constant bones fitted to those keypoints, frame by frame.  Built
 like lift_ops.py: a public function composes lift_args' checks (``_fuse_front`` and ``_take_front`` are the
 fronts two of them share), then uploads and calls its private launcher, which allocates the outputs and goes through ``_launch``.
 """
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, lift_args
-from .lift_ops import PATH_SIGMA, PATH_SWITCH, REFINE_MAXITERS, _host_f32, _launch, _seq_table, camera_table
+from .lift_ops import PATH_SIGMA, PATH_SWITCH, REFINE_MAXITERS, _host_f32, _launch, _parents_c, _seq_table, _skeleton_of, camera_table
 
 FUSE_MAXV, FUSE_MAXK = 4, 8  # MP_LIFT_FUSE_MAXV, MP_LIFT_FUSE_MAXK of include/manipose_hip.h: views of a take, hypotheses of a view
 FUSE_SIGMA, FUSE_SCORE_WEIGHT = 0.02, 1.0    # defaults of fuse_views: the views' disagreement in metres (not tuned), the weight of -log(score)
@@ -153,17 +154,18 @@ def _take_cameras(cameras, V):
     return intr, quat, trans, present
 
 
-def _take_front(who, pose, keypoints_2d, cameras, valid, take_offset, weights, roots=None):
+def _take_front(who, pose, keypoints_2d, cameras, valid, take_offset, weights, roots=None, ok_name="root_ok"):
     """What place_views and bundle_views do before their uploads: the checks of the take's pose, keypoints, masks, cameras and weights - with ``roots`` =
-    (root, root_ok, fixed) also of bundle_views' three, each where bundle_views has always checked it -, the refusal of CPU tensors, the offsets'
+    (root, root_ok, fixed) also of bundle_views' three, each where bundle_views has always checked it (a root of None: there is none, and the mask
+    of the frames goes by ``ok_name``) -, the refusal of CPU tensors, the offsets'
     upload, and the mask that makes a missing view (None in ``cameras``) invalid in every frame of its take: (valid, d_off, G, (intr, quat, trans,
     present) host tables, h_w, h_fixed)"""
     root, root_ok, fixed = roots if roots is not None else (None, None, None)
-    given = (pose, keypoints_2d) if roots is None else (pose, root, keypoints_2d)
+    given = (pose, keypoints_2d) if root is None else (pose, root, keypoints_2d)
     if all(torch.is_tensor(t) for t in given):
         V, ftot, J = lift_args.take_pose_keypoints(pose, keypoints_2d, FUSE_MAXV, root)
         lift_args.mask(valid, (V, ftot), "valid")
-        lift_args.mask(root_ok, (ftot,), "root_ok", bare=True)
+        lift_args.mask(root_ok, (ftot,), ok_name, bare=True)
         cams = _take_cameras(cameras, V)
         G, present = cams[0].shape[0], cams[3]
         h_fixed = None
@@ -419,3 +421,85 @@ def triangulate_views(pose, root, keypoints_2d, cameras, valid=None, take_offset
     return _triangulate(_lib.load(), pose, root.contiguous(), root_ok.contiguous() if root_ok is not None else None, keypoints_2d.contiguous(),
                         kp_weight.contiguous() if kp_weight is not None else None, valid, d_off, G, torch.from_numpy(quat).to(dev),
                         torch.from_numpy(trans).to(dev), torch.from_numpy(intr).to(dev), distort, sigma, prior, refine)
+
+
+# defaults of fit_skeleton_views (not tuned).  The pull of 1e-4 keeps a frame with an unseen limb solvable: it weighs a 1 cm move at 1e-8 against
+# 4e-6 for one keypoint at noise 0.002
+SKELETON_SIGMA, SKELETON_PRIOR, SKELETON_STEPS = float("inf"), 1e-4, 3
+# What fit_skeleton_views returns: pose (Ftot, J, 3), err (Ftot, 2) float32, ok, steps (Ftot) uint8, lengths (G, J - 1) float32: the bone tables used
+ViewSkeleton = namedtuple("ViewSkeleton", "pose err ok steps lengths")
+
+
+def _fit_skeleton(lib, start, start_ok, kp, kp_weight, valid, d_off, G, d_quat, d_trans, d_intr, d_lengths, parents, distort, sigma, prior, iters):
+    """``mp_lift_fit_skeleton`` on start (Ftot, J, 3), kp (V, Ftot, J, 2), lengths (G, J - 1): (pose, err, ok, steps), new tensors (zeros where no
+    take holds a frame)"""
+    V, ftot, J = int(kp.shape[0]), int(kp.shape[1]), int(kp.shape[2])
+    dev = start.device
+    pose = torch.zeros(ftot, J, 3, dtype=torch.float32, device=dev)
+    err = torch.zeros(ftot, 2, dtype=torch.float32, device=dev)
+    ok, steps = (torch.zeros(ftot, dtype=torch.uint8, device=dev) for _ in range(2))
+    if ftot > 0:
+        _launch(dev, "mp_lift_fit_skeleton", _lib.ptr(start), _lib.ptr(start_ok), _lib.ptr(kp), _lib.ptr(kp_weight), V, ftot, J, _lib.ptr(valid),
+                _lib.ptr(d_off), G, _lib.ptr(d_quat), _lib.ptr(d_trans), _lib.ptr(d_intr), _lib.ptr(d_lengths), parents, int(bool(distort)), float(sigma),
+                float(prior), int(iters), _lib.ptr(pose), _lib.ptr(err), _lib.ptr(ok), _lib.ptr(steps))
+    return pose, err, ok, steps
+
+
+def _median_bones(start, start_ok, d_off, G, parents):
+    """(G, J - 1) float32: per take and bone the median over the take's start_ok frames of the start's bone lengths (torch's median: the lower of
+    two middle values); a take without such a frame gets NaN, which mp_lift_fit_skeleton does not fit"""
+    ftot, J = int(start.shape[0]), int(start.shape[1])
+    par = torch.tensor(list(parents)[1:], dtype=torch.int64, device=start.device)
+    bones = (start[:, 1:].double() - start[:, par].double()).norm(dim=-1)
+    use = torch.isfinite(bones).all(dim=1)
+    if start_ok is not None:
+        use &= start_ok != 0
+    off = d_off.cpu().clamp(0, ftot).tolist()
+    out = torch.full((G, J - 1), float("nan"), dtype=torch.float32, device=start.device)
+    for g in range(G):
+        rows = bones[off[g]:max(off[g], off[g + 1])][use[off[g]:max(off[g], off[g + 1])]]
+        if rows.shape[0]:
+            out[g] = rows.median(dim=0).values.float()
+    return out
+
+
+def fit_skeleton_views(start, keypoints_2d, cameras, lengths=None, valid=None, take_offset=None, start_ok=None, kp_weight=None, skeleton=None,
+                       distort=True, sigma=SKELETON_SIGMA, prior=SKELETON_PRIOR, refine=SKELETON_STEPS):
+    """``mp_lift_fit_skeleton`` on device tensors: ONE SKELETON fitted to a fused take's keypoints.  ``triangulate_views`` leaves a cloud of points
+    per frame, with bone lengths that change from frame to frame; ``project_rigid`` makes bones constant but re-assembles the pose bone by bone,
+    without asking the keypoints.  Here a frame's pose is its root and one unit direction per bone of a fixed bone table, fitted to the keypoints
+    of all joints at once.  ``start`` (Ftot, J, 3) float32 WORLD joints - the triangulated points, or the fused pose plus root -, the pose to start
+    from and to be pulled towards; ``start_ok`` (Ftot) uint8 or None: 0 where a frame is not to be fitted; ``keypoints_2d`` (V, Ftot, J, 2),
+    ``cameras``, ``valid``, ``take_offset``, ``kp_weight`` and ``distort`` as for ``triangulate_views``; ``lengths`` (G, J - 1) or (J - 1,), tensor
+    or array, in the poses' unit: one bone table per take, or None: per take and bone the median over the take's ``start_ok`` frames of the
+    start's bone lengths; ``skeleton``: default the 17-joint H36M tree.  The start is made rigid as ``project_rigid`` does (each bone's direction
+    kept, a bone without one taking its parent's); then up to ``refine`` (0..16) undamped Gauss-Newton steps over the root and two tangent
+    coordinates per bone direction on sum w rho(|res|^2) + prior sum_j |p_j - start_j|^2, rho(e) = e / (1 + e / sigma^2); ``sigma`` > 0 in
+    normalised screen units (inf: plain least squares), ``prior`` >= 0; a step is taken while the cost does not rise (``place_poses``' rule;
+    include/manipose_hip.h has the rule in full).  The defaults are not tuned: the pull of 1e-4 only keeps a frame with an unseen limb solvable.
+    Returns a ``ViewSkeleton``: ``(pose (Ftot, J, 3) world joints with the table's bone lengths, err (Ftot, 2): the frame's weighted mean
+    reprojection distance at the rigid start and at the result, ok (Ftot) uint8: bit 0 a finite result, bit 1 every bone of the start had a
+    direction of its own, steps (Ftot) uint8, lengths (G, J - 1): the tables used)``, new device tensors; a frame without a result is 0 with
+    bit 0 of ok clear.  Inputs are not modified; identical bits on every call.  Not measured on real data."""
+    lift_args.robust_scale(sigma)
+    lift_args.prior_weight(prior)
+    if not lift_args.is_int_in(refine, 0, REFINE_MAXITERS):
+        raise ValueError(f"refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: the rigid start alone), got {refine!r}")
+    h_len = parents = None
+    if all(torch.is_tensor(t) for t in (start, keypoints_2d)):
+        _, _, J = lift_args.take_pose_keypoints(start, keypoints_2d, FUSE_MAXV)
+        lift_args.keypoint_weights(kp_weight, tuple(keypoints_2d.shape[:3]))
+        parents = _parents_c(_skeleton_of(skeleton=skeleton), J)
+        if lengths is not None:
+            G = lift_args.take_count(take_offset)
+            h_len = _host_f32(lengths, (G, J - 1), "lengths", row=(J - 1,))      # (a length that is not > 0: the kernel does not fit its take)
+    valid, d_off, G, (intr, quat, trans, _), _, _ = _take_front("fit_skeleton_views", start, keypoints_2d, cameras, valid, take_offset, None,
+                                                                roots=(None, start_ok, None), ok_name="start_ok")
+    lift_args.need_device("fit_skeleton_views", start, optional=(kp_weight,))
+    dev = start.device
+    start_ok = start_ok.contiguous() if start_ok is not None else None
+    d_len = torch.from_numpy(h_len).to(dev) if h_len is not None else _median_bones(start, start_ok, d_off, G, parents)
+    res = _fit_skeleton(_lib.load(), start, start_ok, keypoints_2d.contiguous(), kp_weight.contiguous() if kp_weight is not None else None, valid, d_off,
+                        G, torch.from_numpy(quat).to(dev), torch.from_numpy(trans).to(dev), torch.from_numpy(intr).to(dev), d_len, parents, distort,
+                        sigma, prior, refine)
+    return ViewSkeleton(*res, d_len)

@@ -13,6 +13,11 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --align [frames=3000] [reps=20]
     python tools/lift_bench.py --bundle [frames=3000] [reps=20]
     python tools/lift_bench.py --triangulate [frames=3000] [reps=20]
+    python tools/lift_bench.py --skeleton [frames=3000] [reps=20]
+--skeleton times mp_lift_fit_skeleton (one skeleton of constant bones fitted to a fused take's keypoints: one kernel, one 64-lane workgroup per
+frame, the system of 35 unknowns in LDS) through its private launcher on --fuse's scene, the start that scene's triangulated joints
+(mp_lift_triangulate, 3 steps), the bone table the start's median, sigma = inf, the default pull, at iters 0, 1 and 3, as ONE take and cut
+into 16, next to mp_lift_triangulate's time for the same frames.
 --triangulate times mp_lift_triangulate (every joint of a fused take triangulated on the 2-D keypoints: one kernel, one lane per (frame, joint))
 through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints, pinhole keypoints with 0.01 of noise, the lifted pose
 0.03 m N(0, 1) off, the roots fitted by mp_lift_fuse_place - at iters 0, 1 and 3, as ONE take and cut into 16, next to mp_lift_fuse_place's time
@@ -421,6 +426,43 @@ def triangulate_bench(argv):
                   f"and {(res.points - (pose + root[:, None])).norm(dim=2).mean().item() * 1e3:.1f} mm from the true pose plus the fitted root", flush=True)
 
 
+def skeleton_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.lift_ops import _launch, _parents_c, _skeleton_of
+    from manipose_amd.lift_views import SKELETON_PRIOR, _fit_skeleton, _fuse_place, _median_bones, _triangulate
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib, V, (quat, trans, intr), pose, _, kp = fuse_scene(frames, 2)
+    g = torch.Generator(device="cuda").manual_seed(4)
+    lifted = pose + 0.03 * torch.randn(frames, 17, 3, device="cuda", generator=g)      # the lifted body: 0.03 m N(0, 1) off per coordinate
+    lifted[:, 0] = 0
+    parents = _parents_c(_skeleton_of(), 17)
+    print(f"--skeleton: {V} views x {frames} frames x 17 joints, one workgroup a frame, pinhole keypoints with 0.01 of noise, the start the triangulated joints, "
+          f"the median bone table, sigma = inf, prior = {SKELETON_PRIOR}; {reps} calls each after 5 of warm-up (the output allocations are inside the time)", flush=True)
+    for G in (1, 16):
+        off = torch.tensor([frames * i // G for i in range(G + 1)], dtype=torch.int64, device="cuda")
+        q, t, k = quat.expand(G, V, 4).contiguous(), trans.expand(G, V, 3).contiguous(), intr.expand(G, V, 9).contiguous()
+        root, _, ok, _ = _fuse_place(lib, lifted, kp, None, off, G, q, t, k, None, False, 3)
+        tri = lambda: _triangulate(lib, lifted, root, ok, kp, None, None, off, G, q, t, k, False, float("inf"), 0.0, 3)
+        start = tri().points
+        print(f"mp_lift_triangulate, {G} take(s), iters=3, on the same frames: {timed_us(tri, reps):,.1f} us", flush=True)
+        table = _median_bones(start, None, off, G, [int(p) for p in parents])
+        for iters in (0, 1, 3):
+            call = lambda: _fit_skeleton(lib, start, None, kp, None, None, off, G, q, t, k, table, parents, False, float("inf"), SKELETON_PRIOR, iters)
+            res = call()
+            us = timed_us(call, reps)
+            direct = lambda: _launch(start.device, "mp_lift_fit_skeleton", _lib.ptr(start), None, _lib.ptr(kp), None, V, frames, 17, None, _lib.ptr(off), G,
+                                     _lib.ptr(q), _lib.ptr(t), _lib.ptr(k), _lib.ptr(table), parents, 0, float("inf"), float(SKELETON_PRIOR), iters, _lib.ptr(res[0]),
+                                     _lib.ptr(res[1]), _lib.ptr(res[2]), _lib.ptr(res[3]))
+            alone = timed_us(direct, reps)                                # the entry point into outputs allocated once: the kernel without the launcher's four fills
+            print(f"mp_lift_fit_skeleton, {G} take(s), iters={iters}: {us:,.1f} us ({alone:,.1f} us into outputs allocated once: {alone * 1e3 / frames:,.1f} ns a frame); "
+                  f"{res[3].float().mean().item():.2f} steps a frame, {(res[2] == 3).float().mean().item():.3f} with a result, mean reprojection "
+                  f"{res[1][:, 0].mean().item():.5f} -> {res[1][:, 1].mean().item():.5f}, {(res[0] - start).norm(dim=2).mean().item() * 1e3:.1f} mm from the start", flush=True)
+
+
+if "--skeleton" in sys.argv:
+    skeleton_bench([a for a in sys.argv[1:] if a != "--skeleton"])
+    sys.exit(0)
 if "--triangulate" in sys.argv:
     triangulate_bench([a for a in sys.argv[1:] if a != "--triangulate"])
     sys.exit(0)
