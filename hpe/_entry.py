@@ -278,7 +278,7 @@ LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj
                  "__cam_rms", "__cam_trans_rms", "__cam_used", "__cam_ok", "__cam_err_deg", "__cam_err_m", "__cam_quat_align", "__cam_trans_align",
                  "__cam_err_deg_align", "__cam_err_m_align", "__cam_bundle_reproj", "__cam_bundle_cost", "__cam_bundle_steps", "__cam_bundle_ok",
                  "__cam_bundle_used", "__tri", "__tri_err", "__tri_views", "__tri_ok", "__tri_steps", "__skel", "__skel_bones", "__skel_err", "__skel_ok",
-                 "__skel_steps", "__skel_quat", "__skel_quat_ok")
+                 "__skel_steps", "__skel_quat", "__skel_quat_ok", "__skel_err_smooth", "__skel_moves")
 
 
 def _scale_and_cost(scale, cost=None, unit="metres"):
@@ -502,6 +502,22 @@ def lift_fuse_skeleton_options(cfg):
     return True, steps, float(sigma), float(prior)
 
 
+def lift_fuse_skeleton_smooth_options(cfg):
+    """(smooth, sweeps) of lift.fuse_skeleton_smooth / lift.fuse_skeleton_sweeps; ValueError for a value or a combination that cannot run - before
+    any model is built."""
+    smooth, sweeps = cfg.lift.get("fuse_skeleton_smooth", 0.0), cfg.lift.get("fuse_skeleton_sweeps", 8)
+    if not is_number(smooth):
+        raise ValueError(f"lift.fuse_skeleton_smooth is a number, got {smooth!r}")
+    if not 0 <= float(smooth) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"lift.fuse_skeleton_smooth must be finite and >= 0 (0: every frame fitted on its own), got {smooth!r}")
+    if not is_int_in(sweeps, 0, 64):
+        raise ValueError(f"lift.fuse_skeleton_sweeps counts sweeps over a take's frames, an integer in 0..64, got {sweeps!r}")
+    if not lift_fuse_skeleton_options(cfg)[0] and (smooth != 0.0 or sweeps != 8):
+        raise ValueError("lift.fuse_skeleton_smooth / lift.fuse_skeleton_sweeps describe the skeleton fit of a fused take along time: set "
+                         "lift.fuse_skeleton=true")
+    return float(smooth), sweeps
+
+
 def _camera_index(cam):
     """fetch()'s 17th number, a camera dict's "index", or None"""
     if isinstance(cam, dict):
@@ -620,7 +636,9 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     triangulated point where it has a result and the fused pose plus root elsewhere, a frame is fitted where its root was placed or every joint
     was triangulated, the bone table is the take's lift.rigid table or the start's median; ``__skel`` (N, 17, 3), in the frame of
     ``<name>.fused<t>``, ``__skel_bones`` (16,), ``__skel_err`` (N, 2), ``__skel_ok``, ``__skel_steps`` (N,) and with lift.rotations ``__skel_quat``
-    (N, 17, 4), ``__skel_quat_ok`` (N,) are added; with ``targets`` the fitted pose's score goes into ``skel_scores`` (the frames without a
+    (N, 17, 4), ``__skel_quat_ok`` (N,) are added; with lift.fuse_skeleton_smooth > 0 the take is fitted along time (lift.fuse_skeleton_sweeps
+    sweeps): ``__skel``, ``__skel_quat`` and the score are the smoothed fit's, ``__skel_err`` stays (N, 2) and ``__skel_err_smooth`` (N,),
+    ``__skel_moves`` (N,) are added; with ``targets`` the fitted pose's score goes into ``skel_scores`` (the frames without a
     result left out)."""
     from manipose_amd import (bundle_views, camera_table, fit_skeleton_views, fuse_views, fuse_views_path, place_views, pose_rotations, project_rigid,
                               score_poses, score_traj, to_world, triangulate_views)
@@ -681,6 +699,7 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     if tri_on:                                 # lift.fuse_triangulate: every joint on its own, under the cameras and the root of the last placement
         tri = triangulate_views(pose, root, kp, placed_cams, place_valid, off, placed, sigma=tri_sigma, prior=tri_prior, refine=tri_steps)
     skel_on, skel_steps, skel_sigma, skel_prior = lift_fuse_skeleton_options(cfg)
+    skel_smooth, skel_sweeps = lift_fuse_skeleton_smooth_options(cfg)
     skel = skel_rot = None
     if skel_on:                                # lift.fuse_skeleton: one body of constant bones per frame, fitted to the keypoints under the same cameras
         start, start_ok = pose + root[:, None], placed
@@ -688,7 +707,7 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
             start = torch.where((tri.ok != 0)[..., None], tri.points, start)
             start_ok = placed | (tri.ok != 0).all(dim=1).to(torch.uint8)
         skel = fit_skeleton_views(start.contiguous(), kp, placed_cams, tables, place_valid, off, start_ok.contiguous(), sigma=skel_sigma,
-                                  prior=skel_prior, refine=skel_steps)
+                                  prior=skel_prior, refine=skel_steps, smooth=skel_smooth, sweeps=skel_sweeps)
         rotations, rot_continuous = lift_rotations_options(cfg)
         if rotations:
             skel_rot = pose_rotations(skel.pose, seq_offset=off, continuous=rot_continuous)
@@ -739,7 +758,9 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
             fitted = skel.pose[sl].clone()
             if floor:                          # the frame of the fused pose: the same offset off z (a frame without a result stays 0)
                 fitted[..., 2] = torch.where((skel.ok[sl] & 1 != 0)[:, None], fitted[..., 2] - d_floor[t], fitted[..., 2])
-            out[key + "__skel"], out[key + "__skel_bones"], out[key + "__skel_err"] = fitted.cpu().numpy(), skel.lengths[t].cpu().numpy(), skel.err[sl].cpu().numpy()
+            out[key + "__skel"], out[key + "__skel_bones"], out[key + "__skel_err"] = fitted.cpu().numpy(), skel.lengths[t].cpu().numpy(), skel.err[sl, :2].cpu().numpy()
+            if skel_smooth > 0:                # lift.fuse_skeleton_smooth: __skel is the smoothed fit; its distance and the accepted visits
+                out[key + "__skel_err_smooth"], out[key + "__skel_moves"] = skel.err[sl, 2].cpu().numpy(), skel.moves[sl].cpu().numpy()
             out[key + "__skel_ok"], out[key + "__skel_steps"] = skel.ok[sl].cpu().numpy(), skel.steps[sl].cpu().numpy()
             if skel_rot is not None:
                 out[key + "__skel_quat"], out[key + "__skel_quat_ok"] = skel_rot[0][sl].cpu().numpy(), skel_rot[1][sl].cpu().numpy()
@@ -903,6 +924,7 @@ def run(argv, extra_defaults=None):
     lift_fuse_bundle_options(cfg)              # ... and a lift.fuse_bundle without lift.fuse_cameras=estimate
     lift_fuse_triangulate_options(cfg)         # ... and a lift.fuse_triangulate without lift.fuse
     lift_fuse_skeleton_options(cfg)            # ... and a lift.fuse_skeleton without lift.fuse
+    lift_fuse_skeleton_smooth_options(cfg)     # ... and a lift.fuse_skeleton_smooth without lift.fuse_skeleton
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")

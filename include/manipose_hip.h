@@ -950,6 +950,51 @@ int mp_lift_fit_skeleton(const float* start, const uint8_t* start_ok, const floa
                          const float* lengths, const int32_t* parents, int distort, float sigma, float prior, int iters, float* pose, float* err,
                          uint8_t* ok, uint8_t* steps, void* stream);
 
+/* Fitting a fused take's skeleton ALONG TIME.  mp_lift_fit_skeleton fits every frame on its own: every frame keeps its own keypoint noise, and the
+ * fitted body jitters.  Here the frames of a take share one cost - the frames' own costs plus smooth times the squared second differences of
+ * the joint positions - which sweeps over the frames lower, one Gauss-Newton step of a frame at a time with its neighbours held.  The 19 inputs,
+ * the conventions, the checks and the numeric rules are mp_lift_fit_skeleton's: fp64 between the float32 loads and the float32 stores, no
+ * contraction, a sum a + b + c is (a + b) + c, no atomics, fixed orders, identical bits on every call, inputs untouched, no synchronisation.
+ * smooth >= 0 and finite: the weight of a squared second difference in square metres against the cost's normalised screen units squared;
+ * 0 <= sweeps <= MP_LIFT_SKELETON_MAXSWEEPS.  scratch: device memory, 8-byte aligned, of at least
+ * mp_lift_fit_skeleton_smooth_scratch_bytes(Ftot, J) = 48 Ftot J bytes (0 for arguments out of range); its contents after the call are not
+ * specified.  Not measured on real data; smooth = 0.1 and 8 sweeps, the bindings' defaults, are untuned and come from a synthetic motion.
+ * STAGE A.  Every frame is fitted by rules 0 to 10 of mp_lift_fit_skeleton: pose, err[:, 0:2], ok and steps are that function's bits.  The
+ *   frame's state (r, d) and its positions p stay in fp64 in scratch and never make a float32 round trip between visits.  A frame is USABLE iff
+ *   bit 0 of its ok is set.  err[:, 2] = err[:, 1], moves = 0.
+ * STAGE B, iff smooth > 0 and sweeps > 0.  The cost of a take is the sum of its usable frames' F (rule 3, the pull towards the start included)
+ *   plus  smooth sum_s sum_j |p_j(s-1) - 2 p_j(s) + p_j(s+1)|^2  over every take-local frame index s whose frames s-1, s, s+1 all lie in the
+ *   take (its clamped range) and are all usable: a term never crosses a take's border or an unusable frame.
+ *  S1. The stencil of frame t.  t appears in the terms centred at t-1 (coefficient 1), t (-2) and t+1 (1).  With u(k) = frame k lies in the take
+ *     and is usable:  a = u(t-2) and u(t-1),  b = u(t-1) and u(t+1),  c = u(t+1) and u(t+2)  say which of them exist, and
+ *     W_t = a + 4 b + c, one of 0, 1, 4, 5, 6.  With the other frames held, the terms that exist are  smooth W_t sum_j |p_j - q_j|^2  plus a
+ *     constant, where per coordinate, with c1- = 2 a + 2 b, c1+ = 2 b + 2 c, c2- = a, c2+ = c (each 0, 1, 2 or 4),
+ *       q_j = ((c1- p_j(t-1) + c1+ p_j(t+1)) - (c2- p_j(t-2) + c2+ p_j(t+2))) / W_t
+ *     in exactly this order; a frame whose coefficient is 0 is not read and counts as 0.  The full stencil gives
+ *     q = (4 (p(t-1) + p(t+1)) - (p(t-2) + p(t+2))) / 6  (the products are exact), b alone the midpoint of t-1 and t+1, a alone 2 p(t-1) - p(t-2).
+ *  S2. The order of the visits.  For sweep = 0 .. sweeps-1, for colour = 0, 1, 2: every usable frame t of every take with
+ *     (t - the take's first frame) mod 3 = colour and W_t > 0 is visited.  A visited frame reads frames t+-1 and t+-2, which have other colours:
+ *     the visits of a colour are independent, and the result does not depend on their order.
+ *  S3. A visit is ONE step of rules 3 to 9 from the frame's current state.  Rule 3 is evaluated with a second pull, added after the pull towards
+ *     the start and exactly as that one is, with lambda = (double)smooth * W_t:  F_j += lambda |p_j - q_j|^2 (the squares summed (x + y) + z),
+ *     the diagonal of S_j += lambda,  g_j += lambda (p_j - q_j).  If the state's evaluation is not deep or its F is not finite, a pivot fails
+ *     (rule 7), the candidate is not finite (rule 8), or the candidate is refused (rule 9: it stands iff it is deep and F' <= (1 + 1e-6) F, on
+ *     this conditional cost, so the take's cost never rises by more than that slack), the frame's state stays and the frame is visited again
+ *     in the next sweep.  An accepted candidate becomes the state; pose and err[:, 2] are written from it, moves += 1.
+ * Outputs: pose (Ftot, J, 3) floats: p after the last sweep;  err (Ftot, 3) floats: E / W at the rigid start, after stage A, and at the result
+ * (the pulls do not enter E / W);  ok (Ftot), steps (Ftot) bytes or null: stage A's;  moves (Ftot) bytes or null: the accepted visits.  With
+ * smooth = 0 or sweeps = 0, pose, err[:, 0:2], ok and steps are bit for bit mp_lift_fit_skeleton's.  A frame outside every take's clamped range is
+ * not written.  Stage A is one launch, stage B 3 sweeps launches, one 64-lane workgroup a frame in each.
+ * MP_ERR_ARG before anything is launched: what mp_lift_fit_skeleton refuses; smooth negative or not finite; sweeps out of range; scratch null,
+ * not 8-byte aligned or smaller than mp_lift_fit_skeleton_smooth_scratch_bytes. */
+#define MP_LIFT_SKELETON_MAXSWEEPS 64
+int64_t mp_lift_fit_skeleton_smooth_scratch_bytes(int64_t Ftot, int J);
+int mp_lift_fit_skeleton_smooth(const float* start, const uint8_t* start_ok, const float* kp, const float* kp_weight, int V, int64_t Ftot, int J,
+                                const uint8_t* valid, const int64_t* take_offset, int G, const float* quat, const float* trans, const float* intr,
+                                const float* lengths, const int32_t* parents, int distort, float sigma, float prior, int iters, float smooth,
+                                int sweeps, float* pose, float* err, uint8_t* ok, uint8_t* steps, uint8_t* moves, void* scratch,
+                                int64_t scratch_bytes, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -19,7 +19,7 @@ objs=()
 for f in "$HERE"/*.hip; do
   o="$OBJ/$(basename "${f%.hip}").o"
   objs+=("$o")                 # the link takes the objects of the sources that are present, not a stale one of a deleted source
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/common.h" -nt "$o" ] || [ "$HERE/kernels.h" -nt "$o" ] || [ "$HERE/hazard.h" -nt "$o" ] || [ "$HERE/kloop_asm.inc" -nt "$o" ] || [ "$HERE/lift_common.h" -nt "$o" ] || [ "$HERE/lift_geom.h" -nt "$o" ] || [ "$HERE/../../include/manipose_hip.h" -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/common.h" -nt "$o" ] || [ "$HERE/kernels.h" -nt "$o" ] || [ "$HERE/hazard.h" -nt "$o" ] || [ "$HERE/kloop_asm.inc" -nt "$o" ] || [ "$HERE/lift_common.h" -nt "$o" ] || [ "$HERE/lift_geom.h" -nt "$o" ] || [ "$HERE/lift_skeleton.h" -nt "$o" ] || [ "$HERE/../../include/manipose_hip.h" -nt "$o" ]; then
     $HIPCC $FLAGS -c "$f" -o "$o" 2> >(grep -v "is not a recognized feature for this target" >&2) &
     pids+=($!)
   fi

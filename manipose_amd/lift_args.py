@@ -128,6 +128,18 @@ def prior_weight(prior):
         raise ValueError(f"prior must be a finite number >= 0 (0: no pull towards the fused pose), got {prior!r}")
 
 
+def smooth_weight(smooth):
+    """smooth is a finite number >= 0 (a float32): the weight of a squared second difference"""
+    if not is_number(smooth) or not 0 <= float(smooth) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"smooth must be a finite number >= 0 (0: every frame fitted on its own), got {smooth!r}")
+
+
+def sweep_count(sweeps, highest):
+    """sweeps is an integer in 0..highest"""
+    if not is_int_in(sweeps, 0, highest):
+        raise ValueError(f"sweeps counts sweeps over a take's frames, an integer in 0..{highest} (0: every frame fitted on its own), got {sweeps!r}")
+
+
 def take_count(take_offset):
     """the G of a (G + 1) table of first frames, host or device, read from its size alone (None: one take)"""
     if take_offset is None:

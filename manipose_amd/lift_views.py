@@ -445,6 +445,31 @@ def _fit_skeleton(lib, start, start_ok, kp, kp_weight, valid, d_off, G, d_quat, 
     return pose, err, ok, steps
 
 
+# defaults of fit_skeleton_views' smoothing along time (not tuned: taken from a synthetic motion), and the entry point's bound on the sweeps
+SKELETON_SMOOTH, SKELETON_SWEEPS, SKELETON_MAXSWEEPS = 0.0, 8, 64
+# What fit_skeleton_views returns with smooth > 0: err is (Ftot, 3), its third column the result's; moves (Ftot) uint8: the accepted visits
+ViewSkeletonSmooth = namedtuple("ViewSkeletonSmooth", "pose err ok steps lengths moves")
+
+
+def _fit_skeleton_smooth(lib, start, start_ok, kp, kp_weight, valid, d_off, G, d_quat, d_trans, d_intr, d_lengths, parents, distort, sigma, prior, iters,
+                         smooth, sweeps):
+    """``mp_lift_fit_skeleton_smooth`` on ``_fit_skeleton``'s arguments: (pose, err (Ftot, 3), ok, steps, moves), new tensors (zeros where no take
+    holds a frame)"""
+    V, ftot, J = int(kp.shape[0]), int(kp.shape[1]), int(kp.shape[2])
+    dev = start.device
+    pose = torch.zeros(ftot, J, 3, dtype=torch.float32, device=dev)
+    err = torch.zeros(ftot, 3, dtype=torch.float32, device=dev)
+    ok, steps, moves = (torch.zeros(ftot, dtype=torch.uint8, device=dev) for _ in range(3))
+    if ftot > 0:
+        n = int(lib.mp_lift_fit_skeleton_smooth_scratch_bytes(ftot, J))
+        scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
+        _launch(dev, "mp_lift_fit_skeleton_smooth", _lib.ptr(start), _lib.ptr(start_ok), _lib.ptr(kp), _lib.ptr(kp_weight), V, ftot, J, _lib.ptr(valid),
+                _lib.ptr(d_off), G, _lib.ptr(d_quat), _lib.ptr(d_trans), _lib.ptr(d_intr), _lib.ptr(d_lengths), parents, int(bool(distort)), float(sigma),
+                float(prior), int(iters), float(smooth), int(sweeps), _lib.ptr(pose), _lib.ptr(err), _lib.ptr(ok), _lib.ptr(steps), _lib.ptr(moves),
+                _lib.ptr(scratch), n)
+    return pose, err, ok, steps, moves
+
+
 def _median_bones(start, start_ok, d_off, G, parents):
     """(G, J - 1) float32: per take and bone the median over the take's start_ok frames of the start's bone lengths (torch's median: the lower of
     two middle values); a take without such a frame gets NaN, which mp_lift_fit_skeleton does not fit"""
@@ -464,7 +489,7 @@ def _median_bones(start, start_ok, d_off, G, parents):
 
 
 def fit_skeleton_views(start, keypoints_2d, cameras, lengths=None, valid=None, take_offset=None, start_ok=None, kp_weight=None, skeleton=None,
-                       distort=True, sigma=SKELETON_SIGMA, prior=SKELETON_PRIOR, refine=SKELETON_STEPS):
+                       distort=True, sigma=SKELETON_SIGMA, prior=SKELETON_PRIOR, refine=SKELETON_STEPS, smooth=SKELETON_SMOOTH, sweeps=SKELETON_SWEEPS):
     """``mp_lift_fit_skeleton`` on device tensors: ONE SKELETON fitted to a fused take's keypoints.  ``triangulate_views`` leaves a cloud of points
     per frame, with bone lengths that change from frame to frame; ``project_rigid`` makes bones constant but re-assembles the pose bone by bone,
     without asking the keypoints.  Here a frame's pose is its root and one unit direction per bone of a fixed bone table, fitted to the keypoints
@@ -480,9 +505,18 @@ def fit_skeleton_views(start, keypoints_2d, cameras, lengths=None, valid=None, t
     Returns a ``ViewSkeleton``: ``(pose (Ftot, J, 3) world joints with the table's bone lengths, err (Ftot, 2): the frame's weighted mean
     reprojection distance at the rigid start and at the result, ok (Ftot) uint8: bit 0 a finite result, bit 1 every bone of the start had a
     direction of its own, steps (Ftot) uint8, lengths (G, J - 1): the tables used)``, new device tensors; a frame without a result is 0 with
-    bit 0 of ok clear.  Inputs are not modified; identical bits on every call.  Not measured on real data."""
+    bit 0 of ok clear.  Inputs are not modified; identical bits on every call.  Not measured on real data.
+
+    ``smooth`` > 0 fits the take ALONG TIME (``mp_lift_fit_skeleton_smooth``): after the fit above, ``sweeps`` (0..64) sweeps over the frames
+    lower the frames' costs plus ``smooth`` times the squared second differences of the joint positions, a frame at a time taking one
+    Gauss-Newton step with its neighbours held (the terms never cross a take's border or a frame without a result).  It then returns a
+    ``ViewSkeletonSmooth``: ``err`` is (Ftot, 3), its third column the distance at the smoothed result, and ``moves (Ftot) uint8``, the accepted
+    visits, follows ``lengths``.  With ``smooth=0`` (the default) the call and its result are what they are without the two arguments.
+    ``smooth=0.1`` with 8 sweeps is what a synthetic motion suggested; neither is tuned."""
     lift_args.robust_scale(sigma)
     lift_args.prior_weight(prior)
+    lift_args.smooth_weight(smooth)
+    lift_args.sweep_count(sweeps, SKELETON_MAXSWEEPS)
     if not lift_args.is_int_in(refine, 0, REFINE_MAXITERS):
         raise ValueError(f"refine counts Gauss-Newton steps, an integer in 0..{REFINE_MAXITERS} (0: the rigid start alone), got {refine!r}")
     h_len = parents = None
@@ -499,7 +533,9 @@ def fit_skeleton_views(start, keypoints_2d, cameras, lengths=None, valid=None, t
     dev = start.device
     start_ok = start_ok.contiguous() if start_ok is not None else None
     d_len = torch.from_numpy(h_len).to(dev) if h_len is not None else _median_bones(start, start_ok, d_off, G, parents)
-    res = _fit_skeleton(_lib.load(), start, start_ok, keypoints_2d.contiguous(), kp_weight.contiguous() if kp_weight is not None else None, valid, d_off,
-                        G, torch.from_numpy(quat).to(dev), torch.from_numpy(trans).to(dev), torch.from_numpy(intr).to(dev), d_len, parents, distort,
-                        sigma, prior, refine)
-    return ViewSkeleton(*res, d_len)
+    args = (_lib.load(), start, start_ok, keypoints_2d.contiguous(), kp_weight.contiguous() if kp_weight is not None else None, valid, d_off, G,
+            torch.from_numpy(quat).to(dev), torch.from_numpy(trans).to(dev), torch.from_numpy(intr).to(dev), d_len, parents, distort, sigma, prior, refine)
+    if float(smooth) > 0:
+        pose, err, ok, steps, moves = _fit_skeleton_smooth(*args, smooth, sweeps)
+        return ViewSkeletonSmooth(pose, err, ok, steps, d_len, moves)
+    return ViewSkeleton(*_fit_skeleton(*args), d_len)

@@ -14,6 +14,11 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --bundle [frames=3000] [reps=20]
     python tools/lift_bench.py --triangulate [frames=3000] [reps=20]
     python tools/lift_bench.py --skeleton [frames=3000] [reps=20]
+    python tools/lift_bench.py --skeleton-smooth [frames=3000] [reps=20]
+--skeleton-smooth times mp_lift_fit_skeleton_smooth (a fused take's skeleton fitted along time: mp_lift_fit_skeleton's kernel as stage A, then three
+launches a sweep, one per colour, each visited frame one Gauss-Newton step with its neighbours held) through its private launcher and through the
+entry point into outputs allocated once, on --skeleton's scene and start, iters = 3, smooth = 0.1, at sweeps 1 and 8, as ONE take and cut into
+16, next to mp_lift_fit_skeleton at iters 1 and 3 on the same scene in the same process; a sweep's time is (8 sweeps - 1 sweep) / 7.
 --skeleton times mp_lift_fit_skeleton (one skeleton of constant bones fitted to a fused take's keypoints: one kernel, one 64-lane workgroup per
 frame, the system of 35 unknowns in LDS) through its private launcher on --fuse's scene, the start that scene's triangulated joints
 (mp_lift_triangulate, 3 steps), the bone table the start's median, sigma = inf, the default pull, at iters 0, 1 and 3, as ONE take and cut
@@ -460,6 +465,57 @@ def skeleton_bench(argv):
                   f"{res[1][:, 0].mean().item():.5f} -> {res[1][:, 1].mean().item():.5f}, {(res[0] - start).norm(dim=2).mean().item() * 1e3:.1f} mm from the start", flush=True)
 
 
+def skeleton_smooth_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.lift_ops import _launch, _parents_c, _skeleton_of
+    from manipose_amd.lift_views import SKELETON_PRIOR, _fit_skeleton, _fit_skeleton_smooth, _fuse_place, _median_bones, _triangulate
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib, V, (quat, trans, intr), pose, _, kp = fuse_scene(frames, 2)
+    g = torch.Generator(device="cuda").manual_seed(4)
+    lifted = pose + 0.03 * torch.randn(frames, 17, 3, device="cuda", generator=g)      # the lifted body: 0.03 m N(0, 1) off per coordinate
+    lifted[:, 0] = 0
+    parents = _parents_c(_skeleton_of(), 17)
+    smooth = 0.1
+    print(f"--skeleton-smooth: {V} views x {frames} frames x 17 joints, one workgroup a frame, --skeleton's scene and start, the median bone table, sigma = inf, "
+          f"prior = {SKELETON_PRIOR}, iters = 3, smooth = {smooth}; {reps} calls each after 5 of warm-up (the output allocations are inside the first time)", flush=True)
+    for G in (1, 16):
+        off = torch.tensor([frames * i // G for i in range(G + 1)], dtype=torch.int64, device="cuda")
+        q, t, k = quat.expand(G, V, 4).contiguous(), trans.expand(G, V, 3).contiguous(), intr.expand(G, V, 9).contiguous()
+        root, _, ok, _ = _fuse_place(lib, lifted, kp, None, off, G, q, t, k, None, False, 3)
+        start = _triangulate(lib, lifted, root, ok, kp, None, None, off, G, q, t, k, False, float("inf"), 0.0, 3).points
+        table = _median_bones(start, None, off, G, [int(p) for p in parents])
+        base = {}
+        for iters in (1, 3):
+            res = _fit_skeleton(lib, start, None, kp, None, None, off, G, q, t, k, table, parents, False, float("inf"), SKELETON_PRIOR, iters)
+            direct = lambda: _launch(start.device, "mp_lift_fit_skeleton", _lib.ptr(start), None, _lib.ptr(kp), None, V, frames, 17, None, _lib.ptr(off), G,
+                                     _lib.ptr(q), _lib.ptr(t), _lib.ptr(k), _lib.ptr(table), parents, 0, float("inf"), float(SKELETON_PRIOR), iters, _lib.ptr(res[0]),
+                                     _lib.ptr(res[1]), _lib.ptr(res[2]), _lib.ptr(res[3]))
+            base[iters] = timed_us(direct, reps)
+            print(f"mp_lift_fit_skeleton, {G} take(s), iters={iters}: {base[iters]:,.1f} us into outputs allocated once", flush=True)
+        alone = {}
+        for sweeps in (1, 8):
+            call = lambda: _fit_skeleton_smooth(lib, start, None, kp, None, None, off, G, q, t, k, table, parents, False, float("inf"), SKELETON_PRIOR, 3, smooth, sweeps)
+            res = call()
+            us = timed_us(call, reps)
+            n = int(lib.mp_lift_fit_skeleton_smooth_scratch_bytes(frames, 17))
+            scratch = torch.empty(n // 8, dtype=torch.float64, device="cuda")
+            direct = lambda: _launch(start.device, "mp_lift_fit_skeleton_smooth", _lib.ptr(start), None, _lib.ptr(kp), None, V, frames, 17, None, _lib.ptr(off), G,
+                                     _lib.ptr(q), _lib.ptr(t), _lib.ptr(k), _lib.ptr(table), parents, 0, float("inf"), float(SKELETON_PRIOR), 3, smooth, sweeps,
+                                     _lib.ptr(res[0]), _lib.ptr(res[1]), _lib.ptr(res[2]), _lib.ptr(res[3]), _lib.ptr(res[4]), _lib.ptr(scratch), n)
+            alone[sweeps] = timed_us(direct, reps)
+            sd = lambda p: (p[:-2] - 2 * p[1:-1] + p[2:]).norm(dim=2).mean().item() * 1e3
+            print(f"mp_lift_fit_skeleton_smooth, {G} take(s), sweeps={sweeps}: {us:,.1f} us ({alone[sweeps]:,.1f} us into outputs allocated once); "
+                  f"{res[4].float().mean().item():.2f} accepted visits a frame, mean reprojection {res[1][:, 1].mean().item():.5f} -> {res[1][:, 2].mean().item():.5f}, "
+                  f"mean second difference {sd(res[0]):.2f} mm a frame^2 (the start's {sd(start):.2f})", flush=True)
+        sweep = (alone[8] - alone[1]) / 7
+        print(f"  one sweep (three launches), {G} take(s): {sweep:,.1f} us = {sweep / base[1]:.2f} x the iters=1 call, {sweep / base[3]:.2f} x the iters=3 call; "
+              f"stage A and one sweep together {alone[1]:,.1f} us", flush=True)
+
+
+if "--skeleton-smooth" in sys.argv:
+    skeleton_smooth_bench([a for a in sys.argv[1:] if a != "--skeleton-smooth"])
+    sys.exit(0)
 if "--skeleton" in sys.argv:
     skeleton_bench([a for a in sys.argv[1:] if a != "--skeleton"])
     sys.exit(0)
