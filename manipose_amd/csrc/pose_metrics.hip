@@ -286,6 +286,7 @@ __global__ void bone_length_table_kernel(const float* __restrict__ pred, const f
 }
 
 int bone_length_table(const float* pred, const long* ps, const float* gt, const long* gs, int B, int L, int signed_, float* out, hipStream_t st) {
+  MP_CHECK(pred && ps && gt && gs && out, MP_ERR_ARG, "bone_length_table: null pointer");
   MP_CHECK(B > 0 && L > 0, MP_ERR_ARG, "bone_length_table: B=%d L=%d", B, L);
   hipLaunchKernelGGL(bone_length_table_kernel, dim3(cdiv((long)B * L, 256)), dim3(256), 0, st, pred, gt, ps[0], ps[1], ps[2], ps[3], gs[0], gs[1],
                      gs[2], gs[3], B, L, signed_, out);

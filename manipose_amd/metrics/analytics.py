@@ -165,7 +165,8 @@ class AnalyticsAccumulator:
     chains the windows IT evaluates, in its own order: jumps across window boundaries are those of that order and the reported index is
     local to the rank that holds the largest jump (``all_reduce``).  With one rank the result is the reference's."""
 
-    def __init__(self):
+    def __init__(self, auc_steps: int = 31):
+        self.auc_steps = int(auc_steps)   # thresholds of the AUC grid the added sums were counted on (report() averages over them)
         self.scal = None            # (12,) float64
         self.pairs = None           # (6, 2)
         self.joints = None          # (17, 2)
@@ -299,7 +300,7 @@ class AnalyticsAccumulator:
                "mpsce": var.sqrt().mean().item(),                       # segments_time_consistency(flattened, mode="std")
                "seg_len_err": (s[4] / (n * NB)).item(),                 # segments_len_err(mode="average", signed=False)
                "pck": (100.0 * s[6] / s[8]).item() if s[8] > 0 else float("nan"),
-               "auc": (100.0 * s[7] / (31.0 * s[8])).item() if s[8] > 0 else float("nan"),
+               "auc": (100.0 * s[7] / (float(self.auc_steps) * s[8])).item() if s[8] > 0 else float("nan"),
                "jointwise_err": (self.joints[:, 0] / n).tolist(),
                "mpsce_per_bone": var.sqrt().tolist(), "mpsse_per_pair": (self.pairs[:, 0] / n).tolist()}
         # mean_velocity_error(axis=1, squared=False): mean over (window, frame pair, joint)
@@ -319,7 +320,7 @@ class AnalyticsAccumulator:
         if self.proc is not None:                # Protocol #2 and the Procrustes-aligned 3DPCK / AUC
             out["p_mpjpe"] = (self.proc[0] / (self.proc[4] * NJ)).item()
             out["pck_procrustes"] = (100.0 * self.proc[1] / self.proc[3]).item()
-            out["auc_procrustes"] = (100.0 * self.proc[2] / (31.0 * self.proc[3])).item()
+            out["auc_procrustes"] = (100.0 * self.proc[2] / (float(self.auc_steps) * self.proc[3])).item()
         return out
 
 
