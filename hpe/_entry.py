@@ -278,7 +278,8 @@ LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj
                  "__cam_rms", "__cam_trans_rms", "__cam_used", "__cam_ok", "__cam_err_deg", "__cam_err_m", "__cam_quat_align", "__cam_trans_align",
                  "__cam_err_deg_align", "__cam_err_m_align", "__cam_bundle_reproj", "__cam_bundle_cost", "__cam_bundle_steps", "__cam_bundle_ok",
                  "__cam_bundle_used", "__tri", "__tri_err", "__tri_views", "__tri_ok", "__tri_steps", "__skel", "__skel_bones", "__skel_err", "__skel_ok",
-                 "__skel_steps", "__skel_quat", "__skel_quat_ok", "__skel_err_smooth", "__skel_moves")
+                 "__skel_steps", "__skel_quat", "__skel_quat_ok", "__skel_err_smooth", "__skel_moves", "__sync_lag", "__sync_contrast", "__sync_used", "__sync_ok",
+                 "__sync_curve")
 
 
 def _scale_and_cost(scale, cost=None, unit="metres"):
@@ -446,6 +447,32 @@ def lift_fuse_align_options(cfg):
     return True, float(sigma), iters
 
 
+def lift_fuse_sync_options(cfg):
+    """(estimate, max_lag, min_overlap, sigma, interp) of lift.fuse_sync / lift.fuse_sync_max_lag / lift.fuse_sync_min_overlap / lift.fuse_sync_sigma /
+    lift.fuse_sync_interp; ValueError for a value or a combination that cannot run - before any model is built."""
+    sync = cfg.lift.get("fuse_sync", "none")
+    sync = "none" if sync is None else sync    # (an override lift.fuse_sync=none is read as the null it spells)
+    max_lag, overlap = cfg.lift.get("fuse_sync_max_lag", 32), cfg.lift.get("fuse_sync_min_overlap", 16)
+    sigma, interp = cfg.lift.get("fuse_sync_sigma", 0.05), cfg.lift.get("fuse_sync_interp", "linear")
+    if sync not in ("none", "estimate"):
+        raise ValueError(f"lift.fuse_sync must be none or estimate, got {sync!r}")
+    if not is_int_in(max_lag, 0, 256):
+        raise ValueError(f"lift.fuse_sync_max_lag is the search range in frames, an integer in 0..256, got {max_lag!r}")
+    if not is_int_in(overlap, 1, 2 ** 31 - 1):
+        raise ValueError(f"lift.fuse_sync_min_overlap counts the pairs of frames a lag needs, an integer >= 1, got {overlap!r}")
+    _scale_and_cost(("fuse_sync_sigma", sigma))
+    if interp not in ("linear", "nearest"):
+        raise ValueError(f"lift.fuse_sync_interp must be linear or nearest, got {interp!r}")
+    if sync != "estimate":
+        if max_lag != 32 or overlap != 16 or sigma != 0.05 or interp != "linear":
+            raise ValueError("lift.fuse_sync_max_lag / lift.fuse_sync_min_overlap / lift.fuse_sync_sigma / lift.fuse_sync_interp describe the estimate of "
+                             "the views' lags in time: set lift.fuse_sync=estimate")
+        return False, max_lag, overlap, float(sigma), interp
+    if not lift_fuse_options(cfg)[0]:
+        raise ValueError("lift.fuse_sync=estimate synchronises the views the fusion reads: set lift.fuse=true")
+    return True, max_lag, overlap, float(sigma), interp
+
+
 def lift_fuse_bundle_options(cfg):
     """(steps, sigma) of lift.fuse_bundle / lift.fuse_bundle_sigma; ValueError for a value or a combination that cannot run - before any model is
     built."""
@@ -575,14 +602,50 @@ def _camera_error(q, t, unit, trans):
     return np.degrees(2.0 * np.arctan2(np.linalg.norm(rel), abs(float(q @ unit)))), np.linalg.norm(t.astype(np.float64) - trans)
 
 
-def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, refine, sigma, iters):
+SYNC_KEYS = ("lag", "contrast", "used", "ok", "curve")       # of sync_takes' dict -> "<fused key>__sync_<k>" in lift.npz
+
+
+def sync_takes(name, res, takes, off, valid, max_lag, min_overlap, sigma, interp):
+    """lift.fuse_sync=estimate on one group: every view's lag in time against its take's first view with a usable frame (sync_views on the views'
+    merged poses as they were emitted: the signal is each joint's distance from the root, which no camera and no frame of reference changes).  A
+    view whose lag could not be estimated keeps lag 0, and so does one whose minimum lies at the border of the search range (the true lag may lie
+    outside it); both are reported.  Returns ``(rec, shift)``: rec = {SYNC_KEYS: host arrays (G, V, ..)} as sync_views returned them;
+    shift(x, mask=None) = shift_views(x, the lags that are applied, ``mask`` or the takes' own ``valid``, off, interp), which puts a per-view
+    array on the take's clock, the reference view's."""
+    from manipose_amd import shift_views, sync_views
+    V, ftot = int(valid.shape[0]), int(valid.shape[1])
+    J, dev = int(res.poses[0].shape[1]), valid.device
+    poses = torch.zeros(V, ftot, J, 3, dtype=torch.float32, device=dev)
+    for t, views in enumerate(takes):
+        for v, i in enumerate(views):
+            poses[v, off[t]:off[t + 1]] = res.poses[i]
+    got = sync_views(poses, valid, off, max_lag, min_overlap, sigma)
+    rec = {k: getattr(got, k).cpu().numpy() for k in SYNC_KEYS}
+    applied, lag_int = rec["lag"].copy(), got.lag_int.cpu().numpy()
+    for t, views in enumerate(takes):
+        for v in range(len(views)):
+            if not rec["ok"][t, v] & 1:
+                applied[t, v] = 0.0
+                print(f"lift.fuse_sync [{name}]: take {t}, view {views[v]}: its lag could not be estimated ({int(rec['used'][t, v])} frames used): "
+                      f"the view keeps lag 0", flush=True)
+            elif max_lag > 0 and abs(int(lag_int[t, v])) == max_lag:
+                applied[t, v] = 0.0
+                print(f"lift.fuse_sync [{name}]: take {t}, view {views[v]}: its lag could not be estimated: the minimum lies at the border of the search "
+                      f"range (lag {int(lag_int[t, v])}, lift.fuse_sync_max_lag={max_lag}): the view keeps lag 0", flush=True)
+    d_lag = torch.from_numpy(applied).to(dev)
+    return rec, lambda x, mask=None: shift_views(x, d_lag, valid if mask is None else mask, off, interp)
+
+
+def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, refine, sigma, iters, shift=None):
     """lift.fuse_cameras=estimate on one group: every take's extrinsics from its views' merged poses (align_views), the first view's dataset camera
     as the reference - so the world is the dataset's and its z is up.  The views' poses are taken root-relative in their cameras' frames (with
     lift.frame=world they are rotated back, and so are ``hyps``, IN PLACE), every view's root trajectory is fitted on its own (place_poses with the
     view's intrinsics and ``refine`` steps), and the rotation comes from the poses, the translation from the trajectories.  Returns
     ``(est, nested, valid, place_valid)``: est = {CAMERA_KEYS: host arrays (G, V, ..)}, err_deg / err_m the angle and the distance between the
     estimated and the dataset's extrinsics; nested: place_views' cameras with the dataset's intrinsics and the estimated extrinsics; valid without
-    the views whose rotation could not be estimated, place_valid also without those whose translation could not."""
+    the views whose rotation could not be estimated, place_valid also without those whose translation could not.  ``shift`` (sync_takes',
+    lift.fuse_sync=estimate; ``hyps``, ``kp`` and ``valid`` are then the UNSHIFTED ones): every view's roots are fitted on its own frames, and the
+    merged poses, the roots and their masks are put on the take's clock before align_views reads them; the masks returned are the shifted ones."""
     from manipose_amd import align_views, camera_table, place_poses, to_world
     V, ftot, J, dev, G = int(hyps.shape[0]), int(hyps.shape[1]), int(hyps.shape[3]), hyps.device, len(takes)
     intr, quat, trans = (a.astype(np.float64) for a in camera_table(cams))
@@ -601,8 +664,11 @@ def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, 
             table[v, t] = intr[i]
     starts = np.concatenate([v * ftot + off[:-1] for v in range(V)] + [[V * ftot]]).astype(np.int64)
     traj, _, traj_ok = place_poses(merged.reshape(V * ftot, J, 3), kp.reshape(V * ftot, J, 2), table.reshape(V * G, 9), starts, refine=refine)
-    got = align_views(merged, valid, off, traj.reshape(V, ftot, 3), traj_ok.reshape(V, ftot) & valid, sigma, iters,
-                      reference=[cams[views[0]] for views in takes])
+    traj, traj_ok = traj.reshape(V, ftot, 3), traj_ok.reshape(V, ftot) & valid
+    if shift is not None:                      # lift.fuse_sync=estimate: on the take's clock; a root is there where its fit was ok in the frames it comes from
+        merged, valid = shift(merged)
+        traj, traj_ok = shift(traj.contiguous(), traj_ok)
+    got = align_views(merged, valid, off, traj, traj_ok, sigma, iters, reference=[cams[views[0]] for views in takes])
     est = {k: getattr(got, k).cpu().numpy() for k in CAMERA_KEYS[:6]}
     est["err_deg"], est["err_m"] = np.zeros((G, V), np.float32), np.zeros((G, V), np.float32)
     nested, valid, place_valid = [], valid.clone(), valid.clone()
@@ -629,6 +695,10 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     placed with ONE world root per frame (place_views); with lift.floor the take stands on z = 0.  ``res``: the group's _Lifted with hypotheses, taken
     after the smoothing and rigid stages.  Writes ``<name>.fused<t>`` and its ``__root``, ``__choice``, ``__spread``, ``__cost``, ``__ok`` (consensus
     and root fit both ok), ``__reproj`` (V, N), ``__steps``, ``__views`` (and ``__floor``) into ``out``; with ``targets`` the take's score into ``scores``.
+    With lift.fuse_sync=estimate the views are first synchronised in time (sync_takes: every view's lag against the take's first view, from the merged
+    poses, before any camera is estimated) and the hypotheses, the keypoints, the masks and what estimate_cameras reads are put on the first view's
+    clock (shift_views, lift.fuse_sync_interp) - the take's clock: the ground truth stays the first view's -; ``__sync_lag``, ``__sync_contrast``,
+    ``__sync_used``, ``__sync_ok`` (V,) and ``__sync_curve`` (V, 2 max_lag + 1) are added, as sync_views returned them.
     With lift.fuse_triangulate every joint is then triangulated on the keypoints (triangulate_views, under the cameras and with the root and ok of the last place_views call) and ``__tri`` (N, 17, 3), in the
     frame of ``<name>.fused<t>``, ``__tri_err``, ``__tri_views``, ``__tri_ok``, ``__tri_steps`` (N, 17) are added; with ``targets`` the triangulated
     pose's score goes into ``tri_scores`` (the frames with a joint whose ok is 0 left out).
@@ -672,10 +742,19 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
             quat[t, v] = camera_table([cams[i]])[1][0]
     nested = [[cams[i] for i in views] + [None] * (V - len(views)) for views in takes]
     estimate, align_sigma, align_iters = lift_fuse_align_options(cfg)
+    sync_on, sync_max_lag, sync_overlap, sync_sigma, sync_interp = lift_fuse_sync_options(cfg)
+    sync = shift = None
+    if sync_on:                                # lift.fuse_sync=estimate: the views' lags in time, before any camera is estimated
+        sync, shift = sync_takes(name, res, takes, off, valid, sync_max_lag, sync_overlap, sync_sigma, sync_interp)
     est, q_arg, place_valid = None, None if world else quat, valid
     if estimate:                               # lift.fuse_cameras=estimate: the extrinsics come from the poses, not from the dataset
-        est, nested, valid, place_valid = estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, refine, align_sigma, align_iters)
+        est, nested, valid, place_valid = estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, refine, align_sigma, align_iters, shift)
         q_arg = est["quat"]                    # (the hypotheses are back in their cameras' frames)
+    if shift is not None:                      # every per-view array the later stages read, on the take's clock (with linear, head k of a frame with
+        hyps, moved = shift(hyps)              # head k of the next, scores included: the heads' identity over time is assumed)
+        kp = shift(kp)[0]
+        if not estimate:
+            valid = place_valid = moved
     if along:                                  # lift.fuse_path: the same choice, made jointly over the whole take
         pose, choice, cost, spread, ok, path_cost = fuse_views_path(hyps, q_arg, valid, off, sigma, weight, path_sigma, path_switch)
     else:
@@ -739,6 +818,9 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
         out[key + "__ok"] = (ok[sl] & placed[sl]).cpu().numpy()
         out[key + "__reproj"], out[key + "__steps"] = reproj[:len(views), sl].cpu().numpy(), steps[sl].cpu().numpy()
         out[key + "__views"] = np.array(views, dtype=np.int64)
+        if sync is not None:
+            for k in SYNC_KEYS:
+                out[f"{key}__sync_{k}"] = sync[k][t, :len(views)]
         if est is not None:
             for k in CAMERA_KEYS:
                 out[f"{key}__cam_{k}"] = est[k][t, :len(views)]
@@ -820,6 +902,9 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     to ``__cam_quat_align``, ``__cam_trans_align``, ``__cam_err_deg_align``, ``__cam_err_m_align``, and ``__cam_bundle_reproj`` (V, 2),
     ``__cam_bundle_cost`` (2,) float64, ``__cam_bundle_steps``, ``__cam_bundle_ok`` (scalars) and ``__cam_bundle_used`` (V,) are added; with ``targets`` the dict
     ``fused_scores`` receives {fused key: score dict} of the fused pose and root against the first view's ground truth in the world.  With
+    lift.fuse_sync=estimate (lift.fuse_sync_max_lag, lift.fuse_sync_min_overlap, lift.fuse_sync_sigma, lift.fuse_sync_interp) the views of a take are
+    first synchronised in time (sync_takes) and ``__sync_lag``, ``__sync_contrast``, ``__sync_used``, ``__sync_ok`` (V,), ``__sync_curve``
+    (V, 2 max_lag + 1) are added.  With
     lift.fuse_triangulate (lift.fuse_triangulate_steps, lift.fuse_triangulate_sigma, lift.fuse_triangulate_prior) every joint of a fused take is
     triangulated on the keypoints of the views that see it (triangulate_views) and ``__tri`` (N, 17, 3), ``__tri_err``, ``__tri_views``, ``__tri_ok``,
     ``__tri_steps`` (N, 17) are added; with ``targets`` the dict ``tri_scores`` receives {fused key: score dict} of the triangulated pose.  With
@@ -922,6 +1007,7 @@ def run(argv, extra_defaults=None):
     lift_fuse_path_options(cfg)                # ... and a lift.fuse_path without lift.fuse
     lift_fuse_align_options(cfg)               # ... and a lift.fuse_cameras=estimate without lift.fuse
     lift_fuse_bundle_options(cfg)              # ... and a lift.fuse_bundle without lift.fuse_cameras=estimate
+    lift_fuse_sync_options(cfg)                # ... and a lift.fuse_sync=estimate without lift.fuse
     lift_fuse_triangulate_options(cfg)         # ... and a lift.fuse_triangulate without lift.fuse
     lift_fuse_skeleton_options(cfg)            # ... and a lift.fuse_skeleton without lift.fuse
     lift_fuse_skeleton_smooth_options(cfg)     # ... and a lift.fuse_skeleton_smooth without lift.fuse_skeleton

@@ -795,6 +795,66 @@ int mp_lift_align_views(const float* poses, int V, int64_t Ftot, int J, int C, c
                         const float* traj, const uint8_t* traj_ok, float sigma, int iters, float* quat, float* trans, float* rms, float* trans_rms,
                         int32_t* used, uint8_t* ok, void* stream);
 
+/* Synchronising the views of a take IN TIME: every operator above assumes that frame f of every view shows the same instant.  Cameras that were
+ * never calibrated against each other were not gen-locked either: their views start a few frames apart, often by a fraction of a frame.  This
+ * estimates every view's lag against a reference view from the lifted poses themselves, before any camera is known, and mp_lift_shift_views puts
+ * a per-view array on the reference's clock.  The signal is the distance of every joint from the root: it does not depend on the camera's
+ * orientation, and mirroring the camera's z - the lifter's depth ambiguity - leaves it untouched.  (Joint speeds, the obvious alternative, failed
+ * by tens of frames at 10 mm of noise in a numpy prototype.)  The conventions are mp_lift_align_views': takes, take_offset (entries clamped to
+ * 0 .. Ftot), valid (V, Ftot) bytes or null, 1 <= V <= MP_LIFT_FUSE_MAXV; fp64 between the float32 loads and the float32 stores, without
+ * contraction into fused multiply-adds; no atomics, fixed orders: identical bits on every call; a take's result does not depend on the other
+ * takes of the call; the call does not synchronise.  Not measured on real data.
+ * poses (V, Ftot, J, C) read only, C = 3 or 4 (channel 3 is not read), 2 <= J <= 32: one pose per view and frame in that view's camera frame;
+ * 0 <= max_lag <= MP_LIFT_SYNC_MAXLAG, written L; min_overlap >= 1; sigma > 0 in the poses' unit (+inf: plain squares).  Per take g with frames
+ * [f0, f1):
+ * 1. d[v][f][j] = |x[v][f][j] - x[v][f][0]|, j = 1 .. J - 1: the square root of the squared differences added in channel order.  Frame f is
+ *    USABLE in view v if it is valid there and all 3 J coordinates are finite.
+ * 2. used[g][v] = the number of usable frames;  m[v][j] = the mean of d over them (lane l of 256 sums the take's frames l, l + 256, .. in order, the
+ *    lanes' sums are added by a butterfly within a wave and the four waves' in wave order);  s[v][f][j] = d - m.  The mean is removed so that a view whose lifter sees the body slightly larger does not pay
+ *    for it at every lag.
+ * 3. The reference view r is the lowest view with a usable frame.  Its row: lag = 0, lag_int = 0, a curve of zeros, contrast = 0, ok = 1.  A take
+ *    without such a view writes zeros and ok = 0 for every view.
+ * 4. For a view v != r and a lag d in -L .. L the PAIRS are the frames f with f and f + d both inside the take, r usable at f and v usable at
+ *    f + d; n(d) is their number.  n(d) < min_overlap: the lag is INELIGIBLE and curve[d] = +inf.  Else
+ *    e_f = (sum_j (s[v][f+d][j] - s[r][f][j])^2) / (J - 1), joints in order, and  curve[d] = (sum_f e_f / (1 + e_f / sigma^2)) / n(d); with sigma = +inf every
+ *    term is exactly e_f.  The order of the sum: the take's n frames are cut into chunks of max(256, 64 ceil(n / 4096)) frames; slot s of 16 sums
+ *    a chunk's frames s, s + 16, .. in order, the 16 sums are added in order, then the chunks' sums in order.  A value
+ *    that is not finite makes the lag ineligible.
+ * 5. d* is the eligible lag with the smallest curve value; ties go to the smaller |d|, then to the positive lag.  No eligible lag: ok = 0,
+ *    lag = 0, lag_int = 0, contrast = 0.
+ * 6. The sub-frame part, in fp64 from the fp64 curve values c: if |d*| < L, both neighbours are eligible and
+ *    den = c[d*-1] - 2 c[d*] + c[d*+1] > 0, then delta = clamp(0.5 (c[d*-1] - c[d*+1]) / den, -0.5, 0.5); otherwise delta = 0.
+ *    lag = float32(d* + delta), lag_int = d*.  The parabola is biased: on noise-free synthetic views the estimate was off by up to 0.08 frame.
+ * 7. ok is a byte: bit 0 a lag was estimated, bit 1 the minimum is interior (step 6's conditions held; without it the true lag may lie outside
+ *    the search range).  contrast = 1 - c[d*] / (the mean of the eligible curve values, summed in lag order by 64 lanes and a butterfly), and 0
+ *    where that mean is not > 0.
+ * 8. Meaning: frame f + lag of view v shows what frame f of the reference shows.
+ * lag, contrast (G, V) floats; lag_int, used (G, V) int32; curve (G, V, 2 L + 1) floats, lag d at d + L; ok (G, V) bytes.
+ * scratch: at least mp_lift_sync_views_scratch_bytes(V, Ftot, J) bytes = V Ftot (8 (J - 1) + 80 + 1) rounded up to 8 (the signals; per take,
+ * lag and chunk a sum and a number of pairs - a take of n frames has at most 2 n - 1 lags with a pair, and fewer than 5 n such entries -; the
+ * usable bytes), 8-byte aligned; 0 for arguments out of range.
+ * Three kernels: one workgroup per (take, view) writes s and the usable bytes; one workgroup per (take, view, block of 16 lags, chunk) stages
+ * tiles of 64 reference rows and the view's 79 rows that pair with them in LDS; one wave per (take, view) adds the chunks and takes the minimum.
+ * MP_ERR_ARG before anything is launched: poses, take_offset or an output null; V, J or C out of range; Ftot or G <= 0, G > Ftot, Ftot or
+ * G V > 2^31 - 1; max_lag or min_overlap out of range; sigma not > 0; scratch null, misaligned or too small.
+ * mp_lift_shift_views: in and out (V, Ftot, M) are rows of M floats per frame, 1 <= M <= MP_LIFT_SHIFT_MAXM; they must not overlap.  lag (G, V)
+ * device floats.  Per take, view and frame f:  p = (f - f0) + lag in fp64.
+ * mode 0, nearest: i = floor(p + 0.5); the row is a copy, bit for bit, of frame f0 + i where i is inside the take and valid there.
+ * mode 1, linear: i = floor(p), a = p - i; with a == 0 the row is a copy of frame f0 + i; otherwise frames i and i + 1 must both be inside the
+ * take and valid, and out = (1 - a) x_i + a x_{i+1}: two products and one sum in fp64, not contracted, rounded once.
+ * A frame without a result gets zeros and valid_out = 0, a frame with one valid_out = 1; so does every frame no take holds.  A lag that is not
+ * finite invalidates the whole view of that take.  A lag of 0 reproduces in at the valid frames and valid (as 0 / 1) exactly.
+ * MP_ERR_ARG before anything is launched: in, take_offset, lag, out or valid_out null; V or M out of range; Ftot or G <= 0, G > Ftot; an
+ * unknown mode; in and out overlapping; more floats than one grid holds. */
+#define MP_LIFT_SYNC_MAXLAG 256
+#define MP_LIFT_SHIFT_MAXM 1048576
+int64_t mp_lift_sync_views_scratch_bytes(int V, int64_t Ftot, int J);
+int mp_lift_sync_views(const float* poses, int V, int64_t Ftot, int J, int C, const uint8_t* valid, const int64_t* take_offset, int G,
+                       int max_lag, int min_overlap, float sigma, float* lag, int32_t* lag_int, float* curve, float* contrast,
+                       int32_t* used, uint8_t* ok, void* scratch, int64_t scratch_bytes, void* stream);
+int mp_lift_shift_views(const float* in, int V, int64_t Ftot, int64_t M, const uint8_t* valid, const int64_t* take_offset, int G,
+                        const float* lag, int mode, float* out, uint8_t* valid_out, void* stream);
+
 /* Bundle-adjusting a take's cameras: mp_lift_align_views gives the extrinsics in closed form from the lifted poses and the per-view roots, and the
  * 2-D keypoints - the only measured quantity - decide nothing about them.  This is the joint Gauss-Newton refinement of all free cameras and all
  * per-frame world roots of a take on the robust reprojection error, the roots eliminated by a Schur complement.  The reference has no counterpart.

@@ -138,6 +138,9 @@ _SIGNATURES = {
     "mp_lift_fuse_path_scratch_bytes": (i64, [i32, i64, i32]),
     "mp_lift_fuse_path": (i32, [vp, i32, i64, i32, i32, i32, vp, vp, i32, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "mp_lift_align_views": (i32, [vp, i32, i64, i32, i32, vp, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "mp_lift_sync_views_scratch_bytes": (i64, [i32, i64, i32]),
+    "mp_lift_sync_views": (i32, [vp, i32, i64, i32, i32, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "mp_lift_shift_views": (i32, [vp, i32, i64, i64, vp, vp, i32, vp, i32, vp, vp, vp]),
     "mp_lift_bundle_views_scratch_bytes": (i64, [i32, i64]),
     "mp_lift_bundle_views": (i32, [vp, vp, vp, vp, i32, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "mp_lift_triangulate": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp, i32, vp, vp, vp, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp]),

@@ -5,7 +5,8 @@ cuts a group's sequences into takes and calls them.  ``fuse_views``: one hypothe
 a mirrored body - cannot make the fused motion flicker; ``place_views``: one world root per frame from all views; ``align_views``: the views'
 extrinsics estimated from their lifted poses, for takes that were never calibrated; ``bundle_views``: those cameras and the roots refined jointly
 on the reprojection error; ``triangulate_views``: every joint of the fused take triangulated on the keypoints of the cameras that see it;
-``fit_skeleton_views``: one skeleton of constant bones fitted to those keypoints, frame by frame.  Built
+``fit_skeleton_views``: one skeleton of constant bones fitted to those keypoints, frame by frame; ``sync_views`` /
+``shift_views``: the views' lags in time estimated from their poses, and any per-view array put on the reference view's clock.  Built
 like lift_ops.py: a public function composes lift_args' checks (``_fuse_front`` and ``_take_front`` are the
 fronts two of them share), then uploads and calls its private launcher, which allocates the outputs and goes through ``_launch``.
 """
@@ -311,6 +312,112 @@ def align_views(poses, valid=None, take_offset=None, traj=None, traj_ok=None, si
         return res
     q, t = _align_compose(res.quat.cpu().numpy(), res.trans.cpu().numpy() if res.trans is not None else None, res.ok.cpu().numpy(), ref_quat, ref_trans)
     return res._replace(quat=torch.from_numpy(q).to(poses.device), trans=torch.from_numpy(t).to(poses.device) if t is not None else None)
+
+
+SYNC_MAXLAG, SHIFT_MAXM = 256, 1 << 20       # MP_LIFT_SYNC_MAXLAG, MP_LIFT_SHIFT_MAXM of include/manipose_hip.h
+# defaults of sync_views: the search range and the fewest pairs of a lag in frames, the robust scale in metres (not tuned, not measured on real data)
+SYNC_MAX_LAG, SYNC_MIN_OVERLAP, SYNC_SIGMA = 32, 16, 0.05
+SHIFT_MODES = {"nearest": 0, "linear": 1}
+# What sync_views returns: lag, contrast (G, V) float32, lag_int, used (G, V) int32, curve (G, V, 2 max_lag + 1) float32, ok (G, V) uint8
+ViewSync = namedtuple("ViewSync", "lag lag_int curve contrast used ok")
+
+
+def _sync(lib, poses, valid, d_off, G, max_lag, min_overlap, sigma):
+    """``mp_lift_sync_views`` on poses (V, Ftot, J, C): a ViewSync of new tensors"""
+    V, ftot, J, ch = (int(v) for v in poses.shape)
+    dev = poses.device
+    lag, contrast = torch.zeros(G, V, dtype=torch.float32, device=dev), torch.zeros(G, V, dtype=torch.float32, device=dev)
+    lag_int, used = torch.zeros(G, V, dtype=torch.int32, device=dev), torch.zeros(G, V, dtype=torch.int32, device=dev)
+    curve = torch.zeros(G, V, 2 * int(max_lag) + 1, dtype=torch.float32, device=dev)
+    ok = torch.zeros(G, V, dtype=torch.uint8, device=dev)
+    if ftot > 0:
+        n = int(lib.mp_lift_sync_views_scratch_bytes(V, ftot, J))
+        scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
+        _launch(dev, "mp_lift_sync_views", _lib.ptr(poses), V, ftot, J, ch, _lib.ptr(valid), _lib.ptr(d_off), G, int(max_lag), int(min_overlap),
+                float(sigma), _lib.ptr(lag), _lib.ptr(lag_int), _lib.ptr(curve), _lib.ptr(contrast), _lib.ptr(used), _lib.ptr(ok), _lib.ptr(scratch), n)
+    return ViewSync(lag, lag_int, curve, contrast, used, ok)
+
+
+def sync_views(poses, valid=None, take_offset=None, max_lag=SYNC_MAX_LAG, min_overlap=SYNC_MIN_OVERLAP, sigma=SYNC_SIGMA):
+    """``mp_lift_sync_views`` on device tensors: the lag IN TIME of every view of a take against a reference view, estimated from the lifted poses
+    themselves, for cameras that were not gen-locked - every other take-level operator assumes that frame f of every view shows the same instant.
+    ``poses`` (V, Ftot, J, 3 | 4) float32, one pose per view and frame in that view's camera frame (channel 3 is not read); ``valid`` (V, Ftot)
+    uint8 device tensor or None; ``take_offset`` (G + 1) as for ``fuse_views``.  A view's signal is the distance of every joint from the root, its
+    mean over the take removed: it knows neither the camera's orientation nor the lifter's depth mirror.  Per take the lowest view with a usable
+    frame is the reference; for every other view and every lag d in -``max_lag`` .. ``max_lag`` (0..256) with at least ``min_overlap`` (>= 1) pairs
+    of frames the curve is the mean of e / (1 + e / sigma^2), e the mean squared difference of the two signals at frames f + d and f; ``sigma`` > 0
+    in the poses' unit (inf: plain squares).  The lag is the curve's minimum (ties: the smaller |d|, then the positive lag) plus the vertex of the
+    parabola through it and its neighbours, clamped to half a frame (include/manipose_hip.h has the rule; the parabola is biased by up to 0.08 frame
+    on noise-free synthetic views).  The defaults are not tuned.  Frame f + lag of view v shows what frame f of the reference shows: ``shift_views``
+    with these lags puts a per-view array on the reference's clock.  Returns a ``ViewSync``: ``(lag (G, V) float32, lag_int (G, V) int32: the
+    minimum's lag, curve (G, V, 2 max_lag + 1) float32 (+inf: too few pairs), contrast (G, V) float32: 1 - minimum / mean of the curve, used (G, V)
+    int32: the usable frames, ok (G, V) uint8: bit 0 a lag was estimated, bit 1 the minimum is interior - without it the true lag may lie outside the
+    range)``, new device tensors; the reference's row is zeros with ok = 1.  Inputs are not modified; identical bits on every call.  Not measured
+    on real data."""
+    if not lift_args.is_int_in(max_lag, 0, SYNC_MAXLAG):
+        raise ValueError(f"max_lag is the search range in frames, an integer in 0..{SYNC_MAXLAG}, got {max_lag!r}")
+    if not lift_args.is_int_in(min_overlap, 1, 2 ** 31 - 1):
+        raise ValueError(f"min_overlap counts the pairs of frames a lag needs, an integer >= 1, got {min_overlap!r}")
+    if not lift_args.is_number(sigma) or not float(np.float32(sigma)) > 0:
+        raise ValueError(f"sigma must be a number > 0 (inf: plain squares), got {sigma!r}")
+    if torch.is_tensor(poses):
+        lift_args.view_poses4(poses, FUSE_MAXV)
+        V, ftot = int(poses.shape[0]), int(poses.shape[1])
+        lift_args.mask(valid, (V, ftot), "valid")
+    lift_args.need_device("sync_views", poses, optional=(valid,))
+    valid = valid.contiguous() if valid is not None else None
+    d_off, G = _seq_table(take_offset, ftot, poses.device)
+    return _sync(_lib.load(), poses, valid, d_off, G, max_lag, min_overlap, sigma)
+
+
+def _shift(lib, x, valid, d_off, G, d_lag, mode):
+    """``mp_lift_shift_views`` on x (V, Ftot, ...) contiguous: (out like x, valid_out (V, Ftot) uint8), new tensors"""
+    V, ftot = int(x.shape[0]), int(x.shape[1])
+    M = int(x.numel()) // max(V * ftot, 1)
+    out = torch.zeros_like(x)
+    valid_out = torch.zeros(V, ftot, dtype=torch.uint8, device=x.device)
+    if ftot > 0:
+        _launch(x.device, "mp_lift_shift_views", _lib.ptr(x), V, ftot, M, _lib.ptr(valid), _lib.ptr(d_off), G, _lib.ptr(d_lag), int(mode), _lib.ptr(out),
+                _lib.ptr(valid_out))
+    return out, valid_out
+
+
+def shift_views(x, lag, valid=None, take_offset=None, mode="linear"):
+    """``mp_lift_shift_views`` on device tensors: a per-view array put on the reference view's clock.  ``x`` (V, Ftot, ...) float32, anything per
+    view and frame - poses, hypotheses, keypoints, roots; ``lag`` (G, V) or, for one take, (V,): ``sync_views``' lags in frames, device tensor, host
+    tensor or array (a lag that is not finite invalidates its view); ``valid`` (V, Ftot) uint8 device tensor or None; ``take_offset`` (G + 1) as for
+    ``fuse_views``.  Frame f of the result shows frame p = f + lag of the view, counted inside its take: ``mode="nearest"`` copies the frame
+    nearest to p, bit for bit; ``mode="linear"`` interpolates between the two frames around p in fp64 (a p that is a whole number: a copy) -
+    every float of a row with the same float of the next row, so hypothesis k of a frame with hypothesis k of the next, scores included: the
+    heads' identity over time is assumed, not guaranteed, and ``nearest`` avoids the question.  A frame whose source lies outside the take or is not
+    valid is zeros with ``valid_out`` 0.  A lag of 0 reproduces ``x`` at the valid frames and ``valid`` exactly.  Returns ``(out like x, valid_out
+    (V, Ftot) uint8)``, new device tensors.  Inputs are not modified; identical bits on every call."""
+    if mode not in SHIFT_MODES:
+        raise ValueError(f"mode must be nearest or linear, got {mode!r}")
+    if torch.is_tensor(x):
+        if x.dim() < 2 or x.dtype != torch.float32 or not 1 <= int(x.shape[0]) <= FUSE_MAXV:
+            raise ValueError(f"x must be float32 (V <= {FUSE_MAXV}, Ftot, ...), got {tuple(x.shape)} {x.dtype}")
+        V, ftot = int(x.shape[0]), int(x.shape[1])
+        M = int(np.prod([int(s) for s in x.shape[2:]], dtype=np.int64))
+        if not 1 <= M <= SHIFT_MAXM:
+            raise ValueError(f"x holds {M} floats per frame: 1..{SHIFT_MAXM} expected")
+        lift_args.mask(valid, (V, ftot), "valid")
+        G = lift_args.take_count(take_offset)
+        h_lag = lag
+        if not (torch.is_tensor(lag) and lag.is_cuda):
+            h = lag.detach().cpu().numpy() if torch.is_tensor(lag) else np.asarray(lag)
+            h = h.reshape(1, V) if h.shape == (V,) and G == 1 else h
+            if h.dtype.kind not in "fiu" or h.shape != (G, V):
+                raise ValueError(f"lag must be ({G}, {V}) numbers, got shape {tuple(h.shape)} {h.dtype}")
+            h_lag = np.array(h, dtype=np.float32, order="C")
+        else:
+            lag2 = lag.reshape(1, V) if tuple(lag.shape) == (V,) and G == 1 else lag
+            lift_args.f32(lag2, (G, V), "lag")
+            h_lag = lag2.contiguous()
+    lift_args.need_device("shift_views", x, optional=(valid,))
+    d_lag = h_lag if torch.is_tensor(h_lag) else torch.from_numpy(h_lag).to(x.device)
+    d_off, G = _seq_table(take_offset, ftot, x.device)
+    return _shift(_lib.load(), x.contiguous(), valid.contiguous() if valid is not None else None, d_off, G, d_lag, SHIFT_MODES[mode])
 
 
 BUNDLE_MAXITERS = 8          # MP_LIFT_BUNDLE_MAXITERS of include/manipose_hip.h: Gauss-Newton steps mp_lift_bundle_views takes at most

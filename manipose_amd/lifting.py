@@ -40,7 +40,7 @@ from .lift_ops import (FLOOR_SHARES, PATH_MAXK, PATH_SIGMA, PATH_SWITCH, REFINE_
                        bone_length_means, camera_table, place_poses, pose_rotations, project_rigid, reproject_poses, score_poses, score_traj,
                        select_path, smooth_poses, smooth_traj, to_world)
 from .lift_views import (ALIGN_ITERS, ALIGN_MAXITERS, ALIGN_SIGMA, BUNDLE_ITERS, BUNDLE_MAXITERS, BUNDLE_SIGMA, FUSE_MAXK, FUSE_MAXV,  # noqa: F401
-                         FUSE_SCORE_WEIGHT, FUSE_SIGMA, ViewAlignment, ViewBundle, ViewSkeleton, ViewSkeletonSmooth, ViewTriangulation, align_views, bundle_views, fuse_views, fuse_views_path,
+                         FUSE_SCORE_WEIGHT, FUSE_SIGMA, ViewAlignment, ViewBundle, ViewSync, SYNC_MAXLAG, SYNC_MAX_LAG, SYNC_MIN_OVERLAP, SYNC_SIGMA, sync_views, shift_views, ViewSkeleton, ViewSkeletonSmooth, ViewTriangulation, align_views, bundle_views, fuse_views, fuse_views_path,
                          fit_skeleton_views, place_views, triangulate_views)
 
 AGG = {"weighted_ave": 0, "best_score": 1}
@@ -641,5 +641,5 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
 
 
 __all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "reproject_poses", "pose_rotations", "to_world", "smooth_poses", "smooth_traj",
-           "select_path", "score_poses", "score_traj", "fuse_views", "fuse_views_path", "place_views", "align_views", "bundle_views", "triangulate_views", "fit_skeleton_views", "lift_sequences",
+           "select_path", "score_poses", "score_traj", "fuse_views", "fuse_views_path", "place_views", "align_views", "sync_views", "shift_views", "bundle_views", "triangulate_views", "fit_skeleton_views", "lift_sequences",
            "lift_action"]

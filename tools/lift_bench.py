@@ -11,6 +11,7 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --fuse [frames=3000] [K=5] [reps=200]
     python tools/lift_bench.py --fuse-path [frames=3000] [K=5] [reps=20]
     python tools/lift_bench.py --align [frames=3000] [reps=20]
+    python tools/lift_bench.py --sync [frames=3000] [reps=20]
     python tools/lift_bench.py --bundle [frames=3000] [reps=20]
     python tools/lift_bench.py --triangulate [frames=3000] [reps=20]
     python tools/lift_bench.py --skeleton [frames=3000] [reps=20]
@@ -31,6 +32,11 @@ for the same frames.
 frame and one with a workgroup per take, iters + 1 passes) through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints,
 pinhole keypoints with 0.01 of noise - with the cameras of views 1..3 started 0.3 degrees and 0.15 m off S11's calibration and the roots fitted
 under them by mp_lift_fuse_place, as ONE take and cut into 16, and prints how far the cameras are from the calibration before and after.
+--sync times mp_lift_sync_views (a take's views synchronised in time: a signal kernel with one workgroup per (take, view), a curve kernel with one
+workgroup per (take, view, block of 16 lags), a pick kernel with one wave per (take, view)) through its private launcher on 4 views x `frames`
+frames of 17 joints of a smooth synthetic motion with lags of 0, 3, -7.5 and 12.25 frames, at max_lag 0 (the signal and pick kernels and an
+all-but-empty curve kernel), 32 and 256, as ONE take and cut into 16, and mp_lift_shift_views in both modes on the poses (51 floats a frame) and
+on hypotheses (5 x 17 x 4 floats a frame), each beside the bytes its passes must move at least once.
 --align times mp_lift_align_views (a take's extrinsics from its views' poses: one workgroup per (take, view), iters + 2 passes over the poses, with
 a trajectory iters + 4) through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints, in 30 % of the frames of views 1..3
 the hypothesis moved along the depth axis - as ONE take and cut into 16, and prints how far the estimate is from S11's calibration.
@@ -355,6 +361,53 @@ def align_bench(argv):
             print(f"mp_lift_align_views, {G} take(s), iters={iters}, {'with' if with_traj else 'no'} traj: {us:,.1f} us  {passes} passes, {us / passes:,.1f} us a pass", flush=True)
 
 
+def sync_bench(argv):
+    from manipose_amd import _lib, sync_views
+    from manipose_amd.lift_views import _shift, _sync
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    assert torch.cuda.is_available(), "needs an MI355X"
+    lib, V, J, K = _lib.load(), 4, 17, 5
+    true = torch.tensor([0.0, 3.0, -7.5, 12.25], device="cuda")
+    g = torch.Generator(device="cuda").manual_seed(3)
+    rnd = lambda *shape: torch.rand(*shape, device="cuda", generator=g)
+    rest, amp = 0.3 * torch.randn(J, 3, device="cuda", generator=g), 0.1 * torch.randn(4, J, 3, device="cuda", generator=g)
+    freq, phase = 2 * np.pi / (20 + 100 * rnd(4, J, 3)), 2 * np.pi * rnd(4, J, 3)
+    time = torch.arange(frames, device="cuda")[None, :] - true[:, None]                              # frame f of view v shows time f - lag_v
+    body = rest + (amp * torch.sin(freq * time[:, :, None, None, None] + phase)).sum(dim=2)          # (V, frames, J, 3): a motion smooth in time
+    body[:, :, 0] = 0
+    poses = torch.empty_like(body)
+    for v in range(V):                                                                               # every view in a camera frame of its own, 10 mm of noise
+        q = torch.randn(4, device="cuda", generator=g)
+        w, x, y, z = (q / q.norm()).tolist()
+        R = torch.tensor([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                          [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]], device="cuda")
+        poses[v] = body[v] @ R.T + 0.01 * torch.randn(frames, J, 3, device="cuda", generator=g)
+    poses = poses.contiguous()
+    hyps = torch.randn(V, frames, K, J, 4, device="cuda", generator=g)
+    sig_mb = (poses.numel() * 4 + V * frames * (J - 1) * 8) / 1e6
+    pair_mb = (V - 1) * 2 * frames * (J - 1) * 8 / 1e6
+    print(f"--sync: {V} views x {frames} frames x {J} joints, {poses.numel() * 4 / 1e6:.2f} MB of poses; {reps} calls each after 5 of warm-up (the output and "
+          f"scratch allocations are inside the time).  At least once: the signal kernel reads the poses and writes the signals ({sig_mb:.2f} MB), the curve "
+          f"kernel reads a view's and the reference's signals per view ({pair_mb:.2f} MB)", flush=True)
+    got = sync_views(poses)
+    print(f"defaults: lags {', '.join(f'{x:.3f}' for x in got.lag[0].tolist())} (true {', '.join(f'{x:g}' for x in true.tolist())}), contrast "
+          f"{', '.join(f'{x:.2f}' for x in got.contrast[0].tolist())}, ok {got.ok[0].tolist()}", flush=True)
+    for G in (1, 16):
+        off = torch.tensor([frames * i // G for i in range(G + 1)], dtype=torch.int64, device="cuda")
+        for L in (0, 32, 256):
+            us = timed_us(lambda: _sync(lib, poses, None, off, G, L, 16, 0.05), reps)
+            terms = (2 * L + 1) * frames * (J - 1) * (V - 1)
+            print(f"mp_lift_sync_views, {G} take(s), max_lag={L}: {us:,.1f} us  {2 * L + 1} lags, at most {terms / 1e6:,.1f} M terms, {terms / us / 1e3:,.2f} G terms/s; "
+                  f"{(sig_mb + pair_mb) / us * 1e3:,.1f} GB/s of the bytes to move once", flush=True)
+    one = torch.tensor([0, frames], dtype=torch.int64, device="cuda")
+    for name, x in (("poses (51 floats a frame)", poses), ("hypotheses (340 floats a frame)", hyps)):
+        for mode, code in (("nearest", 0), ("linear", 1)):
+            us = timed_us(lambda: _shift(lib, x, None, one, 1, got.lag, code), reps)
+            mb = 2 * x.numel() * 4 / 1e6
+            print(f"mp_lift_shift_views, {mode}, {name}: {us:,.1f} us  read once, write once {mb:.2f} MB: {mb / us * 1e3:,.1f} GB/s", flush=True)
+
+
 def bundle_bench(argv):
     from manipose_amd.lift_views import _bundle, _fuse_place
     frames = int(argv[0]) if len(argv) > 0 else 3000
@@ -524,6 +577,9 @@ if "--triangulate" in sys.argv:
     sys.exit(0)
 if "--bundle" in sys.argv:
     bundle_bench([a for a in sys.argv[1:] if a != "--bundle"])
+    sys.exit(0)
+if "--sync" in sys.argv:
+    sync_bench([a for a in sys.argv[1:] if a != "--sync"])
     sys.exit(0)
 if "--align" in sys.argv:
     align_bench([a for a in sys.argv[1:] if a != "--align"])
