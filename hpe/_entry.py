@@ -279,7 +279,8 @@ LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj
                  "__cam_err_deg_align", "__cam_err_m_align", "__cam_bundle_reproj", "__cam_bundle_cost", "__cam_bundle_steps", "__cam_bundle_ok",
                  "__cam_bundle_used", "__tri", "__tri_err", "__tri_views", "__tri_ok", "__tri_steps", "__skel", "__skel_bones", "__skel_err", "__skel_ok",
                  "__skel_steps", "__skel_quat", "__skel_quat_ok", "__skel_err_smooth", "__skel_moves", "__sync_lag", "__sync_contrast", "__sync_used", "__sync_ok",
-                 "__sync_curve")
+                 "__sync_curve", "__cal", "__cam_intr", "__cam_focal", "__cam_focal_err", "__cal_reproj", "__cal_cost", "__cal_steps", "__cal_ok", "__cal_used",
+                 "__cam_quat_bundle", "__cam_trans_bundle", "__cam_err_deg_bundle", "__cam_err_m_bundle")
 
 
 def _scale_and_cost(scale, cost=None, unit="metres"):
@@ -489,6 +490,47 @@ def lift_fuse_bundle_options(cfg):
     return steps, float(sigma)
 
 
+def lift_fuse_calibrate_options(cfg):
+    """(steps, sigma, prior, focal, start_focal) of lift.fuse_calibrate / lift.fuse_calibrate_sigma / lift.fuse_calibrate_prior /
+    lift.fuse_calibrate_focal / lift.fuse_calibrate_start_focal (0.0: the dataset's intrinsics); ValueError for a value or a combination that
+    cannot run - before any model is built."""
+    steps, sigma, prior = cfg.lift.get("fuse_calibrate", 0), cfg.lift.get("fuse_calibrate_sigma", 0.05), cfg.lift.get("fuse_calibrate_prior", 0.001)
+    focal, start = cfg.lift.get("fuse_calibrate_focal", True), cfg.lift.get("fuse_calibrate_start_focal", 0.0)
+    if not is_int_in(steps, 0, 8):
+        raise ValueError(f"lift.fuse_calibrate counts Gauss-Newton steps, an integer in 0..8 (0: off), got {steps!r}")
+    _scale_and_cost(("fuse_calibrate_sigma", sigma), unit="normalised screen units")
+    if not is_number(prior) or not 0 < float(np.float32(prior)) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"lift.fuse_calibrate_prior must be a finite number > 0 (the keypoints leave the scale free: the pull towards the fused pose "
+                         f"pins it), got {prior!r}")
+    if not isinstance(focal, bool):
+        raise ValueError(f"lift.fuse_calibrate_focal must be true or false, got {focal!r}")
+    if not is_number(start) or not 0 <= float(start) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"lift.fuse_calibrate_start_focal is a focal length in normalised screen units, finite and > 0 (0: the dataset's intrinsics), "
+                         f"got {start!r}")
+    if start > 0 and not lift_fuse_align_options(cfg)[0]:
+        raise ValueError("lift.fuse_calibrate_start_focal replaces the intrinsics of a run that estimates its cameras: set lift.fuse_cameras=estimate")
+    if steps == 0:
+        if sigma != 0.05 or prior != 0.001 or focal is not True:
+            raise ValueError("lift.fuse_calibrate_sigma / lift.fuse_calibrate_prior / lift.fuse_calibrate_focal describe the calibration of a take on "
+                             "its keypoints: set lift.fuse_calibrate=N, N steps")
+        return 0, float(sigma), float(prior), focal, float(start)
+    if not lift_fuse_align_options(cfg)[0]:
+        raise ValueError("lift.fuse_calibrate refines the cameras that lift.fuse_cameras=estimate estimates: set lift.fuse_cameras=estimate")
+    return steps, float(sigma), float(prior), focal, float(start)
+
+
+def start_focal_cameras(cams, f):
+    """lift.fuse_calibrate_start_focal: the cameras with the intrinsics (f, f, 0, 0, 0, 0, 0, 0, 0) - no principal point, no distortion - and their
+    own extrinsics and index, as rows of 16 or 17 numbers"""
+    from manipose_amd import camera_table
+    rows = []
+    for cam in cams:
+        _, quat, trans = camera_table([cam])
+        idx = _camera_index(cam)
+        rows.append(np.concatenate([[f, f, 0, 0, 0, 0, 0, 0, 0], quat[0], trans[0], [] if idx is None else [idx]]).astype(np.float32))
+    return rows
+
+
 def lift_fuse_triangulate_options(cfg):
     """(triangulate, steps, sigma, prior) of lift.fuse_triangulate / lift.fuse_triangulate_steps / lift.fuse_triangulate_sigma /
     lift.fuse_triangulate_prior; ValueError for a value or a combination that cannot run - before any model is built."""
@@ -595,6 +637,34 @@ def bundle_cameras(est, cams, takes, bun):
         est["bundle_" + k] = getattr(bun, k).cpu().numpy()
 
 
+# what lift.fuse_calibrate adds: the cameras before it (suffix _bundle after lift.fuse_bundle, else _align) and the calibration's own record
+CALIBRATE_MOVED = ("quat", "trans", "err_deg", "err_m")
+CALIBRATE_KEYS = ("__cal", "__cam_intr", "__cam_focal", "__cam_focal_err", "__cal_reproj", "__cal_cost", "__cal_steps", "__cal_ok", "__cal_used")
+
+
+def calibrate_cameras(est, cams, true_cams, takes, cal, suffix):
+    """lift.fuse_calibrate on estimate_cameras' dict, IN PLACE: quat and trans become the calibration's (calibrate_views' ViewCalibration ``cal``),
+    err_deg and err_m are recomputed for them against the dataset's extrinsics, the earlier values move to ``*<suffix>``; intr (G, V, 9), focal
+    (G, V, 2): fx at the start and at the end, focal_err (G, V): |fx / the dataset's fx - 1| at the end (``true_cams``: the dataset's cameras,
+    ``cams``: the ones the run read), and the calibration's reproj, cost, steps, ok, used are added as ``cal_*``."""
+    from manipose_amd import camera_table
+    start = camera_table(cams)[0].astype(np.float64)
+    true, quat, trans = (a.astype(np.float64) for a in camera_table(true_cams))
+    unit = quat / np.linalg.norm(quat, axis=1, keepdims=True)
+    for k in CALIBRATE_MOVED:
+        est[k + suffix] = est[k].copy()
+    est["quat"], est["trans"], est["intr"] = cal.quat.cpu().numpy(), cal.trans.cpu().numpy(), cal.intr.cpu().numpy()
+    G, V = est["quat"].shape[:2]
+    est["focal"], est["focal_err"] = np.zeros((G, V, 2), np.float32), np.zeros((G, V), np.float32)
+    for t, views in enumerate(takes):
+        for v, i in enumerate(views):
+            est["err_deg"][t, v], est["err_m"][t, v] = _camera_error(est["quat"][t, v], est["trans"][t, v], unit[i], trans[i])
+            est["focal"][t, v] = start[i, 0], est["intr"][t, v, 0]
+            est["focal_err"][t, v] = abs(float(est["intr"][t, v, 0]) / true[i, 0] - 1.0)
+    for k in ("reproj", "cost", "steps", "ok", "used"):
+        est["cal_" + k] = getattr(cal, k).cpu().numpy()
+
+
 def _camera_error(q, t, unit, trans):
     """(degrees, metres) between an estimated camera (q float32 unit, t) and the dataset's (unit quaternion, translation), in float64"""
     q = q.astype(np.float64)
@@ -689,7 +759,7 @@ def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, 
     return est, nested, valid, place_valid
 
 
-def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_scores=None, skel_scores=None):
+def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_scores=None, skel_scores=None, cal_scores=None, true_cams=None):
     """lift.fuse on one group: its sequences are cut into takes (split_takes), every take's views are fused (fuse_views: one hypothesis per view,
     chosen jointly; their mean, root-relative in the world's orientation), with lift.rigid re-assembled with the mean of the views' bone tables, and
     placed with ONE world root per frame (place_views); with lift.floor the take stands on z = 0.  ``res``: the group's _Lifted with hypotheses, taken
@@ -699,6 +769,10 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     poses, before any camera is estimated) and the hypotheses, the keypoints, the masks and what estimate_cameras reads are put on the first view's
     clock (shift_views, lift.fuse_sync_interp) - the take's clock: the ground truth stays the first view's -; ``__sync_lag``, ``__sync_contrast``,
     ``__sync_used``, ``__sync_ok`` (V,) and ``__sync_curve`` (V, 2 max_lag + 1) are added, as sync_views returned them.
+    With lift.fuse_calibrate=N the take is then calibrated on its keypoints (calibrate_views on the fused pose at its placed root, after
+    lift.fuse_bundle if that is on, the first view's pose held; calibrate_cameras has the keys), the roots are placed once more and the later
+    stages read the new cameras; ``true_cams``: the dataset's cameras where ``cams`` are lift.fuse_calibrate_start_focal's; with ``targets`` the
+    calibrated points' score goes into ``cal_scores`` (the frames without a placed root left out).
     With lift.fuse_triangulate every joint is then triangulated on the keypoints (triangulate_views, under the cameras and with the root and ok of the last place_views call) and ``__tri`` (N, 17, 3), in the
     frame of ``<name>.fused<t>``, ``__tri_err``, ``__tri_views``, ``__tri_ok``, ``__tri_steps`` (N, 17) are added; with ``targets`` the triangulated
     pose's score goes into ``tri_scores`` (the frames with a joint whose ok is 0 left out).
@@ -710,7 +784,7 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     sweeps): ``__skel``, ``__skel_quat`` and the score are the smoothed fit's, ``__skel_err`` stays (N, 2) and ``__skel_err_smooth`` (N,),
     ``__skel_moves`` (N,) are added; with ``targets`` the fitted pose's score goes into ``skel_scores`` (the frames without a
     result left out)."""
-    from manipose_amd import (bundle_views, camera_table, fit_skeleton_views, fuse_views, fuse_views_path, place_views, pose_rotations, project_rigid,
+    from manipose_amd import (bundle_views, calibrate_views, camera_table, fit_skeleton_views, fuse_views, fuse_views_path, place_views, pose_rotations, project_rigid,
                               score_poses, score_traj, to_world, triangulate_views)
     from manipose_amd.lifting import SCORE_FIELDS
     _, sigma, weight, refine = lift_fuse_options(cfg)
@@ -773,6 +847,17 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
         bundle_cameras(est, cams, takes, bun)
         root, reproj, placed, steps = place_views(pose, kp, bun.cameras, place_valid, off, refine=refine, return_steps=True)
         placed_cams = bun.cameras
+    cal_steps, cal_sigma, cal_prior, cal_focal, _ = lift_fuse_calibrate_options(cfg)
+    cal = None
+    if cal_steps:                              # lift.fuse_calibrate: cameras, focal factors and every joint as a free point, the first view's pose held
+        held = np.zeros((len(takes), V), np.uint8)
+        held[:, 0] = 1
+        cal_in = placed.clone()                # the frames whose start, the fused pose at its placed root, the calibration may use
+        cal = calibrate_views((pose + root[:, None]).contiguous(), kp, placed_cams, place_valid, off, placed, held, focal=cal_focal, sigma=cal_sigma,
+                              prior=cal_prior, iters=cal_steps)
+        calibrate_cameras(est, cams, cams if true_cams is None else true_cams, takes, cal, "_bundle" if bundle_steps else "_align")
+        root, reproj, placed, steps = place_views(pose, kp, cal.cameras, place_valid, off, refine=refine, return_steps=True)
+        placed_cams = cal.cameras
     tri_on, tri_steps, tri_sigma, tri_prior = lift_fuse_triangulate_options(cfg)
     tri = None
     if tri_on:                                 # lift.fuse_triangulate: every joint on its own, under the cameras and the root of the last placement
@@ -807,6 +892,9 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
         if tri is not None:                    # the triangulated pose, made root-relative, against the same ground truth
             tri_rec = score_poses(tri.points, d_pose, seq_offset=off, valid=(tri.ok != 0).all(dim=1).to(torch.uint8), root_relative=True)
             tri_ate = score_traj(tri.points[:, 0].contiguous(), d_root, ok=(tri.ok[:, 0] != 0).to(torch.uint8), seq_offset=off)
+        if cal is not None:                    # the calibrated points likewise (the frames the calibration did not use left out)
+            cal_rec = score_poses(cal.points, d_pose, seq_offset=off, valid=cal_in, root_relative=True)
+            cal_ate = score_traj(cal.points[:, 0].contiguous(), d_root, ok=cal_in, seq_offset=off)
         if skel is not None:                   # the fitted pose likewise
             skel_rec = score_poses(skel.pose, d_pose, seq_offset=off, valid=(skel.ok & 1).contiguous(), root_relative=True)
             skel_ate = score_traj(skel.pose[:, 0].contiguous(), d_root, ok=(skel.ok & 1).contiguous(), seq_offset=off)
@@ -826,6 +914,16 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
                 out[f"{key}__cam_{k}"] = est[k][t, :len(views)]
             for k in BUNDLE_KEYS if bundle_steps else ():
                 out[f"{key}__cam_{k}"] = est[k][t, :len(views)] if est[k].ndim > 1 and k != "bundle_cost" else est[k][t]
+        if cal is not None:
+            for k in CALIBRATE_MOVED:
+                out[f"{key}__cam_{k}_{'bundle' if bundle_steps else 'align'}"] = est[k + ("_bundle" if bundle_steps else "_align")][t, :len(views)]
+            for k in ("intr", "focal", "focal_err"):
+                out[f"{key}__cam_{k}"] = est[k][t, :len(views)]
+            points = cal.points[sl].clone()
+            if floor:                          # the frame of the fused pose: the same offset off z
+                points[..., 2] = points[..., 2] - d_floor[t]
+            out[key + "__cal"], out[key + "__cal_reproj"], out[key + "__cal_used"] = points.cpu().numpy(), est["cal_reproj"][t, :len(views)], est["cal_used"][t, :len(views)]
+            out[key + "__cal_cost"], out[key + "__cal_steps"], out[key + "__cal_ok"] = est["cal_cost"][t], est["cal_steps"][t], est["cal_ok"][t]
         if along:
             out[key + "__path_cost"] = path_cost[t].cpu().numpy()
         if floor:
@@ -852,6 +950,9 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
         if targets is not None and tri is not None and tri_scores is not None:
             tri_scores[key] = {f: getattr(tri_rec, f)[t].cpu().numpy() for f in SCORE_FIELDS}
             tri_scores[key]["traj"] = {"ate": tri_ate.ate[t].cpu().numpy(), "frames": tri_ate.frames[t].cpu().numpy()}
+        if targets is not None and cal is not None and cal_scores is not None:
+            cal_scores[key] = {f: getattr(cal_rec, f)[t].cpu().numpy() for f in SCORE_FIELDS}
+            cal_scores[key]["traj"] = {"ate": cal_ate.ate[t].cpu().numpy(), "frames": cal_ate.frames[t].cpu().numpy()}
         if targets is not None and skel is not None and skel_scores is not None:
             skel_scores[key] = {f: getattr(skel_rec, f)[t].cpu().numpy() for f in SCORE_FIELDS}
             skel_scores[key]["traj"] = {"ate": skel_ate.ate[t].cpu().numpy(), "frames": skel_ate.frames[t].cpu().numpy()}
@@ -871,7 +972,8 @@ def synthetic_cameras(groups):
     return cams
 
 
-def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None, fused_scores=None, tri_scores=None, skel_scores=None):
+def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None, fused_scores=None, tri_scores=None, skel_scores=None,
+                           cal_scores=None):
     """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
     hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
     it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
@@ -911,7 +1013,16 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     lift.fuse_skeleton (lift.fuse_skeleton_steps, lift.fuse_skeleton_sigma, lift.fuse_skeleton_prior) one skeleton of constant bones is fitted to
     the keypoints of every fused take (fit_skeleton_views) and ``__skel`` (N, 17, 3), ``__skel_bones`` (16,), ``__skel_err`` (N, 2), ``__skel_ok``,
     ``__skel_steps`` (N,) and with lift.rotations ``__skel_quat`` (N, 17, 4), ``__skel_quat_ok`` (N,) are added; with ``targets`` the dict
-    ``skel_scores`` receives {fused key: score dict} of the fitted pose."""
+    ``skel_scores`` receives {fused key: score dict} of the fitted pose.  With lift.fuse_calibrate=N (lift.fuse_calibrate_sigma,
+    lift.fuse_calibrate_prior, lift.fuse_calibrate_focal; lift.fuse_cameras=estimate needed) every take is then calibrated on its keypoints
+    (calibrate_views, after lift.fuse_bundle if that is on: the first view's pose held, every view's focal factor, the other views' poses and every
+    joint of the fused pose at its root free), the roots are fitted once more, and triangulation and skeleton fit read the new cameras: ``__cal``
+    (N, 17, 3) in the frame of ``<name>.fused<t>``, ``__cam_intr`` (V, 9), ``__cam_focal`` (V, 2): fx at the start and at the end,
+    ``__cam_focal_err`` (V,): |fx / the dataset's - 1|, ``__cal_reproj`` (V, 2), ``__cal_cost`` (2,) float64, ``__cal_steps``, ``__cal_ok``,
+    ``__cal_used`` (V,) are added; ``__cam_quat``, ``__cam_trans``, ``__cam_err_deg``, ``__cam_err_m`` become the calibrated cameras' and the
+    earlier values move to the suffix ``_bundle`` (after lift.fuse_bundle) or ``_align``; with ``targets`` the dict ``cal_scores`` receives {fused
+    key: score dict} of the calibrated points.  With lift.fuse_calibrate_start_focal=f every camera the lifting stages read has the intrinsics
+    (f, f, 0, 0, 0, 0, 0, 0, 0): the dataset's intrinsics are read for ``__cam_focal_err`` alone."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
     out = {}
@@ -932,6 +1043,9 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
         raise ValueError("lift.place / lift.frame=world need the sequences' cameras")
     if fuse and cameras is None:
         raise ValueError("lift.fuse needs the sequences' cameras")
+    start_focal, true_cameras = lift_fuse_calibrate_options(cfg)[4], cameras
+    if start_focal > 0:                        # lift.fuse_calibrate_start_focal: no stage reads the dataset's intrinsics
+        cameras = {name: start_focal_cameras(cams, start_focal) for name, cams in cameras.items()}
     for name, seqs in groups.items():
         res = _lift_sequences(model, seqs, stride=cfg.lift.stride, tta=cfg.train.tta, agg=agg, blend=cfg.lift.blend,
                               return_hyps=want_hyps or fuse, batch=cfg.train.batch_size_test, rigid=rigid, lengths=cfg.lift.get("lengths", None),
@@ -959,7 +1073,8 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
             if res.score is not None and scores is not None:
                 scores[key] = to_host(asked(res.score[i]))
         if fuse:
-            fuse_group(out, name, res, seqs, cameras[name], cfg, targets[name] if targets is not None else None, fused_scores, tri_scores, skel_scores)
+            fuse_group(out, name, res, seqs, cameras[name], cfg, targets[name] if targets is not None else None, fused_scores, tri_scores, skel_scores,
+                       cal_scores, true_cameras[name])
     np.savez(path, **out)
     return out
 
@@ -1007,6 +1122,7 @@ def run(argv, extra_defaults=None):
     lift_fuse_path_options(cfg)                # ... and a lift.fuse_path without lift.fuse
     lift_fuse_align_options(cfg)               # ... and a lift.fuse_cameras=estimate without lift.fuse
     lift_fuse_bundle_options(cfg)              # ... and a lift.fuse_bundle without lift.fuse_cameras=estimate
+    lift_fuse_calibrate_options(cfg)           # ... and a lift.fuse_calibrate without lift.fuse_cameras=estimate
     lift_fuse_sync_options(cfg)                # ... and a lift.fuse_sync=estimate without lift.fuse
     lift_fuse_triangulate_options(cfg)         # ... and a lift.fuse_triangulate without lift.fuse
     lift_fuse_skeleton_options(cfg)            # ... and a lift.fuse_skeleton without lift.fuse
@@ -1181,10 +1297,10 @@ def run(argv, extra_defaults=None):
         cams = None
         if any(lift_place_options(cfg)[:2]) or lift_fuse_options(cfg)[0]:
             cams = seqs["test_cams"] if real else synthetic_cameras(groups)
-        targets, scores, fused_scores, tri_scores, skel_scores = None, {}, {}, {}, {}
+        targets, scores, fused_scores, tri_scores, skel_scores, cal_scores = None, {}, {}, {}, {}, {}
         if lift_score_options(cfg):            # the 3-D ground truth beside the 2-D sequences that are lifted
             targets = {name: sq[0] for name, sq in seqs["test"].items()} if real else synthetic_sequences_3d(cfg, cfg.run.seed)
-        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores, tri_scores, skel_scores)
+        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores, tri_scores, skel_scores, cal_scores)
         is_pose = lambda k: not k.endswith(LIFT_SUFFIXES) and ".fused" not in k
         print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if is_pose(k))} frames of {len(groups)} groups -> {path}", flush=True)
         if lift_fuse_options(cfg)[0]:
@@ -1202,6 +1318,9 @@ def run(argv, extra_defaults=None):
                       flush=True)
             if tri_scores:
                 print(f"lift score, triangulated takes -> {report.write_lift_score_report(out_dir, tri_scores, name='lift_score_tri', joints=False)[0]}",
+                      flush=True)
+            if cal_scores:
+                print(f"lift score, calibrated takes -> {report.write_lift_score_report(out_dir, cal_scores, name='lift_score_cal', joints=False)[0]}",
                       flush=True)
             if skel_scores:
                 print(f"lift score, fitted skeletons -> {report.write_lift_score_report(out_dir, skel_scores, name='lift_score_skel', joints=False)[0]}",

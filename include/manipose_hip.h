@@ -914,6 +914,66 @@ int mp_lift_bundle_views(const float* pose, const float* root, const uint8_t* ro
                          const float* weights, int distort, float sigma, int iters, float* quat_out, float* trans_out, float* root_out, float* reproj,
                          double* cost, uint8_t* steps, uint8_t* ok, int32_t* used, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* Calibrating a take on its keypoints: mp_lift_bundle_views holds the fused pose fixed as structure and reads the focal lengths from a calibration,
+ * so whatever the lifter got wrong - a scale error above all - goes into the cameras.  This is the full bundle adjustment of a take: every joint of
+ * every used frame is a free 3-D point, every free camera has its six pose parameters, every view with a used frame one focal factor, all fitted
+ * to the 2-D keypoints by undamped Gauss-Newton steps, the points eliminated one by one by a Schur complement.  The start enters only as a weak
+ * prior on the points.  The reference has no counterpart.  The conventions are mp_lift_bundle_views': takes, take_offset, valid, quat (G, V, 4),
+ * trans (G, V, 3), intr (G, V, 9), fixed (G, V) bytes or null, weights (J) or null, distort, sigma; fp64 between the float32 loads and the float32
+ * stores, without contraction; no atomics, fixed orders: identical bits on every call; a take's result does not depend on the other takes of the
+ * call; the call does not synchronise.  Not measured on real data.
+ * WHY AT LEAST TWO VIEWS: from one view's lifted poses the focal length is a linear fit once the per-frame (f tx, f ty, tz) are eliminated - exact on
+ * noise-free poses, but what is left as regressor is only the perspective part of the body (about 16 mm), below a lifter's error: in float64 on
+ * 3000 synthetic frames, true f = 2.29, keypoint noise 0.002, 20 mm of pose noise gave f = 1.53 .. 1.60 and 45 mm gave 0.66 .. 0.74.
+ * WHY prior > 0: the keypoints leave one gauge freedom, the scale of points and camera positions together; with prior = 0 the reduced system's
+ * condition number is 1e17 and the points drift (0.35 m in the float64 prototype); with prior 1e-3 it was 2.4e6 .. 2.4e7.
+ * Read only: start (Ftot, J, 3) world points (the fused pose plus its root); start_ok (Ftot) bytes or null; kp (V, Ftot, J, 2); the camera tables;
+ * focal 0 or 1; prior finite and > 0; 0 <= iters <= MP_LIFT_CALIBRATE_MAXITERS.  Per take g with frames [f0, f1):
+ * 1. Observations.  mp_lift_bundle_views' step 1 with "the root and the pose are finite" replaced by "all 3 J coordinates of start are finite"
+ *    and root_ok by start_ok.  A frame with no used observation is outside the problem.  used[g][v] = the used frames of view v.
+ * 2. Gauge.  FIXED and FREE views as in mp_lift_bundle_views' step 2 (no fixed view with a used frame, or no free view: no camera moves); the free
+ *    views' slots k = 0, 1, .. own the columns 6 k .. 6 k + 5 of the reduced system.  With focal = 1 every view with a used frame, fixed ones
+ *    included, has a focal factor g_v, starting at 1; their columns follow the cameras' in view order: N <= 22 columns.  The take ITERATES iff
+ *    N >= 1 and at least two views have a used frame; otherwise it evaluates only: steps = 0, everything copied through, reproj and cost written
+ *    (start = end).
+ * 3. Residuals.  State in fp64: per view q, T (as in mp_lift_bundle_views) and g_v, per used frame and joint the point X_fj, starting at start.
+ *    P = R(q)^T (X - T); the projection of mp_lift_bundle_views' step 3 with fx = g_v fx0, fy = g_v fy0 (the products in fp64; the principal
+ *    point and the distortion coefficients stay); res, e, t, rho, omega as there.  A joint of weight 0 is skipped: no camera sees it and it stays
+ *    at start.  Per frame and view F_fv = sum_j w_j rho, E_fv = sum_j w_j sqrt(e), W_fv = sum_j w_j, joints in order;  P_f = sum_j w_j
+ *    ((dx^2 + dy^2) + dz^2) with d = X_fj - start_fj;  F_f = (sum_v F_fv, the used views in order) + prior P_f;  F, E_v, W_v: the frames in
+ *    increasing order.  deep as in mp_lift_bundle_views.
+ * 4. Parameters.  A point moves by dX with Jacobian J_x = J_pi R^T; a free camera as in mp_lift_bundle_views' step 4 (J_c, 2x6, and its update);
+ *    a focal factor moves additively, g <- g + dg, with the Jacobian column J_g = ((res + keypoint) - (cx, cy)) / g, which is (pi(P) - c) / g for
+ *    either value of distort, pi(P) taken back from the residual.
+ * 5. One step.  Per point, with the weights w_j omega over the views that use the frame, in view order:  U = prior w_j I + sum J_x^T J_x,
+ *    b = prior w_j (X - start) + sum J_x^T res (the prior's term first), W = the 3 x N matrix whose columns of view v are w_j omega J_x^T [J_c | J_g]
+ *    (zero for a view that does not use the frame or has no such column), a likewise from [J_c | J_g]^T res, and A_rc = w_j omega (J_r . J_c) where
+ *    columns r and c belong to the same view, else 0.  U^-1 by cofactors with mp_lift_place_refine's test.  The point's term of the reduced system is
+ *    S_rc = A_rc - W_r^T (U^-1 W_c) for c <= r and s_c = a_c - W_c^T (U^-1 b), every product of three summed as (p0 + p1) + p2; the terms are added
+ *    to zero, a frame's joints in order, then the frames in increasing order.  S = L L^T, the pivot test, dc = -S^-1 s as in mp_lift_bundle_views;
+ *    dX = -(U^-1 b + sum_c (U^-1 W)_c dc_c), columns in order.  The candidate is the state moved by (dc, dX).  The step is taken iff every U and
+ *    the factorisation pass, dc and the candidate cameras are finite, every candidate g is finite and > 0, deep holds at the candidate and
+ *    F' <= (1 + 1e-6) F.  The first step not taken ends the take's iteration and its state stays.  If the first evaluation is not deep or F is not
+ *    finite: ok = 0, everything copied through, steps = 0; otherwise ok = 1.  At most iters steps.
+ * 6. Outputs.  quat_out, trans_out, reproj, cost, steps, ok, used as mp_lift_bundle_views writes them.  intr_out (G, V, 9): while steps = 0 intr bit
+ *    for bit, else fx, fy of a view with a focal factor are (float)(g fx0), (float)(g fy0) and the other entries copied.  points (Ftot, J, 3): a
+ *    used frame's weighted joints rounded to float32 (start's bits while steps = 0), everything else copied from start bit for bit.
+ * Schedule: one lane per frame goes through the frame's points one by one, the point's blocks by column in lane-private LDS, and adds each point's
+ * term of S and s (at most 253 + 22 doubles) to the frame's row in the scratch; one workgroup per take sums the rows, lane e entry e, frames in
+ * increasing order, then decides, factorises and forms the candidate cameras and focal factors; the next pass of the frame kernel applies dc and
+ * its own dX at its head.  iters + 1 passes, launched in a fixed sequence.
+ * scratch: at least mp_lift_calibrate_views_scratch_bytes(V, Ftot, J) bytes = 8 Ftot (286 + 1 + 75 J + 96), 8-byte aligned; 0 for arguments out
+ * of range.
+ * MP_ERR_ARG before anything is launched: what mp_lift_bundle_views rejects (start_ok, valid, fixed, weights may be null), focal not 0 or 1, prior
+ * not finite or not > 0. */
+#define MP_LIFT_CALIBRATE_MAXITERS 8
+int64_t mp_lift_calibrate_views_scratch_bytes(int V, int64_t Ftot, int J);
+int mp_lift_calibrate_views(const float* start, const uint8_t* start_ok, const float* kp, int V, int64_t Ftot, int J, const uint8_t* valid,
+                            const int64_t* take_offset, int G, const float* quat, const float* trans, const float* intr, const uint8_t* fixed,
+                            const float* weights, int focal, int distort, float sigma, float prior, int iters, float* quat_out, float* trans_out,
+                            float* intr_out, float* points, float* reproj, double* cost, uint8_t* steps, uint8_t* ok, int32_t* used, void* scratch,
+                            int64_t scratch_bytes, void* stream);
+
 /* Triangulating a fused take's joints on the 2-D keypoints: after mp_lift_fuse, mp_lift_fuse_place and mp_lift_bundle_views the keypoints - the only
  * measured quantity - decide the root (three numbers per frame) and the cameras; the body is still the mean of one lifted hypothesis per view,
  * though every joint is seen by up to four cameras.  Here every joint of every frame becomes a world point of its own, triangulated from its

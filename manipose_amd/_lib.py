@@ -143,6 +143,9 @@ _SIGNATURES = {
     "mp_lift_shift_views": (i32, [vp, i32, i64, i64, vp, vp, i32, vp, i32, vp, vp, vp]),
     "mp_lift_bundle_views_scratch_bytes": (i64, [i32, i64]),
     "mp_lift_bundle_views": (i32, [vp, vp, vp, vp, i32, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "mp_lift_calibrate_views_scratch_bytes": (i64, [i32, i64, i32]),
+    "mp_lift_calibrate_views": (i32, [vp, vp, vp, i32, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64,
+                                      vp]),
     "mp_lift_triangulate": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp, i32, vp, vp, vp, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp]),
     "mp_lift_fit_skeleton": (i32, [vp, vp, vp, vp, i32, i64, i32, vp, vp, i32, vp, vp, vp, vp, C.POINTER(i32), i32, f32, f32, i32, vp, vp, vp, vp, vp]),
     "mp_lift_fit_skeleton_smooth_scratch_bytes": (i64, [i64, i32]),

@@ -1,12 +1,12 @@
 // The geometry the multi-view lifting kernels share (lift_place.hip, lift_fuse.hip, lift_fuse_path.hip, lift_align.hip, lift_bundle.hip,
-// lift_score.hip): a camera's rotation from its quaternion and the test whether a take's quaternion is usable, the H36M camera model with its
+// lift_calibrate.hip, lift_score.hip): a camera's rotation from its quaternion and the test whether a take's quaternion is usable, the H36M camera model with its
 // analytic Jacobian, the Gauss-Newton sums with their 3x3 solve by cofactors and accept rule, and the cyclic Jacobi on a symmetric 4x4.  ONE COPY:
 // the camera model, the 1e-12 rules and the sweep limit change here or nowhere.  tests/golden/lift_place_bits.npz and lift_geom_bits.npz pin
 // the bits of every kernel that includes this file.  (One loop keeps a copy of its own, for speed: bundle_frame_kernel's joint loop in
 // lift_bundle.hip states the projection, the normal equations and the cofactor inverse itself; the reason is written there.)
 // CONTRACTION: this header carries no `#pragma clang fp contract` of its own, so its code takes the mode of the file that includes it at the
 // point of inclusion.  lift_place.hip and lift_fuse.hip compile with the default (fused multiply-adds); lift_fuse_path.hip, lift_align.hip,
-// lift_bundle.hip and lift_score.hip state `#pragma clang fp contract(off)` and MUST include this header AFTER that line - included before it,
+// lift_bundle.hip, lift_calibrate.hip and lift_score.hip state `#pragma clang fp contract(off)` and MUST include this header AFTER that line - included before it,
 // the shared code would fuse and their bits would move.
 // Everything is fp64 and __device__ __forceinline__; nothing is indexed at run time (every array below is indexed by unrolled constants).
 #pragma once

@@ -128,6 +128,18 @@ def prior_weight(prior):
         raise ValueError(f"prior must be a finite number >= 0 (0: no pull towards the fused pose), got {prior!r}")
 
 
+def prior_pull(prior):
+    """prior is a finite number > 0 as the kernel takes it (a float32): the pull that pins what the keypoints leave free"""
+    if not is_number(prior) or not 0 < float(np.float32(prior)) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"prior must be a finite number > 0 (the keypoints leave the scale free: without the pull the points drift), got {prior!r}")
+
+
+def step_count(iters, highest):
+    """iters is an integer in 0..highest"""
+    if not is_int_in(iters, 0, highest):
+        raise ValueError(f"iters counts Gauss-Newton steps, an integer in 0..{highest} (0: the evaluation alone), got {iters!r}")
+
+
 def smooth_weight(smooth):
     """smooth is a finite number >= 0 (a float32): the weight of a squared second difference"""
     if not is_number(smooth) or not 0 <= float(smooth) <= float(np.finfo(np.float32).max):

@@ -4,7 +4,8 @@ cuts a group's sequences into takes and calls them.  ``fuse_views``: one hypothe
 ``fuse_views_path``: that choice made jointly over the whole take, a Viterbi path over the combinations, so that a hypothesis all views agree on -
 a mirrored body - cannot make the fused motion flicker; ``place_views``: one world root per frame from all views; ``align_views``: the views'
 extrinsics estimated from their lifted poses, for takes that were never calibrated; ``bundle_views``: those cameras and the roots refined jointly
-on the reprojection error; ``triangulate_views``: every joint of the fused take triangulated on the keypoints of the cameras that see it;
+on the reprojection error; ``calibrate_views``: cameras, focal lengths and every joint as a free point fitted to the keypoints;
+``triangulate_views``: every joint of the fused take triangulated on the keypoints of the cameras that see it;
 ``fit_skeleton_views``: one skeleton of constant bones fitted to those keypoints, frame by frame; ``sync_views`` /
 ``shift_views``: the views' lags in time estimated from their poses, and any per-view array put on the reference view's clock.  Built
 like lift_ops.py: a public function composes lift_args' checks (``_fuse_front`` and ``_take_front`` are the
@@ -476,6 +477,63 @@ def bundle_views(pose, root, keypoints_2d, cameras, valid=None, take_offset=None
     q, t = res[0].cpu().numpy(), res[1].cpu().numpy()
     nested = [[np.concatenate([intr[g, v], q[g, v], t[g, v]]) if present[g, v] else None for v in range(V)] for g in range(G)]
     return ViewBundle(nested, *res)
+
+
+CALIBRATE_MAXITERS = 8       # MP_LIFT_CALIBRATE_MAXITERS of include/manipose_hip.h
+CALIBRATE_SIGMA, CALIBRATE_PRIOR, CALIBRATE_ITERS = 0.05, 1e-3, 3          # defaults of calibrate_views (the float64 prototype's; not tuned)
+# What calibrate_views returns: cameras: the nested list [take][view] with the new intrinsics and extrinsics; quat (G, V, 4), trans (G, V, 3),
+# intr (G, V, 9), points (Ftot, J, 3), reproj (G, V, 2) float32, cost (G, 2) float64, steps, ok (G) uint8, used (G, V) int32
+ViewCalibration = namedtuple("ViewCalibration", "cameras quat trans intr points reproj cost steps ok used")
+
+
+def _calibrate(lib, points, points_ok, kp, valid, d_off, G, d_quat, d_trans, d_intr, d_fixed, d_w, focal, distort, sigma, prior, iters):
+    """``mp_lift_calibrate_views``: (quat, trans, intr, points, reproj, cost, steps, ok, used), new tensors"""
+    V, ftot, J = int(kp.shape[0]), int(kp.shape[1]), int(kp.shape[2])
+    dev = points.device
+    quat, trans, intr = d_quat.clone(), d_trans.clone(), d_intr.clone()
+    out = points.clone()
+    reproj = torch.zeros(G, V, 2, dtype=torch.float32, device=dev)
+    cost = torch.zeros(G, 2, dtype=torch.float64, device=dev)
+    steps, ok = torch.zeros(G, dtype=torch.uint8, device=dev), torch.zeros(G, dtype=torch.uint8, device=dev)
+    used = torch.zeros(G, V, dtype=torch.int32, device=dev)
+    if ftot > 0:
+        n = int(lib.mp_lift_calibrate_views_scratch_bytes(V, ftot, J))
+        scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
+        _launch(dev, "mp_lift_calibrate_views", _lib.ptr(points), _lib.ptr(points_ok), _lib.ptr(kp), V, ftot, J, _lib.ptr(valid), _lib.ptr(d_off), G,
+                _lib.ptr(d_quat), _lib.ptr(d_trans), _lib.ptr(d_intr), _lib.ptr(d_fixed), _lib.ptr(d_w), int(bool(focal)), int(bool(distort)),
+                float(sigma), float(prior), int(iters), _lib.ptr(quat), _lib.ptr(trans), _lib.ptr(intr), _lib.ptr(out), _lib.ptr(reproj), _lib.ptr(cost),
+                _lib.ptr(steps), _lib.ptr(ok), _lib.ptr(used), _lib.ptr(scratch), n)
+    return quat, trans, intr, out, reproj, cost, steps, ok, used
+
+
+def calibrate_views(points, keypoints_2d, cameras, valid=None, take_offset=None, points_ok=None, fixed=None, weights=None, distort=True, focal=True,
+                    sigma=CALIBRATE_SIGMA, prior=CALIBRATE_PRIOR, iters=CALIBRATE_ITERS):
+    """``mp_lift_calibrate_views`` on device tensors: a take CALIBRATED on its keypoints - the full bundle adjustment behind ``bundle_views``, which
+    holds the fused pose fixed and reads the focal lengths from a calibration.  ``points`` (Ftot, J, 3) float32 world points, the fused pose plus
+    its root, and ``points_ok`` (Ftot) uint8 or None; ``keypoints_2d`` (V, Ftot, J, 2), ``cameras``, ``valid``, ``take_offset``, ``fixed``,
+    ``weights`` and ``distort`` as for ``bundle_views``.  Every joint of every used frame is a free point, every free camera has its six pose
+    parameters and, with ``focal``, every view that observes a frame - the fixed ones too - one factor g on its focal lengths (fx, fy) = g (fx0, fy0);
+    up to ``iters`` (0..8) undamped Gauss-Newton steps on sum w_j rho(|res|^2) + prior sum w_j |X - start|^2, the points eliminated one by one by a
+    Schur complement (include/manipose_hip.h has the rule in full).  ``sigma`` > 0 in normalised screen units (inf: plain least squares);
+    ``prior`` > 0: the keypoints leave the scale of points and camera positions free, and the pull towards the start pins it.  A take needs two
+    views that observe a frame (one view's poses do not decide its focal length); otherwise it is evaluated and copied through.  The defaults are
+    a float64 prototype's, not tuned.  Returns a ``ViewCalibration``: ``(cameras: the nested list with the new intrinsics and extrinsics, to be
+    passed on (this waits for the kernel), quat (G, V, 4), trans (G, V, 3), intr (G, V, 9), points (Ftot, J, 3), reproj (G, V, 2), cost (G, 2)
+    float64, steps (G) uint8, ok (G) uint8, used (G, V) int32)``, new device tensors.  Every view of a take that took no step is copied through bit
+    for bit.  Inputs are not modified; identical bits on every call.  Not measured on real data."""
+    lift_args.robust_scale(sigma)
+    lift_args.prior_pull(prior)
+    lift_args.step_count(iters, CALIBRATE_MAXITERS)
+    valid, d_off, G, (intr, quat, trans, present), h_w, h_fixed = _take_front("calibrate_views", points, keypoints_2d, cameras, valid, take_offset, weights,
+                                                                             roots=(None, points_ok, fixed), ok_name="points_ok")
+    dev, V = points.device, int(keypoints_2d.shape[0])
+    res = _calibrate(_lib.load(), points, points_ok.contiguous() if points_ok is not None else None, keypoints_2d.contiguous(), valid, d_off, G,
+                     torch.from_numpy(quat).to(dev), torch.from_numpy(trans).to(dev), torch.from_numpy(intr).to(dev),
+                     torch.from_numpy(h_fixed).to(dev) if h_fixed is not None else None, torch.from_numpy(h_w).to(dev) if h_w is not None else None,
+                     focal, distort, sigma, prior, iters)
+    q, t, k = res[0].cpu().numpy(), res[1].cpu().numpy(), res[2].cpu().numpy()
+    nested = [[np.concatenate([k[g, v], q[g, v], t[g, v]]) if present[g, v] else None for v in range(V)] for g in range(G)]
+    return ViewCalibration(nested, *res)
 
 
 TRIANGULATE_SIGMA, TRIANGULATE_PRIOR, TRIANGULATE_STEPS = float("inf"), 0.0, 3          # defaults of triangulate_views (not tuned)

@@ -13,6 +13,7 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --align [frames=3000] [reps=20]
     python tools/lift_bench.py --sync [frames=3000] [reps=20]
     python tools/lift_bench.py --bundle [frames=3000] [reps=20]
+    python tools/lift_bench.py --calibrate [frames=3000] [reps=20]
     python tools/lift_bench.py --triangulate [frames=3000] [reps=20]
     python tools/lift_bench.py --skeleton [frames=3000] [reps=20]
     python tools/lift_bench.py --skeleton-smooth [frames=3000] [reps=20]
@@ -28,6 +29,10 @@ into 16, next to mp_lift_triangulate's time for the same frames.
 through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints, pinhole keypoints with 0.01 of noise, the lifted pose
 0.03 m N(0, 1) off, the roots fitted by mp_lift_fuse_place - at iters 0, 1 and 3, as ONE take and cut into 16, next to mp_lift_fuse_place's time
 for the same frames.
+--calibrate times mp_lift_calibrate_views (a take calibrated on its keypoints: per pass one kernel with a lane per frame, which goes through the
+frame's 17 points one by one, and one with a workgroup per take, iters + 1 passes) through its private launcher on --bundle's scene as ONE take,
+the start the fused pose at its placed root, every view's focal lengths started 10, -10, 7 and -8 % off S11's, prior 1e-3, sigma 0.05, at iters
+0, 1 and 3, beside mp_lift_bundle_views at the same iters on the same take - the yardstick - and prints the focal errors before and after.
 --bundle times mp_lift_bundle_views (the bundle adjustment of a take's cameras and roots on the 2-D keypoints: per pass one kernel with a lane per
 frame and one with a workgroup per take, iters + 1 passes) through its private launcher on --fuse's scene - 4 views x `frames` frames of 17 joints,
 pinhole keypoints with 0.01 of noise - with the cameras of views 1..3 started 0.3 degrees and 0.15 m off S11's calibration and the roots fitted
@@ -451,6 +456,45 @@ def bundle_bench(argv):
                   f"cost {res[4][0, 0].item():.4f} -> {res[4][0, 1].item():.4f}, off by {off_by(res[0][0], res[1][0])}", flush=True)
 
 
+def calibrate_bench(argv):
+    from manipose_amd.lift_views import _bundle, _calibrate, _fuse_place
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib, V, (quat, trans, intr), pose, _, kp = fuse_scene(frames, 2)
+    g = np.random.default_rng(3)
+    q0 = (quat[0] / quat[0].norm(dim=1, keepdim=True)).double().cpu().numpy()
+    t0 = trans[0].double().cpu().numpy()
+    for v in range(1, V):                                                 # views 1..3 start 0.3 degrees and 0.15 m off, as in --bundle
+        axis, d = g.standard_normal(3), g.standard_normal(3)
+        h = 0.5 * np.radians(0.3)
+        b = np.concatenate([[np.cos(h)], np.sin(h) * axis / np.linalg.norm(axis)])
+        a = q0[v].copy()
+        q0[v] = [a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                 a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]]
+        t0[v] += 0.15 * d / np.linalg.norm(d)
+    print(f"--calibrate: {V} views x {frames} frames x 17 joints, ONE take, pinhole keypoints with 0.01 of noise, prior 1e-3, sigma 0.05; {reps} calls each "
+          f"after 5 of warm-up (the allocations of outputs and scratch are inside the time); synthetic data", flush=True)
+    fixed = torch.tensor([[1, 0, 0, 0]], dtype=torch.uint8, device="cuda")
+    off = torch.tensor([0, frames], dtype=torch.int64, device="cuda")
+    q = torch.from_numpy(q0.astype(np.float32)).cuda().reshape(1, V, 4).contiguous()
+    t = torch.from_numpy(t0.astype(np.float32)).cuda().reshape(1, V, 3).contiguous()
+    k = intr.reshape(1, V, 9).clone()
+    root, _, ok, _ = _fuse_place(lib, pose, kp, None, off, 1, q, t, k, None, False, 3)
+    start = (pose + root[:, None]).contiguous()
+    k0 = k.clone()
+    k0[0, :, :2] *= torch.tensor([1.10, 0.90, 1.07, 0.92], device="cuda")[:V, None]
+    err = lambda x: ", ".join(f"{e:.4f}" for e in (x[0, :, 0] / k[0, :, 0] - 1).abs().tolist())
+    print(f"start: focal lengths off S11's by {err(k0)}", flush=True)
+    for iters in (0, 1, 3):
+        cal = lambda: _calibrate(lib, start, ok, kp, None, off, 1, q, t, k0, fixed, None, True, False, 0.05, 1e-3, iters)
+        bun = lambda: _bundle(lib, pose, root, ok, kp, None, off, 1, q, t, k, fixed, None, False, 0.05, iters)
+        res = cal()
+        us, us_b = timed_us(cal, reps), timed_us(bun, reps)
+        print(f"mp_lift_calibrate_views, iters={iters}: {us:,.1f} us  {iters + 1} passes, {us / (iters + 1):,.1f} us a pass; {int(res[6][0])} steps, cost "
+              f"{res[5][0, 0].item():.4f} -> {res[5][0, 1].item():.4f}, focal lengths off by {err(res[2])};  mp_lift_bundle_views, iters={iters}: {us_b:,.1f} us "
+              f"({us / us_b:.2f} x)", flush=True)
+
+
 def triangulate_bench(argv):
     from manipose_amd import _lib
     from manipose_amd.lift_ops import _launch
@@ -571,6 +615,9 @@ if "--skeleton-smooth" in sys.argv:
     sys.exit(0)
 if "--skeleton" in sys.argv:
     skeleton_bench([a for a in sys.argv[1:] if a != "--skeleton"])
+    sys.exit(0)
+if "--calibrate" in sys.argv:
+    calibrate_bench([a for a in sys.argv[1:] if a != "--calibrate"])
     sys.exit(0)
 if "--triangulate" in sys.argv:
     triangulate_bench([a for a in sys.argv[1:] if a != "--triangulate"])
