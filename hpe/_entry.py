@@ -280,7 +280,9 @@ LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj
                  "__cam_bundle_used", "__tri", "__tri_err", "__tri_views", "__tri_ok", "__tri_steps", "__skel", "__skel_bones", "__skel_err", "__skel_ok",
                  "__skel_steps", "__skel_quat", "__skel_quat_ok", "__skel_err_smooth", "__skel_moves", "__sync_lag", "__sync_contrast", "__sync_used", "__sync_ok",
                  "__sync_curve", "__cal", "__cam_intr", "__cam_focal", "__cam_focal_err", "__cal_reproj", "__cal_cost", "__cal_steps", "__cal_ok", "__cal_used",
-                 "__cam_quat_bundle", "__cam_trans_bundle", "__cam_err_deg_bundle", "__cam_err_m_bundle")
+                 "__cam_quat_bundle", "__cam_trans_bundle", "__cam_err_deg_bundle", "__cam_err_m_bundle", "__ground_normal", "__ground_offset",
+                 "__ground_quat", "__ground_trans", "__ground_rms", "__ground_gap", "__ground_used", "__ground_ok", "__ground_err_deg", "__ground_z",
+                 "__contact", "__foot_height", "__skate", "__skate_pairs")
 
 
 def _scale_and_cost(scale, cost=None, unit="metres"):
@@ -587,6 +589,81 @@ def lift_fuse_skeleton_smooth_options(cfg):
     return float(smooth), sweeps
 
 
+GROUND_DEFAULTS = dict(speed=0.01, radius=2, sigma=0.03, prior=0.05, iters=5, foot_height=0.0)      # estimate_ground's own, untuned
+
+
+def lift_ground_options(cfg):
+    """(estimate, kwargs of estimate_ground) of lift.ground / lift.ground_speed / lift.ground_radius / lift.ground_sigma / lift.ground_prior /
+    lift.ground_iters / lift.ground_foot_height; ValueError for a value or a combination that cannot run - before any model is built."""
+    ground = cfg.lift.get("ground", "none")
+    ground = "none" if ground is None else ground      # (an override lift.ground=none is read as the null it spells)
+    kw = {k: cfg.lift.get("ground_" + k, v) for k, v in GROUND_DEFAULTS.items()}
+    if ground not in ("none", "estimate"):
+        raise ValueError(f"lift.ground must be none or estimate, got {ground!r}")
+    if not is_int_in(kw["radius"], 1, 8):
+        raise ValueError(f"lift.ground_radius is the half width of the speed's central difference in frames, an integer in 1..8, got {kw['radius']!r}")
+    if not is_int_in(kw["iters"], 0, 8):
+        raise ValueError(f"lift.ground_iters counts the re-weighted solves of the plane, an integer in 0..8, got {kw['iters']!r}")
+    if not is_number(kw["speed"]) or not 0 < kw["speed"] < float("inf"):
+        raise ValueError(f"lift.ground_speed must be finite and > 0 (metres per frame), got {kw['speed']!r}")
+    _scale_and_cost(("ground_sigma", kw["sigma"]), ("ground_prior", kw["prior"]))
+    if not is_number(kw["foot_height"]) or not abs(kw["foot_height"]) < float("inf"):
+        raise ValueError(f"lift.ground_foot_height must be finite (metres), got {kw['foot_height']!r}")
+    if ground != "estimate":
+        if any(kw[k] != v for k, v in GROUND_DEFAULTS.items()):
+            raise ValueError("lift.ground_speed / lift.ground_radius / lift.ground_sigma / lift.ground_prior / lift.ground_iters / "
+                             "lift.ground_foot_height describe the estimate of the floor: set lift.ground=estimate")
+        return False, kw
+    if not cfg.run.get("lift", False):
+        raise ValueError("lift.ground=estimate stands lifted sequences on their floor: set run.lift=true")
+    if not lift_fuse_options(cfg)[0] and not lift_place_options(cfg)[0]:
+        raise ValueError("lift.ground=estimate reads absolute joint positions: set lift.fuse=true (a take's fused pose at its root) or lift.place=true "
+                         "(a sequence's poses at their fitted trajectory)")
+    return True, {k: (int(v) if k in ("radius", "iters") else float(v)) for k, v in kw.items()}
+
+
+GROUND_KEYS = ("normal", "offset", "quat", "trans", "rms", "gap", "used", "ok")       # of estimate_ground's record -> "<key>__ground_<k>" in lift.npz
+
+
+def ground_outputs(out, rows, keys, points, off, valid, up, kw):
+    """lift.ground=estimate on the absolute joint positions ``points`` (Ntot, 17, 3) of the sequences or takes ``keys`` (frames ``off``, ``valid``
+    (Ntot) uint8), as they are emitted: estimate_ground's record goes into ``out`` as ``<key>__ground_normal``, ``__ground_offset``, ``__ground_quat``,
+    ``__ground_trans``, ``__ground_rms``, ``__ground_gap``, ``__ground_used``, ``__ground_ok``, ``__contact`` (N, 2) uint8, ``__foot_height`` (N, 2),
+    ``__skate``, ``__skate_pairs``; held against ``up`` (S, 3), the direction that is up in the frame of the points by the dataset's calibration:
+    ``__ground_err_deg``, the angle between the normal and up (NaN without a plane), and ``__ground_z``, the mean of the contact points along up (the
+    ankle's height if the dataset's floor is up . x = 0; NaN without a contact).  ``rows`` receives lift_ground.csv's row per key.  The poses are not
+    moved: ``__ground_quat`` and ``__ground_trans`` stand them up, to_world's convention."""
+    from manipose_amd import estimate_ground
+    g = estimate_ground(points.contiguous(), seq_offset=off, valid=valid.contiguous(), **kw)
+    host = {k: getattr(g, k).cpu().numpy() for k in g._fields}
+    feet = points[:, [3, 6]].cpu().numpy().astype(np.float64)
+    for s, key in enumerate(keys):
+        sl = slice(int(off[s]), int(off[s + 1]))
+        for k in GROUND_KEYS:
+            out[f"{key}__ground_{k}"] = host[k][s]
+        out[key + "__contact"], out[key + "__foot_height"] = host["contact"][sl], host["height"][sl]
+        out[key + "__skate"], out[key + "__skate_pairs"] = host["skate"][s], host["skate_pairs"][s]
+        u = np.asarray(up[s], np.float64)
+        u = u / np.linalg.norm(u)
+        plane, touch = bool(host["ok"][s] & 1), host["contact"][sl] != 0
+        err = float(np.degrees(np.arccos(np.clip(host["normal"][s].astype(np.float64) @ u, -1.0, 1.0)))) if plane else float("nan")
+        z = float((feet[sl][touch] @ u).mean()) if touch.any() else float("nan")
+        out[key + "__ground_err_deg"], out[key + "__ground_z"] = np.float32(err), np.float32(z)
+        rows.append(dict(key=key, frames=sl.stop - sl.start, contacts=int(host["used"][s]), rms_mm=1000.0 * float(host["rms"][s]), gap=float(host["gap"][s]),
+                         err_deg=err, z_mm=1000.0 * z, skate_mm=1000.0 * float(host["skate"][s]), skate_pairs=int(host["skate_pairs"][s])))
+
+
+def write_lift_ground_report(out_dir, rows):
+    """lift_ground.csv: one row per take or sequence of lift.ground=estimate"""
+    path = os.path.join(out_dir, "lift_ground.csv")
+    cols = ("frames", "contacts", "rms_mm", "gap", "err_deg", "z_mm", "skate_mm", "skate_pairs")
+    with open(path, "w") as f:
+        f.write("key," + ",".join(cols) + "\n")
+        for r in rows:
+            f.write(r["key"] + "," + ",".join(str(r[c]) if isinstance(r[c], int) else f"{r[c]:.6g}" for c in cols) + "\n")
+    return path
+
+
 def _camera_index(cam):
     """fetch()'s 17th number, a camera dict's "index", or None"""
     if isinstance(cam, dict):
@@ -759,7 +836,8 @@ def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, 
     return est, nested, valid, place_valid
 
 
-def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_scores=None, skel_scores=None, cal_scores=None, true_cams=None):
+def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_scores=None, skel_scores=None, cal_scores=None, true_cams=None,
+               ground_rows=None):
     """lift.fuse on one group: its sequences are cut into takes (split_takes), every take's views are fused (fuse_views: one hypothesis per view,
     chosen jointly; their mean, root-relative in the world's orientation), with lift.rigid re-assembled with the mean of the views' bone tables, and
     placed with ONE world root per frame (place_views); with lift.floor the take stands on z = 0.  ``res``: the group's _Lifted with hypotheses, taken
@@ -783,7 +861,10 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     (N, 17, 4), ``__skel_quat_ok`` (N,) are added; with lift.fuse_skeleton_smooth > 0 the take is fitted along time (lift.fuse_skeleton_sweeps
     sweeps): ``__skel``, ``__skel_quat`` and the score are the smoothed fit's, ``__skel_err`` stays (N, 2) and ``__skel_err_smooth`` (N,),
     ``__skel_moves`` (N,) are added; with ``targets`` the fitted pose's score goes into ``skel_scores`` (the frames without a
-    result left out)."""
+    result left out).
+    With lift.ground=estimate every take's floor is estimated (ground_outputs has the keys) on ``__skel`` where lift.fuse_skeleton is on (the frames
+    with a result), else on the fused pose at its root (the frames fused and placed), as emitted - in the dataset's world, so the estimate is held
+    against world +z; nothing that is emitted moves.  ``ground_rows`` receives lift_ground.csv's rows."""
     from manipose_amd import (bundle_views, calibrate_views, camera_table, fit_skeleton_views, fuse_views, fuse_views_path, place_views, pose_rotations, project_rigid,
                               score_poses, score_traj, to_world, triangulate_views)
     from manipose_amd.lifting import SCORE_FIELDS
@@ -878,6 +959,13 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     unit = np.tile(np.array([1, 0, 0, 0], np.float32), (len(takes), 1))
     scene = to_world(pose.clone(), unit, traj=root, seq_offset=off, floor=True if floor else False)
     scene, d_floor = scene if floor else (scene, None)
+    ground_on, ground_kw = lift_ground_options(cfg)
+    if ground_on:                              # lift.ground=estimate: contacts and floor of every take, on the points as they are emitted
+        points, known = (skel.pose.clone(), skel.ok & 1) if skel is not None else (pose + root[:, None], ok & placed)
+        if floor:
+            points[..., 2] -= d_floor.repeat_interleave(torch.as_tensor(frames, device=dev))[:, None]
+        ground_outputs(out, ground_rows if ground_rows is not None else [], [f"{name}.fused{t}" for t in range(len(takes))], points, off, known,
+                       np.tile(np.array([0.0, 0.0, 1.0]), (len(takes), 1)), ground_kw)
     if targets is not None:
         gt_pose, gt_root = [], []
         for views in takes:                    # the first view's ground truth, rotated into the world
@@ -973,7 +1061,7 @@ def synthetic_cameras(groups):
 
 
 def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None, fused_scores=None, tri_scores=None, skel_scores=None,
-                           cal_scores=None):
+                           cal_scores=None, ground_rows=None):
     """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
     hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
     it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
@@ -1022,7 +1110,14 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     ``__cal_used`` (V,) are added; ``__cam_quat``, ``__cam_trans``, ``__cam_err_deg``, ``__cam_err_m`` become the calibrated cameras' and the
     earlier values move to the suffix ``_bundle`` (after lift.fuse_bundle) or ``_align``; with ``targets`` the dict ``cal_scores`` receives {fused
     key: score dict} of the calibrated points.  With lift.fuse_calibrate_start_focal=f every camera the lifting stages read has the intrinsics
-    (f, f, 0, 0, 0, 0, 0, 0, 0): the dataset's intrinsics are read for ``__cam_focal_err`` alone."""
+    (f, f, 0, 0, 0, 0, 0, 0, 0): the dataset's intrinsics are read for ``__cam_focal_err`` alone.
+    With lift.ground=estimate (lift.ground_speed, lift.ground_radius, lift.ground_sigma, lift.ground_prior, lift.ground_iters,
+    lift.ground_foot_height; lift.fuse or lift.place needed) the floor under the motion is estimated from the feet that stand still
+    (estimate_ground): per fused take with lift.fuse, else per placed sequence on the poses at their trajectory, and ``__ground_normal`` (3,),
+    ``__ground_offset``, ``__ground_quat`` (4,), ``__ground_trans`` (3,), ``__ground_rms``, ``__ground_gap``, ``__ground_used``, ``__ground_ok``,
+    ``__contact`` (N, 2) uint8, ``__foot_height`` (N, 2), ``__skate``, ``__skate_pairs``, ``__ground_err_deg`` (the angle to the dataset's up: world
+    +z, under lift.frame=camera the camera's rotation's) and ``__ground_z`` are added under the take's or the sequence's key; the list ``ground_rows``
+    receives a row each for lift_ground.csv.  No emitted pose is moved: ``__ground_quat`` and ``__ground_trans`` stand the take up (to_world)."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
     out = {}
@@ -1035,6 +1130,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     rotations, rot_continuous = lift_rotations_options(cfg)
     rot_kw = dict(rotations=True, rotations_continuous=rot_continuous, return_rotations=True) if rotations else {}
     use_cams = place or world
+    ground_on, ground_kw = lift_ground_options(cfg)
     fuse, want_hyps = lift_fuse_options(cfg)[0], bool(cfg.lift.hyps)       # the fusion reads the hypotheses whether or not lift.hyps writes them
     score_kw = lambda name: dict(targets=targets[name], return_score=True) if targets is not None else {}
     to_host = lambda v: {k: to_host(x) for k, x in v.items()} if isinstance(v, dict) else v.cpu().numpy()
@@ -1074,7 +1170,15 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
                 scores[key] = to_host(asked(res.score[i]))
         if fuse:
             fuse_group(out, name, res, seqs, cameras[name], cfg, targets[name] if targets is not None else None, fused_scores, tri_scores, skel_scores,
-                       cal_scores, true_cameras[name])
+                       cal_scores, true_cameras[name], ground_rows)
+        elif ground_on:                        # lift.ground=estimate on placed sequences: the poses at their trajectory, in the frame they are emitted in
+            keys = [name if len(res.poses) == 1 else f"{name}.{i}" for i in range(len(res.poses))]
+            points = torch.cat([p if world else p + res.place[i]["traj"][:, None] for i, p in enumerate(res.poses)])
+            known = torch.cat([res.place[i]["ok"] for i in range(len(res.poses))])
+            off = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in res.poses])]).astype(np.int64)
+            up = [np.array([0.0, 0.0, 1.0]) if world else _qrot(cam_rows[i][9:13] * np.array([1, -1, -1, -1]), np.array([[0.0, 0.0, 1.0]]))[0]
+                  for i in range(len(res.poses))]      # world +z; in a camera's frame its rotation's up, R^T z
+            ground_outputs(out, ground_rows if ground_rows is not None else [], keys, points, off, known, up, ground_kw)
     np.savez(path, **out)
     return out
 
@@ -1127,6 +1231,7 @@ def run(argv, extra_defaults=None):
     lift_fuse_triangulate_options(cfg)         # ... and a lift.fuse_triangulate without lift.fuse
     lift_fuse_skeleton_options(cfg)            # ... and a lift.fuse_skeleton without lift.fuse
     lift_fuse_skeleton_smooth_options(cfg)     # ... and a lift.fuse_skeleton_smooth without lift.fuse_skeleton
+    lift_ground_options(cfg)                   # ... and a lift.ground=estimate with neither lift.fuse nor lift.place
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")
@@ -1300,7 +1405,10 @@ def run(argv, extra_defaults=None):
         targets, scores, fused_scores, tri_scores, skel_scores, cal_scores = None, {}, {}, {}, {}, {}
         if lift_score_options(cfg):            # the 3-D ground truth beside the 2-D sequences that are lifted
             targets = {name: sq[0] for name, sq in seqs["test"].items()} if real else synthetic_sequences_3d(cfg, cfg.run.seed)
-        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores, tri_scores, skel_scores, cal_scores)
+        ground_rows = []
+        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores, tri_scores, skel_scores, cal_scores, ground_rows)
+        if lift_ground_options(cfg)[0]:
+            print(f"lift.ground: {len(ground_rows)} floors estimated -> {write_lift_ground_report(out_dir, ground_rows)}", flush=True)
         is_pose = lambda k: not k.endswith(LIFT_SUFFIXES) and ".fused" not in k
         print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if is_pose(k))} frames of {len(groups)} groups -> {path}", flush=True)
         if lift_fuse_options(cfg)[0]:

@@ -1115,6 +1115,60 @@ int mp_lift_fit_skeleton_smooth(const float* start, const uint8_t* start_ok, con
                                 int sweeps, float* pose, float* err, uint8_t* ok, uint8_t* steps, uint8_t* moves, void* scratch,
                                 int64_t scratch_bytes, void* stream);
 
+/* Standing a take on its floor: contacts, ground plane, foot skate.  Every operator above either reads which way is up from a calibration
+ * (mp_lift_world's quaternion, its floor "the lowest joint on z = 0") or has no up at all (a camera's frame, the frame of estimated cameras).
+ * The motion carries it: a foot that stands still is standing on something, and over a sequence those points span the floor.  This estimates, per
+ * sequence, which frames each foot is in contact, the plane through the contact points - robustly, with the body's mean axis as a weak prior - the
+ * rotation and shift that stand the sequence on z = foot_height, each foot's height over the plane, and how far the feet slide while in contact
+ * (the foot skate: a quality measure that needs neither 3-D ground truth nor a calibration).  The reference has no counterpart.  The layout is the
+ * per-sequence operators': seq_offset (S + 1) device int64, entries clamped to 0 .. Ntot, sequence s = frames [f0, f1); valid (Ntot) bytes or null;
+ * fp64 between the float32 loads and the float32 stores, without contraction into fused multiply-adds; no atomics, fixed orders: identical bits on
+ * every call; a sequence's result does not depend on the other sequences of the call; the call does not synchronise.  The defaults the Python layer
+ * passes (radius 2, speed 0.01, sigma 0.03, prior 0.05, iters 5) are untuned.  Not measured on real data.
+ * points (Ntot, J, C) read only, C = 3 or 4 (channel 3 is not read), 2 <= J <= 32: absolute joint positions in ANY rigid frame, a camera's or a
+ * world; feet: nf joint indices, 1 <= nf <= MP_LIFT_GROUND_MAXFEET (host table); axis_from != axis_to: two joints whose difference points up the
+ * body (pelvis, thorax); radius r in 1 .. MP_LIFT_GROUND_MAXRADIUS frames; speed > 0 in the points' unit per frame; sigma > 0 in that unit (+inf:
+ * every weight is exactly 1); prior >= 0 in that unit; 0 <= iters <= MP_LIFT_GROUND_MAXITERS; foot_height in that unit.  Frame f is GOOD if
+ * valid[f] != 0 (valid null: every frame); a joint of a frame is FINITE if its three coordinates are.
+ * A. Contacts, per frame f and foot k with joint j = feet[k]: contact[f][k] = 1 if f - r >= f0 and f + r < f1, the frames f - r, f, f + r are
+ *    good, p[.][j] is finite in all three, and with d = p[f+r][j] - p[f-r][j]:  (dx^2 + dy^2) + dz^2 <= ((2 r) speed)^2, the threshold formed in
+ *    fp64 from the float32 speed.  Else 0 - the first and last r frames of a sequence, and a frame that no sequence holds, included.
+ * B. Body axis: B = sum over the good frames f with p[f][axis_to] and p[f][axis_from] finite, in frame order, of d / |d|, d = p[f][axis_to] -
+ *    p[f][axis_from]; a term with |d| < 1e-12 is passed over.  |B| < 1e-12 (or no term): the sequence has NO AXIS; else b = B / |B|.
+ * C. The plane, iters + 1 solves over the contact points x_i = p[f][feet[k]] (frames in order, within a frame the feet in order); used = their
+ *    number.  Solve 0: w_i = 1.  Solve t > 0: r_i = ((n . x_i) - offset) under the plane of solve t - 1, w_i = 1 / (1 + r_i^2 / sigma^2)^2.  A solve
+ *    takes two passes:  W = sum w_i,  m = (sum w_i x_i) / W;  then C = sum w_i (x_i - m)(x_i - m)^T.  A = C - prior^2 W b b^T, the second term only
+ *    with an axis and prior > 0: of the planes the data leave open - two ankles in place span a line - it picks the one most perpendicular to the
+ *    body; with contacts spread over decimetres the data outweigh prior = 0.05 by orders of magnitude.  A's eigenvalues a1 <= a2 <= a3 and the
+ *    eigenvector of a1 come from the symmetric 4x4 Jacobi of mp_lift_align_views on s I - A, s = tr C + prior^2 W, padded with a zero row and
+ *    column (positive semidefinite; its eigenvalues are s - a).  n = that vector, normalised; with an axis and n . b != 0 its sign is the one
+ *    with n . b > 0 (ok bit 1); else the first non-zero component is positive (bit 1 clear).  offset = n . m.
+ *    NO PLANE: used < 3; at any solve W not > 0, a sum, m or s not finite, or  a2 - a1 <= 1e-9 max(|a1|, |a3|).
+ * D. Per sequence: normal (S, 3) = n;  offset (S);  quat (S, 4) = the shortest rotation taking n onto +z, normalize(1 + n_z, n_y, -n_x, 0), and
+ *    (0, 1, 0, 0) where 1 + n_z < 1e-12 - its w is never negative: canonical;  trans (S, 3) = (0, 0, foot_height - offset): with mp_lift_world's
+ *    convention p' = qrot(quat, p) + trans a contact foot ends at z = foot_height, the heading and the horizontal origin stay the input frame's;
+ *    rms (S) = sqrt(sum w_i r_i^2 / sum w_i), r_i under the final plane, w_i the weights of the last solve (1 for iters = 0);
+ *    gap (S) = (a2 - a1) / (a3 - a1) of the last solve, 0 where a3 == a1: near 0 the contact points lie on a line and the prior or noise chose
+ *    the plane, near 1 they are spread evenly;  used (S) int32;  ok (S) bytes: bit 0 a plane exists, bit 1 the body axis decided its up side.
+ *    Without a plane: normal = (0, 0, 1), quat = (1, 0, 0, 0), offset, trans, rms, gap zero, ok = 0; contact, used, skate, skate_pairs all the same.
+ * E. height (Ntot, nf) = (n . p[f][feet[k]]) - offset for a good frame with that joint finite in a sequence with a plane, else 0.
+ *    skate (S) = the mean over the contact pairs - contact[f][k] and contact[f+1][k], both frames in the sequence - of |d - (n . d) n|,
+ *    d = p[f+1][feet[k]] - p[f][feet[k]]: the in-plane length of the step, in the points' unit per frame; without a plane |d|.  0 where there is
+ *    no pair.  skate_pairs (S) int32 = their number.
+ * Two launches: one lane per (frame, foot) for A; one workgroup of 256 lanes per sequence for the rest - a lane sums the frames f0 + lane,
+ * f0 + lane + 256, ... in order, the lanes' sums are added by a butterfly within a wave and the four waves' in wave order, every lane solves the
+ * eigenproblem; the 2 (iters + 1) + 1 passes follow one another inside the workgroup.  No scratch memory.
+ * MP_ERR_ARG before anything is launched: J, C, Ntot or S out of range (S > Ntot, Ntot nf > 2^31 - 1); points, seq_offset, feet or an output null;
+ * nf out of range; a foot or an axis joint outside 0 .. J - 1; axis_from == axis_to; radius or iters out of range; speed not > 0 or not finite;
+ * sigma not > 0; prior negative or not finite; foot_height not finite. */
+#define MP_LIFT_GROUND_MAXFEET 4
+#define MP_LIFT_GROUND_MAXRADIUS 8
+#define MP_LIFT_GROUND_MAXITERS 8
+int mp_lift_ground(const float* points, int64_t Ntot, int J, int C, const uint8_t* valid, const int64_t* seq_offset, int S, const int32_t* feet, int nf,
+                   int axis_from, int axis_to, int radius, float speed, float sigma, float prior, int iters, float foot_height, float* normal,
+                   float* offset, float* quat, float* trans, float* rms, float* gap, int32_t* used, uint8_t* ok, uint8_t* contact, float* height,
+                   float* skate, int32_t* skate_pairs, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -152,6 +152,45 @@ def sweep_count(sweeps, highest):
         raise ValueError(f"sweeps counts sweeps over a take's frames, an integer in 0..{highest} (0: every frame fitted on its own), got {sweeps!r}")
 
 
+def points3(points):
+    """points (Ntot, J, 3 | 4) contiguous float32 with 2..32 joints, a tensor -> (Ntot, J)"""
+    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[2] not in (3, 4) or points.dtype != torch.float32 or not points.is_contiguous():
+        raise ValueError(f"points must be a contiguous float32 tensor (Ntot, J, 3 | 4), got {_got(points)}")
+    _count("points", int(points.shape[1]), "joints", 2, 32)
+    return int(points.shape[0]), int(points.shape[1])
+
+
+def ground_joints(feet, axis, J, maxfeet):
+    """feet: 1..maxfeet joint indices, axis: two different ones, all integers in 0..J-1 -> (feet, axis) as tuples of int"""
+    try:
+        feet, axis = tuple(feet), tuple(axis)
+    except TypeError:
+        raise ValueError(f"feet and axis are sequences of joint indices, got {feet!r}, {axis!r}") from None
+    if not 1 <= len(feet) <= maxfeet or not all(is_int_in(j, 0, J - 1) for j in feet):
+        raise ValueError(f"feet must be 1..{maxfeet} joint indices in 0..{J - 1}, got {feet!r}")
+    if len(axis) != 2 or not all(is_int_in(j, 0, J - 1) for j in axis) or int(axis[0]) == int(axis[1]):
+        raise ValueError(f"axis must be two different joint indices in 0..{J - 1} (from, to: up the body), got {axis!r}")
+    return tuple(int(j) for j in feet), tuple(int(j) for j in axis)
+
+
+def ground_options(radius, speed, sigma, prior, iters, foot_height, maxradius, maxiters):
+    """the scalars of estimate_ground as the kernel takes them (float32): radius and iters integers in range, speed finite and > 0, sigma > 0 (+inf is
+    allowed), prior finite and >= 0, foot_height finite"""
+    big = float(np.finfo(np.float32).max)
+    if not is_int_in(radius, 1, maxradius):
+        raise ValueError(f"radius must be an integer in 1..{maxradius} frames, got {radius!r}")
+    if not is_number(speed) or not 0 < float(np.float32(speed)) <= big:
+        raise ValueError(f"speed must be a finite number > 0 (the points' unit per frame), got {speed!r}")
+    if not is_number(sigma) or not float(np.float32(sigma)) > 0:
+        raise ValueError(f"sigma must be a number > 0 in the points' unit (inf: no robust weight), got {sigma!r}")
+    if not is_number(prior) or not 0 <= float(prior) <= big:
+        raise ValueError(f"prior must be a finite number >= 0 (0: the body axis does not pull the plane), got {prior!r}")
+    if not is_int_in(iters, 0, maxiters):
+        raise ValueError(f"iters counts re-weighted solves, an integer in 0..{maxiters} (0: the plain fit alone), got {iters!r}")
+    if not is_number(foot_height) or not abs(float(foot_height)) <= big:
+        raise ValueError(f"foot_height must be a finite number, got {foot_height!r}")
+
+
 def take_count(take_offset):
     """the G of a (G + 1) table of first frames, host or device, read from its size alone (None: one take)"""
     if take_offset is None:

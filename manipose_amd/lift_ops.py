@@ -47,6 +47,12 @@ Scoring (``targets`` / ``return_score``, off by default): ``mp_lift_score`` hold
 sequence and on the device - MPJPE, P-MPJPE, velocity and acceleration errors, per-joint errors, bone-length statistics, and the trajectory's error
 with ``place`` (include/manipose_hip.h has the rule; ``score_poses`` / ``score_traj`` are the stand-alone forms).  It is the instrument for the
 sentences above that say "has not been measured"; no number is claimed here.
+
+Standing a sequence on its floor (``estimate_ground``, off everywhere by default): placing and the world frame read which way is up from a calibration.
+``mp_lift_ground`` takes it from the motion: a foot that stands still is standing on something, the contact points of a sequence span its floor, and the
+plane through them - robustly, the body's mean axis a weak prior - gives the rotation and shift ``to_world`` applies, each foot's height over the plane and
+the foot skate, how far the feet slide while in contact (include/manipose_hip.h has the rule).  It reads ABSOLUTE positions (poses plus trajectory) in any
+rigid frame and moves nothing.  The defaults are untuned and nothing has been measured on real data (no dataset here).
 """
 from __future__ import annotations
 
@@ -424,6 +430,59 @@ def score_traj(traj, target, ok=None, seq_offset=None):
 def _traj_record(rows):
     n = rows[..., 0]
     return TrajScore(n, _ratio(rows[..., 1], n), torch.sqrt(_ratio(rows[..., 2], n)), _ratio(rows[..., 4], rows[..., 3]), _ratio(rows[..., 6], rows[..., 5]))
+
+
+GROUND_MAXFEET, GROUND_MAXRADIUS, GROUND_MAXITERS = 4, 8, 8      # MP_LIFT_GROUND_* of include/manipose_hip.h
+# What estimate_ground returns, device tensors: per sequence normal (S, 3), offset (S), quat (S, 4), trans (S, 3), rms (S), gap (S) float32, used (S)
+# int32, ok (S) uint8; per frame and foot contact (Ntot, nf) uint8, height (Ntot, nf) float32; skate (S) float32, skate_pairs (S) int32
+Ground = namedtuple("Ground", "normal offset quat trans rms gap used ok contact height skate skate_pairs")
+
+
+def _ground(lib, points, valid, d_off, S, feet, axis, radius, speed, sigma, prior, iters, foot_height):
+    """``mp_lift_ground`` on points (Ntot, J, C) with valid (Ntot) uint8 or None: a ``Ground`` of new tensors"""
+    ntot, J, ch = (int(v) for v in points.shape)
+    dev, nf = points.device, len(feet)
+    f32s = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    i32s = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    g = Ground(f32s(S, 3), f32s(S), f32s(S, 4), f32s(S, 3), f32s(S), f32s(S), i32s(S), torch.empty(S, dtype=torch.uint8, device=dev),
+               torch.empty(ntot, nf, dtype=torch.uint8, device=dev), f32s(ntot, nf), f32s(S), i32s(S))
+    _launch(dev, "mp_lift_ground", _lib.ptr(points), ntot, J, ch, _lib.ptr(valid), _lib.ptr(d_off), S, (C.c_int32 * nf)(*feet), nf, axis[0], axis[1],
+            int(radius), float(speed), float(sigma), float(prior), int(iters), float(foot_height), *(_lib.ptr(t) for t in g))
+    return g
+
+
+def estimate_ground(points, seq_offset=None, valid=None, feet=(3, 6), axis=(0, 8), radius=2, speed=0.01, sigma=0.03, prior=0.05, iters=5,
+                    foot_height=0.0):
+    """``mp_lift_ground`` on device tensors: which way is up and where the floor is, from the motion itself.  ``points`` (Ntot, J, 3 | 4) float32:
+    ABSOLUTE joint positions (poses plus their root trajectory) in any rigid frame, a camera's or a world (channel 3 is not read); ``seq_offset``
+    (S + 1): first frame of every sequence, HOST table or device int64 tensor (default: one sequence); ``valid`` uint8 (Ntot) or None.  ``feet``:
+    1..4 joint indices (default the H36M ankles), ``axis``: two joints whose difference points up the body (default pelvis, thorax).  A foot is in
+    CONTACT in frame f where its central difference over f - radius .. f + radius (radius 1..8, all three frames valid, finite and in one
+    sequence) is at most ``speed`` per frame; the plane through a sequence's contact points is the smallest eigenvector of their scatter,
+    re-weighted ``iters`` times (0..8) with 1 / (1 + r^2 / sigma^2)^2 so that a slow foot held in the air is shed (``sigma`` = inf: no weight), and
+    pulled by ``prior`` (a length; 0: off) towards the plane perpendicular to the body's mean axis - what decides a sequence whose feet never move,
+    two points that span a line.  The axis also decides which side is up.  include/manipose_hip.h has the rule.  Returns a ``Ground`` of new device
+    tensors: ``normal`` (S, 3), ``offset`` (S) = normal . a point of the plane, ``quat`` (S, 4) the shortest rotation taking the normal onto +z and
+    ``trans`` (S, 3) = (0, 0, foot_height - offset): ``to_world(points, g.quat, translation=g.trans, seq_offset=...)`` stands every sequence up with
+    its contact feet at z = ``foot_height``, heading and horizontal origin unchanged; ``rms`` (S) the weighted RMS distance of the contact points from
+    the plane; ``gap`` (S) in 0..1, (a2 - a1) / (a3 - a1) of the scatter's eigenvalues: near 0 the contacts lie on a line and the prior chose the
+    plane; ``used`` (S) int32 contact points; ``ok`` (S) uint8: bit 0 a plane exists (else normal (0, 0, 1), quat (1, 0, 0, 0), zeros), bit 1 the
+    body axis decided the up side; ``contact`` (Ntot, nf) uint8; ``height`` (Ntot, nf) each foot's height over the plane; ``skate`` (S) the mean
+    in-plane step of a foot between two consecutive frames in contact, per frame, and ``skate_pairs`` (S) int32 the number of such pairs.  points is
+    not modified; fp64 inside, identical bits on every call.  The defaults are untuned, and nothing here has been measured on real data."""
+    lift_args.ground_options(radius, speed, sigma, prior, iters, foot_height, GROUND_MAXRADIUS, GROUND_MAXITERS)
+    ntot, J = lift_args.points3(points)                  # (the ValueErrors come before the refusal of a CPU tensor)
+    feet, axis = lift_args.ground_joints(feet, axis, J, GROUND_MAXFEET)
+    lift_args.mask(valid, (ntot,), "valid")
+    if ntot < 1:
+        raise ValueError("points hold no frame")
+    shape = None if seq_offset is None else tuple(seq_offset.shape if torch.is_tensor(seq_offset) else np.shape(seq_offset))
+    if shape is not None and (len(shape) != 1 or shape[0] < 2 or shape[0] - 1 > ntot):
+        raise ValueError(f"seq_offset must hold S + 1 >= 2 frame numbers, S <= {ntot} frames, got shape {shape}")
+    lift_args.need_device("estimate_ground", points, optional=(valid,))
+    d_off, S = _seq_table(seq_offset, ntot, points.device)
+    return _ground(_lib.load(), points, None if valid is None else valid.contiguous(), d_off, S, feet, axis, radius, speed, sigma, prior, iters,
+                   foot_height)
 
 
 REFINE_MAXITERS = 16         # MP_LIFT_REFINE_MAXITERS of include/manipose_hip.h: Gauss-Newton steps mp_lift_place_refine takes at most

@@ -17,6 +17,11 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --triangulate [frames=3000] [reps=20]
     python tools/lift_bench.py --skeleton [frames=3000] [reps=20]
     python tools/lift_bench.py --skeleton-smooth [frames=3000] [reps=20]
+    python tools/lift_bench.py --ground [frames=3000] [reps=20]
+--ground times mp_lift_ground (contacts, ground plane and foot skate of a sequence: a contact kernel with one lane per (frame, foot) and a plane
+kernel with one 256-lane workgroup per sequence, 2 (iters + 1) + 1 passes inside it) through its private launcher on synthetic walkers on a tilted
+floor with 5 mm of noise, as ONE take of `frames` frames and as 64 sequences of `frames` / 10, at iters 0, 5 and 8, and prints how far the
+normal is from the floor's.
 --skeleton-smooth times mp_lift_fit_skeleton_smooth (a fused take's skeleton fitted along time: mp_lift_fit_skeleton's kernel as stage A, then three
 launches a sweep, one per colour, each visited frame one Gauss-Newton step with its neighbours held) through its private launcher and through the
 entry point into outputs allocated once, on --skeleton's scene and start, iters = 3, smooth = 0.1, at sweeps 1 and 8, as ONE take and cut into
@@ -610,6 +615,51 @@ def skeleton_smooth_bench(argv):
               f"stage A and one sweep together {alone[1]:,.1f} us", flush=True)
 
 
+def ground_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.lift_ops import _ground
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib = _lib.load()
+
+    def walker(n, seed):
+        """a walker on a tilted floor: a 40-frame step cycle, 60 % stance, 5 mm of noise, 17 joints"""
+        g = np.random.default_rng(seed)
+        f = np.arange(n)
+        pts = np.zeros((n, 17, 3))
+        for k, j in enumerate((3, 6)):
+            c, t = np.divmod(f + 20 * k, 40)
+            u = np.clip((t - 23) / 17.0, 0.0, 1.0)
+            e = 0.5 - 0.5 * np.cos(np.pi * u)
+            pts[:, j] = np.stack([0.6 * (c + e) + 0.3 * k, np.full(n, 0.2 * k - 0.1) + 0.5 * np.sin(0.4 * (c + e)), 0.12 * np.sin(np.pi * u)], axis=1)
+        centre = 0.5 * (pts[:, 3] + pts[:, 6]) * [1, 1, 0]
+        pts[:, [0, 1, 2, 4, 5, 7, 9, 10, 11, 12, 13, 14, 15, 16]] = (centre + [0, 0, 0.9])[:, None] + 0.25 * g.standard_normal((14, 3))
+        pts[:, 0], pts[:, 8] = centre + [0, 0, 0.9], centre + [0, 0, 1.4]
+        pts += 0.005 * g.standard_normal(pts.shape)
+        a, b = 0.4, -0.3                                                   # a tilt of the floor: about x, then about y
+        R = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]]) @ np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
+        return (pts @ R.T + [1.0, -2.0, 3.0]).astype(np.float32), R[:, 2]
+
+    print(f"--ground: walkers of 17 joints on a tilted floor, 5 mm of noise, the defaults (radius 2, speed 0.01, sigma 0.03, prior 0.05, iters 5: 13 passes); "
+          f"{reps} calls each after 5 of warm-up (the output allocations are inside the time)", flush=True)
+    for S, n in ((1, frames), (64, max(frames // 10, 1))):
+        scenes = [walker(n, 100 * S + s) for s in range(S)]
+        pts = torch.from_numpy(np.concatenate([p for p, _ in scenes])).cuda()
+        off = torch.tensor([n * s for s in range(S + 1)], dtype=torch.int64, device="cuda")
+        run = lambda iters=5: _ground(lib, pts, None, off, S, (3, 6), (0, 8), 2, 0.01, 0.03, 0.05, iters, 0.0)
+        got = run()
+        torch.cuda.synchronize()
+        cos = np.clip((got.normal.double().cpu().numpy() * np.stack([u for _, u in scenes])).sum(axis=1), -1, 1)
+        print(f"{S} sequence(s) of {n} frames: ok {sorted(set(got.ok.tolist()))}, {int(got.used.sum())} contacts, the normal off the floor's by at most "
+              f"{np.degrees(np.arccos(cos)).max():.3f} degrees, rms {1e3 * float(got.rms.max()):.2f} mm, skate {1e3 * float(got.skate.max()):.2f} mm a frame", flush=True)
+        for iters in (0, 5, 8):
+            us = timed_us(lambda: run(iters), reps)
+            print(f"mp_lift_ground, {S} sequence(s) of {n} frames, iters={iters}: {us:,.1f} us  (contact kernel + {2 * (iters + 1) + 1} passes of the plane kernel)", flush=True)
+
+
+if "--ground" in sys.argv:
+    ground_bench([a for a in sys.argv[1:] if a != "--ground"])
+    sys.exit(0)
 if "--skeleton-smooth" in sys.argv:
     skeleton_smooth_bench([a for a in sys.argv[1:] if a != "--skeleton-smooth"])
     sys.exit(0)
