@@ -282,7 +282,8 @@ LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj
                  "__sync_curve", "__cal", "__cam_intr", "__cam_focal", "__cam_focal_err", "__cal_reproj", "__cal_cost", "__cal_steps", "__cal_ok", "__cal_used",
                  "__cam_quat_bundle", "__cam_trans_bundle", "__cam_err_deg_bundle", "__cam_err_m_bundle", "__ground_normal", "__ground_offset",
                  "__ground_quat", "__ground_trans", "__ground_rms", "__ground_gap", "__ground_used", "__ground_ok", "__ground_err_deg", "__ground_z",
-                 "__contact", "__foot_height", "__skate", "__skate_pairs")
+                 "__contact", "__foot_height", "__skate", "__skate_pairs", "__locked", "__lock_flags", "__lock_moved", "__lock_run", "__skate_locked",
+                 "__skate_pairs_locked")
 
 
 def _scale_and_cost(scale, cost=None, unit="metres"):
@@ -622,19 +623,47 @@ def lift_ground_options(cfg):
     return True, {k: (int(v) if k in ("radius", "iters") else float(v)) for k, v in kw.items()}
 
 
+FOOTLOCK_DEFAULTS = dict(blend=5, stretch=1.0, floor=True)      # lock_feet's own (floor: the estimated plane is handed over), untuned
+
+
+def lift_footlock_options(cfg):
+    """(lock, kwargs for ground_outputs' ``lock``) of lift.footlock / lift.footlock_blend / lift.footlock_stretch / lift.footlock_floor; ValueError for
+    a value or a combination that cannot run - before any model is built."""
+    on = cfg.lift.get("footlock", False)
+    kw = {k: cfg.lift.get("footlock_" + k, v) for k, v in FOOTLOCK_DEFAULTS.items()}
+    if not isinstance(on, bool):
+        raise ValueError(f"lift.footlock must be true or false, got {on!r}")
+    if not is_int_in(kw["blend"], 0, 32):
+        raise ValueError(f"lift.footlock_blend counts the frames of the ease into and out of a stance run, an integer in 0..32, got {kw['blend']!r}")
+    if not is_number(kw["stretch"]) or not 0 < kw["stretch"] <= 1:
+        raise ValueError(f"lift.footlock_stretch is the share of thigh + shank a leg may reach, a number in (0, 1], got {kw['stretch']!r}")
+    if not isinstance(kw["floor"], bool):
+        raise ValueError(f"lift.footlock_floor must be true or false, got {kw['floor']!r}")
+    if not on:
+        if any(kw[k] != v for k, v in FOOTLOCK_DEFAULTS.items()):
+            raise ValueError("lift.footlock_blend / lift.footlock_stretch / lift.footlock_floor describe the pinning of the feet: set lift.footlock=true")
+        return False, kw
+    if not lift_ground_options(cfg)[0]:
+        raise ValueError("lift.footlock pins the feet on the contacts of the ground estimate: set lift.ground=estimate")
+    return True, dict(blend=int(kw["blend"]), stretch=float(kw["stretch"]), floor=kw["floor"])
+
+
 GROUND_KEYS = ("normal", "offset", "quat", "trans", "rms", "gap", "used", "ok")       # of estimate_ground's record -> "<key>__ground_<k>" in lift.npz
 
 
-def ground_outputs(out, rows, keys, points, off, valid, up, kw):
+def ground_outputs(out, rows, keys, points, off, valid, up, kw, lock=None, lock_rows=None):
     """lift.ground=estimate on the absolute joint positions ``points`` (Ntot, 17, 3) of the sequences or takes ``keys`` (frames ``off``, ``valid``
     (Ntot) uint8), as they are emitted: estimate_ground's record goes into ``out`` as ``<key>__ground_normal``, ``__ground_offset``, ``__ground_quat``,
     ``__ground_trans``, ``__ground_rms``, ``__ground_gap``, ``__ground_used``, ``__ground_ok``, ``__contact`` (N, 2) uint8, ``__foot_height`` (N, 2),
     ``__skate``, ``__skate_pairs``; held against ``up`` (S, 3), the direction that is up in the frame of the points by the dataset's calibration:
     ``__ground_err_deg``, the angle between the normal and up (NaN without a plane), and ``__ground_z``, the mean of the contact points along up (the
     ankle's height if the dataset's floor is up . x = 0; NaN without a contact).  ``rows`` receives lift_ground.csv's row per key.  The poses are not
-    moved: ``__ground_quat`` and ``__ground_trans`` stand them up, to_world's convention."""
+    moved: ``__ground_quat`` and ``__ground_trans`` stand them up, to_world's convention.  ``lock`` (lift.footlock: blend, stretch, floor) or None:
+    footlock_outputs on the same points, frames and validity, with the contacts and - ``floor`` - the plane estimated here."""
     from manipose_amd import estimate_ground
     g = estimate_ground(points.contiguous(), seq_offset=off, valid=valid.contiguous(), **kw)
+    if lock is not None:
+        footlock_outputs(out, lock_rows if lock_rows is not None else [], keys, points.contiguous(), off, valid.contiguous(), g, lock)
     host = {k: getattr(g, k).cpu().numpy() for k in g._fields}
     feet = points[:, [3, 6]].cpu().numpy().astype(np.float64)
     for s, key in enumerate(keys):
@@ -651,6 +680,40 @@ def ground_outputs(out, rows, keys, points, off, valid, up, kw):
         out[key + "__ground_err_deg"], out[key + "__ground_z"] = np.float32(err), np.float32(z)
         rows.append(dict(key=key, frames=sl.stop - sl.start, contacts=int(host["used"][s]), rms_mm=1000.0 * float(host["rms"][s]), gap=float(host["gap"][s]),
                          err_deg=err, z_mm=1000.0 * z, skate_mm=1000.0 * float(host["skate"][s]), skate_pairs=int(host["skate_pairs"][s])))
+
+
+def footlock_outputs(out, rows, keys, points, off, valid, ground, kw):
+    """lift.footlock on what ground_outputs estimated the floor from: lock_feet's record goes into ``out`` as ``<key>__locked`` (N, 17, 3), the points
+    with the feet pinned, ``__lock_flags`` (N, 2) uint8, ``__lock_moved`` (N, 2), ``__lock_run`` (N, 2) int32, ``__skate_locked`` and
+    ``__skate_pairs_locked`` (the skate of ``__locked`` over the contact pairs of ``__contact``: to be read beside ``__skate``); ``rows`` receives
+    lift_footlock.csv's row per key.  Nothing that is emitted elsewhere moves."""
+    from manipose_amd import lock_feet
+    r = lock_feet(points, ground.contact, seq_offset=off, valid=valid, ground=ground if kw["floor"] else None, blend=kw["blend"], stretch=kw["stretch"])
+    host = {k: getattr(r, k).cpu().numpy() for k in r._fields}
+    before = ground.skate.cpu().numpy()
+    for s, key in enumerate(keys):
+        sl = slice(int(off[s]), int(off[s + 1]))
+        out[key + "__locked"], out[key + "__lock_flags"] = host["points"][sl], host["flags"][sl]
+        out[key + "__lock_moved"], out[key + "__lock_run"] = host["moved"][sl], host["run"][sl]
+        out[key + "__skate_locked"], out[key + "__skate_pairs_locked"] = host["skate"][s], host["skate_pairs"][s]
+        flags, moved = host["flags"][sl], host["moved"][sl].astype(np.float64)
+        reached = flags != 0
+        rows.append(dict(key=key, frames=sl.stop - sl.start, runs_r=int(host["runs"][s, 0]), runs_l=int(host["runs"][s, 1]), locked=int((flags & 1 != 0).sum()),
+                         clamped=int((flags & 4 != 0).sum()), moved_mean_mm=1000.0 * float(moved[reached].mean()) if reached.any() else 0.0,
+                         moved_max_mm=1000.0 * float(moved.max()) if moved.size else 0.0, skate_mm=1000.0 * float(before[s]),
+                         skate_locked_mm=1000.0 * float(host["skate"][s])))
+
+
+def write_lift_footlock_report(out_dir, rows):
+    """lift_footlock.csv: one row per take or sequence of lift.footlock - runs per foot (right, left), locked and reach-clamped (frame, foot)s, the mean
+    (over the feet a pin or an ease reached) and the largest distance an ankle was moved, the skate before and after"""
+    path = os.path.join(out_dir, "lift_footlock.csv")
+    cols = ("frames", "runs_r", "runs_l", "locked", "clamped", "moved_mean_mm", "moved_max_mm", "skate_mm", "skate_locked_mm")
+    with open(path, "w") as f:
+        f.write("key," + ",".join(cols) + "\n")
+        for r in rows:
+            f.write(r["key"] + "," + ",".join(str(r[c]) if isinstance(r[c], int) else f"{r[c]:.6g}" for c in cols) + "\n")
+    return path
 
 
 def write_lift_ground_report(out_dir, rows):
@@ -837,7 +900,7 @@ def estimate_cameras(name, res, seqs, cams, takes, off, hyps, kp, valid, world, 
 
 
 def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_scores=None, skel_scores=None, cal_scores=None, true_cams=None,
-               ground_rows=None):
+               ground_rows=None, footlock_rows=None):
     """lift.fuse on one group: its sequences are cut into takes (split_takes), every take's views are fused (fuse_views: one hypothesis per view,
     chosen jointly; their mean, root-relative in the world's orientation), with lift.rigid re-assembled with the mean of the views' bone tables, and
     placed with ONE world root per frame (place_views); with lift.floor the take stands on z = 0.  ``res``: the group's _Lifted with hypotheses, taken
@@ -864,7 +927,8 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     result left out).
     With lift.ground=estimate every take's floor is estimated (ground_outputs has the keys) on ``__skel`` where lift.fuse_skeleton is on (the frames
     with a result), else on the fused pose at its root (the frames fused and placed), as emitted - in the dataset's world, so the estimate is held
-    against world +z; nothing that is emitted moves.  ``ground_rows`` receives lift_ground.csv's rows."""
+    against world +z; nothing that is emitted moves.  ``ground_rows`` receives lift_ground.csv's rows; with lift.footlock the feet of the same
+    points are pinned (footlock_outputs has the keys) and ``footlock_rows`` receives lift_footlock.csv's."""
     from manipose_amd import (bundle_views, calibrate_views, camera_table, fit_skeleton_views, fuse_views, fuse_views_path, place_views, pose_rotations, project_rigid,
                               score_poses, score_traj, to_world, triangulate_views)
     from manipose_amd.lifting import SCORE_FIELDS
@@ -960,12 +1024,13 @@ def fuse_group(out, name, res, seqs, cams, cfg, targets=None, scores=None, tri_s
     scene = to_world(pose.clone(), unit, traj=root, seq_offset=off, floor=True if floor else False)
     scene, d_floor = scene if floor else (scene, None)
     ground_on, ground_kw = lift_ground_options(cfg)
+    lock_on, lock_kw = lift_footlock_options(cfg)
     if ground_on:                              # lift.ground=estimate: contacts and floor of every take, on the points as they are emitted
         points, known = (skel.pose.clone(), skel.ok & 1) if skel is not None else (pose + root[:, None], ok & placed)
         if floor:
             points[..., 2] -= d_floor.repeat_interleave(torch.as_tensor(frames, device=dev))[:, None]
         ground_outputs(out, ground_rows if ground_rows is not None else [], [f"{name}.fused{t}" for t in range(len(takes))], points, off, known,
-                       np.tile(np.array([0.0, 0.0, 1.0]), (len(takes), 1)), ground_kw)
+                       np.tile(np.array([0.0, 0.0, 1.0]), (len(takes), 1)), ground_kw, lock_kw if lock_on else None, footlock_rows)
     if targets is not None:
         gt_pose, gt_root = [], []
         for views in takes:                    # the first view's ground truth, rotated into the world
@@ -1061,7 +1126,7 @@ def synthetic_cameras(groups):
 
 
 def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None, fused_scores=None, tri_scores=None, skel_scores=None,
-                           cal_scores=None, ground_rows=None):
+                           cal_scores=None, ground_rows=None, footlock_rows=None):
     """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
     hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
     it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
@@ -1117,7 +1182,10 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     ``__ground_offset``, ``__ground_quat`` (4,), ``__ground_trans`` (3,), ``__ground_rms``, ``__ground_gap``, ``__ground_used``, ``__ground_ok``,
     ``__contact`` (N, 2) uint8, ``__foot_height`` (N, 2), ``__skate``, ``__skate_pairs``, ``__ground_err_deg`` (the angle to the dataset's up: world
     +z, under lift.frame=camera the camera's rotation's) and ``__ground_z`` are added under the take's or the sequence's key; the list ``ground_rows``
-    receives a row each for lift_ground.csv.  No emitted pose is moved: ``__ground_quat`` and ``__ground_trans`` stand the take up (to_world)."""
+    receives a row each for lift_ground.csv.  No emitted pose is moved: ``__ground_quat`` and ``__ground_trans`` stand the take up (to_world).
+    With lift.footlock (lift.footlock_blend, lift.footlock_stretch, lift.footlock_floor; lift.ground=estimate needed) the feet of the same points are
+    pinned where they stand (lock_feet): ``__locked`` (N, 17, 3), ``__lock_flags``, ``__lock_moved``, ``__lock_run`` (N, 2), ``__skate_locked`` and
+    ``__skate_pairs_locked`` are added, and the list ``footlock_rows`` receives a row each for lift_footlock.csv."""
     from manipose_amd import camera_table
     from manipose_amd.lifting import _lift_sequences
     out = {}
@@ -1131,6 +1199,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
     rot_kw = dict(rotations=True, rotations_continuous=rot_continuous, return_rotations=True) if rotations else {}
     use_cams = place or world
     ground_on, ground_kw = lift_ground_options(cfg)
+    lock_on, lock_kw = lift_footlock_options(cfg)
     fuse, want_hyps = lift_fuse_options(cfg)[0], bool(cfg.lift.hyps)       # the fusion reads the hypotheses whether or not lift.hyps writes them
     score_kw = lambda name: dict(targets=targets[name], return_score=True) if targets is not None else {}
     to_host = lambda v: {k: to_host(x) for k, x in v.items()} if isinstance(v, dict) else v.cpu().numpy()
@@ -1170,7 +1239,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
                 scores[key] = to_host(asked(res.score[i]))
         if fuse:
             fuse_group(out, name, res, seqs, cameras[name], cfg, targets[name] if targets is not None else None, fused_scores, tri_scores, skel_scores,
-                       cal_scores, true_cameras[name], ground_rows)
+                       cal_scores, true_cameras[name], ground_rows, footlock_rows)
         elif ground_on:                        # lift.ground=estimate on placed sequences: the poses at their trajectory, in the frame they are emitted in
             keys = [name if len(res.poses) == 1 else f"{name}.{i}" for i in range(len(res.poses))]
             points = torch.cat([p if world else p + res.place[i]["traj"][:, None] for i, p in enumerate(res.poses)])
@@ -1178,7 +1247,7 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
             off = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in res.poses])]).astype(np.int64)
             up = [np.array([0.0, 0.0, 1.0]) if world else _qrot(cam_rows[i][9:13] * np.array([1, -1, -1, -1]), np.array([[0.0, 0.0, 1.0]]))[0]
                   for i in range(len(res.poses))]      # world +z; in a camera's frame its rotation's up, R^T z
-            ground_outputs(out, ground_rows if ground_rows is not None else [], keys, points, off, known, up, ground_kw)
+            ground_outputs(out, ground_rows if ground_rows is not None else [], keys, points, off, known, up, ground_kw, lock_kw if lock_on else None, footlock_rows)
     np.savez(path, **out)
     return out
 
@@ -1232,6 +1301,7 @@ def run(argv, extra_defaults=None):
     lift_fuse_skeleton_options(cfg)            # ... and a lift.fuse_skeleton without lift.fuse
     lift_fuse_skeleton_smooth_options(cfg)     # ... and a lift.fuse_skeleton_smooth without lift.fuse_skeleton
     lift_ground_options(cfg)                   # ... and a lift.ground=estimate with neither lift.fuse nor lift.place
+    lift_footlock_options(cfg)                 # ... and a lift.footlock without lift.ground=estimate
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")
@@ -1405,10 +1475,13 @@ def run(argv, extra_defaults=None):
         targets, scores, fused_scores, tri_scores, skel_scores, cal_scores = None, {}, {}, {}, {}, {}
         if lift_score_options(cfg):            # the 3-D ground truth beside the 2-D sequences that are lifted
             targets = {name: sq[0] for name, sq in seqs["test"].items()} if real else synthetic_sequences_3d(cfg, cfg.run.seed)
-        ground_rows = []
-        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores, tri_scores, skel_scores, cal_scores, ground_rows)
+        ground_rows, footlock_rows = [], []
+        lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores, tri_scores, skel_scores, cal_scores, ground_rows,
+                                        footlock_rows)
         if lift_ground_options(cfg)[0]:
             print(f"lift.ground: {len(ground_rows)} floors estimated -> {write_lift_ground_report(out_dir, ground_rows)}", flush=True)
+        if lift_footlock_options(cfg)[0]:
+            print(f"lift.footlock: feet pinned in {len(footlock_rows)} takes or sequences -> {write_lift_footlock_report(out_dir, footlock_rows)}", flush=True)
         is_pose = lambda k: not k.endswith(LIFT_SUFFIXES) and ".fused" not in k
         print(f"lift: {sum(v.shape[0] for k, v in lifted.items() if is_pose(k))} frames of {len(groups)} groups -> {path}", flush=True)
         if lift_fuse_options(cfg)[0]:

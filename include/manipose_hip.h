@@ -1169,6 +1169,54 @@ int mp_lift_ground(const float* points, int64_t Ntot, int J, int C, const uint8_
                    float* offset, float* quat, float* trans, float* rms, float* gap, int32_t* used, uint8_t* ok, uint8_t* contact, float* height,
                    float* skate, int32_t* skate_pairs, void* stream);
 
+/* Pinning a take's feet where they stand: leg IK on contacts.  mp_lift_ground measures how far a foot slides while it stands and moves nothing;
+ * this removes the slide.  A foot in a stance run is pinned to ONE anchor point, the swing frames before and after a run are eased into and out of
+ * the pin, optionally the anchors are put on the estimated floor and swing feet kept above it, and each leg is re-posed by analytic two-bone IK with
+ * the frame's OWN thigh and shank lengths (a rigid sequence stays rigid); the hip and the rest of the body do not move.  The reference has no
+ * counterpart.  The layout and the conventions are mp_lift_ground's: seq_offset (S + 1) device int64 clamped to 0 .. Ntot, valid (Ntot) bytes or
+ * null, fp64 between the float32 loads and the float32 stores without contraction, no atomics, fixed orders (identical bits on every call), a
+ * sequence's result independent of the other sequences of the call, no synchronisation.  The defaults the Python layer passes (blend 5,
+ * stretch 1) are untuned.  Not measured on real data.
+ * points (Ntot, J, C) read only, C = 3 or 4, 2 <= J <= 32: absolute joint positions in any rigid frame;  contact (Ntot, nf) bytes: what
+ * mp_lift_ground wrote, or the caller's own;  legs (nf, 3) HOST int32, 1 <= nf <= MP_LIFT_GROUND_MAXFEET: (hip, knee, ankle) of every foot, the
+ * 3 nf joints all different;  normal (S, 3), offset (S), plane_ok (S) bytes: all three or none, the floor n . x = offset; sequence s HAS A FLOOR if
+ * they are given, bit 0 of plane_ok[s] is set and n and offset are finite (n is taken as a unit vector, as mp_lift_ground writes it);
+ * blend B in 0 .. MP_LIFT_FOOTLOCK_MAXBLEND frames;  0 < stretch <= 1 (a float32, used in fp64).  Frame f is GOOD if valid[f] != 0 (valid null:
+ * every frame), HELD if it lies in [f0, f1) of the last sequence s with seq_offset[s] <= f; a joint is FINITE if its three coordinates are.
+ * seq_offset MUST NOT DECREASE (the per-sequence operators' shared assumption: the clamp keeps every access inside the Ntot frames whatever the table
+ * holds, but sequences that overlap would have two waves write the same frames, and which sequence holds a frame would be undefined).
+ * |v| = sqrt((vx^2 + vy^2) + vz^2), a . b = (ax bx + ay by) + az bz, h / k / a = hip / knee / ankle of leg k in the input.
+ * A. Frame f, foot k is LOCKABLE if f is held and good, contact[f][k] != 0 and h, k, a are finite in f.  A RUN is a maximal stretch of consecutive
+ *    lockable frames of one foot inside one sequence.  run[f][k] = the run's length inside it, 0 elsewhere; runs[s][k] = the foot's runs in s.
+ * B. The run's ANCHOR = (sum of a over its frames) / length in fp64 (the sum's order is the kernel's: a tree inside every 64 frames counted from
+ *    f0, the blocks in order); with a floor then A - ((n . A) - offset) n; then ROUNDED TO float32, once: the float32 is the anchor everywhere below.
+ * C. The target t of every held, good (f, k) with h, k, a finite.  In a run: t = the anchor (flags bit 0).  Else t = a, and with fa the last frame
+ *    of the nearest run before f and fb the first frame of the nearest run after f in the sequence (either may be missing), L = min(B + 1, fb - fa)
+ *    if both exist, else B + 1:  w_prev = 1 - (f - fa) / L,  w_next = 1 - (fb - f) / L,  s(w) = (w w)(3 - 2 w);  where w_prev > 0:
+ *    t = t + s(w_prev) (anchor(fa) - a[fa]);  then where w_next > 0:  t = t + s(w_next) (anchor(fb) - a[fb]);  bit 1 if either weight is > 0.
+ *    (A run further than B frames away carries no weight, so B frames each way are searched.)  With a floor, outside runs: hh = (n . t) - offset;
+ *    if hh < 0:  t = t - hh n  (bit 3).
+ * D. Leg IK.  l1 = |k - h|, l2 = |a - k|, d = t - h, D = |d|.  l1, l2 or D below 1e-12: flags = 32 ALONE, target and moved 0, the leg keeps its
+ *    bits.  Dmin = |l1 - l2|, Dmax = max(stretch (l1 + l2), Dmin), u = d / D.  D > Dmax: D' = Dmax, else D < Dmin: D' = Dmin, either way
+ *    t' = h + u D' (bit 2); else D' = D, t' = t.  WHERE t' == a IN ALL THREE COORDINATES THE LEG KEEPS ITS BITS (moved 0, target a): a foot that
+ *    is where it belongs is not re-posed, and without contacts out is points bit for bit.  Else the pole b = (k - h) - ((k - h) . u) u; if
+ *    |b| < 1e-9 l1:  b = e - u_i u, e the unit axis i of u's smallest |component|, the first on a tie (bit 4).  x = ((D'^2 + l1^2) - l2^2) / (2 D'),
+ *    y = sqrt(max(0, l1^2 - x^2)),  knee' = (h + x u) + y (b / |b|),  ankle' = t' as it is stored (not h + D' u recomputed: without a reach clamp
+ *    every frame of a run carries the same ankle bits).  target = t';  moved = |ankle' - a| of the stored float32 ankle'.
+ * E. out: every float of points, channel 3 included; only the knee and ankle of the legs D re-posed differ.  A frame that is not held or not
+ *    good, and a foot with a leg joint that is not finite, keep their bits, with target, moved and flags 0 (run 0 too for a frame not held).
+ * One copy and three launches: one WAVE per (sequence, foot) walks the frames in blocks of 64 - the lockable bits' ballot gives the run borders, a
+ * segmented scan and a carry in uniform registers the sums; forward it leaves length and anchor at each run's last frame, backward it spreads
+ * them over the run (run, target); then one lane per (frame, foot), first the frames outside runs (they read anchors of run frames, write their
+ * own), then the frames inside (they read and write their own): no lane reads what another writes.  No scratch memory.
+ * MP_ERR_ARG before anything is launched: J, C, Ntot or S out of range (S > Ntot, Ntot nf > 2^31 - 1); points, contact, seq_offset, legs or an
+ * output null; out == points; nf out of range; a leg joint outside 0 .. J - 1 or named twice (in a leg or by two legs: two lanes would write it);
+ * blend out of range; stretch not in (0, 1]; normal, offset, plane_ok neither all given nor all null. */
+#define MP_LIFT_FOOTLOCK_MAXBLEND 32
+int mp_lift_footlock(const float* points, int64_t Ntot, int J, int C, const uint8_t* valid, const int64_t* seq_offset, int S, const uint8_t* contact,
+                     const int32_t* legs, int nf, const float* normal, const float* offset, const uint8_t* plane_ok, int blend, float stretch,
+                     float* out, int32_t* run, float* target, float* moved, uint8_t* flags, int32_t* runs, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

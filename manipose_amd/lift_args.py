@@ -191,6 +191,44 @@ def ground_options(radius, speed, sigma, prior, iters, foot_height, maxradius, m
         raise ValueError(f"foot_height must be a finite number, got {foot_height!r}")
 
 
+def leg_joints(legs, J, maxfeet):
+    """legs: 1..maxfeet triples (hip, knee, ankle) of integers in 0..J-1, no joint named twice -> a tuple of tuples of int"""
+    try:
+        legs = tuple(tuple(leg) for leg in legs)
+    except TypeError:
+        raise ValueError(f"legs is a sequence of (hip, knee, ankle) joint indices, got {legs!r}") from None
+    if not 1 <= len(legs) <= maxfeet or not all(len(leg) == 3 and all(is_int_in(j, 0, J - 1) for j in leg) for leg in legs):
+        raise ValueError(f"legs must be 1..{maxfeet} triples (hip, knee, ankle) of joint indices in 0..{J - 1}, got {legs!r}")
+    named = [int(j) for leg in legs for j in leg]
+    if len(set(named)) != len(named):
+        raise ValueError(f"legs name a joint twice: a leg is three different joints, and no two legs share one, got {legs!r}")
+    return tuple(tuple(int(j) for j in leg) for leg in legs)
+
+
+def footlock_options(blend, stretch, maxblend):
+    """the scalars of lock_feet as the kernel takes them: blend an integer in 0..maxblend frames, stretch a float32 in (0, 1]"""
+    if not is_int_in(blend, 0, maxblend):
+        raise ValueError(f"blend counts the frames of the ease into and out of a stance run, an integer in 0..{maxblend}, got {blend!r}")
+    if not is_number(stretch) or not 0 < float(np.float32(stretch)) <= 1:
+        raise ValueError(f"stretch is the share of thigh + shank a leg may reach, a number in (0, 1], got {stretch!r}")
+
+
+def floor_record(ground, S):
+    """ground is None or carries ``normal`` (S, 3) float32, ``offset`` (S) float32 and ``ok`` (S) uint8 tensors (a ``Ground``) -> those three or None"""
+    if ground is None:
+        return None
+    try:
+        normal, offset, ok = ground.normal, ground.offset, ground.ok
+    except AttributeError:
+        raise ValueError(f"ground must be None or a Ground record (normal, offset, ok), got {type(ground).__name__}") from None
+    f32(normal, (S, 3), "ground.normal")
+    f32(offset, (S,), "ground.offset")
+    if ok is None:
+        raise ValueError(f"ground.ok must be a uint8 tensor of shape {(S,)}, got None")
+    mask(ok, (S,), "ground.ok")
+    return normal, offset, ok
+
+
 def take_count(take_offset):
     """the G of a (G + 1) table of first frames, host or device, read from its size alone (None: one take)"""
     if take_offset is None:

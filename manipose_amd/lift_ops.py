@@ -53,6 +53,11 @@ Standing a sequence on its floor (``estimate_ground``, off everywhere by default
 plane through them - robustly, the body's mean axis a weak prior - gives the rotation and shift ``to_world`` applies, each foot's height over the plane and
 the foot skate, how far the feet slide while in contact (include/manipose_hip.h has the rule).  It reads ABSOLUTE positions (poses plus trajectory) in any
 rigid frame and moves nothing.  The defaults are untuned and nothing has been measured on real data (no dataset here).
+
+Pinning the feet (``lock_feet``, off everywhere by default): ``mp_lift_footlock`` removes the slide the ground estimate measures.  A foot in a stance run
+is pinned to the mean of its ankle positions (on the estimated floor where a ``Ground`` is handed over), the swing frames around a run are eased into
+and out of the pin, and each leg is re-posed by analytic two-bone IK with the frame's own bone lengths; hips and the rest of the body keep their bits
+(include/manipose_hip.h has the rule).  The defaults are untuned and nothing has been measured on real data (no dataset here).
 """
 from __future__ import annotations
 
@@ -483,6 +488,100 @@ def estimate_ground(points, seq_offset=None, valid=None, feet=(3, 6), axis=(0, 8
     d_off, S = _seq_table(seq_offset, ntot, points.device)
     return _ground(_lib.load(), points, None if valid is None else valid.contiguous(), d_off, S, feet, axis, radius, speed, sigma, prior, iters,
                    foot_height)
+
+
+FOOTLOCK_MAXBLEND = 32       # MP_LIFT_FOOTLOCK_MAXBLEND of include/manipose_hip.h
+H36M_LEGS = ((1, 2, 3), (4, 5, 6))      # (hip, knee, ankle) of the right and the left leg of the 17-joint H36M tree
+# What lock_feet returns, device tensors: points (Ntot, J, C) float32; per frame and foot run (Ntot, nf) int32, target (Ntot, nf, 3), moved (Ntot, nf)
+# float32, flags (Ntot, nf) uint8; per sequence runs (S, nf) int32, skate (S) float32, skate_pairs (S) int32
+FootLock = namedtuple("FootLock", "points run target moved flags runs skate skate_pairs")
+
+
+def _footlock(lib, points, contact, valid, d_off, S, legs, floor, blend, stretch):
+    """``mp_lift_footlock`` on points (Ntot, J, C), contact (Ntot, nf) uint8, valid (Ntot) uint8 or None, floor (normal, offset, ok) or None: (out, run,
+    target, moved, flags, runs), new tensors"""
+    ntot, J, ch = (int(v) for v in points.shape)
+    dev, nf = points.device, len(legs)
+    res = (torch.empty_like(points), torch.empty(ntot, nf, dtype=torch.int32, device=dev), torch.empty(ntot, nf, 3, dtype=torch.float32, device=dev),
+           torch.empty(ntot, nf, dtype=torch.float32, device=dev), torch.empty(ntot, nf, dtype=torch.uint8, device=dev),
+           torch.empty(S, nf, dtype=torch.int32, device=dev))
+    normal, offset, ok = floor if floor is not None else (None, None, None)
+    _launch(dev, "mp_lift_footlock", _lib.ptr(points), ntot, J, ch, _lib.ptr(valid), _lib.ptr(d_off), S, _lib.ptr(contact),
+            (C.c_int32 * (3 * nf))(*(j for leg in legs for j in leg)), nf, _lib.ptr(normal), _lib.ptr(offset), _lib.ptr(ok), int(blend), float(stretch),
+            *(_lib.ptr(t) for t in res))
+    return res
+
+
+def _skate(points, contact, valid, d_off, S, ankles, floor):
+    """The foot skate of ``points`` over the contact pairs of ``contact``, as mp_lift_ground reports it, with plain torch on the device: per sequence the
+    mean over the pairs (contact[f][k] and contact[f + 1][k], both frames in the sequence, valid and the ankle finite: what mp_lift_ground's own
+    contacts always are) of the ankle's step, its part in the plane where the sequence has one, in fp64 -> (skate (S) float32, 0 without a pair,
+    skate_pairs (S) int32).  Every sequence is summed on its own, in frame order (``torch.segment_reduce`` over the sequences' frames): no atomics,
+    nothing is read back to the host."""
+    ntot, dev = int(points.shape[0]), points.device
+    bounds = torch.cummax(d_off.clamp(0, ntot), dim=0)[0]                # (first frames that do not decrease: every frame in one segment at most)
+    frame = torch.arange(ntot, device=dev)
+    seq = (torch.searchsorted(bounds, frame, right=True) - 1).clamp(0, S - 1)
+    held = (frame >= bounds[seq]) & (frame < bounds[seq + 1])
+    a = points[:, list(ankles), :3].double()
+    good = held if valid is None else held & (valid != 0)
+    touch = (contact != 0) & good[:, None] & torch.isfinite(a).all(dim=2)
+    pair = (seq[:-1] == seq[1:])[:, None] & touch[:-1] & touch[1:]
+    d = a[1:] - a[:-1]                                                   # (Ntot - 1, nf, 3)
+    if floor is not None:
+        n = floor[0].double()[seq[:-1]]                                  # (Ntot - 1, 3)
+        has = ((floor[2][seq[:-1]] & 1) != 0) & torch.isfinite(n).all(dim=1) & torch.isfinite(floor[1][seq[:-1]])
+        n = torch.where(has[:, None], n, torch.zeros_like(n))[:, None]   # (without a plane the whole step)
+        d = d - (d * n).sum(dim=2, keepdim=True) * n
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    per_frame = torch.zeros(ntot, 2, dtype=torch.float64, device=dev)    # a pair belongs to its first frame: (the feet's steps, their number)
+    per_frame[:-1, 0] = torch.where(pair, d.norm(dim=2), zero).sum(dim=1)
+    per_frame[:-1, 1] = pair.sum(dim=1).double()
+    sums = torch.segment_reduce(per_frame, "sum", offsets=bounds, axis=0, unsafe=True)      # (S, 2); a count in fp64 is exact
+    skate = torch.where(sums[:, 1] > 0, sums[:, 0] / sums[:, 1].clamp(min=1.0), zero)
+    return skate.float(), sums[:, 1].int()
+
+
+def lock_feet(points, contact, seq_offset=None, valid=None, legs=H36M_LEGS, ground=None, blend=5, stretch=1.0):
+    """``mp_lift_footlock`` on device tensors: the feet pinned where they stand, by leg IK on the contacts.  ``points`` (Ntot, J, 3 | 4) float32: ABSOLUTE
+    joint positions in any rigid frame (channel 3 is copied); ``contact`` (Ntot, nf) uint8: ``estimate_ground(...).contact``, or the caller's own;
+    ``seq_offset`` (S + 1): first frame of every sequence, HOST table or device int64 tensor (default: one sequence); ``valid`` uint8 (Ntot) or None;
+    ``legs``: 1..4 triples (hip, knee, ankle), no joint named twice (default the H36M legs, their ankles ``estimate_ground``'s default feet).
+    A RUN is a maximal stretch of consecutive frames of one sequence in which a foot is in contact (the frame valid, the leg finite).  The foot is
+    pinned to the run's anchor, the mean of its ankle positions; the frames within ``blend`` (0..32) frames of a run are eased into and out of the
+    pin by a smoothstep, and between two runs closer than that the correction passes from one pin to the next.  ``ground``: a ``Ground`` of the same
+    sequences or None; only its ``normal``, ``offset`` and ``ok`` are read: where a sequence has a plane the anchors are put on it and a swing foot
+    below it is lifted onto it.  Every leg is then re-posed by analytic two-bone IK with the frame's own thigh and shank lengths, the knee on the side
+    it was on; ``stretch`` in (0, 1] is the share of thigh + shank the leg may reach.  The hip and every other joint keep their bits, and so does a
+    leg whose foot is already where it belongs.  include/manipose_hip.h has the rule.  Returns a ``FootLock`` of new device tensors: ``points``
+    (Ntot, J, C); ``run`` (Ntot, nf) int32 the length of the run a frame lies in, else 0; ``target`` (Ntot, nf, 3) where the ankle was sent;
+    ``moved`` (Ntot, nf) how far it went; ``flags`` (Ntot, nf) uint8: 1 pinned, 2 eased, 4 reach clamped, 8 lifted onto the floor, 16 straight leg (the
+    knee's side comes from an axis), 32 a leg without length, left alone; ``runs`` (S, nf) int32 runs per foot; ``skate`` (S) float32 and
+    ``skate_pairs`` (S) int32: the foot skate of the RETURNED points over the contact pairs of ``contact`` - the mean step of an ankle between two
+    consecutive valid frames in contact with the ankle finite, its part in the plane where ``ground`` has one - comparable with ``Ground.skate`` of the
+    input.  The inputs are not modified and nothing is read back to the host; fp64 inside, identical bits on every call.  The defaults are untuned,
+    and nothing here has been measured on real data."""
+    lift_args.footlock_options(blend, stretch, FOOTLOCK_MAXBLEND)
+    ntot, J = lift_args.points3(points)                  # (the ValueErrors come before the refusal of a CPU tensor)
+    legs = lift_args.leg_joints(legs, J, GROUND_MAXFEET)
+    if contact is None:
+        raise ValueError(f"contact must be a uint8 tensor of shape {(ntot, len(legs))}, got None")
+    lift_args.mask(contact, (ntot, len(legs)), "contact")
+    lift_args.mask(valid, (ntot,), "valid")
+    if ntot < 1:
+        raise ValueError("points hold no frame")
+    shape = None if seq_offset is None else tuple(seq_offset.shape if torch.is_tensor(seq_offset) else np.shape(seq_offset))
+    if shape is not None and (len(shape) != 1 or shape[0] < 2 or shape[0] - 1 > ntot):
+        raise ValueError(f"seq_offset must hold S + 1 >= 2 frame numbers, S <= {ntot} frames, got shape {shape}")
+    floor = lift_args.floor_record(ground, 1 if shape is None else shape[0] - 1)
+    lift_args.need_device("lock_feet", points, contact, optional=(valid,) + (floor or ()))
+    d_off, S = _seq_table(seq_offset, ntot, points.device)
+    contact = contact.contiguous()
+    floor = None if floor is None else tuple(t.contiguous() for t in floor)
+    out, run, target, moved, flags, runs = _footlock(_lib.load(), points, contact, None if valid is None else valid.contiguous(), d_off, S, legs, floor,
+                                                     blend, stretch)
+    skate, pairs = _skate(out, contact, valid, d_off, S, [leg[2] for leg in legs], floor)
+    return FootLock(out, run, target, moved, flags, runs, skate, pairs)
 
 
 REFINE_MAXITERS = 16         # MP_LIFT_REFINE_MAXITERS of include/manipose_hip.h: Gauss-Newton steps mp_lift_place_refine takes at most

@@ -18,6 +18,11 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --skeleton [frames=3000] [reps=20]
     python tools/lift_bench.py --skeleton-smooth [frames=3000] [reps=20]
     python tools/lift_bench.py --ground [frames=3000] [reps=20]
+    python tools/lift_bench.py --footlock [frames=3000] [reps=20]
+--footlock times mp_lift_footlock (the feet pinned on their contacts: a copy, the run kernel with one wave per (sequence, foot), the pose kernel
+with one lane per (frame, foot) twice) through its private launcher on --ground's walkers, contacts and planes, as ONE take of `frames` frames and
+as 64 sequences of `frames` / 10, at blend 0, 5 and 32, with and without the floor; beside each time the bytes the copy and the kernels must move
+and the bandwidth that implies (the operator has no predecessor: there is no time to hold it against).
 --ground times mp_lift_ground (contacts, ground plane and foot skate of a sequence: a contact kernel with one lane per (frame, foot) and a plane
 kernel with one 256-lane workgroup per sequence, 2 (iters + 1) + 1 passes inside it) through its private launcher on synthetic walkers on a tilted
 floor with 5 mm of noise, as ONE take of `frames` frames and as 64 sequences of `frames` / 10, at iters 0, 5 and 8, and prints how far the
@@ -615,38 +620,43 @@ def skeleton_smooth_bench(argv):
               f"stage A and one sweep together {alone[1]:,.1f} us", flush=True)
 
 
+def ground_walker(n, seed):
+    """a walker on a tilted floor: a 40-frame step cycle, 60 % stance, 5 mm of noise, 17 joints"""
+    g = np.random.default_rng(seed)
+    f = np.arange(n)
+    pts = np.zeros((n, 17, 3))
+    for k, j in enumerate((3, 6)):
+        c, t = np.divmod(f + 20 * k, 40)
+        u = np.clip((t - 23) / 17.0, 0.0, 1.0)
+        e = 0.5 - 0.5 * np.cos(np.pi * u)
+        pts[:, j] = np.stack([0.6 * (c + e) + 0.3 * k, np.full(n, 0.2 * k - 0.1) + 0.5 * np.sin(0.4 * (c + e)), 0.12 * np.sin(np.pi * u)], axis=1)
+    centre = 0.5 * (pts[:, 3] + pts[:, 6]) * [1, 1, 0]
+    pts[:, [0, 1, 2, 4, 5, 7, 9, 10, 11, 12, 13, 14, 15, 16]] = (centre + [0, 0, 0.9])[:, None] + 0.25 * g.standard_normal((14, 3))
+    pts[:, 0], pts[:, 8] = centre + [0, 0, 0.9], centre + [0, 0, 1.4]
+    pts += 0.005 * g.standard_normal(pts.shape)
+    a, b = 0.4, -0.3                                                   # a tilt of the floor: about x, then about y
+    R = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]]) @ np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
+    return (pts @ R.T + [1.0, -2.0, 3.0]).astype(np.float32), R[:, 2]
+
+
+def ground_scenes(lib, S, n):
+    """S walkers of n frames laid end to end and mp_lift_ground on them at the defaults: (the walkers, points, seq_offset, a launcher by iters)"""
+    from manipose_amd.lift_ops import _ground
+    scenes = [ground_walker(n, 100 * S + s) for s in range(S)]
+    pts = torch.from_numpy(np.concatenate([p for p, _ in scenes])).cuda()
+    off = torch.tensor([n * s for s in range(S + 1)], dtype=torch.int64, device="cuda")
+    return scenes, pts, off, lambda iters=5: _ground(lib, pts, None, off, S, (3, 6), (0, 8), 2, 0.01, 0.03, 0.05, iters, 0.0)
+
+
 def ground_bench(argv):
     from manipose_amd import _lib
-    from manipose_amd.lift_ops import _ground
     frames = int(argv[0]) if len(argv) > 0 else 3000
     reps = int(argv[1]) if len(argv) > 1 else 20
     lib = _lib.load()
-
-    def walker(n, seed):
-        """a walker on a tilted floor: a 40-frame step cycle, 60 % stance, 5 mm of noise, 17 joints"""
-        g = np.random.default_rng(seed)
-        f = np.arange(n)
-        pts = np.zeros((n, 17, 3))
-        for k, j in enumerate((3, 6)):
-            c, t = np.divmod(f + 20 * k, 40)
-            u = np.clip((t - 23) / 17.0, 0.0, 1.0)
-            e = 0.5 - 0.5 * np.cos(np.pi * u)
-            pts[:, j] = np.stack([0.6 * (c + e) + 0.3 * k, np.full(n, 0.2 * k - 0.1) + 0.5 * np.sin(0.4 * (c + e)), 0.12 * np.sin(np.pi * u)], axis=1)
-        centre = 0.5 * (pts[:, 3] + pts[:, 6]) * [1, 1, 0]
-        pts[:, [0, 1, 2, 4, 5, 7, 9, 10, 11, 12, 13, 14, 15, 16]] = (centre + [0, 0, 0.9])[:, None] + 0.25 * g.standard_normal((14, 3))
-        pts[:, 0], pts[:, 8] = centre + [0, 0, 0.9], centre + [0, 0, 1.4]
-        pts += 0.005 * g.standard_normal(pts.shape)
-        a, b = 0.4, -0.3                                                   # a tilt of the floor: about x, then about y
-        R = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]]) @ np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
-        return (pts @ R.T + [1.0, -2.0, 3.0]).astype(np.float32), R[:, 2]
-
     print(f"--ground: walkers of 17 joints on a tilted floor, 5 mm of noise, the defaults (radius 2, speed 0.01, sigma 0.03, prior 0.05, iters 5: 13 passes); "
           f"{reps} calls each after 5 of warm-up (the output allocations are inside the time)", flush=True)
     for S, n in ((1, frames), (64, max(frames // 10, 1))):
-        scenes = [walker(n, 100 * S + s) for s in range(S)]
-        pts = torch.from_numpy(np.concatenate([p for p, _ in scenes])).cuda()
-        off = torch.tensor([n * s for s in range(S + 1)], dtype=torch.int64, device="cuda")
-        run = lambda iters=5: _ground(lib, pts, None, off, S, (3, 6), (0, 8), 2, 0.01, 0.03, 0.05, iters, 0.0)
+        scenes, pts, off, run = ground_scenes(lib, S, n)
         got = run()
         torch.cuda.synchronize()
         cos = np.clip((got.normal.double().cpu().numpy() * np.stack([u for _, u in scenes])).sum(axis=1), -1, 1)
@@ -657,6 +667,40 @@ def ground_bench(argv):
             print(f"mp_lift_ground, {S} sequence(s) of {n} frames, iters={iters}: {us:,.1f} us  (contact kernel + {2 * (iters + 1) + 1} passes of the plane kernel)", flush=True)
 
 
+def footlock_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.lift_ops import _footlock
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib = _lib.load()
+    print(f"--footlock: --ground's walkers of 17 joints, their contacts and planes under the ground defaults, legs (1, 2, 3) and (4, 5, 6), stretch 1; "
+          f"{reps} calls each after 5 of warm-up (the output allocations are inside the time)", flush=True)
+    for S, n in ((1, frames), (64, max(frames // 10, 1))):
+        _, pts, off, run = ground_scenes(lib, S, n)
+        got = run()
+        torch.cuda.synchronize()
+        legs, floor = ((1, 2, 3), (4, 5, 6)), (got.normal, got.offset, got.ok)
+        lock = lambda blend=5, fl=floor: _footlock(lib, pts, got.contact, None, off, S, legs, fl, blend, 1.0)
+        out, runlen, target, moved, flags, runs = lock()
+        torch.cuda.synchronize()
+        n_lock = int((flags & 1 != 0).sum())
+        # what must move, per frame: the copy reads and writes J C floats; per (frame, foot) the run kernel reads contact (1 byte) and writes run (4)
+        # twice over, and where the foot is lockable reads three joints (36) and reads and writes the anchor (12 + 12); the pose kernel reads
+        # run (4, in both launches), three joints (36) and, in a run, the anchor (12), and writes target, moved, flags (17) and two joints (24)
+        nf, total = 2, S * n
+        nbytes = total * 2 * 17 * 3 * 4 + total * nf * (1 + 4 + 4 + 4) + n_lock * (36 + 24) + total * nf * (8 + 36 + 17 + 24) + n_lock * 12
+        print(f"{S} sequence(s) of {n} frames: {int(runs.sum())} runs, {n_lock} of {total * nf} (frame, foot)s pinned, {int((flags & 2 != 0).sum())} eased, "
+              f"{int((flags & 4 != 0).sum())} reach clamped, {int((flags & 8 != 0).sum())} lifted onto the floor; the longest run {int(runlen.max())} frames, "
+              f"an ankle moved by {1e3 * float(moved.max()):.1f} mm at most; {nbytes / 1e6:.2f} MB must move", flush=True)
+        for blend, fl, word in ((0, floor, "floor"), (5, floor, "floor"), (32, floor, "floor"), (5, None, "no floor")):
+            us = timed_us(lambda: lock(blend, fl), reps)
+            print(f"mp_lift_footlock, {S} sequence(s) of {n} frames, blend={blend}, {word}: {us:,.1f} us  (a copy and three launches; {nbytes / 1e6:.2f} MB: "
+                  f"{nbytes / us / 1e3:,.1f} GB/s)", flush=True)
+
+
+if "--footlock" in sys.argv:
+    footlock_bench([a for a in sys.argv[1:] if a != "--footlock"])
+    sys.exit(0)
 if "--ground" in sys.argv:
     ground_bench([a for a in sys.argv[1:] if a != "--ground"])
     sys.exit(0)
