@@ -283,7 +283,7 @@ LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj
                  "__cam_quat_bundle", "__cam_trans_bundle", "__cam_err_deg_bundle", "__cam_err_m_bundle", "__ground_normal", "__ground_offset",
                  "__ground_quat", "__ground_trans", "__ground_rms", "__ground_gap", "__ground_used", "__ground_ok", "__ground_err_deg", "__ground_z",
                  "__contact", "__foot_height", "__skate", "__skate_pairs", "__locked", "__lock_flags", "__lock_moved", "__lock_run", "__skate_locked",
-                 "__skate_pairs_locked")
+                 "__skate_pairs_locked", "__rt", "__rt_quat", "__rt_root", "__rt_ok", "__rt_taps", "__rt_time", "__rt_fps")
 
 
 def _scale_and_cost(scale, cost=None, unit="metres"):
@@ -646,6 +646,84 @@ def lift_footlock_options(cfg):
     if not lift_ground_options(cfg)[0]:
         raise ValueError("lift.footlock pins the feet on the contacts of the ground estimate: set lift.ground=estimate")
     return True, dict(blend=int(kw["blend"]), stretch=float(kw["stretch"]), floor=kw["floor"])
+
+
+RETIME_DEFAULTS = dict(from_fps=0, radius=0, degree=2, taper="uniform")      # retime_rotations' own; from_fps 0: the dataset's frame rate
+DATASET_FPS = {"h36m": 50}                  # Human36mDataset.fps; the synthetic sequences are H36M-shaped
+
+
+def lift_retime_options(cfg):
+    """(retime, kwargs for retime_outputs) of lift.retime_fps / lift.retime_from_fps / lift.retime_radius / lift.retime_degree / lift.retime_taper;
+    ValueError for a value or a combination that cannot run - before any model is built.  The retimed take is emitted on ONE bone table, so the
+    stage needs lift.rotations (what it reads) and lift.rigid (with per-frame lengths there is nothing constant to keep)."""
+    fps = cfg.lift.get("retime_fps", 0)
+    kw = {k: cfg.lift.get("retime_" + k, v) for k, v in RETIME_DEFAULTS.items()}
+    if not is_int_in(fps, 0, 1 << 20):
+        raise ValueError(f"lift.retime_fps is the output frame rate, a positive integer (0: off), got {fps!r}")
+    if not is_int_in(kw["from_fps"], 0, 1 << 20):
+        raise ValueError(f"lift.retime_from_fps is the input frame rate, a positive integer (0: the dataset's), got {kw['from_fps']!r}")
+    if not is_int_in(kw["radius"], 0, 64):
+        raise ValueError(f"lift.retime_radius must be an integer in 0..64 (0: interpolation), got {kw['radius']!r}")
+    if not is_int_in(kw["degree"], 0, 2):
+        raise ValueError(f"lift.retime_degree must be 0, 1 or 2, got {kw['degree']!r}")
+    if kw["taper"] not in ("uniform", "biweight"):
+        raise ValueError(f"lift.retime_taper must be uniform or biweight, got {kw['taper']!r}")
+    if fps == 0:
+        if any(kw[k] != v for k, v in RETIME_DEFAULTS.items()):
+            raise ValueError("lift.retime_from_fps / lift.retime_radius / lift.retime_degree / lift.retime_taper describe the retiming: set lift.retime_fps")
+        return False, kw
+    if not bool(cfg.run.lift):
+        raise ValueError("lift.retime_fps retimes what run.lift lifts: set run.lift=true")
+    if not lift_rotations_options(cfg)[0]:
+        raise ValueError("lift.retime_fps resamples the joint rotations: set lift.rotations=true")
+    if not bool(cfg.lift.get("rigid", False)):
+        raise ValueError("lift.retime_fps emits the retimed take on one bone table: set lift.rigid=true (with per-frame lengths there is nothing constant to keep)")
+    fps_in = int(kw["from_fps"]) or DATASET_FPS.get(str(cfg.data.dataset), 0)
+    if fps_in == 0:
+        raise ValueError(f"lift.retime_fps: the frame rate of data.dataset={cfg.data.dataset} is not known here: set lift.retime_from_fps")
+    return True, dict(fps_in=fps_in, fps_out=int(fps), radius=int(kw["radius"]), degree=int(kw["degree"]), taper=kw["taper"])
+
+
+def retime_outputs(out, kw, world, targets=None, scores=None):
+    """lift.retime_fps, LAST, on what ``out`` holds as it is emitted.  Per sequence ``<key>`` with ``__quat`` and ``__bones``: (root, ``__quat``,
+    ``__bones``) with validity ``__quat_ok``, the root being ``__traj`` (validity also its ``__filled``, else its ``__ok``) with lift.place in the
+    camera's frame, the poses' own joint 0 with lift.frame=world, else the origin; per fused take ``<key>`` with ``__skel_quat`` and ``__skel_bones``:
+    (``__skel[:, 0]``, ``__skel_quat``, ``__skel_bones``) with validity ``__skel_quat_ok`` & ``__skel_ok``.  retime_rotations then pose_from_rotations
+    add ``<key>__rt`` (M, 17, 3), the positions in the frame of the poses they come from, ``__rt_quat`` (M, 17, 4), ``__rt_root`` (M, 3) where there is
+    a root, ``__rt_ok``, ``__rt_taps`` (M,) uint8, ``__rt_time`` (M,) float64 in input frames and ``__rt_fps`` (2,) int32 (in, out).  ``__locked``, the
+    hypotheses and the per-view poses are not retimed.  ``targets`` ({sequence key: (N, 17, 3)}) with equal rates: score_poses' record of ``__rt`` goes
+    to ``scores`` (ground truth exists at input frames only: a take retimed to another rate is not scored)."""
+    from manipose_amd import pose_from_rotations, retime_rotations, score_poses
+    from manipose_amd.lifting import SCORE_FIELDS
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    jobs = []
+    for k in list(out):
+        if k.endswith("__skel_quat") and k[:-len("__skel_quat")] + "__skel_bones" in out:
+            key = k[:-len("__skel_quat")]
+            jobs.append((key, out[k], out[key + "__skel_bones"], out[key + "__skel"][:, 0], (out[key + "__skel_quat_ok"] != 0) & (out[key + "__skel_ok"] != 0)))
+        elif k.endswith("__quat") and k[:-len("__quat")] + "__bones" in out and k[:-len("__quat")] in out:
+            key = k[:-len("__quat")]
+            valid, root = out[key + "__quat_ok"] != 0, None
+            if world:
+                root = out[key][:, 0]
+            elif key + "__traj" in out:
+                root = out[key + "__traj"]
+                valid = valid & (out[key + ("__filled" if key + "__filled" in out else "__ok")] != 0)
+            jobs.append((key, out[k], out[key + "__bones"], root, valid))
+    for key, quat, bones, root, valid in jobs:
+        r = retime_rotations(up(quat), None if root is None else up(root), up(valid.astype(np.uint8)), None, kw["fps_in"], kw["fps_out"], 0.0, kw["radius"],
+                             kw["degree"], kw["taper"])
+        poses = pose_from_rotations(r.quat, bones, r.root, r.seq_offset)[0]
+        out[key + "__rt"], out[key + "__rt_quat"], out[key + "__rt_ok"] = poses.cpu().numpy(), r.quat.cpu().numpy(), r.ok.cpu().numpy()
+        out[key + "__rt_taps"], out[key + "__rt_time"] = r.taps.cpu().numpy(), r.time.cpu().numpy()
+        out[key + "__rt_fps"] = np.array([kw["fps_in"], kw["fps_out"]], dtype=np.int32)
+        if r.root is not None:
+            out[key + "__rt_root"] = r.root.cpu().numpy()
+        if targets is not None and scores is not None and key in targets and kw["fps_in"] == kw["fps_out"]:
+            rec = score_poses(poses, up(np.asarray(targets[key], dtype=np.float32)), None, (r.ok & 1).contiguous(), root_relative=True)
+            scores[key] = {f: getattr(rec, f).cpu().numpy() for f in SCORE_FIELDS}
+    return len(jobs)
 
 
 GROUND_KEYS = ("normal", "offset", "quat", "trans", "rms", "gap", "used", "ok")       # of estimate_ground's record -> "<key>__ground_<k>" in lift.npz
@@ -1126,7 +1204,7 @@ def synthetic_cameras(groups):
 
 
 def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None, scores=None, fused_scores=None, tri_scores=None, skel_scores=None,
-                           cal_scores=None, ground_rows=None, footlock_rows=None):
+                           cal_scores=None, ground_rows=None, footlock_rows=None, rt_scores=None):
     """run.lift: one 3-D pose per frame of every sequence of ``groups`` = {name: [poses_2d (N, 17, 2), ...]} (the reference's lift_action,
     hpe/eval_utils.py:226-253, on whole sequences: manipose_amd/lifting.py), written as ONE .npz: key = the group's name (``name.i`` when
     it holds several sequences) -> (N, 17, 3) in metres; with lift.hyps also ``<key>__hyps`` -> (N, K, 17, 4); with lift.rigid (constant bone
@@ -1248,6 +1326,12 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
             up = [np.array([0.0, 0.0, 1.0]) if world else _qrot(cam_rows[i][9:13] * np.array([1, -1, -1, -1]), np.array([[0.0, 0.0, 1.0]]))[0]
                   for i in range(len(res.poses))]      # world +z; in a camera's frame its rotation's up, R^T z
             ground_outputs(out, ground_rows if ground_rows is not None else [], keys, points, off, known, up, ground_kw, lock_kw if lock_on else None, footlock_rows)
+    retime_on, retime_kw = lift_retime_options(cfg)
+    if retime_on:                              # lift.retime_fps: last, on what is emitted (retime_outputs has the keys)
+        by_key = None
+        if targets is not None:
+            by_key = {(name if len(seqs) == 1 else f"{name}.{i}"): t for name, seqs in groups.items() for i, t in enumerate(targets[name])}
+        retime_outputs(out, retime_kw, world, by_key, rt_scores)
     np.savez(path, **out)
     return out
 
@@ -1302,6 +1386,7 @@ def run(argv, extra_defaults=None):
     lift_fuse_skeleton_smooth_options(cfg)     # ... and a lift.fuse_skeleton_smooth without lift.fuse_skeleton
     lift_ground_options(cfg)                   # ... and a lift.ground=estimate with neither lift.fuse nor lift.place
     lift_footlock_options(cfg)                 # ... and a lift.footlock without lift.ground=estimate
+    lift_retime_options(cfg)                   # ... and a lift.retime_fps without run.lift, lift.rotations or lift.rigid
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")
@@ -1475,9 +1560,13 @@ def run(argv, extra_defaults=None):
         targets, scores, fused_scores, tri_scores, skel_scores, cal_scores = None, {}, {}, {}, {}, {}
         if lift_score_options(cfg):            # the 3-D ground truth beside the 2-D sequences that are lifted
             targets = {name: sq[0] for name, sq in seqs["test"].items()} if real else synthetic_sequences_3d(cfg, cfg.run.seed)
-        ground_rows, footlock_rows = [], []
+        ground_rows, footlock_rows, rt_scores = [], [], {}
         lifted = lift_sequences_to_file(model, cfg, groups, path, cams, targets, scores, fused_scores, tri_scores, skel_scores, cal_scores, ground_rows,
-                                        footlock_rows)
+                                        footlock_rows, rt_scores)
+        if lift_retime_options(cfg)[0]:
+            kw = lift_retime_options(cfg)[1]
+            print(f"lift.retime: {sum(1 for k in lifted if k.endswith('__rt'))} takes or sequences from {kw['fps_in']} to {kw['fps_out']} fps, radius {kw['radius']}",
+                  flush=True)
         if lift_ground_options(cfg)[0]:
             print(f"lift.ground: {len(ground_rows)} floors estimated -> {write_lift_ground_report(out_dir, ground_rows)}", flush=True)
         if lift_footlock_options(cfg)[0]:
@@ -1494,6 +1583,8 @@ def run(argv, extra_defaults=None):
             mean = lambda key: 1000.0 * float(np.nansum(n * np.array([float(v[key]) for v in scores.values()])) / max(1.0, n.sum()))
             print(f"lift score (mm, {int(n.sum())} frames of {len(scores)} sequences): mpjpe {mean('mpjpe'):.3f}, p-mpjpe {mean('p_mpjpe'):.3f}, "
                   f"mpjve {mean('mpjve'):.3f}, accel {mean('accel'):.3f} -> {written[0]}", flush=True)
+            if rt_scores:                      # lift.retime_fps at the input's rate: rotation-space smoothing, scored at the input's frames
+                print(f"lift score, retimed sequences -> {report.write_lift_score_report(out_dir, rt_scores, name='lift_score_rt', joints=False)[0]}", flush=True)
             if fused_scores:
                 print(f"lift score, fused takes -> {report.write_lift_score_report(out_dir, fused_scores, name='lift_score_fused', joints=False)[0]}",
                       flush=True)

@@ -1217,6 +1217,69 @@ int mp_lift_footlock(const float* points, int64_t Ntot, int J, int C, const uint
                      const int32_t* legs, int nf, const float* normal, const float* offset, const uint8_t* plane_ok, int blend, float stretch,
                      float* out, int32_t* run, float* target, float* moved, uint8_t* flags, int32_t* runs, void* stream);
 
+/* Forward kinematics of (root, quaternions, bone lengths): the inverse of mp_lift_rotations, in the decoder's convention as that entry point states
+ * it.  The reference has no counterpart.  quat (Ntot, inner, J, 4) device floats (w, x, y, z), 16-byte aligned, 2 <= J <= 32; root (Ntot, inner, 3)
+ * device floats or null (the origin); lengths device floats: (S, J - 1), one row per sequence, frame g taking the row of the last s with
+ * seq_offset[s] <= g (always inside 0 .. S-1, whatever the device table holds; seq_offset (S + 1) device int64), or with MP_LIFT_FK_POSE_LENGTHS
+ * (Ntot, inner, J - 1), one row per pose (seq_offset and S are then not read: without mp_lift_rigid only each frame's own measured lengths close the
+ * loop); parents (J) and rest (J, 3) HOST tables exactly as mp_lift_rotations takes them (parents[0] = -1, 0 <= parents[j] < j; rest row j >= 1
+ * normalised here in fp64, row 0 ignored, a zero or non-finite row is MP_ERR_ARG).  Outputs: poses (Ntot, inner, J, 3) device floats, ok
+ * (Ntot, inner) device bytes.  Per pose, on its own, fp64 between the float32 loads and stores:
+ * 1. Every quaternion must be USABLE: n2 = |q|^2 in fp64 finite and >= 1e-12 (the rule of a take's quaternions everywhere in this library).  If one
+ *    of the pose's J is not: every joint gets the root's float32 bits (+0 without a root) and ok = 0.
+ * 2. Otherwise u[j] = q[j] / sqrt(n2[j]);  Rw[0] = u[0],  Rw[j] = Rw[parent] u[j];  p[0] = root,  p[j] = p[parent] + Rw[j] (len_j rest_j) for
+ *    j = 1 .. J-1 in order;  poses[j] = (float) p[j],  ok = 1.  len_j is used as it is stored (a negative or non-finite length gives IEEE results).
+ * mp_lift_fk(mp_lift_rotations(p), the measured lengths of p, p[0]) is p again to float32 rounding.  One lane per (pose, joint); a lane fetches its
+ * parent's world rotation (a quaternion) and position by wavefront shuffles, level by level.  No atomics, no LDS, a fixed order: identical bits on
+ * every call; a pose depends on no other pose.  The call does not synchronise.
+ * MP_ERR_ARG before anything is launched: quat, lengths, rest, parents, poses or ok null; seq_offset null without MP_LIFT_FK_POSE_LENGTHS; another
+ * flag; J, Ntot, inner or S out of range (S > Ntot); quat not 16-byte aligned; poses overlapping quat; a bad parent table or rest row; more work
+ * than one grid holds. */
+#define MP_LIFT_FK_POSE_LENGTHS 1
+int mp_lift_fk(const float* quat, const float* root, const float* lengths, int64_t Ntot, int inner, int J, const int64_t* seq_offset, int S,
+               const int32_t* parents, const float* rest, int flags, float* poses, uint8_t* ok, void* stream);
+
+/* A take resampled in time on its rotations: every output frame samples its sequence at a fractional input time, on SO(3) for the joints and
+ * linearly for the root, by interpolation (radius 0) or by mp_lift_smooth's weighted local polynomial evaluated at that time (radius >= 1).  What
+ * comes out is again (root, quat), so with mp_lift_fk and the take's ONE bone table the retimed positions have exactly the take's bones - averaging
+ * or interpolating POSITIONS shortens a bone by 1 - cos(theta / 2) at the midpoint of two directions theta apart.  The reference has no counterpart.
+ * quat (Ntot, inner, J, 4) device floats (w, x, y, z), 2 <= J <= 32; root (Ntot, inner, 3) or null; valid (Ntot, inner) bytes or null (every frame
+ * valid); seq_offset (S + 1) device int64, the input frames [f0, f1) of every sequence clamped to 0 .. Ntot (n = f1 - f0); out_offset (S + 1) device
+ * int64, its output frames, clamped to 0 .. Mtot; clock (S, 3) device DOUBLES (start, num, den), num and den holding integers (output and input
+ * frames per unit of time); radius R in 0 .. MP_LIFT_SMOOTH_MAXR, degree 0..2, taper 0 (uniform) or 1 (biweight).  Outputs: quat_out
+ * (Mtot, inner, J, 4), root_out (Mtot, inner, 3) (null exactly when root is), ok and taps (Mtot, inner) bytes.  quat and quat_out 16-byte aligned.
+ * Output frame g belongs to the last sequence s with out_offset[s] <= g (always inside 0 .. S-1).  If g lies outside that sequence's clamped output
+ * range, or n = 0: identity quaternions (1, 0, 0, 0), root 0, ok = 0, taps = 0.  Otherwise with h = g - (the sequence's first output frame):
+ *   t = start + (h den) / num  in fp64 (the product an exact integer, ONE division; num <= 0 or NaN counts as 1), in input frames from f0;
+ *   t is clamped into [0, n - 1] (a NaN to 0), and ok gets the value 2 added where it was.
+ * log(r): s = |r.xyz|; 0 where s == 0, else 2 atan2(s, r.w) r.xyz / s.   exp(v): a = |v|; (1, 0, 0, 0) where a == 0, else (cos(a / 2),
+ * sin(a / 2) v / a).   u(k) = q_k / |q_k| in fp64.
+ * R = 0, interpolation.  k = floor(t), al = t - k.
+ *   al == 0 exactly (every integer t, t = n - 1 included): frame k is copied BIT FOR BIT, its quaternions as stored and its root; ok = (valid[k] != 0),
+ *   taps = 1.  With start = 0 and num = den the operator is the identity on every valid frame, bit for bit.
+ *   Otherwise (k + 1 <= n - 1) both frames must be valid; if not: identities, root 0, ok = 0, taps = 0 - nothing is filled in this mode.  Else
+ *   a = u(k), b = u(k + 1) negated where dot(a, b) < 0,  q = a exp(al log(conj(a) b)): the short-way slerp, in the hemisphere of q_k as stored, so
+ *   a sign-continuous track stays one;  root = (1 - al) r_k + al r_(k+1);  ok = 1, taps = 2.
+ * R >= 1, fit.  The taps are the frames k in 0 .. n-1 with |k - t| <= R and valid[k] != 0, cnt of them (taps = cnt).  cnt = 0: identities, root 0,
+ *   ok = 0.  Else ok = 1 and  u_k = (k - t) / R,  w_k = 1 (uniform) or (1 - ((k - t) / (R + 1))^2)^2 (biweight);  d = min(degree, cnt - 1), or d = 0
+ *   when no tap has k <= t or none has k >= t (not bracketed: held, never extrapolated);  c_k = w_k (a0 + a1 u_k + a2 u_k^2), (a0, a1, a2) the first
+ *   row of the inverse of the (d + 1) x (d + 1) normal matrix [sum w u^(i+j)] by cofactors, exactly mp_lift_smooth's with its integer tau replaced by
+ *   k - t; all sums over the taps in increasing k; c_k is computed once per (output frame, inner index) and shared by the root and the J joints.
+ *   k* = the tap nearest to t, the lower one on a tie.  Per joint:  v_k = log(conj(u(k*)) (+-u(k))), the sign that makes dot(u(k*), +-u(k)) >= 0;
+ *   q = u(k*) exp(sum_k c_k v_k).  Per root coordinate: sum_k c_k r_k (at an integer t mp_lift_smooth's sum).  A rotation at constant angular
+ *   velocity about a fixed axis is reproduced for degree >= 1 (its v_k are linear in k); two taps with degree 1 are the slerp above.
+ * All arithmetic between the float32 loads and stores is fp64; a computed zero component is stored as +0.  A non-finite or zero quaternion on a
+ * valid tap gives IEEE results in the output frames that read it; an invalid tap's value never enters the arithmetic.  clock and out_offset are
+ * device data no host check sees: whatever they hold, nothing outside the arrays is read or written (seq_offset and out_offset MUST NOT DECREASE for
+ * the result to be the one stated here: which sequence holds a frame is found by bisection).  One lane per (output pose, joint); no atomics,
+ * no LDS, fixed orders: identical bits on every call; a sequence's result does not depend on the other sequences.  The call does not synchronise.
+ * MP_ERR_ARG before anything is launched: quat, seq_offset, out_offset, clock, quat_out, ok or taps null; root and root_out not both null or both
+ * given; an output overlapping an input or another output; radius, degree, taper, J, Ntot, Mtot, inner or S out of range (S > Ntot); quat or
+ * quat_out not 16-byte aligned; more work than one grid holds. */
+int mp_lift_retime(const float* quat, const float* root, const uint8_t* valid, int64_t Ntot, int inner, int J, const int64_t* seq_offset,
+                   const int64_t* out_offset, const double* clock, int S, int64_t Mtot, int radius, int degree, int taper, float* quat_out,
+                   float* root_out, uint8_t* ok, uint8_t* taps, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

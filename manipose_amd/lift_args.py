@@ -213,6 +213,66 @@ def footlock_options(blend, stretch, maxblend):
         raise ValueError(f"stretch is the share of thigh + shank a leg may reach, a number in (0, 1], got {stretch!r}")
 
 
+def quats4(quat):
+    """quat (Ntot, J, 4) or (Ntot, inner, J, 4), contiguous float32, 2..32 joints, at least one frame -> its 4-D view"""
+    if not torch.is_tensor(quat) or quat.dim() not in (3, 4) or quat.shape[-1] != 4 or quat.dtype != torch.float32 or not quat.is_contiguous():
+        raise ValueError(f"quat must be a contiguous float32 tensor (Ntot, J, 4) or (Ntot, inner, J, 4), got {_got(quat)}")
+    _count("quat", int(quat.shape[-2]), "joints", 2, 32)
+    if int(quat.shape[0]) < 1 or (quat.dim() == 4 and int(quat.shape[1]) < 1):
+        raise ValueError(f"quat holds no frame, got {tuple(quat.shape)}")
+    return quat.unsqueeze(1) if quat.dim() == 3 else quat
+
+
+def retime_options(fps_in, fps_out, radius, degree, taper, maxradius, tapers):
+    """the scalars of retime_rotations as the kernel takes them: both rates integers in 1..2^20 (frames times a rate stay exact in a float64),
+    radius an integer in 0..maxradius (0: interpolation), degree 0..2, taper one of ``tapers``"""
+    for name, v in (("fps_in", fps_in), ("fps_out", fps_out)):
+        if not is_int_in(v, 1, 1 << 20):
+            raise ValueError(f"{name} is a frame rate, an integer in 1..{1 << 20}, got {v!r}")
+    if not is_int_in(radius, 0, maxradius):
+        raise ValueError(f"radius must be an integer in 0..{maxradius} (0: interpolation between the two frames around a sample), got {radius!r}")
+    if not is_int_in(degree, 0, 2):
+        raise ValueError(f"degree must be 0, 1 or 2, got {degree!r}")
+    if taper not in tapers:
+        raise ValueError(f"taper must be one of {sorted(tapers)}, got {taper!r}")
+
+
+def retime_plan(seq_offset, ntot, fps_in, fps_out, start):
+    """The output frames of a retimed take, from HOST numbers alone.  ``seq_offset`` (S + 1) first input frames (None: one sequence of ``ntot``),
+    not decreasing inside 0..ntot, no sequence empty; ``start`` one number or S of them, finite and >= 0, in input frames.  Output frame h of a
+    sequence of n frames samples it at t = start + (h * fps_in) / fps_out - in float64 the product is exact and there is one division, the
+    kernel's expression - and the sequence gets the M frames with t <= n - 1: for start = 0 in integers, M = ((n - 1) * fps_out) // fps_in + 1.
+    Returns (in_offset (S + 1) int64, out_offset (S + 1) int64, clock (S, 3) float64 rows (start, fps_out, fps_in), time (Mtot,) float64)."""
+    off = np.asarray([0, ntot] if seq_offset is None else seq_offset)
+    if off.ndim != 1 or off.size < 2 or off.dtype.kind not in "iu":
+        raise ValueError(f"seq_offset must hold S + 1 >= 2 integer frame numbers, got shape {off.shape} {off.dtype}")
+    off = off.astype(np.int64)
+    S = off.size - 1
+    if off[0] < 0 or off[-1] > ntot or (np.diff(off) < 1).any():
+        raise ValueError(f"seq_offset must increase inside 0..{ntot} (no sequence is empty), got {off.tolist()}")
+    st = np.asarray(start, dtype=np.float64) if is_number(start) or isinstance(start, (list, tuple, np.ndarray)) else None
+    if st is None or st.shape not in ((), (S,)) or not np.isfinite(st).all() or (st < 0).any():
+        raise ValueError(f"start is the first sample in input frames, one finite number >= 0 or one per sequence ({S}), got {start!r}")
+    st = np.broadcast_to(st, (S,)).astype(np.float64)
+    num, den = float(fps_out), float(fps_in)
+    counts, times = [], []
+    for s in range(S):
+        n = int(off[s + 1] - off[s])
+        if st[s] > n - 1:
+            raise ValueError(f"start = {st[s]!r} lies past the last frame of sequence {s} ({n} frames)")
+        at = lambda h: st[s] + (float(h) * den) / num
+        M = ((n - 1) * int(fps_out)) // int(fps_in) + 1 if st[s] == 0 else int(np.floor((n - 1 - st[s]) * num / den)) + 1
+        while M > 1 and at(M - 1) > n - 1:
+            M -= 1
+        while at(M) <= n - 1:
+            M += 1
+        counts.append(M)
+        times.append(st[s] + (np.arange(M, dtype=np.float64) * den) / num)
+    out_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    clock = np.stack([st, np.full(S, num), np.full(S, den)], axis=1)
+    return off, out_off, np.ascontiguousarray(clock), np.concatenate(times)
+
+
 def floor_record(ground, S):
     """ground is None or carries ``normal`` (S, 3) float32, ``offset`` (S) float32 and ``ok`` (S) uint8 tensors (a ``Ground``) -> those three or None"""
     if ground is None:

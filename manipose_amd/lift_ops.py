@@ -58,6 +58,13 @@ Pinning the feet (``lock_feet``, off everywhere by default): ``mp_lift_footlock`
 is pinned to the mean of its ankle positions (on the estimated floor where a ``Ground`` is handed over), the swing frames around a run are eased into
 and out of the pin, and each leg is re-posed by analytic two-bone IK with the frame's own bone lengths; hips and the rest of the body keep their bits
 (include/manipose_hip.h has the rule).  The defaults are untuned and nothing has been measured on real data (no dataset here).
+
+Retiming on the rotations (``retime_rotations`` / ``smooth_rotations`` / ``pose_from_rotations``, off everywhere by default): with ``rotations`` the
+product is the triple (root trajectory, quat, bones), and every operator above that works along time works on joint positions, where averaging or
+interpolating shortens the bones.  ``mp_lift_retime`` resamples the triple at any frame rate, or smooths it at its own, on SO(3) - the short-way slerp
+of the two frames around a sample, or ``mp_lift_smooth``'s local polynomial in the tangent space of the nearest valid frame - and ``mp_lift_fk``, the
+inverse of ``mp_lift_rotations``, turns it back into positions on exactly the take's bone table (include/manipose_hip.h has both rules).  The defaults
+are untuned and nothing has been measured on real data (no dataset here).
 """
 from __future__ import annotations
 
@@ -582,6 +589,120 @@ def lock_feet(points, contact, seq_offset=None, valid=None, legs=H36M_LEGS, grou
                                                      blend, stretch)
     skate, pairs = _skate(out, contact, valid, d_off, S, [leg[2] for leg in legs], floor)
     return FootLock(out, run, target, moved, flags, runs, skate, pairs)
+
+
+FK_POSE_LENGTHS = 1          # MP_LIFT_FK_POSE_LENGTHS of include/manipose_hip.h
+# What retime_rotations returns, device tensors: quat (Mtot[, inner], J, 4) float32, root (Mtot[, inner], 3) float32 or None, ok and taps
+# (Mtot[, inner]) uint8, seq_offset (S + 1) int64 the OUTPUT frames of every sequence, time (Mtot,) float64 the sampled input times
+Retimed = namedtuple("Retimed", "quat root ok taps seq_offset time")
+
+
+def _fk(lib, q4, root, d_lengths, d_off, S, parents, rest, per_pose):
+    """``mp_lift_fk`` on q4 (Ntot, inner, J, 4), root (Ntot, inner, 3) or None, lengths (S, J - 1) or per pose (Ntot, inner, J - 1):
+    (poses (Ntot, inner, J, 3), ok (Ntot, inner) uint8), new tensors"""
+    ntot, inner, J, _ = (int(v) for v in q4.shape)
+    dev = q4.device
+    poses = torch.empty(ntot, inner, J, 3, dtype=torch.float32, device=dev)
+    ok = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
+    _launch(dev, "mp_lift_fk", _lib.ptr(q4), _lib.ptr(root), _lib.ptr(d_lengths), ntot, inner, J, _lib.ptr(d_off), S, parents, rest,
+            FK_POSE_LENGTHS if per_pose else 0, _lib.ptr(poses), _lib.ptr(ok))
+    return poses, ok
+
+
+def pose_from_rotations(quat, bones, root=None, seq_offset=None, skeleton=None):
+    """``mp_lift_fk`` on device tensors, the inverse of ``pose_rotations``: the joint positions of (root, quat, bones) under the decoder's forward
+    kinematics (Rw[0] = q[0], Rw[j] = Rw[parent] q[j], p[0] = root, p[j] = p[parent] + bones[j - 1] Rw[j] rest_j).  ``quat`` (Ntot, J, 4) or
+    (Ntot, inner, J, 4) float32 (w, x, y, z), normalised in fp64 before use; ``bones``: per SEQUENCE (S, J - 1) or (J - 1,), tensor or array, finite
+    and non-negative (what ``lift_sequences(return_bones=True)`` returns), or per POSE a float32 device tensor (Ntot[, inner], J - 1) - without a
+    rigid stage only each frame's own measured lengths give the pose back; ``root`` (Ntot[, inner], 3) float32 or None (the origin);
+    ``seq_offset`` (S + 1): first frame of every sequence, HOST table or device int64 tensor (default: one sequence), read for per-sequence bones
+    alone; ``skeleton``: anything with ``parents`` and ``t_pose_operators`` (default, for J = 17 only: the H36M tree).  Returns ``(poses, ok)``:
+    poses (Ntot[, inner], J, 3) float32; ok (Ntot[, inner]) uint8, 0 where a quaternion of the pose is zero or not finite (|q|^2 < 1e-12): all its
+    joints then sit on its root.  fp64 inside, identical bits on every call (include/manipose_hip.h has the rule)."""
+    q4 = lift_args.quats4(quat)
+    ntot, inner, J = (int(v) for v in q4.shape[:3])
+    lead = tuple(quat.shape[:-2])
+    if skeleton is None and J != 17:
+        raise ValueError(f"quat has {J} joints: the default skeleton is the 17-joint H36M tree; pass a skeleton with parents and t_pose_operators")
+    sk = _skeleton_of(skeleton=skeleton)
+    parents, rest = _parents_c(sk, J), _rest_c(sk, J)
+    if root is not None:
+        lift_args.f32(root, lead + (3,), "root", contiguous=True)
+    shape = None if seq_offset is None else tuple(seq_offset.shape if torch.is_tensor(seq_offset) else np.shape(seq_offset))
+    if shape is not None and (len(shape) != 1 or shape[0] < 2 or shape[0] - 1 > ntot):
+        raise ValueError(f"seq_offset must hold S + 1 >= 2 frame numbers, S <= {ntot} frames, got shape {shape}")
+    S = 1 if shape is None else shape[0] - 1
+    got = tuple(bones.shape) if torch.is_tensor(bones) else np.shape(bones)
+    per_pose = got == lead + (J - 1,) and got not in ((S, J - 1), (J - 1,))
+    if per_pose:
+        lift_args.f32(bones, lead + (J - 1,), "bones (one row per pose)", contiguous=True)
+        table = None
+    else:
+        table = _host_f32(bones, (S, J - 1), "bones", row=(J - 1,), nonneg=True)
+    lift_args.need_device("pose_from_rotations", quat, optional=(root, bones if per_pose else None))
+    d_off = None if per_pose else _seq_table(seq_offset, ntot, quat.device)[0]
+    d_len = bones if per_pose else torch.from_numpy(table).to(quat.device)
+    poses, ok = _fk(_lib.load(), q4, root, d_len, d_off, S, parents, rest, per_pose)
+    return poses.view(lead + (J, 3)), ok.view(lead)
+
+
+def _retime(lib, q4, root, valid, d_off, d_out, d_clock, S, mtot, radius, degree, taper):
+    """``mp_lift_retime`` on q4 (Ntot, inner, J, 4), root (Ntot, inner, 3) or None, valid (Ntot, inner) uint8 or None and the device tables:
+    (quat (Mtot, inner, J, 4), root (Mtot, inner, 3) or None, ok, taps (Mtot, inner) uint8), new tensors"""
+    ntot, inner, J, _ = (int(v) for v in q4.shape)
+    dev = q4.device
+    quat = torch.empty(mtot, inner, J, 4, dtype=torch.float32, device=dev)
+    rout = torch.empty(mtot, inner, 3, dtype=torch.float32, device=dev) if root is not None else None
+    ok, taps = (torch.empty(mtot, inner, dtype=torch.uint8, device=dev) for _ in range(2))
+    _launch(dev, "mp_lift_retime", _lib.ptr(q4), _lib.ptr(root), _lib.ptr(valid), ntot, inner, J, _lib.ptr(d_off), _lib.ptr(d_out), _lib.ptr(d_clock), S,
+            mtot, int(radius), int(degree), TAPER[taper], _lib.ptr(quat), _lib.ptr(rout), _lib.ptr(ok), _lib.ptr(taps))
+    return quat, rout, ok, taps
+
+
+def retime_rotations(quat, root=None, valid=None, seq_offset=None, fps_in=1, fps_out=1, start=0.0, radius=0, degree=2, taper="uniform"):
+    """``mp_lift_retime`` on device tensors: a take resampled in time on its rotations.  ``quat`` (Ntot, J, 4) or (Ntot, inner, J, 4) float32 as
+    ``pose_rotations`` returns it (sign-continuous tracks stay sign-continuous); ``root`` (Ntot[, inner], 3) float32 or None; ``valid`` uint8
+    (Ntot[, inner]) or None (every frame is valid); ``seq_offset`` (S + 1): first frame of every sequence, HOST table or device int64 tensor
+    (default: one sequence; a device table is read back once, the output's frame counts are host numbers).  ``fps_in`` / ``fps_out``: positive
+    integers, the input's and the output's frame rate; ``start`` >= 0 in input frames, one number or one per sequence.  Output frame h of a
+    sequence of n frames samples it at t = start + h fps_in / fps_out; the sequence gets the M = floor((n - 1 - start) fps_out / fps_in) + 1 frames
+    whose t does not pass its last frame.  ``radius`` 0: the short-way slerp of the two frames around t and the root between them linearly, both
+    of which must be valid (nothing is filled); an integer t returns its frame's bits, so fps_in == fps_out with start 0 is the identity.
+    ``radius`` 1..64: ``smooth_poses``' weighted local polynomial (``degree``, ``taper``) over the valid frames within ``radius`` of t, fitted in the
+    tangent space of the frame nearest to t and evaluated at t - holes are filled, a window with valid frames on one side only is held constant;
+    fps_in == fps_out then is smoothing in rotation space (``smooth_rotations``).  Returns a ``Retimed`` of new device tensors: ``quat``
+    (Mtot[, inner], J, 4); ``root`` (Mtot[, inner], 3) or None; ``ok`` uint8: 1 a result (else identities and a zero root), + 2 where t had to be
+    clamped into the sequence; ``taps`` uint8 the input frames the result was formed from; ``seq_offset`` (S + 1) int64 the output frames of every
+    sequence; ``time`` (Mtot,) float64 every output frame's t.  ``pose_from_rotations(r.quat, bones, r.root, r.seq_offset)`` gives the retimed
+    positions, on exactly the take's bone table.  fp64 inside, identical bits on every call (include/manipose_hip.h has the rule)."""
+    lift_args.retime_options(fps_in, fps_out, radius, degree, taper, SMOOTH_MAXR, TAPER)
+    q4 = lift_args.quats4(quat)
+    ntot, inner, J = (int(v) for v in q4.shape[:3])
+    lead = tuple(quat.shape[:-2])
+    if root is not None:
+        lift_args.f32(root, lead + (3,), "root", contiguous=True)
+    lift_args.mask(valid, lead, "valid")
+    on_device = torch.is_tensor(seq_offset) and seq_offset.is_cuda
+    plan = None if on_device else lift_args.retime_plan(seq_offset.numpy() if torch.is_tensor(seq_offset) else seq_offset, ntot, fps_in, fps_out, start)
+    lift_args.need_device("retime_rotations", quat, optional=(root, valid))
+    if plan is None:
+        plan = lift_args.retime_plan(seq_offset.cpu().numpy(), ntot, fps_in, fps_out, start)
+    off, out_off, clock, time = plan
+    dev, S, mtot = quat.device, int(off.size) - 1, int(out_off[-1])
+    d_off, d_out = (torch.from_numpy(t).to(dev) for t in (off, out_off))
+    got = _retime(_lib.load(), q4, None if root is None else root.view(ntot, inner, 3), None if valid is None else valid.contiguous().view(ntot, inner),
+                  d_off, d_out, torch.from_numpy(clock).to(dev), S, mtot, radius, degree, taper)
+    out_lead = (mtot,) + lead[1:]
+    return Retimed(got[0].view(out_lead + (J, 4)), None if got[1] is None else got[1].view(out_lead + (3,)), got[2].view(out_lead), got[3].view(out_lead),
+                   d_out, torch.from_numpy(time).to(dev))
+
+
+def smooth_rotations(quat, root=None, valid=None, seq_offset=None, radius=4, degree=2, taper="uniform"):
+    """Smoothing in rotation space: ``retime_rotations`` at the input's own frames (fps_in == fps_out, start 0) with ``radius`` 1..64 - the filter of
+    ``smooth_poses`` on the rotations and the root instead of the joint positions, so the bones of ``pose_from_rotations`` on the result are the bone
+    table's by construction.  Returns the same ``Retimed`` record (its seq_offset and time are the input's frames)."""
+    _smooth_options(radius, degree, taper)
+    return retime_rotations(quat, root, valid, seq_offset, 1, 1, 0.0, radius, degree, taper)
 
 
 REFINE_MAXITERS = 16         # MP_LIFT_REFINE_MAXITERS of include/manipose_hip.h: Gauss-Newton steps mp_lift_place_refine takes at most

@@ -19,6 +19,12 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --skeleton-smooth [frames=3000] [reps=20]
     python tools/lift_bench.py --ground [frames=3000] [reps=20]
     python tools/lift_bench.py --footlock [frames=3000] [reps=20]
+    python tools/lift_bench.py --retime [frames=3000] [reps=20]
+--retime times mp_lift_retime (a take resampled in time on its rotations: one lane per (output pose, joint)) and mp_lift_fk (the positions of
+(root, quat, bones)) through their private launchers on a smooth synthetic take of 17 joints with 10 % of the frames invalid, as ONE take of
+`frames` frames and as 64 sequences of `frames` / 10, at the rates 50 -> 50, 50 -> 30 and 50 -> 60 and the radii 0, 4 and 64; beside each time the
+bytes the kernel requests and writes and the bandwidth that implies, and mp_lift_smooth on the same quaternion array at the same radius in the same
+run (the operators have no predecessor: that is the figure to hold them against).
 --footlock times mp_lift_footlock (the feet pinned on their contacts: a copy, the run kernel with one wave per (sequence, foot), the pose kernel
 with one lane per (frame, foot) twice) through its private launcher on --ground's walkers, contacts and planes, as ONE take of `frames` frames and
 as 64 sequences of `frames` / 10, at blend 0, 5 and 32, with and without the floor; beside each time the bytes the copy and the kernels must move
@@ -698,6 +704,60 @@ def footlock_bench(argv):
                   f"{nbytes / us / 1e3:,.1f} GB/s)", flush=True)
 
 
+def retime_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd import lift_args
+    from manipose_amd.lift_ops import _fk, _parents_c, _rest_c, _retime, _skeleton_of, _smooth
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib = _lib.load()
+    J = 17
+    sk = _skeleton_of()
+    parents, rest = _parents_c(sk, J), _rest_c(sk, J)
+    print(f"--retime: a smooth synthetic take of {J} joints (every joint turns at up to 0.03 rad a frame), 10 % of the frames invalid, degree 2, biweight; "
+          f"{reps} calls each after 5 of warm-up (the output allocations are inside the time)", flush=True)
+    for S, n in ((1, frames), (64, max(frames // 10, 1))):
+        g = np.random.default_rng(S)
+        t = np.arange(n, dtype=np.float64)[None, :, None]
+        axis = g.standard_normal((S, 1, J, 3))
+        axis /= np.sqrt((axis * axis).sum(-1))[..., None]
+        ang = 0.5 * (g.uniform(-0.03, 0.03, (S, 1, J)) * t + 0.2 * np.sin(g.uniform(0.02, 0.08, (S, 1, J)) * t))
+        q = np.concatenate([np.cos(ang)[..., None], np.sin(ang)[..., None] * axis], axis=-1).reshape(S * n, 1, J, 4).astype(np.float32)
+        quat = torch.from_numpy(q).cuda()
+        root = torch.from_numpy(g.standard_normal((S * n, 1, 3)).astype(np.float32)).cuda()
+        valid = torch.from_numpy((g.uniform(size=(S * n, 1)) > 0.1).astype(np.uint8)).cuda()
+        bones = torch.from_numpy(g.uniform(0.1, 0.5, (S, J - 1)).astype(np.float32)).cuda()
+        seq = [n * s for s in range(S + 1)]
+        for fps_out in (50, 30, 60):
+            off, out_off, clock, _ = lift_args.retime_plan(seq, S * n, 50, fps_out, 0.0)
+            d_off, d_out, d_clock = (torch.from_numpy(a).cuda() for a in (off, out_off, clock))
+            mtot = int(out_off[-1])
+            for R in (0, 4, 64):
+                call = lambda: _retime(lib, quat, root, valid, d_off, d_out, d_clock, S, mtot, R, 2, "biweight")
+                got = call()
+                torch.cuda.synchronize()
+                taps = int(got[3].sum())
+                # requested per tap: a validity byte, a root (12) and J quaternions (16 J); for R >= 1 the validity bytes of the window twice over
+                # (the moments, then the coefficients) and the reference frame's quaternions; written per output pose: 16 J + 12 + 2
+                nbytes = taps * (1 + 12 + 16 * J) + mtot * (16 * J + 12 + 2) + (mtot * (2 * (2 * R + 1) + 16 * J) if R else 0)
+                us = timed_us(call, reps)
+                line = (f"mp_lift_retime, {S} sequence(s) of {n} frames, 50 -> {fps_out} fps ({mtot} output frames), radius={R}: {us:,.1f} us  ({taps / mtot:.1f} taps a "
+                        f"frame, {int((got[2] & 1 == 0).sum())} frames without a result; {nbytes / 1e6:.2f} MB requested and written: {nbytes / us / 1e3:,.1f} GB/s)")
+                if R and fps_out == 50:
+                    sm = timed_us(lambda: _smooth(lib, quat, valid, d_off, S, R, 2, "biweight"), reps)
+                    line += f"; mp_lift_smooth on the same quaternions as (Ntot, 1, {J}, 4) values, radius={R}: {sm:,.1f} us"
+                print(line, flush=True)
+            fk = lambda: _fk(lib, got[0], got[1], bones, d_out, S, parents, rest, False)
+            fk()
+            us = timed_us(fk, reps)
+            nbytes = mtot * (16 * J + 12 + 4 * (J - 1) + 12 * J + 1)
+            print(f"mp_lift_fk, {S} sequence(s), {mtot} frames (the retimed take at {fps_out} fps): {us:,.1f} us  ({nbytes / 1e6:.2f} MB read and written: "
+                  f"{nbytes / us / 1e3:,.1f} GB/s)", flush=True)
+
+
+if "--retime" in sys.argv:
+    retime_bench([a for a in sys.argv[1:] if a != "--retime"])
+    sys.exit(0)
 if "--footlock" in sys.argv:
     footlock_bench([a for a in sys.argv[1:] if a != "--footlock"])
     sys.exit(0)
