@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import copy
 import os
+import re
 import sys
 
 import numpy as np
@@ -283,7 +284,8 @@ LIFT_SUFFIXES = ("__hyps", "__bones", "__traj", "__reproj", "__ok", "__hyps_traj
                  "__cam_quat_bundle", "__cam_trans_bundle", "__cam_err_deg_bundle", "__cam_err_m_bundle", "__ground_normal", "__ground_offset",
                  "__ground_quat", "__ground_trans", "__ground_rms", "__ground_gap", "__ground_used", "__ground_ok", "__ground_err_deg", "__ground_z",
                  "__contact", "__foot_height", "__skate", "__skate_pairs", "__locked", "__lock_flags", "__lock_moved", "__lock_run", "__skate_locked",
-                 "__skate_pairs_locked", "__rt", "__rt_quat", "__rt_root", "__rt_ok", "__rt_taps", "__rt_time", "__rt_fps")
+                 "__skate_pairs_locked", "__rt", "__rt_quat", "__rt_root", "__rt_ok", "__rt_taps", "__rt_time", "__rt_fps", "__bvh_euler", "__bvh_pos",
+                 "__bvh_ok")
 
 
 def _scale_and_cost(scale, cost=None, unit="metres"):
@@ -684,19 +686,12 @@ def lift_retime_options(cfg):
     return True, dict(fps_in=fps_in, fps_out=int(fps), radius=int(kw["radius"]), degree=int(kw["degree"]), taper=kw["taper"])
 
 
-def retime_outputs(out, kw, world, targets=None, scores=None):
-    """lift.retime_fps, LAST, on what ``out`` holds as it is emitted.  Per sequence ``<key>`` with ``__quat`` and ``__bones``: (root, ``__quat``,
-    ``__bones``) with validity ``__quat_ok``, the root being ``__traj`` (validity also its ``__filled``, else its ``__ok``) with lift.place in the
-    camera's frame, the poses' own joint 0 with lift.frame=world, else the origin; per fused take ``<key>`` with ``__skel_quat`` and ``__skel_bones``:
-    (``__skel[:, 0]``, ``__skel_quat``, ``__skel_bones``) with validity ``__skel_quat_ok`` & ``__skel_ok``.  retime_rotations then pose_from_rotations
-    add ``<key>__rt`` (M, 17, 3), the positions in the frame of the poses they come from, ``__rt_quat`` (M, 17, 4), ``__rt_root`` (M, 3) where there is
-    a root, ``__rt_ok``, ``__rt_taps`` (M,) uint8, ``__rt_time`` (M,) float64 in input frames and ``__rt_fps`` (2,) int32 (in, out).  ``__locked``, the
-    hypotheses and the per-view poses are not retimed.  ``targets`` ({sequence key: (N, 17, 3)}) with equal rates: score_poses' record of ``__rt`` goes
-    to ``scores`` (ground truth exists at input frames only: a take retimed to another rate is not scored)."""
-    from manipose_amd import pose_from_rotations, retime_rotations, score_poses
-    from manipose_amd.lifting import SCORE_FIELDS
-    dev = torch.device("cuda", torch.cuda.current_device())
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+def emitted_triples(out, world):
+    """The (root, quat, bones) triples ``out`` holds as they are emitted, what the last stages (lift.retime_fps, lift.bvh) read: a list of
+    (key, quat (N, 17, 4), bones (16,), root (N, 3) or None, valid (N,) bool).  Per sequence ``<key>`` with ``__quat`` and ``__bones``: validity
+    ``__quat_ok``, the root being ``__traj`` (validity also its ``__filled``, else its ``__ok``) with lift.place in the camera's frame, the poses' own
+    joint 0 with lift.frame=world, else none; per fused take ``<key>`` with ``__skel_quat`` and ``__skel_bones``: ``__skel[:, 0]``, validity
+    ``__skel_quat_ok`` & ``__skel_ok``."""
     jobs = []
     for k in list(out):
         if k.endswith("__skel_quat") and k[:-len("__skel_quat")] + "__skel_bones" in out:
@@ -711,6 +706,120 @@ def retime_outputs(out, kw, world, targets=None, scores=None):
                 root = out[key + "__traj"]
                 valid = valid & (out[key + ("__filled" if key + "__filled" in out else "__ok")] != 0)
             jobs.append((key, out[k], out[key + "__bones"], root, valid))
+    return jobs
+
+
+BVH_DEFAULTS = dict(order="ZXY", up="y", scale=100, continuous=True, fps=0)      # fps 0: the dataset's frame rate, or lift.retime_fps
+BVH_ORDERS = ("XYZ", "XZY", "YXZ", "YZX", "ZXY", "ZYX")
+
+
+def lift_bvh_options(cfg):
+    """(bvh, kwargs for bvh_outputs) of lift.bvh / lift.bvh_order / lift.bvh_up / lift.bvh_scale / lift.bvh_continuous / lift.bvh_fps; ValueError
+    for a value or a combination that cannot run - before any model is built.  The file holds ONE hierarchy with constant offsets, so the stage
+    needs lift.rotations (what it reads) and lift.rigid (the take's one bone table)."""
+    on = cfg.lift.get("bvh", False)
+    kw = {k: cfg.lift.get("bvh_" + k, v) for k, v in BVH_DEFAULTS.items()}
+    if not isinstance(on, bool):
+        raise ValueError(f"lift.bvh must be true or false, got {on!r}")
+    if kw["order"] not in BVH_ORDERS:
+        raise ValueError(f"lift.bvh_order must be one of {', '.join(BVH_ORDERS)}, got {kw['order']!r}")
+    if kw["up"] not in ("y", "z"):
+        raise ValueError(f"lift.bvh_up is the file's up axis, y or z, got {kw['up']!r}")
+    if not is_number(kw["scale"]) or not 0 < float(np.float32(kw["scale"])) < float("inf"):
+        raise ValueError(f"lift.bvh_scale is the file's unit, a finite number > 0 (100: centimetres), got {kw['scale']!r}")
+    if not isinstance(kw["continuous"], bool):
+        raise ValueError(f"lift.bvh_continuous must be true or false, got {kw['continuous']!r}")
+    if not is_int_in(kw["fps"], 0, 1 << 20):
+        raise ValueError(f"lift.bvh_fps is the file's frame rate, a positive integer (0: the dataset's, or lift.retime_fps), got {kw['fps']!r}")
+    if not on:
+        if any(kw[k] != v for k, v in BVH_DEFAULTS.items()):
+            raise ValueError("lift.bvh_order / lift.bvh_up / lift.bvh_scale / lift.bvh_continuous / lift.bvh_fps describe the export: set lift.bvh=true")
+        return False, kw
+    if not bool(cfg.run.lift):
+        raise ValueError("lift.bvh exports what run.lift lifts: set run.lift=true")
+    if not lift_rotations_options(cfg)[0]:
+        raise ValueError("lift.bvh writes the joint rotations: set lift.rotations=true")
+    if not bool(cfg.lift.get("rigid", False)):
+        raise ValueError("lift.bvh writes one hierarchy with constant offsets: set lift.rigid=true (with per-frame lengths there is no bone table)")
+    retime_on, retime_kw = lift_retime_options(cfg)
+    fps = int(kw["fps"]) or (retime_kw["fps_out"] if retime_on else DATASET_FPS.get(str(cfg.data.dataset), 0))
+    if fps == 0:
+        raise ValueError(f"lift.bvh: the frame rate of data.dataset={cfg.data.dataset} is not known here: set lift.bvh_fps")
+    return True, dict(order=kw["order"], up=kw["up"], scale=float(kw["scale"]), continuous=kw["continuous"], fps=fps, retimed=retime_on)
+
+
+def bvh_file_name(key):
+    """the file of a take or sequence under <experiment>/bvh: its key with everything but letters, digits, '.', '_' and '-' replaced by '_'"""
+    return re.sub(r"[^A-Za-z0-9._-]", "_", str(key)) + ".bvh"
+
+
+def bvh_outputs(out, kw, world, folder):
+    """lift.bvh, LAST (after retime_outputs), on what ``out`` holds as it is emitted.  With lift.retime_fps every ``<key>__rt_quat``: (``__rt_root``,
+    ``__rt_quat``, the take's bone table, ``__rt_ok`` & 1) at the output rate; otherwise the triples of ``emitted_triples`` at the input's rate.
+    Where ``<key>__ground_quat`` exists with ``__ground_ok`` & 1 the take stands on its estimated floor (basis, shift = the ground transform); with
+    up = "y" the turn that takes z-up to y-up, (x, y, z) -> (x, z, -y), is composed in front - in float64, rounded once.  euler_from_rotations
+    gives ``<key>__bvh_euler`` (M, 17, 3) degrees, ``__bvh_pos`` (M, 3) in the file's unit and ``__bvh_ok`` (M,), and write_bvh
+    ``folder/<sanitised key>.bvh`` (none for a take without a frame that has a result).  Returns the files written."""
+    from manipose_amd import euler_from_rotations
+    from manipose_amd.bvh import write_bvh
+    from manipose_amd.data import Skeleton
+    from manipose_amd.data.ingest import H36M_JOINT_NAMES_17
+    from manipose_amd.data.skeleton import H36M_JOINTS_LEFT, H36M_JOINTS_RIGHT, H36M_PARENTS, T_POSE_OPERATORS
+    sk = Skeleton(list(H36M_PARENTS), list(H36M_JOINTS_LEFT), list(H36M_JOINTS_RIGHT), T_POSE_OPERATORS, joints_names=H36M_JOINT_NAMES_17)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    jobs = []
+    for key, quat, bones, root, valid in emitted_triples(out, world):
+        if kw["retimed"]:
+            quat, root, valid = out[key + "__rt_quat"], out.get(key + "__rt_root"), (out[key + "__rt_ok"] & 1) != 0
+        jobs.append((key, quat, bones, root, valid))
+    written = []
+    for key, quat, bones, root, valid in jobs:
+        basis, shift = torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float64), torch.zeros(3, dtype=torch.float64)
+        if key + "__ground_quat" in out and int(out[key + "__ground_ok"]) & 1:
+            basis = torch.from_numpy(np.asarray(out[key + "__ground_quat"], np.float64).reshape(4))
+            basis = basis / basis.norm()
+            shift = torch.from_numpy(np.asarray(out[key + "__ground_trans"], np.float64).reshape(3))
+        if kw["up"] == "y":
+            basis, shift = bvh_turn_up(basis, shift)
+        root = np.zeros((len(quat), 3), np.float32) if root is None else np.asarray(root, np.float32)
+        e = euler_from_rotations(up(np.asarray(quat, np.float32)), up(root), up(np.asarray(valid).astype(np.uint8)), None, kw["order"], kw["continuous"],
+                                 basis.to(torch.float32), shift.to(torch.float32), kw["scale"])
+        angles, pos, ok = e.angles.cpu().numpy(), e.pos.cpu().numpy(), e.ok.cpu().numpy()
+        out[key + "__bvh_euler"], out[key + "__bvh_pos"], out[key + "__bvh_ok"] = angles, pos, ok
+        path = os.path.join(folder, bvh_file_name(key))
+        if not (ok != 0).any():                # (write_bvh would write nothing: no folder is made for it either)
+            continue
+        os.makedirs(folder, exist_ok=True)
+        if write_bvh(path, sk, np.asarray(bones, np.float64), angles, pos, ok, kw["fps"], kw["order"], kw["scale"]):
+            written.append(path)
+    return written
+
+
+def bvh_turn_up(basis, shift):
+    """(u basis, qrot(u, shift)) in float64 torch tensors, u = (sqrt(1/2), -sqrt(1/2), 0, 0): the quarter turn about x that takes z-up to y-up,
+    (x, y, z) -> (x, z, -y), composed in front of p' = qrot(basis, p) + shift"""
+    h = float(np.sqrt(0.5))
+    w, x, y, z = (float(v) for v in basis.to(torch.float64))
+    turned = torch.tensor([h * w + h * x, h * x - h * w, h * y + h * z, h * z - h * y], dtype=torch.float64)      # (h, -h, 0, 0) (w, x, y, z)
+    sx, sy, sz = (float(v) for v in shift.to(torch.float64))
+    return turned, torch.tensor([sx, sz, -sy], dtype=torch.float64)
+
+
+def retime_outputs(out, kw, world, targets=None, scores=None):
+    """lift.retime_fps, LAST, on what ``out`` holds as it is emitted.  Per sequence ``<key>`` with ``__quat`` and ``__bones``: (root, ``__quat``,
+    ``__bones``) with validity ``__quat_ok``, the root being ``__traj`` (validity also its ``__filled``, else its ``__ok``) with lift.place in the
+    camera's frame, the poses' own joint 0 with lift.frame=world, else the origin; per fused take ``<key>`` with ``__skel_quat`` and ``__skel_bones``:
+    (``__skel[:, 0]``, ``__skel_quat``, ``__skel_bones``) with validity ``__skel_quat_ok`` & ``__skel_ok``.  retime_rotations then pose_from_rotations
+    add ``<key>__rt`` (M, 17, 3), the positions in the frame of the poses they come from, ``__rt_quat`` (M, 17, 4), ``__rt_root`` (M, 3) where there is
+    a root, ``__rt_ok``, ``__rt_taps`` (M,) uint8, ``__rt_time`` (M,) float64 in input frames and ``__rt_fps`` (2,) int32 (in, out).  ``__locked``, the
+    hypotheses and the per-view poses are not retimed.  ``targets`` ({sequence key: (N, 17, 3)}) with equal rates: score_poses' record of ``__rt`` goes
+    to ``scores`` (ground truth exists at input frames only: a take retimed to another rate is not scored)."""
+    from manipose_amd import pose_from_rotations, retime_rotations, score_poses
+    from manipose_amd.lifting import SCORE_FIELDS
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    jobs = emitted_triples(out, world)
     for key, quat, bones, root, valid in jobs:
         r = retime_rotations(up(quat), None if root is None else up(root), up(valid.astype(np.uint8)), None, kw["fps_in"], kw["fps_out"], 0.0, kw["radius"],
                              kw["degree"], kw["taper"])
@@ -1332,6 +1441,11 @@ def lift_sequences_to_file(model, cfg, groups, path, cameras=None, targets=None,
         if targets is not None:
             by_key = {(name if len(seqs) == 1 else f"{name}.{i}"): t for name, seqs in groups.items() for i, t in enumerate(targets[name])}
         retime_outputs(out, retime_kw, world, by_key, rt_scores)
+    bvh_on, bvh_kw = lift_bvh_options(cfg)
+    if bvh_on:                                 # lift.bvh: the very last, on what is emitted (bvh_outputs has the keys and the files)
+        bvh_files = bvh_outputs(out, bvh_kw, world, os.path.join(os.path.dirname(os.path.abspath(path)), "bvh"))
+        print(f"lift.bvh: {len(bvh_files)} files at {bvh_kw['fps']} fps, channels {bvh_kw['order']}, {bvh_kw['up']} up -> {os.path.dirname(bvh_files[0]) if bvh_files else 'none'}",
+              flush=True)
     np.savez(path, **out)
     return out
 
@@ -1387,6 +1501,7 @@ def run(argv, extra_defaults=None):
     lift_ground_options(cfg)                   # ... and a lift.ground=estimate with neither lift.fuse nor lift.place
     lift_footlock_options(cfg)                 # ... and a lift.footlock without lift.ground=estimate
     lift_retime_options(cfg)                   # ... and a lift.retime_fps without run.lift, lift.rotations or lift.rigid
+    lift_bvh_options(cfg)                      # ... and a lift.bvh without them, or a bvh option without lift.bvh
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the lifting entry points need an MI355X (ROCm device); there is no CPU fallback")

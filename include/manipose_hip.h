@@ -1280,6 +1280,47 @@ int mp_lift_retime(const float* quat, const float* root, const uint8_t* valid, i
                    const int64_t* out_offset, const double* clock, int S, int64_t Mtot, int radius, int degree, int taper, float* quat_out,
                    float* root_out, uint8_t* ok, uint8_t* taps, void* stream);
 
+/* Euler channels of a take's joint rotations, for export as a BONE-CENTRED joint hierarchy (BVH, manipose_amd/bvh.py): bone j >= 1 gets a node that
+ * sits at its PARENT joint, carries exactly q[j] and has its child end len_j rest_j away, so the node's world rotation is the decoder's Rw[j] and
+ * every joint position comes out as mp_lift_fk's, with no approximation and no twist estimate.  The reference has no counterpart.
+ * quat (Ntot, inner, J, 4) device floats (w, x, y, z), 16-byte aligned, 2 <= J <= 32; root (Ntot, inner, 3) or null; valid (Ntot, inner) bytes or
+ * null (every frame valid); seq_offset (S + 1) device int64, a sequence's frames [f0, f1) clamped to 0 .. Ntot as in mp_lift_retime, frame g
+ * belonging to the last s with seq_offset[s] <= g (always inside 0 .. S-1); basis (S, 4) and shift (S, 3) device floats or both null (identity,
+ * zero): a rigid transform per sequence in mp_lift_world's convention, p' = qrot(basis, p) + shift; scale a finite float > 0; order 0..5 for XYZ,
+ * XZY, YXZ, YZX, ZXY, ZYX; flags 0 or MP_LIFT_EULER_CONTINUOUS.  Outputs: angles (Ntot, inner, J, 3) floats, DEGREES in channel order; pos
+ * (Ntot, inner, 3), null exactly when root is; ok (Ntot, inner) bytes.
+ * FIRST PASS, per pose, on its own; all arithmetic between the float32 loads and stores is fp64 with contraction off.  A quaternion is USABLE where
+ * n2 = |q|^2 is finite and >= 1e-12.  If one of the pose's J quaternions is not usable, or valid of the frame is 0, or basis of its sequence is
+ * not usable: every angle +0, pos +0, ok = 0.  Otherwise u[j] = q[j] / sqrt(n2[j]); u[0] := unit(basis) u[0] (the quaternion product, basis on
+ * the LEFT); R the matrix of u[j] (1 - 2 (y^2 + z^2), 2 (x y - w z), ... row-major).  The order names the axes (i, j, k), s = +1 where
+ * (j - i) mod 3 == 1, else -1; the angles (al, be, ga) satisfy R = R_i(al) R_j(be) R_k(ga), the channel convention of BVH:
+ *   c2 = R[j][k]^2 + R[k][k]^2;  be = asin(clamp(s R[i][k], -1, 1));
+ *   regular, c2 >= 1e-12:  al = atan2(-s R[j][k], R[k][k]),  ga = atan2(-s R[i][j], R[i][i]);
+ *   gimbal,  c2 <  1e-12:  al = atan2(s R[k][j], R[j][j]),   ga = 0,  and ok gets 2 added (once per pose, whichever joint it was).
+ * pos = (float)(scale * (qrot(unit(basis), root) + shift)), qrot by the matrix of unit(basis), row sums left to right.  An angle is multiplied by
+ * 57.29577951308232 (the double nearest to 180 / pi) and rounded to float32 once; a float32 zero, -0 of a negative value that underflowed included,
+ * is stored as +0 (angles and pos, in both passes); ok = 1 (or 3).
+ * SECOND PASS, MP_LIFT_EULER_CONTINUOUS: per track (sequence, inner index, joint) over the sequence's clamped frames, decided ON THE FLOAT32 ANGLES
+ * AS THE FIRST PASS STORED THEM, in fp64, so that the rule applied to the first pass's output gives the second pass's bits.  c[g] the stored triple;
+ * T(x) = (x0 + 180, 180 - x1, x2 + 180), the other Euler solution of the same rotation;  w(x) = x - 360 floor((x + 180) / 360), in [-180, 180);
+ * d(x, y) = (|w(x0 - y0)| + |w(x1 - y1)|) + |w(x2 - y2)|.  The PREDECESSOR g' of frame g is the last frame before g in the sequence with
+ * ok != 0; a frame with ok = 0 keeps its zeros and is transparent.
+ *   branch: no predecessor: flip[g] = 0; else flip[g] = flip[g'] XOR (d(c[g], T(c[g'])) < d(c[g], c[g'])).  d is unchanged when T is applied to
+ *     both arguments, so this is the greedy choice "the solution nearer to what was chosen for the frame before", as a prefix parity.
+ *   e[g] = flip[g] ? T(c[g]) : c[g].
+ *   turns, per channel: no predecessor: W[g] = 0; else W[g] = W[g'] - rint((e[g] - e[g']) / 360), rint rounding a tie to even.
+ *   stored: (float)(e[g] + 360 W[g]), the sum in fp64 (a zero as +0).
+ * Both scans are integer, exact and associative: the result does not depend on how the frames are cut into chunks; a sequence's result depends on
+ * no other sequence; identical bits on every call.  One lane per (pose, joint), then one wave per track, 64 frames at a time; no atomics, no LDS.
+ * seq_offset is device data no host check sees: whatever it holds, nothing outside the arrays is read or written (it MUST NOT DECREASE for the
+ * result to be the one stated here).  The call does not synchronise.
+ * MP_ERR_ARG before anything is launched: quat, seq_offset, angles or ok null; root and pos not both null or both given; basis and shift not both
+ * null or both given; order, flags, scale, J, Ntot, inner or S out of range (S > Ntot); quat not 16-byte aligned; an output overlapping an input
+ * or another output; more work than one grid holds. */
+#define MP_LIFT_EULER_CONTINUOUS 1
+int mp_lift_euler(const float* quat, const float* root, const uint8_t* valid, int64_t Ntot, int inner, int J, const int64_t* seq_offset, int S,
+                  const float* basis, const float* shift, float scale, int order, int flags, float* angles, float* pos, uint8_t* ok, void* stream);
+
 /* Dataset ingest: the raw arrays of the reference's on-disk formats -> the resident sequences mp_gather_windows reads.
  * mp_ingest_pose3d: raw (frames_raw, raw_joints, 3) device floats; frames (N) device int32 or null (null: the first N raw frames;
  * otherwise the raw frame of every output frame - temporal stride, valid-frame selection); joint_map (J <= 32) HOST int32 or null:

@@ -155,6 +155,7 @@ _SIGNATURES = {
     "mp_lift_footlock": (i32, [vp, i64, i32, i32, vp, vp, i32, vp, C.POINTER(i32), i32, vp, vp, vp, i32, f32] + [vp] * 6 + [vp]),
     "mp_lift_fk": (i32, [vp, vp, vp, i64, i32, i32, vp, i32, C.POINTER(i32), C.POINTER(f32), i32, vp, vp, vp]),
     "mp_lift_retime": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "mp_lift_euler": (i32, [vp, vp, vp, i64, i32, i32, vp, i32, vp, vp, f32, i32, i32, vp, vp, vp, vp]),
     "mp_ingest_pose3d": (i32, [vp, i32, vp, i64, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(f32), i32, i32, f32, vp, vp]),
     "mp_ingest_pose2d": (i32, [vp, i32, i32, vp, i64, C.POINTER(i32), i32, f32, f32, vp, vp]),
     "mp_procrustes_errors": (i32, [vp, vp, vp, i64, i32, f32, f32, f32, f32, i32, vp, vp, i64, vp]),

@@ -273,6 +273,15 @@ def retime_plan(seq_offset, ntot, fps_in, fps_out, start):
     return off, out_off, np.ascontiguousarray(clock), np.concatenate(times)
 
 
+def euler_options(order, scale, orders):
+    """the scalars of euler_from_rotations as the kernel takes them: order one of ``orders`` (the six channel orders), scale a number whose
+    float32 is finite and > 0"""
+    if not isinstance(order, str) or order not in orders:
+        raise ValueError(f"order must be one of {list(orders)} (the rotation channels, first to last), got {order!r}")
+    if not is_number(scale) or not 0 < float(np.float32(scale)) <= float(np.finfo(np.float32).max):
+        raise ValueError(f"scale is the unit of the positions, a finite number > 0 (100: centimetres), got {scale!r}")
+
+
 def floor_record(ground, S):
     """ground is None or carries ``normal`` (S, 3) float32, ``offset`` (S) float32 and ``ok`` (S) uint8 tensors (a ``Ground``) -> those three or None"""
     if ground is None:

@@ -65,6 +65,11 @@ interpolating shortens the bones.  ``mp_lift_retime`` resamples the triple at an
 of the two frames around a sample, or ``mp_lift_smooth``'s local polynomial in the tangent space of the nearest valid frame - and ``mp_lift_fk``, the
 inverse of ``mp_lift_rotations``, turns it back into positions on exactly the take's bone table (include/manipose_hip.h has both rules).  The defaults
 are untuned and nothing has been measured on real data (no dataset here).
+
+Export (``euler_from_rotations``, off everywhere by default): ``mp_lift_euler`` turns the triple's rotations into Euler channels in degrees, in any
+of the six channel orders, re-expressed by a rigid transform per sequence (the estimated floor, an up-axis turn) and made continuous in time; with
+the bone-centred hierarchy of ``manipose_amd.bvh`` (every bone a node at its parent joint that carries exactly q[j]) they are a BVH file whose joint
+positions are ``pose_from_rotations``' (include/manipose_hip.h has the rule).  Nothing has been measured on real data (no dataset here).
 """
 from __future__ import annotations
 
@@ -703,6 +708,66 @@ def smooth_rotations(quat, root=None, valid=None, seq_offset=None, radius=4, deg
     table's by construction.  Returns the same ``Retimed`` record (its seq_offset and time are the input's frames)."""
     _smooth_options(radius, degree, taper)
     return retime_rotations(quat, root, valid, seq_offset, 1, 1, 0.0, radius, degree, taper)
+
+
+EULER_CONTINUOUS = 1         # MP_LIFT_EULER_CONTINUOUS of include/manipose_hip.h
+EULER_ORDERS = ("XYZ", "XZY", "YXZ", "YZX", "ZXY", "ZYX")      # mp_lift_euler's order = the index
+# What euler_from_rotations returns, device tensors: angles (Ntot[, inner], J, 3) float32 degrees in channel order, pos (Ntot[, inner], 3) float32
+# or None, ok (Ntot[, inner]) uint8
+Eulers = namedtuple("Eulers", "angles pos ok")
+
+
+def _euler(lib, q4, root, valid, d_off, S, d_basis, d_shift, scale, order, continuous):
+    """``mp_lift_euler`` on q4 (Ntot, inner, J, 4), root (Ntot, inner, 3) or None, valid (Ntot, inner) uint8 or None, basis (S, 4) and shift (S, 3)
+    device tables or both None: (angles (Ntot, inner, J, 3), pos (Ntot, inner, 3) or None, ok (Ntot, inner) uint8), new tensors"""
+    ntot, inner, J, _ = (int(v) for v in q4.shape)
+    dev = q4.device
+    angles = torch.empty(ntot, inner, J, 3, dtype=torch.float32, device=dev)
+    pos = torch.empty(ntot, inner, 3, dtype=torch.float32, device=dev) if root is not None else None
+    ok = torch.empty(ntot, inner, dtype=torch.uint8, device=dev)
+    _launch(dev, "mp_lift_euler", _lib.ptr(q4), _lib.ptr(root), _lib.ptr(valid), ntot, inner, J, _lib.ptr(d_off), S, _lib.ptr(d_basis), _lib.ptr(d_shift),
+            float(scale), EULER_ORDERS.index(order), EULER_CONTINUOUS if continuous else 0, _lib.ptr(angles), _lib.ptr(pos), _lib.ptr(ok))
+    return angles, pos, ok
+
+
+def euler_from_rotations(quat, root=None, valid=None, seq_offset=None, order="ZXY", continuous=True, basis=None, shift=None, scale=1.0):
+    """``mp_lift_euler`` on device tensors: the Euler channels of a take's joint rotations, what ``manipose_amd.bvh.write_bvh`` writes.  ``quat``
+    (Ntot, J, 4) or (Ntot, inner, J, 4) float32 (w, x, y, z) as ``pose_rotations`` or ``retime_rotations`` return it, normalised in fp64 before
+    use; ``root`` (Ntot[, inner], 3) float32 or None; ``valid`` uint8 (Ntot[, inner]) or None (every frame is valid); ``seq_offset`` (S + 1): first
+    frame of every sequence, HOST table or device int64 tensor (default: one sequence); ``order``: one of XYZ, XZY, YXZ, YZX, ZXY, ZYX - the
+    angles (al, be, ga) of joint j satisfy R(q[j]) = R_i(al) R_j(be) R_k(ga), BVH's channel convention; ``basis`` (S, 4) or (4,) and ``shift``
+    (S, 3) or (3,), tensors or arrays, finite, or None (identity, zero): a rigid transform per sequence in ``to_world``'s convention,
+    p' = qrot(basis, p) + shift, applied to the root's rotation (on the left) and position - ``estimate_ground``'s quat and trans stand the take
+    on its floor; ``scale`` > 0 multiplies the positions (100: centimetres).  ``continuous``: every (sequence, inner index, joint) track is then
+    made continuous in time - where the other Euler solution of the same rotation, (al + 180, 180 - be, ga + 180), lies nearer to the frame before
+    it is taken, and whole turns are added so that no channel jumps by more than 180 degrees between two frames with a result: a curve a tool can
+    interpolate between its keys.  Returns an ``Eulers`` of new device tensors: ``angles`` (Ntot[, inner], J, 3) float32 DEGREES in channel
+    order; ``pos`` (Ntot[, inner], 3) float32 or None; ``ok`` uint8: 0 where the frame is invalid or a quaternion of the pose (or the basis) is
+    zero or not finite (|q|^2 < 1e-12) - angles and pos are then +0 and the frame is transparent to the continuity -, 1 a result, 3 a result with
+    a joint in gimbal lock (be = +-90: ga is then 0 and al carries both).  fp64 inside, identical bits on every call (include/manipose_hip.h has
+    the rule)."""
+    lift_args.euler_options(order, scale, EULER_ORDERS)
+    q4 = lift_args.quats4(quat)
+    ntot, inner, J = (int(v) for v in q4.shape[:3])
+    lead = tuple(quat.shape[:-2])
+    if root is not None:
+        lift_args.f32(root, lead + (3,), "root", contiguous=True)
+    lift_args.mask(valid, lead, "valid")
+    shape = None if seq_offset is None else tuple(seq_offset.shape if torch.is_tensor(seq_offset) else np.shape(seq_offset))
+    if shape is not None and (len(shape) != 1 or shape[0] < 2 or shape[0] - 1 > ntot):
+        raise ValueError(f"seq_offset must hold S + 1 >= 2 frame numbers, S <= {ntot} frames, got shape {shape}")
+    S = 1 if shape is None else shape[0] - 1
+    h_basis = h_shift = None
+    if basis is not None or shift is not None:
+        h_basis = _host_f32(basis if basis is not None else np.array([1.0, 0.0, 0.0, 0.0], np.float32), (S, 4), "basis", row=(4,))
+        h_shift = _host_f32(shift if shift is not None else np.zeros(3, np.float32), (S, 3), "shift", row=(3,))
+    lift_args.need_device("euler_from_rotations", quat, optional=(root, valid))
+    dev = quat.device
+    d_off = _seq_table(seq_offset, ntot, dev)[0]
+    d_basis, d_shift = (None, None) if h_basis is None else (torch.from_numpy(h_basis).to(dev), torch.from_numpy(h_shift).to(dev))
+    angles, pos, ok = _euler(_lib.load(), q4, None if root is None else root.view(ntot, inner, 3), None if valid is None else valid.contiguous().view(ntot, inner),
+                             d_off, S, d_basis, d_shift, scale, order, bool(continuous))
+    return Eulers(angles.view(lead + (J, 3)), None if pos is None else pos.view(lead + (3,)), ok.view(lead))
 
 
 REFINE_MAXITERS = 16         # MP_LIFT_REFINE_MAXITERS of include/manipose_hip.h: Gauss-Newton steps mp_lift_place_refine takes at most

@@ -39,6 +39,7 @@ from .lift_ops import (FLOOR_SHARES, PATH_MAXK, PATH_SIGMA, PATH_SWITCH, REFINE_
                        _place_refine, _pose_record, _rest_c, _rigid, _rotations, _score, _skeleton_of, _smooth, _smooth_options, _traj_record, _world,
                        GROUND_MAXFEET, GROUND_MAXITERS, GROUND_MAXRADIUS, Ground, estimate_ground, FOOTLOCK_MAXBLEND, FootLock, lock_feet,
                        FK_POSE_LENGTHS, Retimed, pose_from_rotations, retime_rotations, smooth_rotations,
+                       EULER_CONTINUOUS, EULER_ORDERS, Eulers, euler_from_rotations,
                        bone_length_means, camera_table, place_poses, pose_rotations, project_rigid, reproject_poses, score_poses, score_traj,
                        select_path, smooth_poses, smooth_traj, to_world)
 from .lift_views import (ALIGN_ITERS, ALIGN_MAXITERS, ALIGN_SIGMA, BUNDLE_ITERS, BUNDLE_MAXITERS, BUNDLE_SIGMA, CALIBRATE_ITERS, CALIBRATE_MAXITERS, CALIBRATE_PRIOR,
@@ -645,4 +646,4 @@ def lift_action(model, poses_2d, config, return_hyps=False) -> np.ndarray:
 
 __all__ = ["plan_windows", "merge_windows", "project_rigid", "bone_length_means", "camera_table", "place_poses", "reproject_poses", "pose_rotations", "to_world", "smooth_poses", "smooth_traj",
            "select_path", "score_poses", "score_traj", "fuse_views", "fuse_views_path", "place_views", "align_views", "sync_views", "shift_views", "bundle_views", "calibrate_views", "triangulate_views", "fit_skeleton_views", "lift_sequences",
-           "lift_action", "estimate_ground", "lock_feet", "pose_from_rotations", "retime_rotations", "smooth_rotations"]
+           "lift_action", "estimate_ground", "lock_feet", "pose_from_rotations", "retime_rotations", "smooth_rotations", "euler_from_rotations"]

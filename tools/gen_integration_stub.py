@@ -23,7 +23,7 @@ SHOWN = ["mp_abi_version", "mp_last_error", "mp_fk_decode_fwd", "mp_fk_decode_bw
          "mp_lift_bundle_views_scratch_bytes", "mp_lift_bundle_views", "mp_lift_calibrate_views_scratch_bytes", "mp_lift_calibrate_views",
          "mp_lift_triangulate", "mp_lift_fit_skeleton",
          "mp_lift_fit_skeleton_smooth_scratch_bytes", "mp_lift_fit_skeleton_smooth", "mp_lift_ground", "mp_lift_footlock", "mp_lift_fk",
-         "mp_lift_retime"]
+         "mp_lift_retime", "mp_lift_euler"]
 
 
 def tname(t):

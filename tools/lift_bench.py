@@ -20,6 +20,11 @@ Then lift_sequences end to end (gather + forward + merge) at the same batch.
     python tools/lift_bench.py --ground [frames=3000] [reps=20]
     python tools/lift_bench.py --footlock [frames=3000] [reps=20]
     python tools/lift_bench.py --retime [frames=3000] [reps=20]
+    python tools/lift_bench.py --bvh [frames=3000] [reps=20]
+--bvh times mp_lift_euler (the Euler channels a BVH file holds: one lane per (pose, joint), then with MP_LIFT_EULER_CONTINUOUS one wave per
+(sequence, joint) track that walks its frames 64 at a time) through its private launcher on a spinning synthetic take of 17 joints with 10 % of the
+frames invalid, a basis and a shift, order ZXY, as ONE sequence of `frames` frames and as 64 sequences of `frames` each: the first pass alone, both
+passes, their difference (the second pass), and the bytes each must move at least once with the bandwidth that implies.
 --retime times mp_lift_retime (a take resampled in time on its rotations: one lane per (output pose, joint)) and mp_lift_fk (the positions of
 (root, quat, bones)) through their private launchers on a smooth synthetic take of 17 joints with 10 % of the frames invalid, as ONE take of
 `frames` frames and as 64 sequences of `frames` / 10, at the rates 50 -> 50, 50 -> 30 and 50 -> 60 and the radii 0, 4 and 64; beside each time the
@@ -755,6 +760,47 @@ def retime_bench(argv):
                   f"{nbytes / us / 1e3:,.1f} GB/s)", flush=True)
 
 
+def bvh_bench(argv):
+    from manipose_amd import _lib
+    from manipose_amd.lift_ops import _euler
+    frames = int(argv[0]) if len(argv) > 0 else 3000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    lib = _lib.load()
+    J = 17
+    print(f"--bvh: a synthetic take of {J} joints, every joint spinning at up to 0.25 rad a frame (the angles cross their branch cuts every few frames), "
+          f"10 % of the frames invalid, order ZXY, scale 100, a basis and a shift per sequence; {reps} calls each after 5 of warm-up (the output "
+          f"allocations are inside the time)", flush=True)
+    for S, n in ((1, frames), (64, frames)):
+        g = np.random.default_rng(S)
+        t = np.arange(n, dtype=np.float64)[None, :, None]
+        axis = g.standard_normal((S, 1, J, 3))
+        axis /= np.sqrt((axis * axis).sum(-1))[..., None]
+        ang = 0.5 * (g.uniform(-0.25, 0.25, (S, 1, J)) * t + g.uniform(0, 6, (S, 1, J)))
+        q = np.concatenate([np.cos(ang)[..., None], np.sin(ang)[..., None] * axis], axis=-1).reshape(S * n, 1, J, 4).astype(np.float32)
+        quat = torch.from_numpy(q).cuda()
+        root = torch.from_numpy(g.standard_normal((S * n, 1, 3)).astype(np.float32)).cuda()
+        valid = torch.from_numpy((g.uniform(size=(S * n, 1)) > 0.1).astype(np.uint8)).cuda()
+        b = g.standard_normal((S, 4))
+        basis = torch.from_numpy((b / np.sqrt((b * b).sum(-1))[:, None]).astype(np.float32)).cuda()
+        shift = torch.from_numpy(g.standard_normal((S, 3)).astype(np.float32)).cuda()
+        d_off = torch.tensor([n * s for s in range(S + 1)], dtype=torch.int64).cuda()
+        one = lambda: _euler(lib, quat, root, valid, d_off, S, basis, shift, 100.0, "ZXY", False)
+        both = lambda: _euler(lib, quat, root, valid, d_off, S, basis, shift, 100.0, "ZXY", True)
+        got = both()
+        torch.cuda.synchronize()
+        live = int((got[2] != 0).sum())
+        first = S * n * (16 * J + 12 + 1 + 12 * J + 12 + 1)              # quaternions, root, valid in; angles, pos, ok out
+        second = S * n * (12 * J + J) + live * 12 * J                    # angles and (once per joint's wave) ok in; the frames with a result out
+        us1, us2 = timed_us(one, reps), timed_us(both, reps)
+        print(f"mp_lift_euler, {S} sequence(s) of {n} frames, first pass: {us1:,.1f} us  ({first / 1e6:.2f} MB: {first / us1 / 1e3:,.1f} GB/s); both passes: "
+              f"{us2:,.1f} us; the second pass ({S * J} tracks, {-(-n // 64)} chunks each): {us2 - us1:,.1f} us  ({second / 1e6:.2f} MB: "
+              f"{second / max(us2 - us1, 1e-9) / 1e3:,.1f} GB/s); {S * n - live} frames without a result, largest |angle| {float(got[0].abs().max()):,.0f} degrees",
+              flush=True)
+
+
+if "--bvh" in sys.argv:
+    bvh_bench([a for a in sys.argv[1:] if a != "--bvh"])
+    sys.exit(0)
 if "--retime" in sys.argv:
     retime_bench([a for a in sys.argv[1:] if a != "--retime"])
     sys.exit(0)
